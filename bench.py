@@ -17,6 +17,11 @@ launcher in the environment the script re-executes itself under torch.distribute
 world size that differs from --gpus, or fewer visible GPUs than ranks, is an ERROR (never a
 silent 1-rank run).  --scaling weak (default): 128 graphs per GPU; strong: 128 graphs split
 over the ranks (lib/training/training_base.py:230-247: Keras splits the global batch).
+
+A plain run sets up, warms up, times --steps steps and prints one JSON line (`value` graphs/s, `ms_per_step`).  --full adds
+everything else the line can carry (roofline and per-kernel table, CPU baseline, the other step mode's figure, the collective
+timed on its own).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy; the inputs, weights and
+random-mask samples are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -412,6 +417,8 @@ def run_core(args, w, dev, lib, rank, world, use_dist):
     fence()
     elapsed = time.perf_counter() - t0
     lib.egt_prof_enable(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(v_att=v_att, h_hat=h_hat, grad_qkv=d_qkv, grad_E=d_E, grad_G=d_G))
     step_ms = sorted(sev[i].elapsed_time(sev[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2] if step_ms else None
     graphs_step = B
@@ -497,6 +504,7 @@ def run_block(args, w, dev, lib, rank, world, use_dist):
     dh = torch.randn(B, N, Dh, generator=g).to(dev); de = torch.randn(B, N, N, De, generator=g).to(dev)
     params = [p for p in blk.parameters()]
     fa = FlatGradAllReduce(params) if use_dist else None
+    last = {}
 
     def step():
         h.grad = e.grad = None
@@ -509,6 +517,8 @@ def run_block(args, w, dev, lib, rank, world, use_dist):
         torch.autograd.backward([h2, e2], [dh, de])
         if fa is not None:
             fa.all_reduce(average=True, force=True)
+        if args.dump_outputs:
+            last.update(h_out=h2.detach(), e_out=e2.detach())
 
     def fence():
         torch.cuda.synchronize()
@@ -533,6 +543,9 @@ def run_block(args, w, dev, lib, rank, world, use_dist):
     fence()
     elapsed = time.perf_counter() - t0
     lib.egt_prof_enable(0)
+    if args.dump_outputs and rank == 0:
+        grads = fa.flat if fa is not None else torch.cat([p.grad.reshape(-1) for p in params])
+        dump_outputs(args.dump_outputs, dict(last, grad_h=h.grad, grad_e=e.grad, grad_params=grads))
     step_ms = sorted(sev[i].elapsed_time(sev[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2] if step_ms else None
     graphs_step = B
@@ -634,7 +647,47 @@ def self_launch(n: int):
            os.path.abspath(__file__)] + sys.argv[1:]
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC (RCCL across processes)
     print("[bench] launching: " + " ".join(cmd), file=sys.stderr, flush=True)
-    os.execv(sys.executable, cmd)
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))   # a child process: this one has already opened the GPU (device_count)
+
+
+def settle_collectives(use_dist):
+    """Before a hipGraph capture: wait until the process group's watchdog thread has retired every collective issued so far.
+    The watchdog polls the events of pending collectives, and an event query from another thread while a capture is open in
+    global mode (torch.cuda.graph's default) is not permitted: the capture fails and the watchdog aborts the rank."""
+    if use_dist:
+        dist.group.WORLD._wait_for_pending_works()
+
+
+DUMP_BYTES = 60 << 20    # --dump-outputs: at most 60 MiB of float32 data in all
+
+
+def dump_outputs(out_dir: str, arrays: dict):
+    """--dump-outputs: each array as out_dir/<name>.npy in float32.  An array larger than its share of DUMP_BYTES is written as a
+    fixed sample of its flattened elements (seeded indices, sorted): the same positions in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // 4 // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > share:
+            idx = torch.randint(0, t.numel(), (share,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
+def rewind_mask_streams(model, seeds):
+    """Every EGT module's random-mask stream back to call 0, in host-side and device-resident (hipGraph) seed mode alike: the
+    timed steps draw the same samples however many steps the warm-up and the step-mode calibration took, so the outputs of the
+    last timed step (--dump-outputs) are the same in every run with the same arguments."""
+    from egt_amd.layers import EGT
+    mods = [m for m in model.modules() if isinstance(m, EGT)]
+    words = []
+    for m in mods:
+        m._calls = -1
+        words.append(m.next_seed())      # the seed word of call 0; the call count is 0 again
+    if seeds is not None:                # (DeviceSeeds.attach lists the same modules in the same order)
+        seeds.load_state_dict(dict(words=words, steps=seeds.steps))
 
 
 def main():
@@ -684,7 +737,18 @@ def main():
                     help="weak: the workload's B graphs per GPU; strong: B graphs split over the ranks")
     ap.add_argument("--dp-backend", default="torch", choices=["torch", "capi"],
                     help="gradient all-reduce through torch.distributed (RCCL) or the library's own egt_dp_* entry points (RCCL)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the roofline and per-kernel table (hipEvents in the timed region and "
+                         "an untimed profiling pass), the CPU baseline, the other step mode's figure in a second process and the "
+                         "collective timed on its own.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last of them computed (outputs, input and parameter gradients) "
+                         "as DIR/<name>.npy, float32, at most 60 MiB in all (larger arrays as a fixed seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_prof = args.no_graph_leg = True
     if args.scope == "layers":
         args.with_ffn = True
     if args.graph == "auto":     # the stack step is ~25 short launches: replayed as one hipGraph (bit-identical to the eager calls,
@@ -839,18 +903,25 @@ def main():
         if zinc is not None:             # whole model: prediction -> MAE -> backward
             if cifar:
                 nf, fm, adj, ycls = zinc
-                sparse_xent_loss(model(nf, fm, adj), ycls).backward()
+                pred = model(nf, fm, adj)
+                loss = sparse_xent_loss(pred, ycls)
             elif pattern:
                 nf, fm, adj, tgt, ycls, cw = zinc
-                logits, nmask = model(nf, adj, return_mask=True)
-                weighted_sparse_xent_loss(logits, ycls, nmask, cw).backward()
+                pred, nmask = model(nf, adj, return_mask=True)
+                loss = weighted_sparse_xent_loss(pred, ycls, nmask, cw)
             else:
                 nf, fm, adj, tgt = zinc
-                mae_loss(model(nf, fm, adj), tgt).backward()
+                pred = model(nf, fm, adj)
+                loss = mae_loss(pred, tgt)
+            loss.backward()
+            if args.dump_outputs:        # (detached: a kept result must not keep the step's autograd graph alive)
+                return dict(pred=pred.detach(), loss=loss.detach())
         else:
             h.grad = None; e.grad = None
             h2, e2 = model(h, e, mask)
             torch.autograd.backward([h2, e2], [dh, de])
+            if args.dump_outputs:
+                return dict(h_out=h2.detach(), e_out=e2.detach(), grad_h=h.grad, grad_e=e.grad)
 
     def reduce():
         if state["flat_ok"] is None:
@@ -883,8 +954,10 @@ def main():
     def eager_step():
         if seeds is not None:
             seeds.advance()
-        compute()
+        out = compute()
         reduce()
+        if args.dump_outputs:            # (replay mode: GraphedStep.result holds the replays' outputs)
+            state["last"] = out
 
     step = eager_step
 
@@ -944,10 +1017,14 @@ def main():
         if in_graph:                     # forward + backward + the RCCL all-reduce of the flat gradient buffer: one graph, one host call
 
             def compute_and_reduce():
-                compute()
-                reduce()
+                out = compute()
+                if torch.cuda.is_current_stream_capturing():   # (GraphedStep's un-captured warm-up call issues no collective)
+                    reduce()
+                return out
+            settle_collectives(use_dist)
             graphed = GraphedStep(compute_and_reduce, seeds, warmup=1)
         else:
+            settle_collectives(use_dist)
             graphed = GraphedStep(compute, seeds, warmup=1)
         state["collective_in_graph"] = in_graph
         lib.egt_prof_enable(0)           # (the event nodes stay inside the graph)
@@ -981,6 +1058,8 @@ def main():
                 for _ in range(2):
                     step()
                 fence()
+    rewind_mask_streams(model, seeds)
+    fence()
     # Timed region.  hipEvents bracket ONLY the dominant kernel's launches here (an event pair
     # around every launch costs ~15% of the step), and of those every PROF_STRIDE-th launch: an event pair costs the stream
     # 4-5 us (ten of them per step were 2.5 % of the headline step), and a stride coprime with the launches per step walks
@@ -1007,6 +1086,9 @@ def main():
     elapsed = time.perf_counter() - t0
     lib.egt_prof_enable(0)
     lib.egt_prof_stride(1)
+    if args.dump_outputs and rank == 0:
+        grads = model.grad_holder.flat if state["flat_ok"] else state["fa"].flat
+        dump_outputs(args.dump_outputs, dict(graphed.result if graphed is not None else state["last"], grad_params=grads))
     step_ms = sorted(sev[i].elapsed_time(sev[i + 1]) for i in range(args.steps))
     median_ms = step_ms[len(step_ms) // 2] if step_ms else None
     graphs_step = w["B"]
@@ -1030,6 +1112,7 @@ def main():
             from egt_amd import GraphedStep
             lib.egt_prof_forget_graphs()
             lib.egt_prof_enable(2)
+            settle_collectives(use_dist)
             pg = GraphedStep(graphed.fn, seeds, warmup=1)
             lib.egt_prof_enable(2)       # drop the warm-up's eager pairs; the graph's pairs stay
             lib.egt_prof_enable(0)
@@ -1054,7 +1137,7 @@ def main():
     pair_ov = event_pair_overhead_us() if (all_prof and graphed is None) else None   # (eager table only: the replay table's pairs are graph nodes)
     # the one exchange step, timed on its own: hipEvents around the flat-buffer collective
     ar_us = None
-    if use_dist:
+    if use_dist and args.full:
         state["ar_events"] = []
         for _ in range(min(args.steps, 10)):
             eager_step()

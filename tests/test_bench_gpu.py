@@ -30,7 +30,7 @@ def _json_line(out: str):
 def test_bench_one_rank_under_launcher_uses_rccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", "29631", os.path.join(REPO, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--layers", "2"]
+           "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--layers", "2"]
     r = subprocess.run(cmd, cwd=REPO, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
@@ -45,7 +45,7 @@ def test_bench_default_calibrates_the_step_mode():
     """--graph auto (the default) at stack scope: a few steps of the eager stream and of the hipGraph replay are timed after the
     warm-up, the faster mode runs the timed region, and the line says which one and by how much (config.step_mode); the other
     mode's figure travels as the secondary leg."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--layers", "2"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-cpu-baseline", "--layers", "2"]
     r = subprocess.run(cmd, cwd=REPO, env=_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
@@ -61,11 +61,35 @@ def test_bench_default_calibrates_the_step_mode():
     assert line["roofline"]["kernel"] == "k_block_bwd" and line["roofline"]["achieved"] > 0
 
 
+def test_bench_plain_run_dumps_the_same_outputs_in_every_step_mode(tmp_path):
+    """A plain run (no --full) prints the headline figures without the --full extras.  --dump-outputs writes what the last timed
+    step computed: float32 .npy files within the size budget, and the same values from the eager stream, the hipGraph replay and
+    the calibrated default (the random-mask streams are rewound before the timed steps, whatever the calibration ran)."""
+    import numpy as np
+    for g in ("auto", "off", "on"):
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "2", "--layers", "2", "--graph", g,
+               "--dump-outputs", str(tmp_path / g)]
+        r = subprocess.run(cmd, cwd=REPO, env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = _json_line(r.stdout)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "graphs/s"
+        assert line["roofline"] is None and line["cpu_baseline"] is None
+        assert line.get("hipgraph_replay") is None and line.get("eager_step") is None
+    names = sorted(os.listdir(tmp_path / "auto"))
+    assert names == ["e_out.npy", "grad_e.npy", "grad_h.npy", "grad_params.npy", "h_out.npy"]
+    assert sum(os.path.getsize(tmp_path / "auto" / n) for n in names) <= 64e6
+    for n in names:
+        want = np.load(tmp_path / "auto" / n)
+        assert want.dtype == np.float32 and np.isfinite(want).all() and want.any(), n
+        for g in ("off", "on"):
+            np.testing.assert_allclose(np.load(tmp_path / g / n), want, rtol=1e-5, atol=1e-6, err_msg=f"{n}: --graph {g}")
+
+
 def test_bench_graph_replay_under_launcher_with_the_eager_collective():
     """--graph on: forward + backward replayed from one hipGraph, the RCCL collective issued eagerly after each replay"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", "29634", os.path.join(REPO, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--layers", "2", "--graph", "on"]
+           "--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--layers", "2", "--graph", "on"]
     r = subprocess.run(cmd, cwd=REPO, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)
@@ -95,7 +119,7 @@ def test_bench_one_rank_through_the_capi_communicator():
     """--dp-backend capi: the step's collective is egt_dp_allreduce (ncclAllReduce on the compute stream)"""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", "29633", os.path.join(REPO, "bench.py"),
-           "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--layers", "2", "--dp-backend", "capi"]
+           "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--layers", "2", "--dp-backend", "capi"]
     r = subprocess.run(cmd, cwd=REPO, env=_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = _json_line(r.stdout)

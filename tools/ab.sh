@@ -4,7 +4,8 @@
 args=$1; shift
 for v in "$@"; do
   if [ "$v" = default ]; then unset EGT_AMD_LIB; else export EGT_AMD_LIB=$PWD/egt_amd/lib/var/libegt_$v.so; fi
-  python bench.py $args --no-cpu-baseline 2> gpurun_out/ab_$v.err | python -c "
+  err=$(mktemp)
+  python bench.py --full $args --no-cpu-baseline 2> $err | python -c "
 import sys,json
 for ln in sys.stdin:
     if ln.startswith('{'):
@@ -12,5 +13,5 @@ for ln in sys.stdin:
         k=r.get('kernels') or {}
         print('$v', round(d['value']), 'graphs/s', round(d['ms_per_step'],3), 'ms', {n:round(x['avg_us'],1) for n,x in list(k.items())[:3]})
 "
-  grep -A14 "phase cycles" gpurun_out/ab_$v.err
+  grep -A14 "phase cycles" $err; rm -f $err
 done

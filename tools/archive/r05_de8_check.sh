@@ -4,9 +4,9 @@ out=gpurun_out/r05_de8; mkdir -p $out
 timeout 1500 python -m pytest tests/test_narrow_gpu.py tests/test_block_gpu.py tests/test_fullsize_gpu.py tests/test_model.py -x -q -m gpu > $out/pytest.log 2>&1; echo "pytest rc=$?"; tail -4 $out/pytest.log
 timeout 600 python tools/sweep_de8.py 8 > $out/sweep_de8.log 2>&1; echo "sweep rc=$?"; tail -3 $out/sweep_de8.log
 for wl in cifar10_n150 cifar10_n150_fp32 pattern500k_n120_b128 pattern500k_n120 zinc500k_n64 zinc100k_n37; do
-  timeout 300 python bench.py --workload $wl --no-cpu-baseline --no-graph-leg > $out/bench_$wl.json 2> $out/bench_$wl.err; echo "$wl rc=$?"
+  timeout 300 python bench.py --full --workload $wl --no-cpu-baseline --no-graph-leg > $out/bench_$wl.json 2> $out/bench_$wl.err; echo "$wl rc=$?"
 done
-timeout 400 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "default rc=$?"
+timeout 400 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "default rc=$?"
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r05_de8/bench_*.json')):

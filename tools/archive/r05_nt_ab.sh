@@ -4,7 +4,7 @@ out=gpurun_out/r05_nt; mkdir -p $out
 for v in default ffnplain prev default ffnplain prev; do
   if [ "$v" = default ]; then unset EGT_AMD_LIB; else export EGT_AMD_LIB=$PWD/egt_amd/lib/var/libegt_$v.so; fi
   for sc in layers model; do
-    timeout 300 python bench.py --scope $sc --no-cpu-baseline --no-graph-leg --steps 20 2> $out/err_${v}_$sc.log | python -c "
+    timeout 300 python bench.py --full --scope $sc --no-cpu-baseline --no-graph-leg --steps 20 2> $out/err_${v}_$sc.log | python -c "
 import sys,json
 for ln in sys.stdin:
     if ln.startswith('{'):

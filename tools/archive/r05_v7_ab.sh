@@ -8,7 +8,7 @@ tail -3 $out/pytest_full.log
 for v in 0 1 default; do
   if [ $v = default ]; then unset EGT_BWD_V7; else export EGT_BWD_V7=$v; fi
   for rep in 1 2; do
-  timeout 600 python bench.py --no-cpu-baseline --no-graph-leg --graph off --steps 50 2> $out/bench_v7_${v}_$rep.err | tee $out/bench_v7_${v}_$rep.json | python -c "
+  timeout 600 python bench.py --full --no-cpu-baseline --no-graph-leg --graph off --steps 50 2> $out/bench_v7_${v}_$rep.err | tee $out/bench_v7_${v}_$rep.json | python -c "
 import sys,json
 for ln in sys.stdin:
     if ln.startswith('{'):

@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-prof --no-graph-leg --graph off"
 for v in 0 2; do
   export EGT_BWD_V7=$v
-  timeout 300 python bench.py --no-cpu-baseline --no-graph-leg --graph off --steps 50 > $OUT/bench_v7_$v.json 2> $OUT/bench_v7_$v.err
+  timeout 300 python bench.py --full --no-cpu-baseline --no-graph-leg --graph off --steps 50 > $OUT/bench_v7_$v.json 2> $OUT/bench_v7_$v.err
   timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kt_$v -o r -- $B > /dev/null 2>> $OUT/err.log
   timeout 400 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE -d $OUT/pmc_sq_$v -o r -- $B > /dev/null 2>> $OUT/err.log
   timeout 400 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_BUSY_CU_CYCLES -d $OUT/pmc_inst_$v -o r -- $B > /dev/null 2>> $OUT/err.log

@@ -6,7 +6,7 @@ python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tai
 for i in 1 2; do
 for v in default prewg; do
   if [ "$v" = default ]; then unset EGT_AMD_LIB; else export EGT_AMD_LIB=$PWD/egt_amd/lib/var/libegt_$v.so; fi
-  python bench.py --no-cpu-baseline --no-graph-leg --graph off --steps 50 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-graph-leg --graph off --steps 50 2>/dev/null | python -c "
 import sys,json
 for ln in sys.stdin:
     if ln.startswith('{'):

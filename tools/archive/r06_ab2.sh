@@ -12,17 +12,17 @@ print(sys.argv[2], round(d['value']), round(d['ms_per_step'],4), {n:round(v['avg
 PY
 }
 for rep in 1 2; do
-  timeout 300 python bench.py --workload synthetic_n512_block --no-cpu-baseline > $OUT/b_nowait_$rep.json 2>> $OUT/err.log; line $OUT/b_nowait_$rep.json nowait+dma4
+  timeout 300 python bench.py --full --workload synthetic_n512_block --no-cpu-baseline > $OUT/b_nowait_$rep.json 2>> $OUT/err.log; line $OUT/b_nowait_$rep.json nowait+dma4
 done
 EGT_ATTN_FLAGS="-DPAIR_LDS_NOWAIT=0" python -c "from egt_amd import build as B; B.build()" >> $OUT/build.log 2>&1
 for rep in 1 2; do
-  EGT_ATTN_FLAGS="-DPAIR_LDS_NOWAIT=0" timeout 300 python bench.py --workload synthetic_n512_block --no-cpu-baseline > $OUT/b_drain_$rep.json 2>> $OUT/err.log; line $OUT/b_drain_$rep.json drains
+  EGT_ATTN_FLAGS="-DPAIR_LDS_NOWAIT=0" timeout 300 python bench.py --full --workload synthetic_n512_block --no-cpu-baseline > $OUT/b_drain_$rep.json 2>> $OUT/err.log; line $OUT/b_drain_$rep.json drains
 done
 python -c "from egt_amd import build as B; B.build()" >> $OUT/build.log 2>&1
 for v in default 4 6; do
   if [ $v = default ]; then unset EGT_BWD_TL; else export EGT_BWD_TL=$v; fi
-  timeout 300 python bench.py --workload pattern500k_n120 --no-cpu-baseline > $OUT/p_tl_$v.json 2>> $OUT/err.log; line $OUT/p_tl_$v.json "pattern500k_n120 EGT_BWD_TL=$v"
+  timeout 300 python bench.py --full --workload pattern500k_n120 --no-cpu-baseline > $OUT/p_tl_$v.json 2>> $OUT/err.log; line $OUT/p_tl_$v.json "pattern500k_n120 EGT_BWD_TL=$v"
 done
 unset EGT_BWD_TL
-EGT_NRW_FWD_WAVES=8 timeout 300 python bench.py --workload pattern500k_n120 --no-cpu-baseline > $OUT/p_fw8.json 2>> $OUT/err.log; line $OUT/p_fw8.json "pattern500k_n120 EGT_NRW_FWD_WAVES=8"
-EGT_NRW_FWD_WAVES=4 timeout 300 python bench.py --workload pattern500k_n120 --no-cpu-baseline > $OUT/p_fw4.json 2>> $OUT/err.log; line $OUT/p_fw4.json "pattern500k_n120 EGT_NRW_FWD_WAVES=4"
+EGT_NRW_FWD_WAVES=8 timeout 300 python bench.py --full --workload pattern500k_n120 --no-cpu-baseline > $OUT/p_fw8.json 2>> $OUT/err.log; line $OUT/p_fw8.json "pattern500k_n120 EGT_NRW_FWD_WAVES=8"
+EGT_NRW_FWD_WAVES=4 timeout 300 python bench.py --full --workload pattern500k_n120 --no-cpu-baseline > $OUT/p_fw4.json 2>> $OUT/err.log; line $OUT/p_fw4.json "pattern500k_n120 EGT_NRW_FWD_WAVES=4"

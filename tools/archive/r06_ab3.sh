@@ -9,6 +9,6 @@ PY
 for f in "-DPAIR_BWD_NT=0" "-DPAIR_BWD_NT=1" "-DPAIR_BWD_NT=5" "-DPAIR_BWD_NT=4"; do
   EGT_ATTN_FLAGS="$f" python -c "from egt_amd import build as B; B.build()" > $OUT/build.log 2>&1
   for rep in 1 2; do
-    EGT_ATTN_FLAGS="$f" timeout 300 python bench.py --workload synthetic_n512_block --no-cpu-baseline > $OUT/b.json 2>> $OUT/err.log; line $OUT/b.json "$f"
+    EGT_ATTN_FLAGS="$f" timeout 300 python bench.py --full --workload synthetic_n512_block --no-cpu-baseline > $OUT/b.json 2>> $OUT/err.log; line $OUT/b.json "$f"
   done
 done

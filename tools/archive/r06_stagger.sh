@@ -10,9 +10,9 @@ print(sys.argv[2], round(d['value']), round(d['ms_per_step'],4), {n:round(v['avg
 PY
 }
 for rep in 1 2; do
-  timeout 300 python bench.py --workload synthetic_n512_block --no-cpu-baseline > $OUT/b_stag_$rep.json 2>> $OUT/err.log; line $OUT/b_stag_$rep.json stagger
+  timeout 300 python bench.py --full --workload synthetic_n512_block --no-cpu-baseline > $OUT/b_stag_$rep.json 2>> $OUT/err.log; line $OUT/b_stag_$rep.json stagger
 done
 EGT_ATTN_FLAGS="-DPAIR_STAGGER=0" python -c "from egt_amd import build as B; B.build()" >> $OUT/build.log 2>&1
 for rep in 1 2; do
-  EGT_ATTN_FLAGS="-DPAIR_STAGGER=0" timeout 300 python bench.py --workload synthetic_n512_block --no-cpu-baseline > $OUT/b_lock_$rep.json 2>> $OUT/err.log; line $OUT/b_lock_$rep.json lockstep
+  EGT_ATTN_FLAGS="-DPAIR_STAGGER=0" timeout 300 python bench.py --full --workload synthetic_n512_block --no-cpu-baseline > $OUT/b_lock_$rep.json 2>> $OUT/err.log; line $OUT/b_lock_$rep.json lockstep
 done

@@ -1,7 +1,7 @@
 # batch sweep of a De = 8 workload: per-launch kernel times against B (tail / quantisation of the workgroup rounds)
 mkdir -p gpurun_out/occ; : > gpurun_out/occ/bsweep.log
 for B in ${BS:-64 96 102 104 112 128 154 160 205}; do
-  EGT_BENCH_B=$B timeout 300 python bench.py --workload ${WL:-cifar10_n150} --no-cpu-baseline --no-graph-leg --steps 20 --warmup 5 2>>gpurun_out/occ/err | python -c "
+  EGT_BENCH_B=$B timeout 300 python bench.py --full --workload ${WL:-cifar10_n150} --no-cpu-baseline --no-graph-leg --steps 20 --warmup 5 | python -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

@@ -14,7 +14,7 @@ if [ -z "$QUICK" ]; then
   timeout 1500 python -m pytest tests -m gpu -q -x > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest_gpu.log
 fi
 for WL in zinc500k_n64 synthetic_n512; do
-  timeout 400 python bench.py --workload $WL > $OUT/bench_$WL.json 2> $OUT/bench_${WL}_err.log
+  timeout 400 python bench.py --full --workload $WL > $OUT/bench_$WL.json 2> $OUT/bench_${WL}_err.log
   B="python bench.py --workload $WL --steps 10 --warmup 3 --no-cpu-baseline --no-prof --no-graph-leg --graph off"   # counters per eager launch
   timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kt_$WL -o r -- $B > $OUT/bench_under_rocprof_$WL.json 2>> $OUT/bench_${WL}_err.log
   timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch_$WL -o r -- $B > /dev/null 2>> $OUT/bench_${WL}_err.log
@@ -26,7 +26,7 @@ for WL in zinc500k_n64 synthetic_n512; do
 done
 if [ -z "$QUICK" ]; then
   for WL in cifar10_n150 pattern500k_n120_b128 zinc100k_n37 pattern500k_n120 synthetic_n512_b32 synthetic_n512_block; do
-    timeout 300 python bench.py --workload $WL --no-cpu-baseline > $OUT/bench_$WL.json 2>> $OUT/bench_err.log
+    timeout 300 python bench.py --full --workload $WL --no-cpu-baseline > $OUT/bench_$WL.json 2>> $OUT/bench_err.log
   done
   timeout 300 python tools/bench_block_cfg5.py > $OUT/block_cfg5.json 2>> $OUT/bench_err.log
 fi

@@ -14,7 +14,7 @@ if [ -z "$QUICK" ]; then
   timeout 2400 python -m pytest tests -m gpu -q -x > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest_gpu.log
 fi
 for WL in zinc500k_n64 synthetic_n512; do
-  timeout 400 python bench.py --workload $WL > $OUT/bench_$WL.json 2> $OUT/bench_${WL}_err.log
+  timeout 400 python bench.py --full --workload $WL > $OUT/bench_$WL.json 2> $OUT/bench_${WL}_err.log
   B="python bench.py --workload $WL --steps 10 --warmup 3 --no-cpu-baseline --no-prof --no-graph-leg --graph off"   # counters per eager launch
   timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/kt_$WL -o r -- $B > $OUT/bench_under_rocprof_$WL.json 2>> $OUT/bench_${WL}_err.log
   timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch_$WL -o r -- $B > /dev/null 2>> $OUT/bench_${WL}_err.log
@@ -23,16 +23,16 @@ for WL in zinc500k_n64 synthetic_n512; do
   timeout 400 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_BUSY_CU_CYCLES -d $OUT/pmc_inst_$WL -o r -- $B > /dev/null 2>> $OUT/bench_${WL}_err.log
 done
 # the driver's own invocation shape, and the step modes side by side
-timeout 300 python bench.py --steps 20 --warmup 10 > $OUT/bench_driver_style.json 2>> $OUT/bench_err.log
-timeout 300 python bench.py --graph on --no-cpu-baseline --no-graph-leg > $OUT/bench_graph_on.json 2>> $OUT/bench_err.log
-timeout 300 python bench.py --graph off --no-cpu-baseline --no-graph-leg > $OUT/bench_graph_off.json 2>> $OUT/bench_err.log
+timeout 300 python bench.py --full --steps 20 --warmup 10 > $OUT/bench_driver_style.json 2>> $OUT/bench_err.log
+timeout 300 python bench.py --full --graph on --no-cpu-baseline --no-graph-leg > $OUT/bench_graph_on.json 2>> $OUT/bench_err.log
+timeout 300 python bench.py --full --graph off --no-cpu-baseline --no-graph-leg > $OUT/bench_graph_off.json 2>> $OUT/bench_err.log
 if [ -z "$QUICK" ]; then
   for WL in cifar10_n150 pattern500k_n120_b128 zinc100k_n37 pattern500k_n120 synthetic_n512_b32 synthetic_n512_block \
             zinc500k_n64_full pattern500k_bmax pattern500k_bmax_b128 pattern500k_n188 pattern500k_n188_b128 cifar10_n150_fp32; do
-    timeout 300 python bench.py --workload $WL --no-cpu-baseline > $OUT/bench_$WL.json 2>> $OUT/bench_err.log
+    timeout 300 python bench.py --full --workload $WL --no-cpu-baseline > $OUT/bench_$WL.json 2>> $OUT/bench_err.log
   done
   for SC in layers model; do
-    timeout 300 python bench.py --scope $SC --no-cpu-baseline > $OUT/bench_scope_$SC.json 2>> $OUT/bench_err.log
+    timeout 300 python bench.py --full --scope $SC --no-cpu-baseline > $OUT/bench_scope_$SC.json 2>> $OUT/bench_err.log
   done
   timeout 300 python tools/bench_block_cfg5.py > $OUT/block_cfg5.json 2>> $OUT/bench_err.log
 fi

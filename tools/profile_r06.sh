@@ -31,18 +31,18 @@ done
 # refreshes from THIS run's counter passes
 python tools/prof_r04_summary.py $OUT r06_$TAG > $OUT/summary_pre.txt 2>&1
 for WL in $FULLPMC $HBMPMC; do
-  timeout 400 python bench.py --workload $WL $( [ $WL = zinc500k_n64 ] || echo --no-cpu-baseline ) > $OUT/bench_$WL.json 2>> $OUT/bench_${WL}_err.log
+  timeout 400 python bench.py --full --workload $WL $( [ $WL = zinc500k_n64 ] || echo --no-cpu-baseline ) > $OUT/bench_$WL.json 2>> $OUT/bench_${WL}_err.log
 done
 # the driver's own invocation shape, and the step modes side by side
-timeout 300 python bench.py --steps 20 --warmup 10 > $OUT/bench_driver_style.json 2>> $OUT/bench_err.log
-timeout 300 python bench.py --graph on --no-cpu-baseline --no-graph-leg > $OUT/bench_graph_on.json 2>> $OUT/bench_err.log
-timeout 300 python bench.py --graph off --no-cpu-baseline --no-graph-leg > $OUT/bench_graph_off.json 2>> $OUT/bench_err.log
+timeout 300 python bench.py --full --steps 20 --warmup 10 > $OUT/bench_driver_style.json 2>> $OUT/bench_err.log
+timeout 300 python bench.py --full --graph on --no-cpu-baseline --no-graph-leg > $OUT/bench_graph_on.json 2>> $OUT/bench_err.log
+timeout 300 python bench.py --full --graph off --no-cpu-baseline --no-graph-leg > $OUT/bench_graph_off.json 2>> $OUT/bench_err.log
 if [ -z "$QUICK" ]; then
   for WL in synthetic_n512_b32 zinc500k_n64_full pattern500k_bmax pattern500k_bmax_b128 pattern500k_n188 pattern500k_n188_b128 cifar10_n150_fp32; do
-    timeout 300 python bench.py --workload $WL --no-cpu-baseline > $OUT/bench_$WL.json 2>> $OUT/bench_err.log
+    timeout 300 python bench.py --full --workload $WL --no-cpu-baseline > $OUT/bench_$WL.json 2>> $OUT/bench_err.log
   done
   for SC in layers model; do
-    timeout 300 python bench.py --scope $SC --no-cpu-baseline > $OUT/bench_scope_$SC.json 2>> $OUT/bench_err.log
+    timeout 300 python bench.py --full --scope $SC --no-cpu-baseline > $OUT/bench_scope_$SC.json 2>> $OUT/bench_err.log
   done
 fi
 python tools/prof_r04_summary.py $OUT r06_$TAG > $OUT/summary_tail.txt 2>&1

@@ -5,7 +5,7 @@ V=$PWD/egt_amd/lib/var
 for rep in ${REPS:-1 2}; do
   for v in "$@"; do
     L=$V/libegt_$v.so; [ $v = new ] && L=""
-    EGT_AMD_LIB=$L timeout 300 python bench.py --workload ${WL:-synthetic_n512_block} --no-cpu-baseline > $OUT/b_${v}_$rep.json 2>> $OUT/err.log
+    EGT_AMD_LIB=$L timeout 300 python bench.py --full --workload ${WL:-synthetic_n512_block} --no-cpu-baseline > $OUT/b_${v}_$rep.json 2>> $OUT/err.log
     python - $OUT/b_${v}_$rep.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=(d.get('roofline') or {}).get('kernels') or {}

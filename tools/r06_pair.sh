@@ -4,7 +4,7 @@ OUT=gpurun_out/r06_pair; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_pair_gpu.py -m gpu -x -q > $OUT/pytest.log 2>&1; echo "rc=$?" >> $OUT/pytest.log
 timeout 600 python -m pytest tests/test_fullsize_gpu.py -m gpu -x -q -k "n512_block" >> $OUT/pytest.log 2>&1; echo "rc=$?" >> $OUT/pytest.log
 grep -E "passed|failed|rc=|Error|error" $OUT/pytest.log | tail -8
-timeout 300 python bench.py --workload synthetic_n512_block --no-cpu-baseline > $OUT/bench_block.json 2> $OUT/bench_block_err.log
+timeout 300 python bench.py --full --workload synthetic_n512_block --no-cpu-baseline > $OUT/bench_block.json 2> $OUT/bench_block_err.log
 python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r06_pair/bench_block.json').read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ run() {
   tag=$1; shift
   EGT_ATTN_FLAGS="$*" python -c "from egt_amd import build as B; B.build()" > $OUT/build_$tag.log 2>&1
   for rep in 1 2; do
-    EGT_ATTN_FLAGS="$*" timeout 300 python bench.py --workload synthetic_n512_block --no-cpu-baseline > $OUT/bench_${tag}_$rep.json 2>> $OUT/err.log
+    EGT_ATTN_FLAGS="$*" timeout 300 python bench.py --full --workload synthetic_n512_block --no-cpu-baseline > $OUT/bench_${tag}_$rep.json 2>> $OUT/err.log
     python - "$OUT/bench_${tag}_$rep.json" "$tag" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=d['roofline']['kernels']
