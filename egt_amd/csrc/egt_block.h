@@ -94,9 +94,19 @@ int egt_device_cus();   // compute units of the current device (egt_block.hip)
 #define WFRAG_FWQ 20480
 #define WFRAG_FLOATS 32768
 
-// De = 8 VALU pair kernels (egt_narrow.hip)
-void egt_narrow_launch_fwd(BlockArgs& a, hipStream_t st);
-void egt_narrow_launch_bwd(BlockArgs& a, int nwg, hipStream_t st);   // same a.pro / partial-buffer contract as k_block_bwd_v4r
+// One launch of a pair kernel in the shape egt_block.hip's plan_block chose: workgroups, threads per workgroup, dynamic LDS bytes.
+struct EgtLaunch { int grid, block; size_t lds; };
+template <void (*K)(BlockArgs)>   // K's dynamic-LDS limit is raised once
+static inline void egt_launch_planned(const char* name, const EgtLaunch& s, hipStream_t st, BlockArgs& a) {
+  EGT_MAX_LDS_ONCE(K);
+  EGT_LAUNCH(name, K, dim3(s.grid), dim3(s.block), s.lds, st, a);
+}
+
+// De = 8 VALU pair kernels (egt_narrow.hip), launched with the waves / rows plan_block chose
+size_t egt_narrow_fwd_lds(int nw);   // dynamic LDS bytes of a workgroup of nw = 4 | 8 waves
+size_t egt_narrow_bwd_lds(int nw);
+void egt_narrow_launch_fwd(BlockArgs& a, int nw, bool half, const EgtLaunch& s, hipStream_t st);   // half: eight-row workgroups (nw = 8)
+void egt_narrow_launch_bwd(BlockArgs& a, int nw, const EgtLaunch& s, hipStream_t st);   // same a.pro / partial-buffer contract as k_block_bwd_v4r
 
 
 // launchers implemented in egt_node.hip

@@ -45,17 +45,25 @@
 // ================================================================ host glue ====
 
 
-// Run-time switches (read ONCE per process: the launch path does no getenv()) -- the complete list, see README.md:
+// Run-time switches of the fused block, read ONCE per process (the launch path does no getenv()) -- the complete list, see README.md:
 //   EGT_NO_NARROW / EGT_NO_NARROW_FWD / EGT_NO_NARROW_BWD: De = 8 falls back from the De = 8 pair kernels (egt_narrow.hip) to the
 //     MFMA-tile kernels (tests exercise both);  EGT_BWD_MATMUL=bf16x3: the backward's channel contractions as 3-term bf16 split
-//     products (opt-in; default exact fp32);  EGT_BWD_TL / EGT_FWD_ROWS: query rows per backward / forward workgroup (tests / sweeps).
+//     products (opt-in; default exact fp32);  EGT_BWD_TL / EGT_FWD_ROWS = 4 .. 16: query rows per backward / forward workgroup
+//     (tests, sweeps; other values are ignored);  EGT_NRW_FWD_WAVES / EGT_NRW_BWD_WAVES = 4 | 8: waves per De = 8 workgroup, and
+//     EGT_NRW_FWD_HALF = 0 | 1: eight-row forward workgroups when that runs eight waves (tests, A/B; other values keep the rule).
 struct EgtBlockEnv {
   bool no_narrow_fwd, no_narrow_bwd;
   int bwd_mm;
+  int bwd_tl, fwd_rows;                            // 0 when unset
+  int nrw_fwd_waves, nrw_bwd_waves, nrw_fwd_half;  // 0 when unset; nrw_fwd_half -1
 };
 static bool env_flag_raw(const char* name) {
   const char* v = getenv(name);
   return v && v[0] && v[0] != '0';
+}
+static int env_int(const char* name, int unset) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : unset;
 }
 static const EgtBlockEnv& block_env() {
   static const EgtBlockEnv e = [] {
@@ -64,6 +72,11 @@ static const EgtBlockEnv& block_env() {
     v.no_narrow_bwd = env_flag_raw("EGT_NO_NARROW_BWD") || env_flag_raw("EGT_NO_NARROW");
     const char* mm = getenv("EGT_BWD_MATMUL");
     v.bwd_mm = (mm && !strcmp(mm, "bf16x3")) ? EGT_MM_BF16X3 : EGT_MM_F32;
+    v.bwd_tl = env_int("EGT_BWD_TL", 0);
+    v.fwd_rows = env_int("EGT_FWD_ROWS", 0);
+    v.nrw_fwd_waves = env_int("EGT_NRW_FWD_WAVES", 0);
+    v.nrw_bwd_waves = env_int("EGT_NRW_BWD_WAVES", 0);
+    v.nrw_fwd_half = env_int("EGT_NRW_FWD_HALF", -1);
     return v;
   }();
   return e;
@@ -99,104 +112,209 @@ extern "C" int egt_block_supported(const egt_block_desc* d) { return block_check
 
 static size_t al(size_t x) { return (x + 63) & ~(size_t)63; }  // in floats
 
-struct BlockLayout {
-  size_t v_att, stats, qkvp, pw_sv, wfrag_sv, saved_total;   // pw_sv: LN-folded edge weights, wfrag_sv: fragment-major Wqkv / Wo -- prepared by the forward, reused by the backward
-  // workspace = [common: dvp dqp[2] dkvp[2]] + per layer [pw epart spart sbo wpart ered dqkv dhbuf]
+// ------------------------------------------------------------------------------------------------------- launch plan ----
+// How the fused block runs for one descriptor -- the kernel family and instance of each direction, the launch shapes, the
+// buffer layout -- is decided in ONE place, plan_block, once per C-ABI call (the layers of a stack call differ only by seed).
+// launch_fwd / launch_bwd (and the De = 8 launchers in egt_narrow.hip) execute the plan; egt_block_bwd_kernel and the
+// *_bytes queries read it.  Families:
+enum class FwdKernel { narrow, r4, tile };      // k_narrow_fwd {NW, half rows} | k_block_fwd_r4 {NW} | k_block_fwd {KVL, ML, FULL}
+enum class BwdKernel { narrow, v4r, v5, v4 };   // k_narrow_bwd {NW} | k_block_bwd_v4r | k_block_bwd_v5 {MM} | k_block_bwd_v4 {ML}
+static const char* const g_bwd_kernel_name[] = {"k_narrow_bwd", "k_block_bwd_v4r", "k_block_bwd_v5", "k_block_bwd_v4"};
+constexpr int V4R_RR = 2;   // k_block_bwd_v4r: rows per iteration (four spill: the rows' carried state + prefetch exceed 256 VGPRs)
+
+struct BlockPlan {
+  bool ml;     // a mask TENSOR is read: the attention mask or a host random-mask buffer (the in-kernel random mask is not one)
+  bool full;   // N is a multiple of 16 (else the kernels' ragged forms)
+  FwdKernel fwd;
+  EgtLaunch fl;
+  int fwd_nw;      // k_narrow_fwd / k_block_fwd_r4: waves per workgroup
+  bool fwd_half;   // k_narrow_fwd: eight-row workgroups
+  bool kvl;        // k_block_fwd: the graph's K / V rows stay in LDS
+  bool epi_ok;     // the geometry allows the pair kernel's node-side epilogue (else k_node_post finishes h')
+  int RGF;         // k_block_fwd: query rows per workgroup (BlockArgs::RGF, set for every forward)
+  BwdKernel bwd;
+  EgtLaunch bl;    // grid = nwg_bwd
+  int bwd_nw;      // k_narrow_bwd: waves per workgroup
+  int mm;          // k_block_bwd_v5: EGT_MM_*
+  int TL, NLR, nwg_bwd, EP;   // query rows per backward workgroup, row groups per graph, workgroups (= edge-parameter partials), floats per partial
+  // buffers, in floats.  saved: pw_sv = LN-folded edge weights, wfrag_sv = fragment-major Wqkv / Wo -- prepared by the forward,
+  // reused by the backward.  workspace = [common: dvp dqp[2] dkvp[2]] + per layer [pw epart spart sbo wpart ered dqkv dhbuf]
   // (dqp / dkvp alternate by layer parity: the prologue of layer l-1 reads layer l's partials while
   //  other workgroups of that launch already write their own)
+  size_t v_att, stats, qkvp, pw_sv, wfrag_sv, saved_total;
   size_t dvp, dqp, dkvp, dqp_sz, dkvp_sz, common_total;
   size_t pw, epart, spart, sbo, wpart, ered, dqkv, dhbuf, layer_total;
-  int TL, NLR, nwg_bwd, EP;   // TL: query rows per backward workgroup
 };
 
-// Query rows per backward workgroup (<= 16: the MFMA tiles of the node-side prologue):
-//  * equal groups: N = 150 is ten groups of 15 rather than nine of 16 and one of 6 -- same workgroup count, no short group
-//    (config 3: 225 -> 216 us per launch; N = 120: 162 -> 156 us);
-//  * a launch of at most one 16-row workgroup per CU (BASELINE config 4 as specified: B = 16, N = 120 -> 128 workgroups on
-//    256 CUs) takes 8 rows per workgroup: twice the partial slots, each prologue on a half-filled tile, every CU busy
-//    (pattern500k_n120, per launch: B = 16: 59.0 us at 16 rows, 43.3 at 8, 47.9 at 6; B = 32: 63.0 / 59.5 / 65.5) -- round 6, with
-//    the eight-wave k_narrow_bwd for such launches: the shortest groups of >= 8 rows that keep the launch at ONE workgroup per CU
-//    (N = 120: B = 16 -> 8 rows, B = 24 -> 12 rows: 51.5 -> 42.5 us, B = 32 -> 15 rows: 54.0 -> 48.4 us against 8 rows);
-//    Smaller groups never pay beyond that: the per-workgroup work that does not shrink with the rows (prologue, K / V tiles,
-//    partial sums) takes over (B = 128, N = 150: 225 us at 16 rows, 253 at 12, 295 at 8).
-// EGT_BWD_TL = 4 .. 16 overrides, for every De (tests, sweeps: tools/dbg/nrw_tlsweep.sh).
-static int bwd_rows_per_wg(const egt_block_desc* d) {
-  static const int forced = getenv("EGT_BWD_TL") ? atoi(getenv("EGT_BWD_TL")) : 0;
-  const int groups = (d->N + BWD_TL - 1) / BWD_TL;
-  if (forced >= 4 && forced <= BWD_TL) return forced;
-  if (d->De != 8) {   // MFMA-tile kernels: two workgroups per CU
-    // equal groups (16 whenever N is a multiple of 16); a launch that leaves slots empty takes more, shorter groups while they
-    // still fit one round and keep 8 rows (ZINC-100K, B = 128, N = 37: 3 x 13 rows = 384 workgroups on 512 slots -> 4 x 10 rows:
-    // k_block_bwd 73.6 -> 64.3 us; 5 x 8 rows = 640 workgroups is a second round: 92.9 us)
-    // ... and 4 rows when even four-row groups leave every CU at most ONE workgroup (B = 16 per GPU at the headline shapes -- a
-    // global batch of 128 over 8 GPUs: 64 sixteen-row workgroups on 512 slots -> 256 four-row ones: 23.8 k -> 30.1 k graphs/s with the
-    // forward's same rule; at B = 24 / 32 four rows measure the same as / below eight: profiles/r06_pair_abl2.txt)
-    const int slots = 2 * egt_device_cus();
-    int g = slots / (d->B > 0 ? d->B : 1);
-    const int cap = d->B * ((d->N + 3) / 4) <= slots / 2 ? (d->N + 3) / 4 : (d->N + 7) / 8;
-    if (g > cap) g = cap;
-    if (g < groups) g = groups;
-    return (d->N + g - 1) / g;
+template <int DE>
+static BlockPlan plan_for(const egt_block_desc* d, bool ml) {
+  using GG = Geo<DE>;
+  const EgtBlockEnv& E = block_env();
+  const int B = d->B, N = d->N, cus = egt_device_cus();
+  const int groups = (N + BWD_TL - 1) / BWD_TL;   // 16-row groups per graph
+  BlockPlan P{};
+  P.ml = ml;
+  P.full = (N % 16) == 0;
+
+  // Row groups per graph of the MFMA-tile kernels (two workgroups per CU), where the forward and backward row rules start:
+  // a launch that leaves slots empty takes more, shorter groups while they still fit one round and keep 8 rows (ZINC-100K, B = 128,
+  // N = 37: backward 3 x 13 rows = 384 workgroups on 512 slots -> 4 x 10 rows: k_block_bwd 73.6 -> 64.3 us; 5 x 8 rows = 640
+  // workgroups is a second round: 92.9 us) ... and 4 rows when even four-row groups leave every CU at most ONE workgroup (B = 16 per
+  // GPU at the headline shapes -- a global batch of 128 over 8 GPUs: 64 sixteen-row workgroups on 512 slots -> 256 four-row ones:
+  // 23.8 k -> 30.1 k graphs/s with the forward's same rule; at B = 24 / 32 four rows measure the same as / below eight:
+  // profiles/r06_pair_abl2.txt)
+  int tg = 2 * cus / B;
+  {
+    const int cap = B * ((N + 3) / 4) <= cus ? (N + 3) / 4 : (N + 7) / 8;
+    if (tg > cap) tg = cap;
   }
-  if (d->B * groups <= egt_device_cus()) {
-    // a launch of at most one 16-row workgroup per CU (it runs the eight-wave k_narrow_bwd): the shortest groups of >= 8 rows that still give
-    // every CU at most ONE workgroup -- B = 16: N = 120 -> 8 rows (240 workgroups), N = 188 -> 12 rows (256; with 8 rows the launch was
-    // 368 four-wave workgroups: 71.4 us against 58.4, `pattern500k_n188` 9.4 k -> 10.9 k graphs/s)
-    if (d->N <= 8) return BWD_TL;
-    for (int tl = 8; tl < BWD_TL; ++tl)
-      if (d->B * ((d->N + tl - 1) / tl) <= egt_device_cus()) return tl;
-    return BWD_TL;
+
+  // ---- forward
+  // k_block_fwd: 16 query rows per workgroup (four per wave); more groups than that take whole multiples of four rows, so the
+  // waves stay balanced (ZINC-100K, B = 128, N = 37: 3 x 16 rows = 384 workgroups -> 4 x 12 rows = 512: the longest wave walks
+  // 3 rows instead of 4).  EGT_FWD_ROWS = 4 .. 16 overrides (tests).
+  P.RGF = tg > groups ? (((N + tg - 1) / tg + 3) / 4) * 4 : 16;
+  if (E.fwd_rows >= 4 && E.fwd_rows <= 16) P.RGF = E.fwd_rows;
+  const size_t lds_tiles = (size_t)8 * GG::TILE_FLOATS * 4;
+  const size_t lds_kv = ((size_t)N * KV_LD + 16 * QS_LD + N) * 4;
+  P.kvl = lds_tiles + lds_kv <= 80 * 1024 - 512;   // two workgroups per CU keep their K/V in LDS
+  // narrow edge channels: four rows per iteration (k_block_fwd_r4).  16-row workgroups when K/V + tiles fit
+  // twice in a CU, else 32-row workgroups (one per CU) as long as K/V fits at all
+  const size_t lds_r4 = (size_t)16 * GG::TILE_FLOATS * 4 + lds_kv;
+  const size_t lds_r8 = (size_t)32 * GG::TILE_FLOATS * 4 + ((size_t)N * KV_LD + 32 * QS_LD + N) * 4;
+  const bool r4 = lds_r4 <= 80 * 1024 - 512, r8 = !r4 && lds_r8 <= 156 * 1024;
+  if (DE == 8 && !ml && !E.no_narrow_fwd) {
+    // VALU pair kernel (egt_narrow.hip): lane = (row, head/channel pair), 4 key quarters per workgroup.  At most one 16-row
+    // workgroup per CU: eight key ranges (eight waves); ... per two CUs: eight-row workgroups.  A forced wave count wins over the
+    // rule; EGT_NRW_FWD_HALF only matters with eight waves.
+    const int grid16 = B * groups;
+    P.fwd = FwdKernel::narrow;
+    P.fwd_nw = E.nrw_fwd_waves == 8 || (E.nrw_fwd_waves != 4 && grid16 <= cus && N >= 64) ? 8 : 4;
+    P.fwd_half = P.fwd_nw == 8 && (E.nrw_fwd_half == 1 || (E.nrw_fwd_half != 0 && 2 * grid16 <= cus));
+    P.fl = {P.fwd_half ? B * ((N + 7) / 8) : grid16, 64 * P.fwd_nw, egt_narrow_fwd_lds(P.fwd_nw)};
+  } else if (DE <= 16 && !ml && (r4 || r8)) {   // (wider channels would not fit the four rows' state in 256 VGPRs: not instantiated)
+    P.fwd = FwdKernel::r4;
+    P.fwd_nw = r4 ? 4 : 8;
+    P.fl = {B * ((N + 4 * P.fwd_nw - 1) / (4 * P.fwd_nw)), 64 * P.fwd_nw, r4 ? lds_r4 : lds_r8};
+  } else {
+    P.fwd = FwdKernel::tile;
+    P.fl = {B * ((N + P.RGF - 1) / P.RGF), 256, lds_tiles + (P.kvl ? lds_kv : 0)};
   }
-  return (d->N + groups - 1) / groups;
+  P.epi_ok = P.fwd != FwdKernel::tile || P.kvl;
+
+  // ---- backward
+  // Query rows per backward workgroup (<= 16: the MFMA tiles of the node-side prologue):
+  //  * equal groups: N = 150 is ten groups of 15 rather than nine of 16 and one of 6 -- same workgroup count, no short group
+  //    (config 3: 225 -> 216 us per launch; N = 120: 162 -> 156 us);
+  //  * MFMA-tile kernels: the row groups above, at least `groups` of them (16 rows whenever N is a multiple of 16 and the launch
+  //    fills the slots).  (N = 6 / 9 at small B come out at 3 rows.)
+  //  * De = 8: a launch of at most one 16-row workgroup per CU (BASELINE config 4 as specified: B = 16, N = 120 -> 128 workgroups
+  //    on 256 CUs) takes 8 rows per workgroup: twice the partial slots, each prologue on a half-filled tile, every CU busy
+  //    (pattern500k_n120, per launch: B = 16: 59.0 us at 16 rows, 43.3 at 8, 47.9 at 6; B = 32: 63.0 / 59.5 / 65.5) -- round 6, with
+  //    the eight-wave k_narrow_bwd for such launches: the shortest groups of >= 8 rows that keep the launch at ONE workgroup per CU
+  //    (N = 120: B = 16 -> 8 rows (240 workgroups), B = 24 -> 12 rows: 51.5 -> 42.5 us, B = 32 -> 15 rows: 54.0 -> 48.4 us against
+  //    8 rows; N = 188: B = 16 -> 12 rows (256; with 8 rows the launch was 368 four-wave workgroups: 71.4 us against 58.4,
+  //    `pattern500k_n188` 9.4 k -> 10.9 k graphs/s)).  Smaller groups never pay beyond that: the per-workgroup work that does not
+  //    shrink with the rows (prologue, K / V tiles, partial sums) takes over (B = 128, N = 150: 225 us at 16 rows, 253 at 12, 295 at 8).
+  // EGT_BWD_TL = 4 .. 16 overrides, for every De (tests, sweeps: tools/dbg/nrw_tlsweep.sh).
+  if (E.bwd_tl >= 4 && E.bwd_tl <= BWD_TL) P.TL = E.bwd_tl;
+  else if (DE != 8) {
+    const int g = tg > groups ? tg : groups;
+    P.TL = (N + g - 1) / g;
+  } else if (B * groups <= cus) {
+    P.TL = BWD_TL;
+    if (N > 8)
+      for (int tl = 8; tl < BWD_TL; ++tl)
+        if (B * ((N + tl - 1) / tl) <= cus) { P.TL = tl; break; }
+  } else P.TL = (N + groups - 1) / groups;
+  P.NLR = (N + P.TL - 1) / P.TL;
+  P.nwg_bwd = B * P.NLR;
+  P.EP = GG::EP;
+  if (DE == 8 && !ml && !E.no_narrow_bwd) {
+    // De = 8 pair kernel (egt_narrow.hip: k_narrow_bwd, three workgroups per CU), ragged N included.  Measured at config 3
+    // against v4r / the round-2 quad-lane kernel (two waves per SIMD both): bf16 edge tensors 226 vs 314 us, fp32 243 vs 320 us.
+    // At most one workgroup per CU: eight waves share its key tiles (a forced wave count wins).
+    P.bwd = BwdKernel::narrow;
+    P.bwd_nw = E.nrw_bwd_waves == 8 || (E.nrw_bwd_waves != 4 && P.nwg_bwd <= cus && N >= 64) ? 8 : 4;
+    P.bl = {P.nwg_bwd, 64 * P.bwd_nw, egt_narrow_bwd_lds(P.bwd_nw)};
+  } else if (DE <= 16 && !ml) {   // narrow edge channels: V4R_RR rows per iteration, ragged N included
+    constexpr int PWR = V4R_RR * (2 * GG::TILE_FLOATS + 256 + 192);
+    P.bwd = BwdKernel::v4r;
+    P.bl = {P.nwg_bwd, 256,
+            ((size_t)(4 * PWR > BWD_PRO_WS ? 4 * PWR : BWD_PRO_WS) + (size_t)BWD_TL * QD_LD + 3 * GG::TILES * 256 + 3 * 2048 + 4) * 4};
+  } else if (DE >= 32 && !ml && d->dtype != EGT_BF16) {   // LDS-DMA staged e tiles, ragged N included
+    P.bwd = BwdKernel::v5;
+    P.mm = E.bwd_mm;
+    P.bl = {P.nwg_bwd, 256, ((size_t)V5_AREA(DE) + (size_t)BWD_TL * QD_LD + 3 * ((GG::TILES + 1) / 2) * 512 + 4) * 4};   // (+ 4: the parked-partial flags)
+  } else {
+    constexpr int PW = 3 * GG::TILE_FLOATS + 256 + 192;
+    P.bwd = BwdKernel::v4;
+    P.bl = {P.nwg_bwd, 256,   // slabs padded to whole 32-channel steps (bf16 operands)
+            ((size_t)(4 * PW > BWD_PRO_WS ? 4 * PW : BWD_PRO_WS) + (size_t)BWD_TL * QD_LD + 3 * ((GG::TILES + 1) / 2) * 512) * 4};
+  }
+
+  // ---- buffers
+  const size_t rows = (size_t)B * N;
+  const int Dh = d->d * d->H;
+  size_t o = 0;
+  P.v_att = o; o += al(rows * Dh);
+  P.stats = o; o += al(rows * BH * 4);
+  P.qkvp = o; o += al(rows * QKVP);
+  P.pw_sv = o; o += al((size_t)GG::DEP * 16 + 16);
+  P.wfrag_sv = o; o += al(Dh <= 64 ? WFRAG_FLOATS : 0);
+  P.saved_total = o;
+  o = 0;
+  P.dvp = o; o += al(rows * 64);
+  P.dqp_sz = al(rows * 64 * (size_t)groups);
+  P.dkvp_sz = al((size_t)P.nwg_bwd * N * 128);
+  P.dqp = o; o += 2 * P.dqp_sz;
+  P.dkvp = o; o += 2 * P.dkvp_sz;
+  P.common_total = o;
+  o = 0;
+  P.pw = o; o += al((size_t)GG::DEP * 16 + 16);
+  P.epart = o; o += al((size_t)P.nwg_bwd * P.EP);
+  {
+    const int node_wg = B * ((N + NODE_RC - 1) / NODE_RC);
+    const size_t nmax = (size_t)(P.nwg_bwd > node_wg ? P.nwg_bwd : node_wg);
+    P.spart = o; o += al(nmax * (5 * Dh));
+    P.sbo = o; o += al(nmax * Dh);
+  }
+  P.wpart = o; o += al((size_t)egt_node_wgrad_chunks((int)rows, 1) * (Dh * 3 * Dh + Dh * Dh));
+  P.ered = o; o += al(P.EP);
+  P.dqkv = o; o += al(rows * 3 * Dh);
+  P.dhbuf = o; o += al(rows * Dh);
+  P.layer_total = o;
+  return P;
 }
 
-static BlockLayout layout(const egt_block_desc* d) {
-  BlockLayout L{};
-  const size_t rows = (size_t)d->B * d->N;
-  const int Dh = d->d * d->H;
-  const int TILES = (d->De + 15) / 16, DEP = TILES * 16;
-  L.EP = DEP * 16 + 16 + DEP * 16;
-  size_t o = 0;
-  L.v_att = o; o += al(rows * Dh);
-  L.stats = o; o += al(rows * BH * 4);
-  L.qkvp = o; o += al(rows * QKVP);
-  L.pw_sv = o; o += al((size_t)DEP * 16 + 16);
-  L.wfrag_sv = o; o += al(Dh <= 64 ? WFRAG_FLOATS : 0);
-  L.saved_total = o;
-  L.TL = bwd_rows_per_wg(d);
-  L.NLR = (d->N + L.TL - 1) / L.TL;
-  L.nwg_bwd = d->B * L.NLR;
-  o = 0;
-  L.dvp = o; o += al(rows * 64);
-  L.dqp_sz = al(rows * 64 * (size_t)((d->N + 15) / 16));
-  L.dkvp_sz = al((size_t)d->B * L.NLR * d->N * 128);
-  L.dqp = o; o += 2 * L.dqp_sz;
-  L.dkvp = o; o += 2 * L.dkvp_sz;
-  L.common_total = o;
-  o = 0;
-  L.pw = o; o += al((size_t)DEP * 16 + 16);
-  L.epart = o; o += al((size_t)L.nwg_bwd * L.EP);
-  {
-    const size_t nmax = (size_t)(L.nwg_bwd > d->B * ((d->N + NODE_RC - 1) / NODE_RC) ? L.nwg_bwd
-                                                                                        : d->B * ((d->N + NODE_RC - 1) / NODE_RC));
-    L.spart = o; o += al(nmax * (5 * Dh));
-    L.sbo = o; o += al(nmax * Dh);
+#define DISPATCH_BDE(De, CALL)                        \
+  switch (De) {                                       \
+    case 8: { constexpr int DE = 8; CALL; } break;    \
+    case 16: { constexpr int DE = 16; CALL; } break;  \
+    case 32: { constexpr int DE = 32; CALL; } break;  \
+    case 48: { constexpr int DE = 48; CALL; } break;  \
+    default: { constexpr int DE = 64; CALL; } break;  \
   }
-  L.wpart = o; o += al((size_t)egt_node_wgrad_chunks((int)rows, 1) * (Dh * 3 * Dh + Dh * Dh));
-  L.ered = o; o += al(L.EP);
-  L.dqkv = o; o += al(rows * 3 * Dh);
-  L.dhbuf = o; o += al(rows * Dh);
-  L.layer_total = o;
-  return L;
+
+static BlockPlan plan_block(const egt_block_desc* d, bool ml) {
+  DISPATCH_BDE(d->De, return plan_for<DE>(d, ml));
+}
+
+// the call passes a host random-mask buffer the kernels read (else they draw the random mask themselves)
+static bool host_rand_mask(const egt_block_desc* d, const uint8_t* rm) {
+  return rm && (d->flags & EGT_BF_TRAINING) && d->random_mask_prob > 0.0f;
+}
+static bool mask_tensor(const egt_block_desc* d, const uint8_t* rm) {
+  return (d->flags & EGT_BF_ATTN_MASK) || host_rand_mask(d, rm);
 }
 
 // workspace pointers of one layer: `wc` = common region, `wl` = that layer's region
-static void bind_ws(const BlockLayout& L, BlockArgs& a, float* wc, float* wl, int parity = 0) {
-  a.dvp = wc + L.dvp; a.dqp = wc + L.dqp + parity * L.dqp_sz; a.dkvp = wc + L.dkvp + parity * L.dkvp_sz;
-  a.epart = wl + L.epart; a.spart = wl + L.spart; a.sbo = wl + L.sbo; a.wpart = wl + L.wpart;
+static void bind_ws(const BlockPlan& P, BlockArgs& a, float* wc, float* wl, int parity = 0) {
+  a.dvp = wc + P.dvp; a.dqp = wc + P.dqp + parity * P.dqp_sz; a.dkvp = wc + P.dkvp + parity * P.dkvp_sz;
+  a.epart = wl + P.epart; a.spart = wl + P.spart; a.sbo = wl + P.sbo; a.wpart = wl + P.wpart;
   a.spart_n = a.sbo_n = a.B * ((a.N + NODE_RC - 1) / NODE_RC);   // k_node_bwd's workgroups (prologue path overrides)
-  a.ered = wl + L.ered; a.dqkv_sv = wl + L.dqkv;
-  a.TL = L.TL; a.NLR = L.NLR; a.NQP = 1;
+  a.ered = wl + P.ered; a.dqkv_sv = wl + P.dqkv;
+  a.TL = P.TL; a.NLR = P.NLR; a.NQP = 1;
   a.xcd = 1;
 }
 
@@ -204,34 +322,36 @@ static void bind_ws(const BlockLayout& L, BlockArgs& a, float* wc, float* wl, in
 // the node side is fused: the families of DESIGN.md section 4 by name.  For tests and bench lines; NULL when `d` is not covered.
 extern "C" const char* egt_block_bwd_kernel(const egt_block_desc* d) {
   if (block_check(d, false)) return nullptr;
-  const BlockLayout L = layout(d);
-  const bool ml = (d->flags & EGT_BF_ATTN_MASK) != 0, bf = d->dtype == EGT_BF16;
-  if (d->De == 8 && !ml && !block_env().no_narrow_bwd) return "k_narrow_bwd";
-  if (d->De <= 16 && !ml) return "k_block_bwd_v4r";
-  if (d->De >= 32 && !ml && !bf) return "k_block_bwd_v5";
-  return "k_block_bwd_v4";
+  return g_bwd_kernel_name[(int)plan_block(d, mask_tensor(d, nullptr)).bwd];
 }
 
 extern "C" size_t egt_block_saved_bytes(const egt_block_desc* d) {
   if (block_check(d, false)) return 0;
-  return layout(d).saved_total * sizeof(float);
+  return plan_block(d, mask_tensor(d, nullptr)).saved_total * sizeof(float);
 }
 extern "C" size_t egt_block_workspace_bytes(const egt_block_desc* d) {
   if (block_check(d, false)) return 0;
-  const BlockLayout L = layout(d);
-  return (L.common_total + L.layer_total) * sizeof(float);
+  const BlockPlan P = plan_block(d, mask_tensor(d, nullptr));
+  return (P.common_total + P.layer_total) * sizeof(float);
+}
+
+// every pointer of a parameter / gradient table (the gate's two, #2 and #3, only when the block is gated)
+static int check_table(const egt_block_params* t, uint32_t flags, const char* what, int layer = -1) {
+  const void* const* tp = reinterpret_cast<const void* const*>(t);
+  for (int i = 0; i < 14; ++i) {
+    if (tp[i] || (!(flags & EGT_BF_GATE) && (i == 2 || i == 3))) continue;
+    if (layer < 0) EGT_FAIL(EGT_E_NULL, "%s #%d is NULL", what, i);
+    EGT_FAIL(EGT_E_NULL, "layer %d %s #%d is NULL", layer, what, i);
+  }
+  return EGT_OK;
 }
 
 static int fill_block(const egt_block_desc* d, const egt_block_params* p, BlockArgs& a) {
   int rc = block_check(d, true);
   if (rc) return rc;
   if (!p) EGT_FAIL(EGT_E_NULL, "params is NULL");
-  const void* const* pp = reinterpret_cast<const void* const*>(p);
-  const bool gated = (d->flags & EGT_BF_GATE) != 0;
-  for (int i = 0; i < 14; ++i) {
-    if (!gated && (i == 2 || i == 3)) continue;
-    if (!pp[i]) EGT_FAIL(EGT_E_NULL, "block parameter #%d is NULL", i);
-  }
+  rc = check_table(p, d->flags, "block parameter");
+  if (rc) return rc;
   a = BlockArgs{};
   a.B = d->B; a.N = d->N; a.De = d->De; a.DK = d->d; a.Dh = d->d * d->H;
   a.flags = d->flags;
@@ -253,30 +373,30 @@ static int fill_block(const egt_block_desc* d, const egt_block_params* p, BlockA
   return EGT_OK;
 }
 
-static void bind_common(const egt_block_desc* d, BlockArgs& a, const void* h, const void* e,
+static void bind_grads(BlockArgs& a, const egt_block_params* g) {
+  a.g_ne_g = (float*)g->norm_edge_gamma; a.g_ne_b = (float*)g->norm_edge_beta;
+  a.g_Wg = (float*)g->attention_gates_kernel; a.g_bg = (float*)g->attention_gates_bias;
+  a.g_We = (float*)g->dense_edge_b_kernel; a.g_be = (float*)g->dense_edge_b_bias;
+  a.g_nm_g = (float*)g->norm_mha_gamma; a.g_nm_b = (float*)g->norm_mha_beta;
+  a.g_Wqkv = (float*)g->dense_qkv_kernel; a.g_bqkv = (float*)g->dense_qkv_bias;
+  a.g_Wo = (float*)g->dense_mha_kernel; a.g_bo = (float*)g->dense_mha_bias;
+  a.g_Wr = (float*)g->dense_edge_r_kernel; a.g_br = (float*)g->dense_edge_r_bias;
+}
+
+static void bind_common(const egt_block_desc* d, const BlockPlan& P, BlockArgs& a, const void* h, const void* e,
                         const uint8_t* km, const void* M, const uint8_t* rm, float* saved, float* ws) {
-  const BlockLayout L = layout(d);
   a.h = (const float*)h; a.e = (const float*)e; a.km = km;
   a.M = (d->flags & EGT_BF_ATTN_MASK) ? (const float*)M : nullptr;
   a.rm = nullptr; a.rng_rm = 0;
   if ((d->flags & EGT_BF_TRAINING) && d->random_mask_prob > 0.0f) {
     if (rm) a.rm = rm; else a.rng_rm = 1;
   }
-  a.v_att = saved + L.v_att; a.stats = saved + L.stats; a.qkvp = saved + L.qkvp;
-  bind_ws(L, a, ws, ws + L.common_total);
-  a.pw = saved + L.pw_sv;
-  a.wfrag = a.Dh <= 64 ? saved + L.wfrag_sv : nullptr;
+  a.v_att = saved + P.v_att; a.stats = saved + P.stats; a.qkvp = saved + P.qkvp;
+  bind_ws(P, a, ws, ws + P.common_total);
+  a.pw = saved + P.pw_sv;
+  a.wfrag = a.Dh <= 64 ? saved + P.wfrag_sv : nullptr;
   a.prep = 1;
 }
-
-#define DISPATCH_BDE(De, CALL)                        \
-  switch (De) {                                       \
-    case 8: { constexpr int DE = 8; CALL; } break;    \
-    case 16: { constexpr int DE = 16; CALL; } break;  \
-    case 32: { constexpr int DE = 32; CALL; } break;  \
-    case 48: { constexpr int DE = 48; CALL; } break;  \
-    default: { constexpr int DE = 64; CALL; } break;  \
-  }
 
 // The node side inside the pair kernels (fwd_node_epilogue / bwd_node_prologue): H = 8 heads of DK <= 8 channels, i.e. node width
 // Dh = 8 DK <= 64 as a zero-padded 64-wide row.  (Wo / Wqkv reach those kernels through the fragment-major copies the preparation
@@ -285,83 +405,64 @@ static bool node_fused_ok(const BlockArgs& a) {
   return a.Dh == BH * a.DK && a.DK >= 1 && a.DK <= 8 && a.wfrag != nullptr;
 }
 
+// The kernel instances of the planned launches: the run-time choices of the plan as template arguments.
+template <int DE, bool BF>
+static void launch_r4(BlockArgs& a, const BlockPlan& P, hipStream_t st) {
+  if (P.fwd_nw == 4) {
+    if (P.full) egt_launch_planned<k_block_fwd_r4<DE, true, 4, BF>>("k_block_fwd", P.fl, st, a);
+    else egt_launch_planned<k_block_fwd_r4<DE, false, 4, BF>>("k_block_fwd", P.fl, st, a);
+  } else {
+    if (P.full) egt_launch_planned<k_block_fwd_r4<DE, true, 8, BF>>("k_block_fwd", P.fl, st, a);
+    else egt_launch_planned<k_block_fwd_r4<DE, false, 8, BF>>("k_block_fwd", P.fl, st, a);
+  }
+}
+template <int DE, bool BF>   // k_block_fwd<DE, KVL, ML, FULL, BF>: five forms, FULL only for the headline one (K/V in LDS, no mask tensor)
+static void launch_tile_fwd(BlockArgs& a, const BlockPlan& P, hipStream_t st) {
+  if (!P.kvl) {
+    if (P.ml) egt_launch_planned<k_block_fwd<DE, false, true, false, BF>>("k_block_fwd", P.fl, st, a);
+    else egt_launch_planned<k_block_fwd<DE, false, false, false, BF>>("k_block_fwd", P.fl, st, a);
+  } else if (P.ml) egt_launch_planned<k_block_fwd<DE, true, true, false, BF>>("k_block_fwd", P.fl, st, a);
+  else if (P.full) egt_launch_planned<k_block_fwd<DE, true, false, true, BF>>("k_block_fwd", P.fl, st, a);
+  else egt_launch_planned<k_block_fwd<DE, true, false, false, BF>>("k_block_fwd", P.fl, st, a);
+}
+template <int DE>
+static void launch_v5(BlockArgs& a, const BlockPlan& P, hipStream_t st) {
+  if (P.mm == EGT_MM_BF16X3) {
+    if (P.full) egt_launch_planned<k_block_bwd_v5<DE, EGT_MM_BF16X3, false>>("k_block_bwd", P.bl, st, a);
+    else egt_launch_planned<k_block_bwd_v5<DE, EGT_MM_BF16X3, true>>("k_block_bwd", P.bl, st, a);
+  } else {
+    if (P.full) egt_launch_planned<k_block_bwd_v5<DE, EGT_MM_F32, false>>("k_block_bwd", P.bl, st, a);
+    else egt_launch_planned<k_block_bwd_v5<DE, EGT_MM_F32, true>>("k_block_bwd", P.bl, st, a);
+  }
+}
+template <int DE, bool BF>
+static void launch_v4(BlockArgs& a, const BlockPlan& P, hipStream_t st) {
+  if (P.ml) {
+    if (P.full) egt_launch_planned<k_block_bwd_v4<DE, true, BF, false>>("k_block_bwd", P.bl, st, a);
+    else egt_launch_planned<k_block_bwd_v4<DE, true, BF, true>>("k_block_bwd", P.bl, st, a);
+  } else {
+    if (P.full) egt_launch_planned<k_block_bwd_v4<DE, false, BF, false>>("k_block_bwd", P.bl, st, a);
+    else egt_launch_planned<k_block_bwd_v4<DE, false, BF, true>>("k_block_bwd", P.bl, st, a);
+  }
+}
+
 // Forward of one block.  `skip_pre`: qkvp (and pw) of this block were already produced (by the
 // previous block's epilogue / k_edge_prep).  a.epi is the epilogue the caller would like; the
 // value actually used is returned (0 when the geometry is outside the epilogue's cover, in
 // which case k_node_post runs and the next block needs its own k_node_pre).
 template <int DE>
-static int launch_fwd(BlockArgs& a, hipStream_t st, bool skip_pre) {
-  const int lgroups = (a.N + 15) / 16;
+static int launch_fwd(BlockArgs& a, const BlockPlan& P, hipStream_t st, bool skip_pre) {
   if (!skip_pre) egt_node_launch_pre(a, st);   // norm_mha + dense_qkv (packed) [+ edge-weight prep]
-  const size_t lds_tiles = (size_t)8 * Geo<DE>::TILE_FLOATS * 4;
-  const size_t lds_kv = ((size_t)a.N * KV_LD + 16 * QS_LD + a.N) * 4;
-  const bool kvl = lds_tiles + lds_kv <= 80 * 1024 - 512;   // two workgroups per CU keep their K/V in LDS
-  const int epi_req = a.epi;
-  if (!(kvl && node_fused_ok(a))) a.epi = 0;
-  const bool ml = a.M != nullptr || a.rm != nullptr;
+  if (!(P.epi_ok && node_fused_ok(a))) a.epi = 0;
   a.guard = 0;   // (the always-taken phase branches of the kernels only shape hipcc's scheduling regions)
-  // k_block_fwd: 16 query rows per workgroup (four per wave); a launch that leaves workgroup slots empty (two per CU) takes
-  // more, shorter groups -- whole multiples of four rows, so the waves stay balanced -- while they fit one round
-  // (ZINC-100K, B = 128, N = 37: 3 x 16 rows = 384 workgroups -> 4 x 12 rows = 512: the longest wave walks 3 rows instead of 4)
-  a.RGF = 16;
-  {
-    static const int forced = getenv("EGT_FWD_ROWS") ? atoi(getenv("EGT_FWD_ROWS")) : 0;   // 4 .. 16 (tests)
-    const int slots = 2 * egt_device_cus();
-    int g = slots / (a.B > 0 ? a.B : 1);
-    // (at least 8 rows per group -- 4 when even four-row groups leave every CU at most one workgroup: bwd_rows_per_wg has the numbers)
-    const int cap = a.B * ((a.N + 3) / 4) <= slots / 2 ? (a.N + 3) / 4 : (a.N + 7) / 8;
-    if (g > cap) g = cap;
-    if (g > lgroups) a.RGF = (((a.N + g - 1) / g + 3) / 4) * 4;
-    if (forced >= 4 && forced <= 16) a.RGF = forced;
+  a.RGF = P.RGF;
+  switch (P.fwd) {
+    case FwdKernel::narrow: egt_narrow_launch_fwd(a, P.fwd_nw, P.fwd_half, P.fl, st); break;
+    case FwdKernel::r4:
+      if constexpr (DE <= 16) { if (a.bf16) launch_r4<DE, true>(a, P, st); else launch_r4<DE, false>(a, P, st); }
+      break;
+    case FwdKernel::tile: if (a.bf16) launch_tile_fwd<DE, true>(a, P, st); else launch_tile_fwd<DE, false>(a, P, st); break;
   }
-  const dim3 grid(a.B * ((a.N + a.RGF - 1) / a.RGF)), block(256);
-  const size_t lds = lds_tiles + (kvl ? lds_kv : 0);
-#define FWD_VARIANT_T(KVL_, ML_, FULL_, BF_)                                                           \
-  do {                                                                                                 \
-    EGT_MAX_LDS_ONCE(k_block_fwd<DE, KVL_, ML_, FULL_, BF_>);                 \
-    EGT_LAUNCH("k_block_fwd", (k_block_fwd<DE, KVL_, ML_, FULL_, BF_>), grid, block, lds, st, a); \
-  } while (0)
-#define FWD_VARIANT(KVL_, ML_, FULL_)                                                                  \
-  do { if (a.bf16) FWD_VARIANT_T(KVL_, ML_, FULL_, true); else FWD_VARIANT_T(KVL_, ML_, FULL_, false); } while (0)
-  const bool full = (a.N % 16) == 0;
-  // narrow edge channels: four rows per iteration (k_block_fwd_r4).  16-row workgroups when K/V + tiles fit
-  // twice in a CU, else 32-row workgroups (one per CU) as long as K/V fits at all
-  const size_t lds_r4 = (size_t)16 * Geo<DE>::TILE_FLOATS * 4 + lds_kv;
-  const size_t lds_r8 = (size_t)32 * Geo<DE>::TILE_FLOATS * 4 + ((size_t)a.N * KV_LD + 32 * QS_LD + a.N) * 4;
-  const bool r4 = lds_r4 <= 80 * 1024 - 512, r8 = !r4 && lds_r8 <= 156 * 1024;
-  bool narrow = false;
-  if constexpr (DE == 8) {   // VALU pair kernel (egt_narrow.hip): lane = (row, head/channel pair), 4 key quarters per workgroup
-    if (!ml && !block_env().no_narrow_fwd) {
-      narrow = true;
-      if (!node_fused_ok(a)) a.epi = 0; else a.epi = epi_req;
-      egt_narrow_launch_fwd(a, st);
-    }
-  }
-  if constexpr (DE <= 16) {
-    if (!narrow) {   // (wider channels would not fit the four rows' state in 256 VGPRs: not instantiated)
-    narrow = !ml && (r4 || r8);
-    if (narrow) {
-    if (!node_fused_ok(a)) a.epi = 0; else a.epi = epi_req;
-#define R4_LAUNCH_T(FULL_, NW_, BF_)                                                                              \
-  do {                                                                                                            \
-    EGT_MAX_LDS_ONCE(k_block_fwd_r4<DE, FULL_, NW_, BF_>); \
-    EGT_LAUNCH("k_block_fwd", (k_block_fwd_r4<DE, FULL_, NW_, BF_>), dim3(a.B * ((a.N + 4 * NW_ - 1) / (4 * NW_))), dim3(64 * NW_), \
-               NW_ == 4 ? lds_r4 : lds_r8, st, a);                                                                \
-  } while (0)
-#define R4_LAUNCH(FULL_, NW_) do { if (a.bf16) R4_LAUNCH_T(FULL_, NW_, true); else R4_LAUNCH_T(FULL_, NW_, false); } while (0)
-    if (r4) { if (full) R4_LAUNCH(true, 4); else R4_LAUNCH(false, 4); }
-    else { if (full) R4_LAUNCH(true, 8); else R4_LAUNCH(false, 8); }
-#undef R4_LAUNCH
-#undef R4_LAUNCH_T
-    }
-    }
-  }
-  if (narrow) {}
-  else if (full && kvl && !ml) FWD_VARIANT(true, false, true);      // the headline variant
-  else if (kvl) { if (ml) FWD_VARIANT(true, true, false); else FWD_VARIANT(true, false, false); }
-  else { if (ml) FWD_VARIANT(false, true, false); else FWD_VARIANT(false, false, false); }
-#undef FWD_VARIANT_T
-#undef FWD_VARIANT
   if (a.epi == 0) egt_node_launch_post(a, st);  // dense_mha + res_mha
   return a.epi;
 }
@@ -369,93 +470,43 @@ static int launch_fwd(BlockArgs& a, hipStream_t st, bool skip_pre) {
 // Backward of one block.  `top`: first block of the chain (its dV_att / delta come from an own
 // launch); otherwise they were produced by the node kernel of the block above.  `below`: the
 // next block of the chain (NULL at the bottom), whose dV_att / delta this block's node kernel
-// produces.  GEMM-shaped weight gradients and all partial reductions are left to the caller.
+// produces.  GEMM-shaped weight gradients and all partial reductions are left to the caller
+// (the pair kernel writes P.nwg_bwd edge-parameter partials into a.epart).
 template <int DE>
-// Returns the number of edge-parameter partials (workgroups) the pair kernel wrote into a.epart.
-static int launch_bwd(BlockArgs& a, const BlockLayout& L, hipStream_t st, bool top, BlockArgs* below, BlockArgs* above, bool fuse) {
-  using GG = Geo<DE>;
-  int nep = L.nwg_bwd;
-  // node-side prologue inside the pair kernel (see bwd_node_prologue): v4 geometry with Dh = 64
-  const bool ml = a.M != nullptr || a.rm != nullptr;
-  // narrow edge channels without mask tensors run k_block_bwd_v4r, which (with the prologue) also covers ragged N
-  const bool narrow_r = DE <= 16 && !ml;
+static void launch_bwd(BlockArgs& a, const BlockPlan& P, hipStream_t st, bool top, BlockArgs* below, BlockArgs* above, bool fuse) {
   static_assert(DE % 16 == 0 || DE == 8, "edge widths of the pair kernels");
+  // node-side prologue inside the pair kernel (see bwd_node_prologue)
   const bool pro = fuse;   // node_fused_ok() of EVERY block of the chain (every backward kernel and the prologue take N that is not a multiple of 16)
   a.pro = 0;
   if (pro) {
     a.pro = top ? 1 : 2;
-    a.sbo_n = L.nwg_bwd;
+    a.sbo_n = P.nwg_bwd;
     if (!top) {
       a.up_h = above->h; a.up_nm_g = above->nm_g; a.up_Wqkv = above->Wqkv; a.up_wfrag = above->wfrag; a.up_dh_out = above->dh_out;
       a.up_dqp = above->dqp; a.up_dkvp = above->dkvp; a.up_dqkv_sv = above->dqkv_sv; a.up_spart = above->spart;
-      above->spart_n = L.nwg_bwd;
+      above->spart_n = P.nwg_bwd;
     }
     if (a.prep) egt_node_launch_prep(&a, 1, st);   // single-block call: the LN-folded edge weights of this layer
   } else if (top) {
     egt_node_launch_bwd(a, &a, false, st);  // dV_att (packed), delta, dbo sums [+ edge-weight prep]
   }
-  constexpr int PW = 3 * GG::TILE_FLOATS + 256 + 192;
-  const bool full = (a.N % 16) == 0;
-  {
-    {
-      const size_t lds_v4 = ((size_t)(4 * PW > BWD_PRO_WS ? 4 * PW : BWD_PRO_WS) + (size_t)BWD_TL * QD_LD + 3 * ((GG::TILES + 1) / 2) * 512) * 4;   // slabs padded to whole 32-channel steps (bf16 operands)
-      a.NQP = (a.N + 15) / 16;
-      a.guard = 0;   // (the always-taken phase branches of the kernels only shape hipcc's scheduling regions)
-#define V4_VARIANT_R(ML_, BF_, RAG_)                                                                       \
-  do {                                                                                                 \
-    EGT_MAX_LDS_ONCE(k_block_bwd_v4<DE, ML_, BF_, RAG_>);                      \
-    EGT_LAUNCH("k_block_bwd", (k_block_bwd_v4<DE, ML_, BF_, RAG_>), dim3(L.nwg_bwd), dim3(256), lds_v4, st, a); \
-  } while (0)
-#define V4_VARIANT(ML_, BF_) do { if (full) V4_VARIANT_R(ML_, BF_, false); else V4_VARIANT_R(ML_, BF_, true); } while (0)
-      if constexpr (DE == 8) {
-        // De = 8 pair kernel (egt_narrow.hip: k_narrow_bwd_m, three workgroups per CU), ragged N included.  Measured at config 3
-        // against v4r / the round-2 quad-lane kernel (two waves per SIMD both): bf16 edge tensors 226 vs 314 us, fp32 243 vs 320 us
-        if (narrow_r && !block_env().no_narrow_bwd) {
-          egt_narrow_launch_bwd(a, L.nwg_bwd, st);
-          goto pair_done;
-        }
-      }
+  a.NQP = (a.N + 15) / 16;
+  a.guard = 0;   // (the always-taken phase branches of the kernels only shape hipcc's scheduling regions)
+  switch (P.bwd) {
+    case BwdKernel::narrow: egt_narrow_launch_bwd(a, P.bwd_nw, P.bl, st); break;
+    case BwdKernel::v4r:
       if constexpr (DE <= 16) {
-        if (narrow_r) {   // narrow edge channels: R rows per iteration, ragged N included
-          constexpr int RR = 2;   // rows per iteration: four spill (the rows' carried state + prefetch exceed 256 VGPRs)
-          constexpr int PWR = RR * (2 * GG::TILE_FLOATS + 256 + 192);
-          const size_t lds_r = ((size_t)(4 * PWR > BWD_PRO_WS ? 4 * PWR : BWD_PRO_WS) + (size_t)BWD_TL * QD_LD + 3 * GG::TILES * 256 + 3 * 2048 + 4) * 4;
-          if (a.bf16) {
-            EGT_MAX_LDS_ONCE(k_block_bwd_v4r<DE, true, RR>);
-            EGT_LAUNCH("k_block_bwd", (k_block_bwd_v4r<DE, true, RR>), dim3(L.nwg_bwd), dim3(256), lds_r, st, a);
-          } else {
-            EGT_MAX_LDS_ONCE(k_block_bwd_v4r<DE, false, RR>);
-            EGT_LAUNCH("k_block_bwd", (k_block_bwd_v4r<DE, false, RR>), dim3(L.nwg_bwd), dim3(256), lds_r, st, a);
-          }
-          goto pair_done;
-        }
+        if (a.bf16) egt_launch_planned<k_block_bwd_v4r<DE, true, V4R_RR>>("k_block_bwd", P.bl, st, a);
+        else egt_launch_planned<k_block_bwd_v4r<DE, false, V4R_RR>>("k_block_bwd", P.bl, st, a);
       }
-      if constexpr (DE >= 32) {
-        if (!ml && !a.bf16) {   // LDS-DMA staged e tiles (k_block_bwd_v5), ragged N included
-          const bool x3 = block_env().bwd_mm == EGT_MM_BF16X3;
-          const size_t lds_v5 = ((size_t)V5_AREA(DE) + (size_t)BWD_TL * QD_LD + 3 * ((GG::TILES + 1) / 2) * 512 + 4) * 4;   // (+ 4: the parked-partial flags)
-#define V5_LAUNCH(MM_, RAG_)                                                                                 \
-  do {                                                                                                       \
-    EGT_MAX_LDS_ONCE(k_block_bwd_v5<DE, MM_, RAG_>);                                                         \
-    EGT_LAUNCH("k_block_bwd", (k_block_bwd_v5<DE, MM_, RAG_>), dim3(L.nwg_bwd), dim3(256), lds_v5, st, a);   \
-  } while (0)
-          if (full) { if (x3) V5_LAUNCH(EGT_MM_BF16X3, false); else V5_LAUNCH(0, false); }
-          else { if (x3) V5_LAUNCH(EGT_MM_BF16X3, true); else V5_LAUNCH(0, true); }
-#undef V5_LAUNCH
-          goto pair_done;
-        }
-      }
-      if (a.bf16) { if (ml) V4_VARIANT(true, true); else V4_VARIANT(false, true); }
-      else if (ml) V4_VARIANT(true, false);
-      else V4_VARIANT(false, false);
-#undef V4_VARIANT
-#undef V4_VARIANT_R
-    }
+      break;
+    case BwdKernel::v5:
+      if constexpr (DE >= 32) launch_v5<DE>(a, P, st);
+      break;
+    case BwdKernel::v4: if (a.bf16) launch_v4<DE, true>(a, P, st); else launch_v4<DE, false>(a, P, st); break;
   }
-pair_done:
   if (!pro) egt_node_launch_bwd(a, below, true, st);   // dQKV -> dh, bias/LN sums; dV_att + delta of the block below
   else if (!below) egt_node_launch_bwd(a, nullptr, true, st);   // bottom of the chain: only dQKV -> dh is left
-  return nep;
 }
 
 
@@ -469,10 +520,11 @@ extern "C" int egt_block_fwd(const egt_block_desc* desc, const egt_block_params*
   if (!h || !e || !h_out || !e_out || !saved || !workspace)
     EGT_FAIL(EGT_E_NULL, "h/e/h_out/e_out/saved/workspace is NULL");
   if ((desc->flags & EGT_BF_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
-  bind_common(desc, a, h, e, key_mask, attn_mask, rand_mask, (float*)saved, (float*)workspace);
+  const BlockPlan P = plan_block(desc, mask_tensor(desc, rand_mask));
+  bind_common(desc, P, a, h, e, key_mask, attn_mask, rand_mask, (float*)saved, (float*)workspace);
   a.h_out = (float*)h_out; a.e_out = (float*)e_out;
   a.epi = 1;
-  DISPATCH_BDE(desc->De, launch_fwd<DE>(a, (hipStream_t)stream, false));
+  DISPATCH_BDE(desc->De, launch_fwd<DE>(a, P, (hipStream_t)stream, false));
   EGT_HIP_LAUNCH_CHECK("egt_block_fwd");
   return EGT_OK;
 }
@@ -490,30 +542,17 @@ extern "C" int egt_block_bwd(const egt_block_desc* desc, const egt_block_params*
   if ((desc->flags & EGT_BF_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
   // every layer's dh' is read again after dh was written (deferred dWo contraction): no in-place dh
   if (d_h == d_h_out) EGT_FAIL(EGT_E_FLAGS, "d_h must not alias d_h_out (d_e may alias d_e_out)");
-  const bool gated = (desc->flags & EGT_BF_GATE) != 0;
-  {
-    const void* const* gp = reinterpret_cast<const void* const*>(grads);
-    for (int i = 0; i < 14; ++i) {
-      if (!gated && (i == 2 || i == 3)) continue;
-      if (!gp[i]) EGT_FAIL(EGT_E_NULL, "gradient pointer #%d is NULL", i);
-    }
-  }
-  bind_common(desc, a, h, e, key_mask, attn_mask, rand_mask, (float*)saved, (float*)workspace);
+  rc = check_table(grads, desc->flags, "gradient pointer");
+  if (rc) return rc;
+  const BlockPlan P = plan_block(desc, mask_tensor(desc, rand_mask));
+  bind_common(desc, P, a, h, e, key_mask, attn_mask, rand_mask, (float*)saved, (float*)workspace);
   a.prep = 0;   // prepared by the forward, kept in `saved`
   a.dh_out = (const float*)d_h_out; a.de_out = (const float*)d_e_out;
   a.dh = (float*)d_h; a.de = (float*)d_e;
-  a.g_ne_g = (float*)grads->norm_edge_gamma; a.g_ne_b = (float*)grads->norm_edge_beta;
-  a.g_Wg = (float*)grads->attention_gates_kernel; a.g_bg = (float*)grads->attention_gates_bias;
-  a.g_We = (float*)grads->dense_edge_b_kernel; a.g_be = (float*)grads->dense_edge_b_bias;
-  a.g_nm_g = (float*)grads->norm_mha_gamma; a.g_nm_b = (float*)grads->norm_mha_beta;
-  a.g_Wqkv = (float*)grads->dense_qkv_kernel; a.g_bqkv = (float*)grads->dense_qkv_bias;
-  a.g_Wo = (float*)grads->dense_mha_kernel; a.g_bo = (float*)grads->dense_mha_bias;
-  a.g_Wr = (float*)grads->dense_edge_r_kernel; a.g_br = (float*)grads->dense_edge_r_bias;
-  const BlockLayout L = layout(desc);
-  int nep = L.nwg_bwd;
-  DISPATCH_BDE(desc->De, nep = launch_bwd<DE>(a, L, (hipStream_t)stream, true, nullptr, nullptr, node_fused_ok(a)));
+  bind_grads(a, grads);
+  DISPATCH_BDE(desc->De, launch_bwd<DE>(a, P, (hipStream_t)stream, true, nullptr, nullptr, node_fused_ok(a)));
   egt_node_launch_wgrads(&a, 1, (hipStream_t)stream);
-  egt_node_launch_reduce(&a, 1, nep, L.EP, (hipStream_t)stream);  // partial sums + edge param grads
+  egt_node_launch_reduce(&a, 1, P.nwg_bwd, P.EP, (hipStream_t)stream);  // partial sums + edge param grads
   EGT_HIP_LAUNCH_CHECK("egt_block_bwd");
   return EGT_OK;
 }
@@ -533,39 +572,37 @@ struct StackLayout {
   size_t h_sz, e_sz;
 };
 
-static StackLayout stack_layout(const egt_block_desc* d, int layers) {
+static StackLayout stack_layout(const egt_block_desc* d, const BlockPlan& P, int layers) {
   StackLayout S{};
-  const BlockLayout L = layout(d);
   S.h_sz = al((size_t)d->B * d->N * d->d * d->H);
   S.e_sz = al((size_t)d->B * d->N * d->N * d->De / (d->dtype == EGT_BF16 ? 2 : 1));   // in floats
   size_t o = 0;
   S.h_act = o; o += S.h_sz * (size_t)(layers > 1 ? layers - 1 : 0);
   S.e_act = o; o += S.e_sz * (size_t)(layers > 1 ? layers - 1 : 0);
-  S.blk = o; o += L.saved_total * (size_t)layers;
+  S.blk = o; o += P.saved_total * (size_t)layers;
   S.saved_total = o;
-  S.ws_total = L.common_total + L.layer_total * (size_t)layers;
+  S.ws_total = P.common_total + P.layer_total * (size_t)layers;
   return S;
 }
 
 extern "C" size_t egt_stack_saved_bytes(const egt_block_desc* d, int32_t layers) {
   if (block_check(d, false) || layers < 1) return 0;
-  return stack_layout(d, layers).saved_total * sizeof(float);
+  return stack_layout(d, plan_block(d, mask_tensor(d, nullptr)), layers).saved_total * sizeof(float);
 }
 extern "C" size_t egt_stack_workspace_bytes(const egt_block_desc* d, int32_t layers) {
   if (block_check(d, false) || layers < 1) return 0;
-  return stack_layout(d, layers).ws_total * sizeof(float);
+  return stack_layout(d, plan_block(d, mask_tensor(d, nullptr)), layers).ws_total * sizeof(float);
 }
 
-static void bind_layer(const egt_block_desc* d, const StackLayout& S, const BlockLayout& L, int l,
-                       BlockArgs& a, float* saved, float* ws) {
-  float* bs = saved + S.blk + L.saved_total * (size_t)l;
-  a.v_att = bs + L.v_att; a.stats = bs + L.stats; a.qkvp = bs + L.qkvp;
+// the saved / workspace regions of layer l (bind_common bound layer 0's)
+static void bind_layer(const StackLayout& S, const BlockPlan& P, int l, BlockArgs& a, float* saved, float* ws) {
+  float* bs = saved + S.blk + P.saved_total * (size_t)l;
+  a.v_att = bs + P.v_att; a.stats = bs + P.stats; a.qkvp = bs + P.qkvp;
   // per-layer workspace: block l's epilogue must not race block l+1's prepared weights, and the
   // deferred reductions / weight gradients need every layer's partials and dQKV rows at the end
-  bind_ws(L, a, ws, ws + L.common_total + L.layer_total * (size_t)l, l & 1);
-  a.pw = bs + L.pw_sv;
-  a.wfrag = a.Dh <= 64 ? bs + L.wfrag_sv : nullptr;
-  (void)d;
+  bind_ws(P, a, ws, ws + P.common_total + P.layer_total * (size_t)l, l & 1);
+  a.pw = bs + P.pw_sv;
+  a.wfrag = a.Dh <= 64 ? bs + P.wfrag_sv : nullptr;
 }
 
 extern "C" int egt_stack_fwd(const egt_block_desc* desc, int32_t layers, const egt_block_params* params,
@@ -578,8 +615,8 @@ extern "C" int egt_stack_fwd(const egt_block_desc* desc, int32_t layers, const e
   if (block_check(desc, true)) return block_check(desc, true);
   if ((desc->flags & EGT_BF_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
   if (layers > 64) EGT_FAIL(EGT_E_SHAPE, "at most 64 layers per stack call");
-  const StackLayout S = stack_layout(desc, layers);
-  const BlockLayout L = layout(desc);
+  const BlockPlan P = plan_block(desc, mask_tensor(desc, nullptr));
+  const StackLayout S = stack_layout(desc, P, layers);
   float* sv = (float*)saved;
   BlockArgs as[64];
   for (int l = 0; l < layers; ++l) {
@@ -590,8 +627,8 @@ extern "C" int egt_stack_fwd(const egt_block_desc* desc, int32_t layers, const e
     if (rc) return rc;
     const float* hin = l == 0 ? (const float*)h : sv + S.h_act + S.h_sz * (size_t)(l - 1);
     const float* ein = l == 0 ? (const float*)e : sv + S.e_act + S.e_sz * (size_t)(l - 1);
-    bind_common(&dl, a, hin, ein, key_mask, attn_mask, nullptr, sv, (float*)workspace);
-    bind_layer(&dl, S, L, l, a, sv, (float*)workspace);
+    bind_common(&dl, P, a, hin, ein, key_mask, attn_mask, nullptr, sv, (float*)workspace);
+    bind_layer(S, P, l, a, sv, (float*)workspace);
     a.h_out = l == layers - 1 ? (float*)h_out : sv + S.h_act + S.h_sz * (size_t)l;
     a.e_out = l == layers - 1 ? (float*)e_out : sv + S.e_act + S.e_sz * (size_t)l;
   }
@@ -612,7 +649,7 @@ extern "C" int egt_stack_fwd(const egt_block_desc* desc, int32_t layers, const e
       a.nx_nm_g = nx.nm_g; a.nx_nm_b = nx.nm_b; a.nx_Wqkv = nx.Wqkv; a.nx_wfrag = nx.wfrag; a.nx_bqkv = nx.bqkv;
       a.nx_qkvp = nx.qkvp;
     }
-    DISPATCH_BDE(desc->De, prev_epi = launch_fwd<DE>(a, (hipStream_t)stream, prev_epi == 2));
+    DISPATCH_BDE(desc->De, prev_epi = launch_fwd<DE>(a, P, (hipStream_t)stream, prev_epi == 2));
   }
   EGT_HIP_LAUNCH_CHECK("egt_stack_fwd");
   return EGT_OK;
@@ -630,10 +667,9 @@ extern "C" int egt_stack_bwd(const egt_block_desc* desc, int32_t layers, const e
   if (block_check(desc, true)) return block_check(desc, true);
   if ((desc->flags & EGT_BF_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
   if (d_h == d_h_out) EGT_FAIL(EGT_E_FLAGS, "d_h must not alias d_h_out (d_e may alias d_e_out)");
-  const StackLayout S = stack_layout(desc, layers);
-  const BlockLayout L = layout(desc);
+  const BlockPlan P = plan_block(desc, mask_tensor(desc, nullptr));
+  const StackLayout S = stack_layout(desc, P, layers);
   float* sv = (float*)saved;
-  const bool gated = (desc->flags & EGT_BF_GATE) != 0;
   BlockArgs as[64];
   for (int l = layers - 1; l >= 0; --l) {
     egt_block_desc dl = *desc;
@@ -641,43 +677,30 @@ extern "C" int egt_stack_bwd(const egt_block_desc* desc, int32_t layers, const e
     BlockArgs& a = as[l];
     int rc = fill_block(&dl, params + l, a);
     if (rc) return rc;
-    const egt_block_params* g = grads + l;
-    {
-      const void* const* gp = reinterpret_cast<const void* const*>(g);
-      for (int i = 0; i < 14; ++i) {
-        if (!gated && (i == 2 || i == 3)) continue;
-        if (!gp[i]) EGT_FAIL(EGT_E_NULL, "layer %d gradient pointer #%d is NULL", l, i);
-      }
-    }
+    rc = check_table(grads + l, desc->flags, "gradient pointer", l);
+    if (rc) return rc;
     const float* hin = l == 0 ? (const float*)h : sv + S.h_act + S.h_sz * (size_t)(l - 1);
     const float* ein = l == 0 ? (const float*)e : sv + S.e_act + S.e_sz * (size_t)(l - 1);
-    bind_common(&dl, a, hin, ein, key_mask, attn_mask, nullptr, sv, (float*)workspace);
-    bind_layer(&dl, S, L, l, a, sv, (float*)workspace);
+    bind_common(&dl, P, a, hin, ein, key_mask, attn_mask, nullptr, sv, (float*)workspace);
+    bind_layer(S, P, l, a, sv, (float*)workspace);
     // d_e flows in place below the top layer; every layer keeps its own dh (the deferred dWo
     // contraction reads dh' of each layer at the end)
-    auto dhbuf = [&](int ll) { return (float*)workspace + L.common_total + L.layer_total * (size_t)ll + L.dhbuf; };
+    auto dhbuf = [&](int ll) { return (float*)workspace + P.common_total + P.layer_total * (size_t)ll + P.dhbuf; };
     a.dh_out = l == layers - 1 ? (const float*)d_h_out : (const float*)dhbuf(l + 1);
     a.de_out = l == layers - 1 ? (const float*)d_e_out : (const float*)d_e;
     a.dh = l == 0 ? (float*)d_h : dhbuf(l);
     a.de = (float*)d_e;
-    a.g_ne_g = (float*)g->norm_edge_gamma; a.g_ne_b = (float*)g->norm_edge_beta;
-    a.g_Wg = (float*)g->attention_gates_kernel; a.g_bg = (float*)g->attention_gates_bias;
-    a.g_We = (float*)g->dense_edge_b_kernel; a.g_be = (float*)g->dense_edge_b_bias;
-    a.g_nm_g = (float*)g->norm_mha_gamma; a.g_nm_b = (float*)g->norm_mha_beta;
-    a.g_Wqkv = (float*)g->dense_qkv_kernel; a.g_bqkv = (float*)g->dense_qkv_bias;
-    a.g_Wo = (float*)g->dense_mha_kernel; a.g_bo = (float*)g->dense_mha_bias;
-    a.g_Wr = (float*)g->dense_edge_r_kernel; a.g_br = (float*)g->dense_edge_r_bias;
+    bind_grads(a, grads + l);
   }
   bool fuse = true;
   for (int l = 0; l < layers; ++l) fuse = fuse && node_fused_ok(as[l]);
-  int nep = L.nwg_bwd;
   for (int l = layers - 1; l >= 0; --l) {
     as[l].prep = 0;   // the LN-folded edge weights were prepared by the forward and live in `saved`
-    DISPATCH_BDE(desc->De, nep = launch_bwd<DE>(as[l], L, (hipStream_t)stream, l == layers - 1, l > 0 ? &as[l - 1] : nullptr,
-                                                   l + 1 < layers ? &as[l + 1] : nullptr, fuse));
+    DISPATCH_BDE(desc->De, launch_bwd<DE>(as[l], P, (hipStream_t)stream, l == layers - 1, l > 0 ? &as[l - 1] : nullptr,
+                                          l + 1 < layers ? &as[l + 1] : nullptr, fuse));
   }
   egt_node_launch_wgrads(as, layers, (hipStream_t)stream);
-  egt_node_launch_reduce(as, layers, nep, L.EP, (hipStream_t)stream);
+  egt_node_launch_reduce(as, layers, P.nwg_bwd, P.EP, (hipStream_t)stream);
   EGT_HIP_LAUNCH_CHECK("egt_stack_bwd");
   return EGT_OK;
 }

@@ -447,35 +447,32 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? NRW_FWDM_OCC : 1) k_narrow_
 }
 static_assert(16 * QS_LD <= NRW_FWD_AREA(4), "the epilogue's staging rows fit the merge area");
 
-// a.epi must already hold the epilogue the geometry allows (launch_fwd decides)
+// The host side below only launches: waves, half rows, grid and LDS come from plan_block (egt_block.hip), and a.epi already
+// holds the epilogue the geometry allows.  Kernel instances: bf16 or fp32 edge tensors, the gated + clipped block as
+// straight-line code (NRW_F_GATED | NRW_F_CLIP) or both read at run time (NRW_F_RUNTIME).
+static bool nrw_feat_full(const BlockArgs& a) { return (a.flags & EGT_BF_GATE) && (a.flags & EGT_BF_CLIP); }
+
+size_t egt_narrow_fwd_lds(int nw) { return ((size_t)(nw == 8 ? NRW_FWD_AREA(8) : NRW_FWD_AREA(4)) + 16 * QS_LD + 80) * 4; }
+
 #ifdef NRW_TIMING
 static const char* const g_nf_names[] = {"constants + first requests", "key loop", "sync + merge", "node-side epilogue"};
 static NrwTimer g_nf{"k_narrow_fwd", g_nf_names, 4};
 #endif
-void egt_narrow_launch_fwd(BlockArgs& a, hipStream_t st) {
-  const int grid16 = a.B * ((a.N + 15) / 16);
-  static const int nw_forced = getenv("EGT_NRW_FWD_WAVES") ? atoi(getenv("EGT_NRW_FWD_WAVES")) : 0;   // 4 | 8 (tests, A/B)
-  static const int hr_forced = getenv("EGT_NRW_FWD_HALF") ? atoi(getenv("EGT_NRW_FWD_HALF")) : -1;    // 0 | 1 (tests, A/B)
-  const bool w8 = nw_forced == 8 || (nw_forced != 4 && grid16 <= egt_device_cus() && a.N >= 64);   // one workgroup per CU at most: eight key ranges
-  const bool hr = w8 && (hr_forced == 1 || (hr_forced != 0 && 2 * grid16 <= egt_device_cus()));       // ... per two CUs: eight-row workgroups
-  const dim3 grid(hr ? a.B * ((a.N + 7) / 8) : grid16);
-  const dim3 block(w8 ? 512 : 256);
+template <bool BF, int FEAT>
+static void nrw_fwd(BlockArgs& a, int nw, bool half, const EgtLaunch& s, hipStream_t st) {
+  if (half) egt_launch_planned<k_narrow_fwd<BF, FEAT, 8, true>>("k_block_fwd", s, st, a);
+  else if (nw == 8) egt_launch_planned<k_narrow_fwd<BF, FEAT, 8, false>>("k_block_fwd", s, st, a);
+  else egt_launch_planned<k_narrow_fwd<BF, FEAT, 4, false>>("k_block_fwd", s, st, a);
+}
+void egt_narrow_launch_fwd(BlockArgs& a, int nw, bool half, const EgtLaunch& s, hipStream_t st) {
 #ifdef NRW_TIMING
   { static bool reg = false; if (!reg) { reg = true; atexit([] { g_nf.report(); }); } }
-  a.dbg = g_nf.attach(grid.x);
+  a.dbg = g_nf.attach(s.grid);
 #endif
-  const size_t lds = ((size_t)(w8 ? NRW_FWD_AREA(8) : NRW_FWD_AREA(4)) + 16 * QS_LD + 80) * 4;
-  const int full = NRW_F_GATED | NRW_F_CLIP;
-  const int feat = ((a.flags & EGT_BF_GATE) ? NRW_F_GATED : 0) | ((a.flags & EGT_BF_CLIP) ? NRW_F_CLIP : 0);
-#define NRW_FWD(BF_, FEAT_) do { \
-    if (hr) { EGT_MAX_LDS_ONCE(k_narrow_fwd<BF_, FEAT_, 8, true>); EGT_LAUNCH("k_block_fwd", (k_narrow_fwd<BF_, FEAT_, 8, true>), grid, block, lds, st, a); } \
-    else if (w8) { EGT_MAX_LDS_ONCE(k_narrow_fwd<BF_, FEAT_, 8, false>); EGT_LAUNCH("k_block_fwd", (k_narrow_fwd<BF_, FEAT_, 8, false>), grid, block, lds, st, a); } \
-    else { EGT_LAUNCH("k_block_fwd", (k_narrow_fwd<BF_, FEAT_, 4, false>), grid, block, lds, st, a); } } while (0)
-  if (a.bf16) { if (feat == full) NRW_FWD(true, NRW_F_GATED | NRW_F_CLIP); else NRW_FWD(true, NRW_F_RUNTIME); }
-  else { if (feat == full) NRW_FWD(false, NRW_F_GATED | NRW_F_CLIP); else NRW_FWD(false, NRW_F_RUNTIME); }
-#undef NRW_FWD
+  if (a.bf16) { if (nrw_feat_full(a)) nrw_fwd<true, NRW_F_GATED | NRW_F_CLIP>(a, nw, half, s, st); else nrw_fwd<true, NRW_F_RUNTIME>(a, nw, half, s, st); }
+  else { if (nrw_feat_full(a)) nrw_fwd<false, NRW_F_GATED | NRW_F_CLIP>(a, nw, half, s, st); else nrw_fwd<false, NRW_F_RUNTIME>(a, nw, half, s, st); }
 #ifdef NRW_TIMING
-  g_nf.collect(grid.x, st);
+  g_nf.collect(s.grid, st);
 #endif
 }
 
@@ -831,22 +828,20 @@ static void nrw_timing_report() {
 }
 #endif
 
-void egt_narrow_launch_bwd(BlockArgs& a, int nwg, hipStream_t st) {
-  const int full = NRW_F_GATED | NRW_F_CLIP;
-  const int feat = ((a.flags & EGT_BF_GATE) ? NRW_F_GATED : 0) | ((a.flags & EGT_BF_CLIP) ? NRW_F_CLIP : 0);
+size_t egt_narrow_bwd_lds(int nw) {   // four waves: 47 KB, three workgroups per CU
   constexpr int AREA4 = 4 * NRW_M_WAVE > BWD_PRO_WS ? 4 * NRW_M_WAVE : BWD_PRO_WS, AREA8 = 8 * NRW_M_WAVE;
   static_assert(AREA8 >= BWD_PRO_WS, "tile areas of eight waves cover the prologue's scratch");
-  static const int nw_forced = getenv("EGT_NRW_BWD_WAVES") ? atoi(getenv("EGT_NRW_BWD_WAVES")) : 0;   // 4 | 8 (tests, A/B)
-  const bool w8 = nw_forced == 8 || (nw_forced != 4 && nwg <= egt_device_cus() && a.N >= 64);   // at most one workgroup per CU: eight waves share its key tiles
-  const size_t lds = ((size_t)(w8 ? AREA8 : AREA4) + BWD_TL * QD_LD + 8) * 4;   // four waves: 47 KB, three workgroups per CU
-#define NRW_BWD(BF_, FEAT_)                                                                     \
-  do {                                                                                            \
-    if (w8) { EGT_MAX_LDS_ONCE(k_narrow_bwd<BF_, FEAT_, 8>);                                       \
-              EGT_LAUNCH("k_block_bwd", (k_narrow_bwd<BF_, FEAT_, 8>), dim3(nwg), dim3(512), lds, st, a); } \
-    else { EGT_MAX_LDS_ONCE(k_narrow_bwd<BF_, FEAT_, 4>);                                          \
-           EGT_LAUNCH("k_block_bwd", (k_narrow_bwd<BF_, FEAT_, 4>), dim3(nwg), dim3(256), lds, st, a); } \
-  } while (0)
+  return ((size_t)(nw == 8 ? AREA8 : AREA4) + BWD_TL * QD_LD + 8) * 4;
+}
+
+template <bool BF, int FEAT>
+static void nrw_bwd(BlockArgs& a, int nw, const EgtLaunch& s, hipStream_t st) {
+  if (nw == 8) egt_launch_planned<k_narrow_bwd<BF, FEAT, 8>>("k_block_bwd", s, st, a);
+  else egt_launch_planned<k_narrow_bwd<BF, FEAT, 4>>("k_block_bwd", s, st, a);
+}
+void egt_narrow_launch_bwd(BlockArgs& a, int nw, const EgtLaunch& s, hipStream_t st) {
 #ifdef NRW_TIMING
+  const int nwg = s.grid;
   if (g_nt_n < nwg) {
     if (g_nt_dev) (void)hipFree(g_nt_dev);
     (void)hipMalloc(&g_nt_dev, (size_t)nwg * 32 * sizeof(unsigned));
@@ -858,9 +853,8 @@ void egt_narrow_launch_bwd(BlockArgs& a, int nwg, hipStream_t st) {
   }
   a.dbg = g_nt_dev; a.dbg2 = g_nt_dev2;
 #endif
-  if (a.bf16) { if (feat == full) NRW_BWD(true, NRW_F_GATED | NRW_F_CLIP); else NRW_BWD(true, NRW_F_RUNTIME); }
-  else { if (feat == full) NRW_BWD(false, NRW_F_GATED | NRW_F_CLIP); else NRW_BWD(false, NRW_F_RUNTIME); }
-#undef NRW_BWD
+  if (a.bf16) { if (nrw_feat_full(a)) nrw_bwd<true, NRW_F_GATED | NRW_F_CLIP>(a, nw, s, st); else nrw_bwd<true, NRW_F_RUNTIME>(a, nw, s, st); }
+  else { if (nrw_feat_full(a)) nrw_bwd<false, NRW_F_GATED | NRW_F_CLIP>(a, nw, s, st); else nrw_bwd<false, NRW_F_RUNTIME>(a, nw, s, st); }
 #ifdef NRW_TIMING
   (void)hipStreamSynchronize(st);
   if (++g_nt_launch > 20) {

@@ -1,5 +1,5 @@
 """GPU tests at BASELINE.json's full sizes: the launch bench.py times (B = 128, N = 64, Dh = De = 64: 512 workgroups,
-XCD remap, `bwd_rows_per_wg` at B = 128, in-kernel RNG, the Ly = 10 one-call stack) against the fp64 oracle -- one block
+XCD remap, `plan_block`'s rows per workgroup at B = 128, in-kernel RNG, the Ly = 10 one-call stack) against the fp64 oracle -- one block
 on all 128 graphs (every output, every input and parameter gradient), the training-mode stack on sampled graphs (graphs
 are independent: the oracle runs on those alone, with the `rng_ref` replica of the in-kernel masks) -- plus
 size-independent properties (fused == composed, linearity of the backward in the upstream gradients,

@@ -50,14 +50,14 @@ def test_random_de8_stacks_under_every_switch():
 @pytest.mark.parametrize("waves", ["4", "8"])
 def test_forward_waves_per_workgroup(waves):
     """k_narrow_fwd splits a workgroup's key range over 4 waves, or over 8 when the launch has at most one workgroup per CU
-    (egt_narrow_launch_fwd).  The tiny test batches take 8 by default from N = 64 up; both sizes are forced here for every
+    (egt_block.hip: plan_block).  The tiny test batches take 8 by default from N = 64 up; both sizes are forced here for every
     geometry (8 waves on N = 37 leaves waves with an empty key range)."""
     _run({"EGT_NRW_FWD_WAVES": waves, "EGT_NRW_FWD_HALF": "0"})
 
 
 def test_forward_half_row_workgroups():
     """With eight waves and a 16-row grid of at most half the CUs, k_narrow_fwd takes EIGHT query rows per workgroup (lanes p and p ^ 8
-    share a row and split a step's key pair; egt_narrow_launch_fwd).  The tiny test batches take that form by default from N = 64 up
+    share a row and split a step's key pair; plan_block).  The tiny test batches take that form by default from N = 64 up
     (the run above switches it off); here it is forced together with the eight waves for every geometry, N = 37 and ragged N included."""
     _run({"EGT_NRW_FWD_WAVES": "8", "EGT_NRW_FWD_HALF": "1"})
 
@@ -65,7 +65,7 @@ def test_forward_half_row_workgroups():
 @pytest.mark.parametrize("waves", ["4", "8"])
 def test_backward_waves_per_workgroup(waves):
     """k_narrow_bwd splits a workgroup's key tiles over 4 waves, or over 8 when the launch has at most one workgroup per CU
-    (egt_narrow_launch_bwd; the node-side prologue stays four waves' work).  The tiny test batches take 8 by default from N = 64
+    (plan_block; the node-side prologue stays four waves' work).  The tiny test batches take 8 by default from N = 64
     up; both sizes are forced here for every geometry (balanced (tile, row) ranges with parked partials, waves without a key tile)."""
     _run({"EGT_NRW_BWD_WAVES": waves})
     _run({"EGT_NRW_BWD_WAVES": waves, "EGT_BWD_TL": "16"})
@@ -73,7 +73,7 @@ def test_backward_waves_per_workgroup(waves):
 
 @pytest.mark.parametrize("rows", ["16", "4"])
 def test_backward_rows_per_workgroup(rows):
-    """The De = 8 backward takes 16, 8 or 4 query rows per workgroup (egt_block.hip: bwd_rows_per_wg; small batches get 8 so
+    """The De = 8 backward takes 16, 8 or 4 query rows per workgroup (egt_block.hip: plan_block; small batches get 8 so
     that every CU has work).  The test batches are tiny, so the default selection already runs 8 rows per workgroup
     everywhere; the other two sizes are forced here, for the De = 8 kernel and for the MFMA-tile fallback."""
     _run({"EGT_BWD_TL": rows})
@@ -88,7 +88,7 @@ WIDE = ["tests/test_block_gpu.py::test_stack_call_vs_oracle", "tests/test_block_
 @pytest.mark.parametrize("rows", ["16", "5"])
 def test_backward_rows_per_workgroup_every_edge_width(rows):
     """Every backward pair kernel takes 4 .. 16 query rows per workgroup; the tiny test batches select 8-row groups by default
-    (bwd_rows_per_wg: a launch that leaves workgroup slots empty takes shorter groups), so the 16-row geometry of the full-size
+    (plan_block: a launch that leaves workgroup slots empty takes shorter groups), so the 16-row geometry of the full-size
     launches (the headline's) and an odd size are forced here for the De >= 16 kernels too."""
     env = dict(os.environ, EGT_BWD_TL=rows)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -101,7 +101,7 @@ def test_backward_rows_per_workgroup_every_edge_width(rows):
 
 @pytest.mark.parametrize("rows", ["16", "13", "4"])
 def test_forward_rows_per_workgroup(rows):
-    """k_block_fwd takes 4 .. 16 query rows per workgroup (launch_fwd: the tiny test batches select shorter groups than the
+    """k_block_fwd takes 4 .. 16 query rows per workgroup (plan_block: the tiny test batches select shorter groups than the
     full-size launches, which take 16); forced here: the headline's 16, an odd size, and one row per wave."""
     env = dict(os.environ, EGT_FWD_ROWS=rows)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
