@@ -43,7 +43,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 #define KEY_OFF (-3.0e38f)   // additive term of key slots past N (below every masked logit, above -inf)
 
 // packed operand arrays, each B*H*NP*d floats, in workspace order: Q rows (pre-scaled), K rows, V^T (what the forward
-// reads), V rows, K^T, dO rows (the backward's); then stats2 [B,H,NP,4] and dA [B,H,NP,NP].  A forward launched with
+// reads), V rows, K^T, dO rows (the backward's); then stats2 and dA (the layout: plan_attn).  A forward launched with
 // EGT_ATTN_WS_SHARED packs the five q/k/v arrays once and the backward, given the same workspace, adds only dO.
 enum { PK_QH = 0, PK_KH, PK_VT, PK_FWD_COUNT, PK_VH = PK_FWD_COUNT, PK_KT, PK_OH, PK_COUNT };
 enum { PACK_Q = 1, PACK_KH = 2, PACK_KT = 4, PACK_VT = 8, PACK_VH = 16, PACK_O = 32 };
@@ -1078,17 +1078,77 @@ extern "C" int egt_attn_mfma_supported(const egt_attn_desc* d, int need_a_tild) 
 
 static int np_of(int N) { return (N + 15) & ~15; }
 
-// both directions: six packed arrays, the per-row constants and the dA tiles; forward alone: its three arrays
-extern "C" size_t egt_attn_mfma_workspace_bytes(const egt_attn_desc* d) {
-  if (!egt_attn_mfma_supported(d, 0)) return 0;
-  const size_t NP = np_of(d->N), arr = (size_t)d->B * AH * NP * d->d;
-  return (PK_COUNT * arr + (size_t)d->B * AH * NP * 4 + (size_t)d->B * AH * NP * NP) * sizeof(float);
+// Every launch and workspace decision of this file is made in ONE place, plan_attn, once per C-ABI call: the size queries return
+// its totals, fill / pair_fill check the descriptor and bind the call's pointers, the entry points bind the workspace and launch
+// from it.  Workspace, in floats: the packed operand arrays (PK_* order, B*H*NP*d each; a forward alone needs only the first
+// PK_FWD_COUNT), stats2 [B,H,NP,4], dA [B,H,NP,NP]; the pair operator appends its parameter-gradient partials, nwg + 1 of each
+// kind (the last one: the reduced image), the 1 KB store dump (PairArgs::dump) and the prepared weight table (PairArgs::wprep).
+struct AttnPlan {
+  int NP;
+  size_t stats2, dA, fwd_total, total;   // fwd_total: egt_attn_mfma_fwd's workspace (all of it with EGT_ATTN_WS_SHARED)
+  int nwg;                               // pair: workgroups of k_pair_fwd / k_pair_bwd = partials of each kind
+  size_t part_proj, red_proj, part_upd, red_upd, dump, wprep;
+  int pack_fwd, pack_bwd;                // PACK_* bits of each direction's k_attn_pack: a shared workspace packs q / k / v once
+  int var_fwd, var_bwd;                  // attention: 1 / 2 the straight-line instances (see Feat), 0 the run-time-switched one; pair: V
+  bool full;                             // pair: N is a multiple of 16 (k_pair_* FULL)
+  EgtLaunch pack, fwd, bwd_kv, bwd_q, prep, pair_fwd, pair_bwd;
+};
+
+static AttnPlan plan_attn(int B, int N, int D, int reserved, bool pair, int var_fwd, int var_bwd) {
+  constexpr int DE = 32, HS = (64 / 16) * 256;   // the pair operator's geometry (d = 64)
+  constexpr size_t PSZ1 = DE * 16 + 16, PSZ2 = AH * DE + DE, WTABLE = (3 * (DE / 16) + 1) * 64 * 4;
+  const bool shared = (reserved & EGT_ATTN_WS_SHARED) != 0;
+  AttnPlan P{};
+  const int NP = P.NP = np_of(N);
+  const size_t arr = (size_t)B * AH * NP * D;
+  P.stats2 = PK_COUNT * arr;
+  P.dA = P.stats2 + (size_t)B * AH * NP * 4;
+  P.total = P.dA + (size_t)B * AH * NP * NP;
+  P.fwd_total = shared ? P.total : PK_FWD_COUNT * arr;
+  P.nwg = B * (NP / 16);
+  if (pair) {
+    P.part_proj = P.total;
+    P.red_proj = P.part_proj + (size_t)P.nwg * PSZ1;
+    P.part_upd = P.red_proj + PSZ1;
+    P.red_upd = P.part_upd + (size_t)P.nwg * PSZ2;
+    P.dump = P.red_upd + PSZ2;
+    P.wprep = P.dump + 256;
+    P.total = P.wprep + WTABLE;
+  }
+  P.pack_fwd = PACK_Q | PACK_KH | PACK_VT | (shared ? (PACK_KT | PACK_VH) : 0);
+  P.pack_bwd = PACK_O | (shared ? 0 : (PACK_Q | PACK_KH | PACK_KT | PACK_VH));
+  P.var_fwd = var_fwd; P.var_bwd = var_bwd;
+  P.full = N % 16 == 0;
+  const size_t keys = (size_t)((NP + 16 + 3) & ~3);   // the forwards' two per-key LDS tables
+  P.pack = {B * (NP / 16), 512, (size_t)AH * (16 * (D == 16 ? 16 : 80) + 4) * 4};
+  P.fwd = {B * ((NP / 16 + FQ - 1) / FQ) * 2, 512, OPS_BYTES + (2 * keys + (size_t)(2 * (var_fwd ? 2 : 3) + 2) * FQ * 4 * PT_PL) * 4};
+  P.bwd_kv = {B * ((NP / 16 + BK - 1) / BK) * 2, 512, OPS_BYTES + ((size_t)2 * 4 * 64 + (size_t)(2 * 3 + 4) * BK * 4 * PT_PL) * 4};
+  P.bwd_q = {B * AH * ((NP / 16 + QW_TILES - 1) / QW_TILES), 512, (size_t)QW_STAGES * (2 * (D / 16) + 2 * QW_TILES) * 1024};
+  P.prep = {1, 64, 0};
+  P.pair_fwd = {P.nwg, 64 * PR_WAVES, ((size_t)2 * AH * HS + 2 * keys + (size_t)6 * AH * PT_PL + 16 + DE) * sizeof(float)};
+  P.pair_bwd = {P.nwg, 64 * PR_WAVES, ((size_t)2 * 4 * 2 * HS + (size_t)2 * 3 * AH * PT_PL + (size_t)2 * AH * 64 + (size_t)4 * 2 * 16 * DE +
+                                       (size_t)3 * (DE / 16) * 64 * 4 + 64 * 4 + 4 * 2 * 4 * 16) * sizeof(float)};
+  return P;
+}
+// The attention's instances depend on which optional pointers the call passes: a = its bound arguments (nullptr: a size query).
+// EGT_ATTN_GENERIC (tests) forces the run-time-switched instance; it is read at the first launch.
+static AttnPlan plan_attn(const egt_attn_desc* d, const AttnMfmaArgs* a = nullptr) {
+  if (!a) return plan_attn(d->B, d->N, d->d, d->reserved, false, 0, 0);
+  static const bool generic = getenv("EGT_ATTN_GENERIC") != nullptr;
+  const bool main_cfg = !generic && a->E && (a->flags & EGT_F_GATE_INPUT) && a->G && !a->M && a->km && (a->flags & EGT_F_CLIP) && !a->rm;
+  const int v = main_cfg ? (a->rng_rm ? 2 : 1) : 0;
+  return plan_attn(d->B, d->N, d->d, d->reserved, false, v, (a->d_h_ext && a->d_E && a->d_G) ? v : 0);
+}
+static AttnPlan plan_attn(const egt_block_desc* d) {   // the pair operator: V = 2 with the in-kernel random mask
+  const int v = ((d->flags & EGT_BF_TRAINING) && d->random_mask_prob > 0.0f) ? 2 : 1;
+  return plan_attn(d->B, d->N, d->d, d->reserved, true, v, v);
 }
 
+extern "C" size_t egt_attn_mfma_workspace_bytes(const egt_attn_desc* d) {
+  return egt_attn_mfma_supported(d, 0) ? plan_attn(d).total * sizeof(float) : 0;
+}
 extern "C" size_t egt_attn_mfma_fwd_workspace_bytes(const egt_attn_desc* d) {
-  if (!egt_attn_mfma_supported(d, 0)) return 0;
-  if (d->reserved & EGT_ATTN_WS_SHARED) return egt_attn_mfma_workspace_bytes(d);   // the forward then packs the backward's arrays too
-  return (size_t)PK_FWD_COUNT * d->B * AH * np_of(d->N) * d->d * sizeof(float);
+  return egt_attn_mfma_supported(d, 0) ? plan_attn(d).fwd_total * sizeof(float) : 0;
 }
 
 static int fill(const egt_attn_desc* desc, const void* qkv, const void* E, const void* G,
@@ -1119,36 +1179,12 @@ static int fill(const egt_attn_desc* desc, const void* qkv, const void* E, const
 }
 
 template <int D>
-static void launch_pack(const AttnMfmaArgs& a, hipStream_t st) {
-  const size_t lds = (size_t)AH * (16 * (D == 16 ? 16 : 80) + 4) * 4;
-  EGT_MAX_LDS_ONCE(k_attn_pack<D>);
-  EGT_LAUNCH("k_attn_pack", k_attn_pack<D>, dim3(a.B * (a.NP / 16)), dim3(512), lds, st, a);
-}
-
-// 1 / 2: the straight-line instances (see Feat), 0: the run-time-switched one (EGT_ATTN_GENERIC forces it: tests)
-static int variant_of(const AttnMfmaArgs& a, bool bwd) {
-  static const bool generic = getenv("EGT_ATTN_GENERIC") != nullptr;
-  const bool main_cfg = a.E && (a.flags & EGT_F_GATE_INPUT) && a.G && !a.M && a.km && (a.flags & EGT_F_CLIP) && !a.rm &&
-                        (!bwd || (a.d_h_ext && a.d_E && a.d_G));
-  if (!main_cfg || generic) return 0;
-  return a.rng_rm ? 2 : 1;
-}
-
-template <int D, int V>
-static void launch_fwd_v(const AttnMfmaArgs& a, hipStream_t st) {
-  const size_t ts = (size_t)FQ * 4 * PT_PL;
-  const size_t lds = OPS_BYTES + ((size_t)2 * ((a.NP + 16 + 3) & ~3) + (size_t)(2 * (V ? 2 : 3) + 2) * ts) * 4;
-  const int lgroups = (a.NP / 16 + FQ - 1) / FQ;
-  EGT_MAX_LDS_ONCE(k_attn_mfma_fwd<D, V>);
-  EGT_LAUNCH("k_attn_mfma_fwd", (k_attn_mfma_fwd<D, V>), dim3(a.B * lgroups * 2), dim3(512), lds, st, a);
-}
-template <int D>
-static void launch_fwd(const AttnMfmaArgs& a, hipStream_t st) {
-  launch_pack<D>(a, st);
-  switch (variant_of(a, false)) {
-    case 1: launch_fwd_v<D, 1>(a, st); break;
-    case 2: launch_fwd_v<D, 2>(a, st); break;
-    default: launch_fwd_v<D, 0>(a, st); break;
+static void launch_fwd(const AttnPlan& P, const AttnMfmaArgs& a, hipStream_t st) {
+  egt_launch_planned<k_attn_pack<D>>("k_attn_pack", P.pack, st, a);
+  switch (P.var_fwd) {
+    case 1: egt_launch_planned<k_attn_mfma_fwd<D, 1>>("k_attn_mfma_fwd", P.fwd, st, a); break;
+    case 2: egt_launch_planned<k_attn_mfma_fwd<D, 2>>("k_attn_mfma_fwd", P.fwd, st, a); break;
+    default: egt_launch_planned<k_attn_mfma_fwd<D, 0>>("k_attn_mfma_fwd", P.fwd, st, a); break;
   }
 }
 
@@ -1161,39 +1197,26 @@ extern "C" int egt_attn_mfma_fwd(const egt_attn_desc* desc, const void* qkv, con
   if (rc) return rc;
   if (!v_att || !h_hat || !rowstats) EGT_FAIL(EGT_E_NULL, "v_att/h_hat/rowstats is NULL");
   a.v_att = (float*)v_att; a.h_hat = (float*)h_hat; a.rowstats = (float*)rowstats;
-  // EGT_ATTN_WS_SHARED: the workspace is egt_attn_mfma_workspace_bytes() large and will be handed to the backward:
-  // pack the backward's q / k / v arrays too, once
-  a.pack_what = PACK_Q | PACK_KH | PACK_VT | ((desc->reserved & EGT_ATTN_WS_SHARED) ? (PACK_KT | PACK_VH) : 0);
+  const AttnPlan P = plan_attn(desc, &a);
+  a.pack_what = P.pack_fwd;
   switch (desc->d) {
-    case 16: launch_fwd<16>(a, (hipStream_t)stream); break;
-    case 32: launch_fwd<32>(a, (hipStream_t)stream); break;
-    default: launch_fwd<64>(a, (hipStream_t)stream); break;
+    case 16: launch_fwd<16>(P, a, (hipStream_t)stream); break;
+    case 32: launch_fwd<32>(P, a, (hipStream_t)stream); break;
+    default: launch_fwd<64>(P, a, (hipStream_t)stream); break;
   }
   EGT_HIP_LAUNCH_CHECK("egt_attn_mfma_fwd");
   return EGT_OK;
 }
 
-template <int D, int V>
-static void launch_bwd_kv_v(const AttnMfmaArgs& a, hipStream_t st) {
-  const size_t lds = OPS_BYTES + ((size_t)2 * 4 * 64 + (size_t)(2 * 3 + 4) * BK * 4 * PT_PL) * 4;
-  const int mgroups = (a.NP / 16 + BK - 1) / BK;
-  EGT_MAX_LDS_ONCE(k_attn_mfma_bwd_kv<D, V>);
-  EGT_LAUNCH("k_attn_mfma_bwd_kv", (k_attn_mfma_bwd_kv<D, V>), dim3(a.B * mgroups * 2), dim3(512), lds, st, a);
-}
 template <int D>
-static void launch_bwd(const AttnMfmaArgs& a, hipStream_t st) {
-  launch_pack<D>(a, st);   // (also the per-row constants, delta = sum_k dO*O among them)
-  switch (variant_of(a, true)) {
-    case 1: launch_bwd_kv_v<D, 1>(a, st); break;
-    case 2: launch_bwd_kv_v<D, 2>(a, st); break;
-    default: launch_bwd_kv_v<D, 0>(a, st); break;
+static void launch_bwd(const AttnPlan& P, const AttnMfmaArgs& a, hipStream_t st) {
+  egt_launch_planned<k_attn_pack<D>>("k_attn_pack", P.pack, st, a);   // (also the per-row constants, delta = sum_k dO*O among them)
+  switch (P.var_bwd) {
+    case 1: egt_launch_planned<k_attn_mfma_bwd_kv<D, 1>>("k_attn_mfma_bwd_kv", P.bwd_kv, st, a); break;
+    case 2: egt_launch_planned<k_attn_mfma_bwd_kv<D, 2>>("k_attn_mfma_bwd_kv", P.bwd_kv, st, a); break;
+    default: egt_launch_planned<k_attn_mfma_bwd_kv<D, 0>>("k_attn_mfma_bwd_kv", P.bwd_kv, st, a); break;
   }
-  {
-    const int qgroups = (a.NP / 16 + QW_TILES - 1) / QW_TILES;
-    const size_t lds = (size_t)QW_STAGES * (2 * (D / 16) + 2 * QW_TILES) * 1024;
-    EGT_MAX_LDS_ONCE(k_attn_mfma_bwd_q<D>);
-    EGT_LAUNCH("k_attn_mfma_bwd_q", (k_attn_mfma_bwd_q<D>), dim3(a.B * AH * qgroups), dim3(512), lds, st, a);
-  }
+  egt_launch_planned<k_attn_mfma_bwd_q<D>>("k_attn_mfma_bwd_q", P.bwd_q, st, a);
 }
 
 // rowstats is read AND written (slot 3 receives delta); workspace: egt_attn_mfma_workspace_bytes()
@@ -1213,14 +1236,13 @@ extern "C" int egt_attn_mfma_bwd(const egt_attn_desc* desc, const void* qkv, con
   a.d_qkv = (float*)d_qkv;
   a.d_E = (desc->flags & EGT_F_EDGE_INPUT) ? (float*)d_E : nullptr;
   a.d_G = (desc->flags & EGT_F_GATE_INPUT) ? (float*)d_G : nullptr;
-  const size_t arr = (size_t)a.B * AH * a.NP * a.d;
-  a.stats2 = a.pk + (size_t)PK_COUNT * arr;
-  a.ws_dA = a.stats2 + (size_t)a.B * AH * a.NP * 4;
-  a.pack_what = PACK_O | ((desc->reserved & EGT_ATTN_WS_SHARED) ? 0 : (PACK_Q | PACK_KH | PACK_KT | PACK_VH));
+  const AttnPlan P = plan_attn(desc, &a);
+  a.stats2 = a.pk + P.stats2; a.ws_dA = a.pk + P.dA;
+  a.pack_what = P.pack_bwd;
   switch (desc->d) {
-    case 16: launch_bwd<16>(a, (hipStream_t)stream); break;
-    case 32: launch_bwd<32>(a, (hipStream_t)stream); break;
-    default: launch_bwd<64>(a, (hipStream_t)stream); break;
+    case 16: launch_bwd<16>(P, a, (hipStream_t)stream); break;
+    case 32: launch_bwd<32>(P, a, (hipStream_t)stream); break;
+    default: launch_bwd<64>(P, a, (hipStream_t)stream); break;
   }
   EGT_HIP_LAUNCH_CHECK("egt_attn_mfma_bwd");
   return EGT_OK;
@@ -1237,28 +1259,21 @@ extern "C" int egt_pair_supported(const egt_block_desc* d) {
   return 1;
 }
 
-static size_t pair_partial_floats(const egt_block_desc* d) {   // per-workgroup partials + one reduced image each
-  const size_t nwg = (size_t)d->B * (np_of(d->N) / 16);
-  return (nwg + 1) * ((size_t)d->De * 16 + 16) + (nwg + 1) * ((size_t)AH * d->De + d->De) + 256   // + the 1 KB store dump (PairArgs::dump)
-         + (3 * ((size_t)d->De / 16) + 1) * 64 * 4;                                                      // + the prepared weight table (PairArgs::wprep)
-}
-
-// packed operand arrays (all six), row constants, dA tiles, parameter-gradient partials.  The forward writes the q / k / v arrays;
-// with desc->reserved & EGT_ATTN_WS_SHARED the caller hands the SAME untouched workspace to egt_pair_bwd, which then adds only dO
+// the attention's workspace plus the pair operator's tail (plan_attn).  The forward writes the q / k / v arrays; with
+// desc->reserved & EGT_ATTN_WS_SHARED the caller hands the SAME untouched workspace to egt_pair_bwd, which then adds only dO
 extern "C" size_t egt_pair_workspace_bytes(const egt_block_desc* d) {
-  if (!egt_pair_supported(d)) return 0;
-  const size_t NP = np_of(d->N), arr = (size_t)d->B * AH * NP * d->d;
-  return (PK_COUNT * arr + (size_t)d->B * AH * NP * 4 + (size_t)d->B * AH * NP * NP + pair_partial_floats(d)) * sizeof(float);
+  return egt_pair_supported(d) ? plan_attn(d).total * sizeof(float) : 0;
 }
 
 static int pair_fill(const egt_block_desc* d, const egt_block_params* P, const void* qkv, const void* e, const uint8_t* key_mask,
-                     void* workspace, AttnMfmaArgs& a, PairArgs& pa) {
+                     void* workspace, AttnPlan& plan, AttnMfmaArgs& a, PairArgs& pa) {
   if (!egt_pair_supported(d)) EGT_FAIL(EGT_E_SHAPE, "configuration not covered by the fused pair operator (d = 64, De = 32, H = 8, gated, fp32)");
   if (!P || !qkv || !e || !workspace) EGT_FAIL(EGT_E_NULL, "params/qkv/e/workspace is NULL");
   if (!P->norm_edge_gamma || !P->norm_edge_beta || !P->attention_gates_kernel || !P->attention_gates_bias || !P->dense_edge_b_kernel ||
       !P->dense_edge_b_bias || !P->dense_edge_r_kernel || !P->dense_edge_r_bias)
     EGT_FAIL(EGT_E_NULL, "an edge-side parameter pointer is NULL");
   if (d->reserved & ~EGT_ATTN_WS_SHARED) EGT_FAIL(EGT_E_FLAGS, "egt_block_desc.reserved: unknown bits 0x%x", d->reserved);
+  plan = plan_attn(d);
   a = AttnMfmaArgs{};
   a.B = d->B; a.N = d->N; a.NP = np_of(d->N); a.d = d->d;
   a.flags = EGT_F_EDGE_INPUT | EGT_F_GATE_INPUT | ((d->flags & EGT_BF_CLIP) ? EGT_F_CLIP : 0);
@@ -1276,36 +1291,28 @@ static int pair_fill(const egt_block_desc* d, const egt_block_params* P, const v
   pa.Wg = (const float*)P->attention_gates_kernel; pa.bg = (const float*)P->attention_gates_bias;
   pa.We = (const float*)P->dense_edge_b_kernel; pa.be = (const float*)P->dense_edge_b_bias;
   pa.Wr = (const float*)P->dense_edge_r_kernel; pa.br = (const float*)P->dense_edge_r_bias;
-  {   // the last 1 KB of the workspace
-    const size_t NP = np_of(d->N), arr = (size_t)d->B * AH * NP * d->d;
-    const size_t wt = (3 * ((size_t)d->De / 16) + 1) * 64 * 4;
-    pa.wprep = (float*)workspace + PK_COUNT * arr + (size_t)d->B * AH * NP * 4 + (size_t)d->B * AH * NP * NP + pair_partial_floats(d) - wt;
-    pa.dump = pa.wprep - 256;
-  }
+  pa.wprep = a.pk + plan.wprep; pa.dump = a.pk + plan.dump;
   return EGT_OK;
 }
 
 extern "C" int egt_pair_fwd(const egt_block_desc* desc, const egt_block_params* params, const void* qkv, const void* e,
                             const uint8_t* key_mask, void* v_att, void* e_out, void* rowstats, void* workspace, void* stream) {
-  AttnMfmaArgs a; PairArgs pa;
-  int rc = pair_fill(desc, params, qkv, e, key_mask, workspace, a, pa);
+  AttnPlan P; AttnMfmaArgs a; PairArgs pa;
+  int rc = pair_fill(desc, params, qkv, e, key_mask, workspace, P, a, pa);
   if (rc) return rc;
   if (!v_att || !e_out || !rowstats) EGT_FAIL(EGT_E_NULL, "v_att/e_out/rowstats is NULL");
   a.v_att = (float*)v_att; a.rowstats = (float*)rowstats;
   pa.e_out = (float*)e_out;
-  a.pack_what = PACK_Q | PACK_KH | PACK_VT | ((desc->reserved & EGT_ATTN_WS_SHARED) ? (PACK_KT | PACK_VH) : 0);
+  a.pack_what = P.pack_fwd;
   hipStream_t st = (hipStream_t)stream;
-  launch_pack<64>(a, st);
-  constexpr int D = 64, DE = 32, HS = (D / 16) * 256;
-  EGT_LAUNCH("k_pair_prep", k_pair_prep<DE>, dim3(1), dim3(64), 0, st, pa);
-  const size_t lds = ((size_t)2 * AH * HS + 2 * (size_t)((a.NP + 16 + 3) & ~3) + (size_t)6 * AH * PT_PL + 16 + DE) * sizeof(float);
-  const int grid = a.B * (a.NP / 16);
-#define PAIR_FWD(V_, F_) do { EGT_MAX_LDS_ONCE(k_pair_fwd<D, DE, V_, F_>); \
-    EGT_LAUNCH("k_pair_fwd", (k_pair_fwd<D, DE, V_, F_>), dim3(grid), dim3(64 * PR_WAVES), lds, st, a, pa); } while (0)
-  const bool full = a.N % 16 == 0;
-  if (a.rng_rm) { if (full) PAIR_FWD(2, true); else PAIR_FWD(2, false); }
-  else { if (full) PAIR_FWD(1, true); else PAIR_FWD(1, false); }
-#undef PAIR_FWD
+  egt_launch_planned<k_attn_pack<64>>("k_attn_pack", P.pack, st, a);
+  EGT_LAUNCH("k_pair_prep", k_pair_prep<32>, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, pa);
+  switch (2 * P.var_fwd + P.full) {   // V, FULL
+    case 5: egt_launch_planned<k_pair_fwd<64, 32, 2, true>>("k_pair_fwd", P.pair_fwd, st, a, pa); break;
+    case 4: egt_launch_planned<k_pair_fwd<64, 32, 2, false>>("k_pair_fwd", P.pair_fwd, st, a, pa); break;
+    case 3: egt_launch_planned<k_pair_fwd<64, 32, 1, true>>("k_pair_fwd", P.pair_fwd, st, a, pa); break;
+    default: egt_launch_planned<k_pair_fwd<64, 32, 1, false>>("k_pair_fwd", P.pair_fwd, st, a, pa); break;
+  }
   EGT_HIP_LAUNCH_CHECK("egt_pair_fwd");
   return EGT_OK;
 }
@@ -1314,8 +1321,8 @@ extern "C" int egt_pair_fwd(const egt_block_desc* desc, const egt_block_params* 
 extern "C" int egt_pair_bwd(const egt_block_desc* desc, const egt_block_params* params, const void* qkv, const void* e,
                             const uint8_t* key_mask, const void* v_att, void* rowstats, const void* d_v_att, const void* d_e_out,
                             void* d_qkv, void* d_e, const egt_block_params* grads, void* workspace, void* stream) {
-  AttnMfmaArgs a; PairArgs pa;
-  int rc = pair_fill(desc, params, qkv, e, key_mask, workspace, a, pa);
+  AttnPlan P; AttnMfmaArgs a; PairArgs pa;
+  int rc = pair_fill(desc, params, qkv, e, key_mask, workspace, P, a, pa);
   if (rc) return rc;
   if (!v_att || !rowstats || !d_v_att || !d_e_out || !d_qkv || !d_e || !grads) EGT_FAIL(EGT_E_NULL, "v_att/rowstats/d_v_att/d_e_out/d_qkv/d_e/grads is NULL");
   if (!grads->norm_edge_gamma || !grads->norm_edge_beta || !grads->attention_gates_kernel || !grads->attention_gates_bias ||
@@ -1324,34 +1331,21 @@ extern "C" int egt_pair_bwd(const egt_block_desc* desc, const egt_block_params* 
   a.v_att_in = (const float*)v_att; a.rowstats = (float*)rowstats;
   a.d_v_att = (const float*)d_v_att; a.d_qkv = (float*)d_qkv;
   pa.d_e_out = (const float*)d_e_out; pa.d_e = (float*)d_e;
-  const size_t arr = (size_t)a.B * AH * a.NP * a.d;
-  a.stats2 = a.pk + (size_t)PK_COUNT * arr;
-  a.ws_dA = a.stats2 + (size_t)a.B * AH * a.NP * 4;
-  constexpr int D = 64, DE = 32, HS = (D / 16) * 256;
-  constexpr int PSZ1 = DE * 16 + 16, PSZ2 = AH * DE + DE;
-  const int nwg = a.B * (a.NP / 16);
-  pa.part_proj = a.ws_dA + (size_t)a.B * AH * a.NP * a.NP;
-  pa.part_upd = pa.part_proj + (size_t)(nwg + 1) * PSZ1;
-  a.pack_what = PACK_O | ((desc->reserved & EGT_ATTN_WS_SHARED) ? 0 : (PACK_Q | PACK_KH | PACK_KT | PACK_VH));
+  a.stats2 = a.pk + P.stats2; a.ws_dA = a.pk + P.dA;
+  pa.part_proj = a.pk + P.part_proj; pa.part_upd = a.pk + P.part_upd;
+  a.pack_what = P.pack_bwd;
   hipStream_t st = (hipStream_t)stream;
-  launch_pack<64>(a, st);   // (also the per-row constants, delta = sum_k dO*O among them)
+  egt_launch_planned<k_attn_pack<64>>("k_attn_pack", P.pack, st, a);   // (also the per-row constants, delta = sum_k dO*O among them)
   if (!(desc->reserved & EGT_ATTN_WS_SHARED))   // (a shared workspace still holds the forward's table: same parameter values by contract)
-    EGT_LAUNCH("k_pair_prep", k_pair_prep<DE>, dim3(1), dim3(64), 0, st, pa);
-  const size_t lds = ((size_t)2 * 4 * 2 * HS + (size_t)2 * 3 * AH * PT_PL + (size_t)2 * AH * 64 + (size_t)4 * 2 * 16 * DE + (size_t)3 * (DE / 16) * 64 * 4 + 64 * 4 + 4 * 2 * 4 * 16) * sizeof(float);
-#define PAIR_BWD(V_, F_) do { EGT_MAX_LDS_ONCE(k_pair_bwd<D, DE, V_, F_>); \
-    EGT_LAUNCH("k_pair_bwd", (k_pair_bwd<D, DE, V_, F_>), dim3(nwg), dim3(64 * PR_WAVES), lds, st, a, pa); } while (0)
-  const bool full = a.N % 16 == 0;
-  if (a.rng_rm) { if (full) PAIR_BWD(2, true); else PAIR_BWD(2, false); }
-  else { if (full) PAIR_BWD(1, true); else PAIR_BWD(1, false); }
-#undef PAIR_BWD
-  {
-    const int qgroups = (a.NP / 16 + QW_TILES - 1) / QW_TILES;
-    const size_t ldsq = (size_t)QW_STAGES * (2 * (D / 16) + 2 * QW_TILES) * 1024;
-    EGT_MAX_LDS_ONCE(k_attn_mfma_bwd_q<D>);
-    EGT_LAUNCH("k_attn_mfma_bwd_q", (k_attn_mfma_bwd_q<D>), dim3(a.B * AH * qgroups), dim3(512), ldsq, st, a);
+    EGT_LAUNCH("k_pair_prep", k_pair_prep<32>, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, pa);
+  switch (2 * P.var_bwd + P.full) {   // V, FULL
+    case 5: egt_launch_planned<k_pair_bwd<64, 32, 2, true>>("k_pair_bwd", P.pair_bwd, st, a, pa); break;
+    case 4: egt_launch_planned<k_pair_bwd<64, 32, 2, false>>("k_pair_bwd", P.pair_bwd, st, a, pa); break;
+    case 3: egt_launch_planned<k_pair_bwd<64, 32, 1, true>>("k_pair_bwd", P.pair_bwd, st, a, pa); break;
+    default: egt_launch_planned<k_pair_bwd<64, 32, 1, false>>("k_pair_bwd", P.pair_bwd, st, a, pa); break;
   }
-  egt_edge_finish_param_grads(DE, pa.gamma, pa.beta, pa.Wg, pa.We, pa.part_proj, pa.part_upd, nwg,
-                              pa.part_proj + (size_t)nwg * PSZ1, pa.part_upd + (size_t)nwg * PSZ2,
+  egt_launch_planned<k_attn_mfma_bwd_q<64>>("k_attn_mfma_bwd_q", P.bwd_q, st, a);
+  egt_edge_finish_param_grads(32, pa.gamma, pa.beta, pa.Wg, pa.We, pa.part_proj, pa.part_upd, P.nwg, a.pk + P.red_proj, a.pk + P.red_upd,
                               (float*)grads->norm_edge_gamma, (float*)grads->norm_edge_beta, (float*)grads->attention_gates_kernel,
                               (float*)grads->attention_gates_bias, (float*)grads->dense_edge_b_kernel, (float*)grads->dense_edge_b_bias,
                               (float*)grads->dense_edge_r_kernel, (float*)grads->dense_edge_r_bias, st);

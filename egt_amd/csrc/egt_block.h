@@ -94,14 +94,6 @@ int egt_device_cus();   // compute units of the current device (egt_block.hip)
 #define WFRAG_FWQ 20480
 #define WFRAG_FLOATS 32768
 
-// One launch of a pair kernel in the shape egt_block.hip's plan_block chose: workgroups, threads per workgroup, dynamic LDS bytes.
-struct EgtLaunch { int grid, block; size_t lds; };
-template <void (*K)(BlockArgs)>   // K's dynamic-LDS limit is raised once
-static inline void egt_launch_planned(const char* name, const EgtLaunch& s, hipStream_t st, BlockArgs& a) {
-  EGT_MAX_LDS_ONCE(K);
-  EGT_LAUNCH(name, K, dim3(s.grid), dim3(s.block), s.lds, st, a);
-}
-
 // De = 8 VALU pair kernels (egt_narrow.hip), launched with the waves / rows plan_block chose
 size_t egt_narrow_fwd_lds(int nw);   // dynamic LDS bytes of a workgroup of nw = 4 | 8 waves
 size_t egt_narrow_bwd_lds(int nw);

@@ -135,6 +135,15 @@ void egt_debug_poison_lds(hipStream_t s);
     hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);      \
   } while (0)
 
+// One launch in the shape a host plan chose (egt_block.hip: plan_block, egt_attn_mfma.hip: plan_attn, egt_ffn.hip: plan_ffn):
+// workgroups, threads per workgroup, dynamic LDS bytes.  egt_launch_planned also raises K's dynamic-LDS limit once.
+struct EgtLaunch { int grid, block; size_t lds; };
+template <auto K, typename... A>
+static inline void egt_launch_planned(const char* name, const EgtLaunch& s, hipStream_t st, const A&... a) {
+  EGT_MAX_LDS_ONCE(K);
+  EGT_LAUNCH(name, K, dim3(s.grid), dim3(s.block), s.lds, st, a...);
+}
+
 // (graph, 16-row group) of a logical workgroup index.  When N is not a multiple of 16 the last row group of every graph is
 // short (its workgroup does a fraction of a full group's work): those workgroups are dealt LAST, so they fill the tail of
 // the launch instead of sitting between full-size workgroups while the last round runs half empty.

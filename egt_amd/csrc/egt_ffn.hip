@@ -1017,163 +1017,138 @@ extern "C" int egt_ffn_supported(const egt_ffn_desc* d) {
   return d->activation == EGT_ACT_RELU || d->activation == EGT_ACT_ELU;
 }
 
-// [slab1 slab2 slab3 slab4 b1p | red | part x FFN_NWG | sA1 sA2 (bf16 modes)]
-static size_t ffn_bf_slab_floats(size_t W) {   // sA1, sA3: [TH][NS1][2][256] floats each; sA2, sA4: [TW][TW][2][256]
-  const size_t TW = W / 16, NS1 = (TW + 1) / 2;
-  return 2 * (2 * TW * NS1 * 2 * 256) + 2 * (TW * TW * 2 * 256);
-}
-static int ffn_bf_prep_blocks(int W) {
-  const int TW = W / 16, NS1 = (TW + 1) / 2;
-  const int n1 = 2 * TW * NS1 * 512, n2 = TW * TW * 512;
-  return ((n1 > n2 ? n1 : n2) + 255) / 256;
-}
-extern "C" size_t egt_ffn_workspace_bytes(const egt_ffn_desc* d) {
-  if (!egt_ffn_supported(d)) return 0;
-  const size_t W = d->width == 8 ? 16 : d->width, slab = 2 * W * W, part = 2 * slab + 3 * W;
-  return (4 * slab + ffn_al(2 * W) + ffn_al(part) + ffn_nwg_cap(W) * part + ffn_bf_slab_floats(W) + 1280) * sizeof(float);
+// Every launch and workspace decision of the fused FFN is made in ONE place, plan_ffn, once per C-ABI call: the size query returns
+// its total, ffn_fill binds the workspace from it, the entry points launch from it.  Workspace, in floats (width 8 lays out as 16):
+//   [slab1 slab2 slab3 slab4 | b1p | red | part x ffn_nwg_cap | sA1 sA2 sA3 sA4 (bf16 modes) | x16 (width 8: F8_* operands)]
+enum FfnFamily { FFN_ROW8, FFN_F32, FFN_BF16 };   // k_ffn8_* (one row per lane) | k_ffn_* fp32 tiles | bf16 tiles (EGT_MM_BF16X3 / _BF16)
+struct FfnPlan {
+  FfnFamily fam;
+  int W;   // layout width
+  size_t slab, b1p, red, part, sA1, sA2, sA3, sA4, x16, total;
+  int part_len;                 // floats per backward workgroup partial
+  EgtLaunch prep, fwd, bwd;     // bwd.grid: backward workgroups (= partials)
+};
+
+static FfnPlan plan_ffn(const egt_ffn_desc* d) {
+  FfnPlan P{};
+  P.fam = d->width == 8 ? FFN_ROW8 : (d->matmul == EGT_MM_F32 ? FFN_F32 : FFN_BF16);
+  const size_t W = P.W = d->width == 8 ? 16 : d->width, TW = W / 16, NS1 = (TW + 1) / 2;
+  const size_t slab = 2 * W * W, part = 2 * slab + 3 * W;                     // slab = W*2W floats; partial = T1 | T2 | s1 | s2
+  const size_t a1 = 2 * TW * NS1 * 2 * 256, a2 = TW * TW * 2 * 256;           // sA1, sA3: [TH][NS1][2][256]; sA2, sA4: [TW][TW][2][256]
+  P.slab = slab; P.b1p = 4 * slab; P.red = P.b1p + ffn_al(2 * W); P.part = P.red + ffn_al(part);
+  P.sA1 = P.part + ffn_nwg_cap(W) * part; P.sA2 = P.sA1 + a1; P.sA3 = P.sA2 + a2; P.sA4 = P.sA3 + a1; P.x16 = P.sA4 + a2;
+  P.total = P.x16 + 1280;
+  auto clamp = [](long v, long hi) { return (int)(v < 1 ? 1 : (v > hi ? hi : v)); };
+  const long tiles = (d->rows + 15) / 16;
+  if (P.fam == FFN_ROW8) {   // one row per lane: 64-row waves, 4 per workgroup
+    const long want = (((d->rows + 63) / 64) + 3) / 4;
+    P.part_len = F8_PART;
+    P.prep = {1, 128, 0};
+    P.fwd = {clamp(want, 2048), 256, 0};
+    P.bwd = {clamp(want, 1024), 256, 0};
+    return P;
+  }
+  P.part_len = (int)part;
+  if (P.fam == FFN_F32) {
+    P.prep = {(int)((slab + 255) / 256), 256, 0};
+    P.fwd = {clamp((tiles + 7) / 8, 256), 512, (2 * slab + 3 * W + 8 * 2 * 16 * W) * 4};
+  } else {
+    P.prep = {(int)(((a1 > a2 ? a1 : a2) + 255) / 256), 256, 0};
+    P.fwd = {clamp((tiles + 7) / 8, 512), 512, (a1 + a2 + 3 * W + 8 * 2 * 16 * W) * 4};
+  }
+  // backward workgroups: one per CU for large inputs; small inputs (node channels) one tile per wave (a tile is ~16 us of dependent
+  // work: spreading beats amortising the slab staging).  LDS: the operand slabs, with the partial staged over them at the end
+  const size_t slabs = P.fam == FFN_BF16 ? 2 * a1 + a2 : 3 * slab;
+  P.bwd = {clamp((tiles + 3) / 4, (long)ffn_nwg_cap(W)), 256, ((slabs > part ? slabs : part) + 2 * W + 4 * 3 * 16 * W) * 4};
+  return P;
 }
 
-static int ffn_fill(const egt_ffn_desc* d, const egt_ffn_params* p, void* ws, FfnArgs& a) {
+extern "C" size_t egt_ffn_workspace_bytes(const egt_ffn_desc* d) {
+  if (!egt_ffn_supported(d)) return 0;
+  return plan_ffn(d).total * sizeof(float);
+}
+
+static int ffn_fill(const egt_ffn_desc* d, const egt_ffn_params* p, void* ws, FfnPlan& P, FfnArgs& a) {
   if (!d || !p || !ws) EGT_FAIL(EGT_E_NULL, "desc/params/workspace is NULL");
   if (!egt_ffn_supported(d))
     EGT_FAIL(EGT_E_SHAPE, "fused FFN covers widths 16/32/48/64 (and 8 with exact fp32 products), fp32, relu/elu "
                           "(got width %d, rows %lld, act %d, matmul %d)", d->width, (long long)d->rows, d->activation, d->matmul);
   if (!p->norm_gamma || !p->norm_beta || !p->lr1_kernel || !p->lr1_bias || !p->lr2_kernel || !p->lr2_bias)
     EGT_FAIL(EGT_E_NULL, "an FFN parameter pointer is NULL");
+  P = plan_ffn(d);
   a = FfnArgs{};
   a.rows = d->rows; a.ln_eps = d->ln_eps; a.W = d->width;
   a.gamma = (const float*)p->norm_gamma; a.beta = (const float*)p->norm_beta;
   a.W1 = (const float*)p->lr1_kernel; a.b1 = (const float*)p->lr1_bias;
   a.W2 = (const float*)p->lr2_kernel; a.b2 = (const float*)p->lr2_bias;
-  const size_t W = d->width == 8 ? 16 : d->width, slab = 2 * W * W, part = 2 * slab + 3 * W;
   float* w = (float*)ws;
-  a.slab1 = w; a.slab2 = w + slab; a.slab3 = w + 2 * slab; a.slab4 = w + 3 * slab;
-  a.b1p = w + 4 * slab;
-  a.red = a.b1p + ffn_al(2 * W);
-  a.part = a.red + ffn_al(part);
+  a.slab1 = w; a.slab2 = w + P.slab; a.slab3 = w + 2 * P.slab; a.slab4 = w + 3 * P.slab;
+  a.b1p = w + P.b1p; a.red = w + P.red; a.part = w + P.part;
   a.mm = d->matmul;
-  {
-    const size_t TW = W / 16, NS1 = (TW + 1) / 2;
-    float* bf = a.part + ffn_nwg_cap(W) * part;
-    const size_t a1 = 2 * TW * NS1 * 2 * 256, a2 = TW * TW * 2 * 256;
-    a.sA1 = reinterpret_cast<uint16_t*>(bf);
-    a.sA2 = reinterpret_cast<uint16_t*>(bf + a1);
-    a.sA3 = reinterpret_cast<uint16_t*>(bf + a1 + a2);
-    a.sA4 = reinterpret_cast<uint16_t*>(bf + 2 * a1 + a2);
-    a.x16 = bf + 2 * a1 + 2 * a2;
-  }
-  a.part_len = (int)part;
-  if (d->width == 8) {   // one row per lane (k_ffn8_*)
-    a.row8 = 1; a.part_len = F8_PART;
-    const long want = (((a.rows + 63) / 64) + 3) / 4;
-    a.nwg = (int)(want < 1 ? 1 : (want > 1024 ? 1024 : want));
-    return EGT_OK;
-  }
-  {   // backward workgroups: one per CU for large inputs; small inputs (node channels) one tile
-      // per wave (a tile is ~16 us of dependent work: spreading beats amortising the slab staging)
-    const long ntiles = (a.rows + 15) / 16;
-    const long want = (ntiles + 3) / 4;
-    const long cap = (long)ffn_nwg_cap(W);
-    a.nwg = (int)(want < 1 ? 1 : (want > cap ? cap : want));
-  }
+  a.sA1 = reinterpret_cast<uint16_t*>(w + P.sA1); a.sA2 = reinterpret_cast<uint16_t*>(w + P.sA2);
+  a.sA3 = reinterpret_cast<uint16_t*>(w + P.sA3); a.sA4 = reinterpret_cast<uint16_t*>(w + P.sA4);
+  a.x16 = w + P.x16;
+  a.part_len = P.part_len; a.row8 = P.fam == FFN_ROW8; a.nwg = P.bwd.grid;
   return EGT_OK;
 }
 
-template <int W>
-static void ffn_launch_fwd(const FfnArgs& a, int act, hipStream_t st) {
-  const size_t lds = (2 * (size_t)(2 * W * W) + 3 * W + 8 * 2 * 16 * W) * 4;
-  const long ntiles = (a.rows + 15) / 16;
-  const long wantf = (ntiles + 7) / 8;
-  const int grid = (int)(wantf < 1 ? 1 : (wantf > 256 ? 256 : wantf));
-  if (act == EGT_ACT_RELU) {
-    EGT_MAX_LDS_ONCE(k_ffn_fwd<W, EGT_ACT_RELU>);
-    EGT_LAUNCH("k_ffn_fwd", (k_ffn_fwd<W, EGT_ACT_RELU>), dim3(grid), dim3(512), lds, st, a);
-  } else {
-    EGT_MAX_LDS_ONCE(k_ffn_fwd<W, EGT_ACT_ELU>);
-    EGT_LAUNCH("k_ffn_fwd", (k_ffn_fwd<W, EGT_ACT_ELU>), dim3(grid), dim3(512), lds, st, a);
+// one instance of the tile kernels: width W, activation ACT, products MM (the forward of the bf16 modes: k_ffn_fwd_bf, SPLIT for bf16x3)
+template <int W, int ACT, int MM>
+static void ffn_launch_tiles(const FfnPlan& P, const FfnArgs& a, bool bwd, bool prep, hipStream_t st) {
+  if (prep) {
+    if constexpr (MM == EGT_MM_F32) EGT_LAUNCH("k_ffn_prep", k_ffn_prep<W>, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
+    else EGT_LAUNCH("k_ffn_prep", k_ffn_prep_bf<W>, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
   }
-}
-
-template <int W>
-static void ffn_launch_fwd_bf(const FfnArgs& a, int act, hipStream_t st) {
-  constexpr int TW = W / 16, NS1 = (TW + 1) / 2;
-  const size_t lds = ((size_t)(2 * TW * NS1 * 2 * 256 + TW * TW * 2 * 256) + 3 * W + 8 * 2 * 16 * W) * 4;
-  const long ntiles = (a.rows + 15) / 16;
-  const long wantf = (ntiles + 7) / 8;
-  const int grid = (int)(wantf < 1 ? 1 : (wantf > 512 ? 512 : wantf));
-  EGT_LAUNCH("k_ffn_prep", k_ffn_prep_bf<W>, dim3(ffn_bf_prep_blocks(W)), dim3(256), 0, st, a);
-#define FBF(ACT_, SPLIT_)                                                                                             \
-  do {                                                                                                                \
-    EGT_MAX_LDS_ONCE(k_ffn_fwd_bf<W, ACT_, SPLIT_>); \
-    EGT_LAUNCH("k_ffn_fwd", (k_ffn_fwd_bf<W, ACT_, SPLIT_>), dim3(grid), dim3(512), lds, st, a);                       \
-  } while (0)
-  const bool split = a.mm == EGT_MM_BF16X3;
-  if (act == EGT_ACT_RELU) { if (split) FBF(EGT_ACT_RELU, true); else FBF(EGT_ACT_RELU, false); }
-  else { if (split) FBF(EGT_ACT_ELU, true); else FBF(EGT_ACT_ELU, false); }
-#undef FBF
-}
-
-template <int W, int MM>
-static void ffn_launch_bwd_mm(const FfnArgs& a, int act, hipStream_t st) {
-  constexpr int TW = W / 16, NS1 = (TW + 1) / 2;
-  constexpr size_t slabs = MM ? (size_t)(2 * (2 * TW * NS1 * 2 * 256) + TW * TW * 2 * 256) : 3 * (size_t)(2 * W * W);
-  // the per-workgroup partial (2 * 2W*W + 3W floats) is staged over the slab area at the end
-  constexpr size_t part = 2 * (size_t)(2 * W * W) + 3 * W;
-  const size_t lds = ((slabs > part ? slabs : part) + 2 * W + 4 * 3 * 16 * W) * 4;
-  if (act == EGT_ACT_RELU) {
-    EGT_MAX_LDS_ONCE(k_ffn_bwd<W, EGT_ACT_RELU, MM>);
-    EGT_LAUNCH("k_ffn_bwd", (k_ffn_bwd<W, EGT_ACT_RELU, MM>), dim3(a.nwg), dim3(256), lds, st, a);
-  } else {
-    EGT_MAX_LDS_ONCE(k_ffn_bwd<W, EGT_ACT_ELU, MM>);
-    EGT_LAUNCH("k_ffn_bwd", (k_ffn_bwd<W, EGT_ACT_ELU, MM>), dim3(a.nwg), dim3(256), lds, st, a);
-  }
+  if (bwd) egt_launch_planned<k_ffn_bwd<W, ACT, MM>>("k_ffn_bwd", P.bwd, st, a);
+  else if constexpr (MM == EGT_MM_F32) egt_launch_planned<k_ffn_fwd<W, ACT>>("k_ffn_fwd", P.fwd, st, a);
+  else egt_launch_planned<k_ffn_fwd_bf<W, ACT, MM == EGT_MM_BF16X3>>("k_ffn_fwd", P.fwd, st, a);
 }
 template <int W>
-static void ffn_launch_bwd(const FfnArgs& a, int act, hipStream_t st) {
-  if (a.mm == EGT_MM_BF16X3) ffn_launch_bwd_mm<W, EGT_MM_BF16X3>(a, act, st);
-  else if (a.mm == EGT_MM_BF16) ffn_launch_bwd_mm<W, EGT_MM_BF16>(a, act, st);
-  else ffn_launch_bwd_mm<W, EGT_MM_F32>(a, act, st);
-}
-
-#define FFN_DISPATCH_W(width, CALL)               \
-  switch (width) {                                \
-    case 16: { constexpr int W = 16; CALL; } break; \
-    case 32: { constexpr int W = 32; CALL; } break; \
-    case 48: { constexpr int W = 48; CALL; } break; \
-    default: { constexpr int W = 64; CALL; } break; \
+static void ffn_launch_w(const FfnPlan& P, const FfnArgs& a, int act, bool bwd, bool prep, hipStream_t st) {
+  switch (2 * a.mm + (act == EGT_ACT_RELU)) {   // products, activation
+    case 2 * EGT_MM_F32 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_F32>(P, a, bwd, prep, st); break;
+    case 2 * EGT_MM_F32: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_F32>(P, a, bwd, prep, st); break;
+    case 2 * EGT_MM_BF16X3 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_BF16X3>(P, a, bwd, prep, st); break;
+    case 2 * EGT_MM_BF16X3: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_BF16X3>(P, a, bwd, prep, st); break;
+    case 2 * EGT_MM_BF16 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_BF16>(P, a, bwd, prep, st); break;
+    default: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_BF16>(P, a, bwd, prep, st); break;
   }
+}
+// prep (unless a backward finds its workspace prepared), then the planned family's forward / backward instance
+static void ffn_launch(const FfnPlan& P, const FfnArgs& a, int act, bool bwd, bool prep, hipStream_t st) {
+  if (P.fam == FFN_ROW8) {
+    if (prep) EGT_LAUNCH("k_ffn_prep", k_ffn8_prep, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
+    const EgtLaunch& s = bwd ? P.bwd : P.fwd;
+    if (bwd && act == EGT_ACT_RELU) EGT_LAUNCH("k_ffn_bwd", k_ffn8_bwd<EGT_ACT_RELU>, dim3(s.grid), dim3(s.block), s.lds, st, a);
+    else if (bwd) EGT_LAUNCH("k_ffn_bwd", k_ffn8_bwd<EGT_ACT_ELU>, dim3(s.grid), dim3(s.block), s.lds, st, a);
+    else if (act == EGT_ACT_RELU) EGT_LAUNCH("k_ffn_fwd", k_ffn8_fwd<EGT_ACT_RELU>, dim3(s.grid), dim3(s.block), s.lds, st, a);
+    else EGT_LAUNCH("k_ffn_fwd", k_ffn8_fwd<EGT_ACT_ELU>, dim3(s.grid), dim3(s.block), s.lds, st, a);
+    return;
+  }
+  switch (P.W) {
+    case 16: ffn_launch_w<16>(P, a, act, bwd, prep, st); break;
+    case 32: ffn_launch_w<32>(P, a, act, bwd, prep, st); break;
+    case 48: ffn_launch_w<48>(P, a, act, bwd, prep, st); break;
+    default: ffn_launch_w<64>(P, a, act, bwd, prep, st); break;
+  }
+}
 
 extern "C" int egt_ffn_fwd(const egt_ffn_desc* desc, const egt_ffn_params* params, const void* x, void* y,
                            void* workspace, void* stream) {
-  FfnArgs a;
-  int rc = ffn_fill(desc, params, workspace, a);
+  FfnPlan P; FfnArgs a;
+  int rc = ffn_fill(desc, params, workspace, P, a);
   if (rc) return rc;
   if (!x || !y) EGT_FAIL(EGT_E_NULL, "x/y is NULL");
   a.x = (const float*)x; a.y = (float*)y;
-  hipStream_t st = (hipStream_t)stream;
-  if (a.row8) {
-    EGT_LAUNCH("k_ffn_prep", k_ffn8_prep, dim3(1), dim3(128), 0, st, a);
-    const long want = (((a.rows + 63) / 64) + 3) / 4;
-    const int grid = (int)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
-    if (desc->activation == EGT_ACT_RELU) EGT_LAUNCH("k_ffn_fwd", k_ffn8_fwd<EGT_ACT_RELU>, dim3(grid), dim3(256), 0, st, a);
-    else EGT_LAUNCH("k_ffn_fwd", k_ffn8_fwd<EGT_ACT_ELU>, dim3(grid), dim3(256), 0, st, a);
-    EGT_HIP_LAUNCH_CHECK("egt_ffn_fwd");
-    return EGT_OK;
-  }
-  if (desc->matmul != EGT_MM_F32) {
-    FFN_DISPATCH_W(desc->width, ffn_launch_fwd_bf<W>(a, desc->activation, st));
-  } else {
-    FFN_DISPATCH_W(desc->width, EGT_LAUNCH("k_ffn_prep", k_ffn_prep<W>, dim3((2 * W * W + 255) / 256), dim3(256), 0, st, a));
-    FFN_DISPATCH_W(desc->width, ffn_launch_fwd<W>(a, desc->activation, st));
-  }
+  ffn_launch(P, a, desc->activation, false, true, (hipStream_t)stream);
   EGT_HIP_LAUNCH_CHECK("egt_ffn_fwd");
   return EGT_OK;
 }
 
 extern "C" int egt_ffn_bwd(const egt_ffn_desc* desc, const egt_ffn_params* params, const void* x, const void* dy,
                            void* dx, const egt_ffn_params* grads, void* workspace, void* stream) {
-  FfnArgs a;
-  int rc = ffn_fill(desc, params, workspace, a);
+  FfnPlan P; FfnArgs a;
+  int rc = ffn_fill(desc, params, workspace, P, a);
   if (rc) return rc;
   if (!x || !dy || !dx || !grads) EGT_FAIL(EGT_E_NULL, "x/dy/dx/grads is NULL");
   if (!grads->norm_gamma || !grads->norm_beta || !grads->lr1_kernel || !grads->lr1_bias || !grads->lr2_kernel || !grads->lr2_bias)
@@ -1183,26 +1158,10 @@ extern "C" int egt_ffn_bwd(const egt_ffn_desc* desc, const egt_ffn_params* param
   a.g_W1 = (float*)grads->lr1_kernel; a.g_b1 = (float*)grads->lr1_bias;
   a.g_W2 = (float*)grads->lr2_kernel; a.g_b2 = (float*)grads->lr2_bias;
   hipStream_t st = (hipStream_t)stream;
-  const bool prepared = (desc->flags & EGT_FFN_WS_PREPARED) != 0;   // the forward's workspace: its prepared operands are still there
-  if (a.row8) {
-    if (!prepared) EGT_LAUNCH("k_ffn_prep", k_ffn8_prep, dim3(1), dim3(128), 0, st, a);
-    if (desc->activation == EGT_ACT_RELU) EGT_LAUNCH("k_ffn_bwd", k_ffn8_bwd<EGT_ACT_RELU>, dim3(a.nwg), dim3(256), 0, st, a);
-    else EGT_LAUNCH("k_ffn_bwd", k_ffn8_bwd<EGT_ACT_ELU>, dim3(a.nwg), dim3(256), 0, st, a);
-    EGT_LAUNCH("k_ffn_sum", k_ffn_sum, dim3((F8_PART + 63) / 64), dim3(1024), 0, st, a);
-    EGT_LAUNCH("k_ffn_param_grads", k_ffn_param_grads, dim3(1), dim3(1024), 0, st, a);
-    EGT_HIP_LAUNCH_CHECK("egt_ffn_bwd");
-    return EGT_OK;
-  }
-  if (!prepared) {   // (the bf16 modes read their own slabs and b1p only: k_ffn_prep_bf writes all of that)
-    if (desc->matmul == EGT_MM_F32) {
-      FFN_DISPATCH_W(desc->width, EGT_LAUNCH("k_ffn_prep", k_ffn_prep<W>, dim3((2 * W * W + 255) / 256), dim3(256), 0, st, a));
-    } else {
-      FFN_DISPATCH_W(desc->width, EGT_LAUNCH("k_ffn_prep", k_ffn_prep_bf<W>, dim3(ffn_bf_prep_blocks(W)), dim3(256), 0, st, a));
-    }
-  }
-  FFN_DISPATCH_W(desc->width, ffn_launch_bwd<W>(a, desc->activation, st));
-  const int part = a.part_len;
-  EGT_LAUNCH("k_ffn_sum", k_ffn_sum, dim3((part + 63) / 64), dim3(1024), 0, st, a);
+  // EGT_FFN_WS_PREPARED: the forward's workspace, its prepared operands are still there (the bf16 modes read their own slabs and b1p
+  // only: k_ffn_prep_bf writes all of that)
+  ffn_launch(P, a, desc->activation, true, !(desc->flags & EGT_FFN_WS_PREPARED), st);
+  EGT_LAUNCH("k_ffn_sum", k_ffn_sum, dim3((P.part_len + 63) / 64), dim3(1024), 0, st, a);
   EGT_LAUNCH("k_ffn_param_grads", k_ffn_param_grads, dim3(1), dim3(1024), 0, st, a);
   EGT_HIP_LAUNCH_CHECK("egt_ffn_bwd");
   return EGT_OK;
