@@ -17,7 +17,7 @@ ABI_VERSION = 4   # include/egt_amd.h EGT_ABI_VERSION
 EGT_OK = 0
 EGT_E_NULL, EGT_E_SHAPE, EGT_E_DTYPE, EGT_E_FLAGS, EGT_E_HIP, EGT_E_WORKSPACE, EGT_E_RCCL = -1, -2, -3, -4, -5, -6, -7
 EGT_F32 = 0
-EGT_BF16 = 1   # fused block/stack: edge tensors bf16 in HBM, everything else fp32
+EGT_BF16 = 1   # fused block/stack, channel FFN, edge embedding: edge tensors bf16 in HBM, everything else fp32
 F_EDGE_INPUT, F_GATE_INPUT, F_ATTN_MASK, F_SCALE_DEGREE = 0x001, 0x002, 0x004, 0x008
 F_SCALER_LINEAR, F_TRAINING, F_CLIP = 0x010, 0x020, 0x040
 ATTN_WS_SHARED = 0x1   # egt_attn_desc.reserved: one workspace for egt_attn_mfma_fwd and _bwd

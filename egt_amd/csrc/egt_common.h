@@ -24,6 +24,20 @@ void egt_set_error(const char* fmt, ...);
       EGT_FAIL(EGT_E_HIP, "%s launch failed: %s", name, hipGetErrorString(e__)); \
   } while (0)
 
+// ---- bfloat16 storage of fp32 values (EGT_BF16 edge tensors): widen = 16-bit shift; narrow on v_cvt_pk_bf16_f32 (gfx950:
+// round to nearest even, NaN stays NaN): one instruction per two elements instead of the ~14 integer ops of a software rounding
+__device__ __forceinline__ float4 bf4_to_f4(uint2 u) {
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u),
+                     __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u));
+}
+typedef __bf16 egt_bf2 __attribute__((ext_vector_type(2)));
+typedef float egt_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t f2_to_bf2(float lo, float hi) {
+  const egt_bf2 b = __builtin_convertvector((egt_f2){lo, hi}, egt_bf2);
+  return *reinterpret_cast<const uint32_t*>(&b);
+}
+__device__ __forceinline__ uint2 f4_to_bf4(float4 v) { return make_uint2(f2_to_bf2(v.x, v.y), f2_to_bf2(v.z, v.w)); }
+
 // ---- counter hash (mirrored bit-exactly by oracle/rng_ref.py) ----------------
 __host__ __device__ inline uint32_t egt_fmix32(uint32_t x) {
   x ^= x >> 16;

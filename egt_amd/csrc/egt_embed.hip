@@ -164,11 +164,16 @@ __global__ void __launch_bounds__(256) k_feature_planes(const float* __restrict_
 }
 
 // e0[pair, c] = fm_table[fmat[pair] + 1, c] + bias[c] + sum_k hops[pair, k] * W[k, c]
-// thread = (pair, 4 channels); W / bias / table staged in LDS
-template <int KMAX>
+// thread = (pair, 4 channels); W / bias / table staged in LDS.  T: storage of e0 (float, or uint16_t = bfloat16 bits: the fp32
+// sum is rounded once, to nearest even, where it is stored)
+__device__ __forceinline__ void embed_store4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ void embed_store4(uint16_t* p, float4 v) { *reinterpret_cast<uint2*>(p) = f4_to_bf4(v); }
+__device__ __forceinline__ float4 embed_load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 embed_load4(const uint16_t* p) { return bf4_to_f4(*reinterpret_cast<const uint2*>(p)); }
+template <int KMAX, typename T>
 __global__ void __launch_bounds__(256) k_edge_embed_fwd(const int32_t* __restrict__ fmat, const float* __restrict__ hops,
                                                         const float* __restrict__ table, const float* __restrict__ W,
-                                                        const float* __restrict__ bias, float* __restrict__ e, long pairs,
+                                                        const float* __restrict__ bias, T* __restrict__ e, long pairs,
                                                         int De, int K, int V) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* Ws = sm;                 // [K][De]
@@ -192,7 +197,7 @@ __global__ void __launch_bounds__(256) k_edge_embed_fwd(const int32_t* __restric
     acc.x = fmaf(hv, w.x, acc.x); acc.y = fmaf(hv, w.y, acc.y);
     acc.z = fmaf(hv, w.z, acc.z); acc.w = fmaf(hv, w.w, acc.w);
   }
-  *reinterpret_cast<float4*>(e + pair * De + 4 * c4) = acc;
+  embed_store4(e + pair * De + 4 * c4, acc);
 }
 
 // backward: dW[k,c] = sum_pairs hops[pair,k] de[pair,c];  dtable[v,c] = sum_{fmat+1 == v} de[pair,c];  dbias = sum de
@@ -200,9 +205,9 @@ __global__ void __launch_bounds__(256) k_edge_embed_fwd(const int32_t* __restric
 // channels get more pair lanes instead of idle threads); each thread owns 4 channels and walks its pairs; the
 // (K + V) x 4 accumulators per thread are reduced over the pair lanes in LDS; one partial per workgroup
 #define EMB_PPB 2048   // pairs per workgroup
-template <int K_, int V_>
+template <int K_, int V_, typename T>   // T: storage of de (float or bfloat16 bits); the sums stay fp32
 __global__ void __launch_bounds__(256) k_edge_embed_bwd(const int32_t* __restrict__ fmat, const float* __restrict__ hops,
-                                                        const float* __restrict__ de, float* __restrict__ part, long pairs,
+                                                        const T* __restrict__ de, float* __restrict__ part, long pairs,
                                                         int De, int C4P) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // [PL pair lanes][(K+V)][De]
   const int C4 = De / 4;
@@ -217,7 +222,7 @@ __global__ void __launch_bounds__(256) k_edge_embed_bwd(const int32_t* __restric
   const long p1 = min(pairs, p0 + EMB_PPB);
   if (c4 < C4) {
     for (long pair = p0 + pl; pair < p1; pair += PL) {
-      const float4 d = *reinterpret_cast<const float4*>(de + pair * De + 4 * c4);
+      const float4 d = embed_load4(de + pair * De + 4 * c4);
       const float* hp = hops + pair;
       int f = fmat[pair] + 1;
       f = min(max(f, 0), V_ - 1);
@@ -285,14 +290,14 @@ static int embed_check(const egt_embed_desc* d) {
   if (d->upto_hop < 1 || d->upto_hop > 16) EGT_FAIL(EGT_E_SHAPE, "upto_hop must be in 1..16 (got %d)", d->upto_hop);
   if (d->num_float_features < 0 || d->num_float_features > 4) EGT_FAIL(EGT_E_SHAPE, "num_float_features must be in 0..4 (got %d)", d->num_float_features);
   if (d->num_edge_features < 0 || d->num_edge_features > 7) EGT_FAIL(EGT_E_SHAPE, "num_edge_features must be in 0..7 (got %d)", d->num_edge_features);
-  if (d->dtype != EGT_F32) EGT_FAIL(EGT_E_DTYPE, "edge embedding is fp32");
+  if (d->dtype != EGT_F32 && d->dtype != EGT_BF16) EGT_FAIL(EGT_E_DTYPE, "edge embedding stores e0 / reads de as EGT_F32 or EGT_BF16 (got %d)", d->dtype);
   return EGT_OK;
 }
 extern "C" int egt_edge_embed_supported(const egt_embed_desc* d) {
   if (!d) return 0;
   return d->B > 0 && d->N > 0 && d->De >= 4 && d->De <= 64 && d->De % 4 == 0 && d->upto_hop >= 1 && d->upto_hop <= 16 &&
          d->num_float_features >= 0 && d->num_float_features <= 4 &&
-         d->num_edge_features >= 0 && d->num_edge_features <= 7 && d->dtype == EGT_F32;
+         d->num_edge_features >= 0 && d->num_edge_features <= 7 && (d->dtype == EGT_F32 || d->dtype == EGT_BF16);
 }
 extern "C" size_t egt_edge_embed_hops_bytes(const egt_embed_desc* d) {
   if (!egt_edge_embed_supported(d)) return 0;
@@ -348,15 +353,20 @@ extern "C" int egt_edge_embed_fwd(const egt_embed_desc* d, const int32_t* featur
                (const float*)float_features, (float*)hops + (size_t)KH * pairs, pairs, d->num_float_features, d->mask_value);
   const long threads = pairs * (d->De / 4);
   const size_t lds = (size_t)(K + V) * d->De * sizeof(float);
-  EGT_LAUNCH("k_edge_embed_fwd", k_edge_embed_fwd<16>, dim3((unsigned)((threads + 255) / 256)), dim3(256), lds, st,
-             feature_matrix, (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias,
-             (float*)e_out, pairs, d->De, K, V);
+  if (d->dtype == EGT_BF16)
+    EGT_LAUNCH("k_edge_embed_fwd", (k_edge_embed_fwd<16, uint16_t>), dim3((unsigned)((threads + 255) / 256)), dim3(256), lds, st,
+               feature_matrix, (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias,
+               (uint16_t*)e_out, pairs, d->De, K, V);
+  else
+    EGT_LAUNCH("k_edge_embed_fwd", (k_edge_embed_fwd<16, float>), dim3((unsigned)((threads + 255) / 256)), dim3(256), lds, st,
+               feature_matrix, (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias,
+               (float*)e_out, pairs, d->De, K, V);
   EGT_HIP_LAUNCH_CHECK("egt_edge_embed_fwd");
   return EGT_OK;
 }
 
-template <int K_>
-static void launch_embed_bwd(const egt_embed_desc* d, const int32_t* fmat, const float* hops, const float* de, float* part,
+template <int K_, typename T>
+static void launch_embed_bwd(const egt_embed_desc* d, const int32_t* fmat, const float* hops, const T* de, float* part,
                              hipStream_t st) {
   const long pairs = (long)d->B * d->N * d->N;
   const int nparts = embed_nparts(d);
@@ -366,8 +376,8 @@ static void launch_embed_bwd(const egt_embed_desc* d, const int32_t* fmat, const
 #define EB(V_)                                                                                                      \
   do {                                                                                                              \
     const size_t lds = (size_t)(256 / c4p) * (K_ + V_) * d->De * sizeof(float);                                     \
-    EGT_MAX_LDS_ONCE(k_edge_embed_bwd<K_, V_>); \
-    EGT_LAUNCH("k_edge_embed_bwd", (k_edge_embed_bwd<K_, V_>), dim3(nparts), dim3(256), lds, st, fmat, hops, de, part, pairs, d->De, c4p); \
+    EGT_MAX_LDS_ONCE((k_edge_embed_bwd<K_, V_, T>)); \
+    EGT_LAUNCH("k_edge_embed_bwd", (k_edge_embed_bwd<K_, V_, T>), dim3(nparts), dim3(256), lds, st, fmat, hops, de, part, pairs, d->De, c4p); \
   } while (0)
   switch (d->num_edge_features + 1) {
     case 1: EB(1); break; case 2: EB(2); break; case 3: EB(3); break; case 4: EB(4); break;
@@ -385,11 +395,15 @@ extern "C" int egt_edge_embed_bwd(const egt_embed_desc* d, const int32_t* featur
     EGT_FAIL(EGT_E_NULL, "feature_matrix/hops/d_e/d_fm_table/d_adj_kernel/d_adj_bias/workspace is NULL");
   hipStream_t st = (hipStream_t)stream;
   const float* h = (const float*)hops;
-  const float* de = (const float*)d_e;
   float* part = (float*)workspace;
   const int KT = d->upto_hop + d->num_float_features;   // hop planes + real-valued feature planes
+  const bool bf = d->dtype == EGT_BF16;
   switch (KT) {
-#define C(K_) case K_: launch_embed_bwd<K_>(d, feature_matrix, h, de, part, st); break;
+#define C(K_)                                                                                   \
+  case K_:                                                                                      \
+    if (bf) launch_embed_bwd<K_, uint16_t>(d, feature_matrix, h, (const uint16_t*)d_e, part, st); \
+    else launch_embed_bwd<K_, float>(d, feature_matrix, h, (const float*)d_e, part, st);         \
+    break;
     C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16) C(17) C(18) C(19) C(20)
 #undef C
   }

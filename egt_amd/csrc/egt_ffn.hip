@@ -175,9 +175,12 @@ __device__ __forceinline__ v4f ffn_gemm1(const float* s1, const float* b1s, cons
 }
 
 // ================================================================== forward =====
-template <int W, int ACT>
+// T: storage type of x / y (float, or uint16_t = bfloat16 bits for EGT_BF16; the LDS tiles and the arithmetic stay fp32)
+template <int W, int ACT, typename T>
 __global__ void __launch_bounds__(512, 2) k_ffn_fwd(FfnArgs a) {
   FFN_GEO(W);
+  const T* xg = reinterpret_cast<const T*>(a.x);
+  T* yg = reinterpret_cast<T*>(a.y);
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* s1 = sm;
   float* s2 = s1 + SLABF;
@@ -195,18 +198,18 @@ __global__ void __launch_bounds__(512, 2) k_ffn_fwd(FfnArgs a) {
   const long ntiles = (a.rows + 15) / 16;
   const long stride = (long)gridDim.x * 8;
   long tile = (long)blockIdx.x * 8 + wave;
-  TileRegs<FW> tr;
-  if (tile < ntiles) tile_gload<FW, EGT_NT_FFN>(tr, a.x + tile * TILEF, lane, (int)min(16L, a.rows - tile * 16));
+  typename TileIn<FW, T>::type tr;
+  if (tile < ntiles) tile_gload<FW, EGT_NT_FFN>(tr, xg + tile * TILEF, lane, (int)min(16L, a.rows - tile * 16));
   long prev = -1;
   for (int it = 0; tile < ntiles; tile += stride, ++it) {
     const int rows_valid = (int)min(16L, a.rows - tile * 16);
     float* tl = tl0 + (it & 1) * TILEF;
     lds_sync();
     if (prev >= 0)   // stream out the previous tile's y from the other buffer
-      tile_from_lds<FW>(tl0 + ((it - 1) & 1) * TILEF, a.y + prev * TILEF, lane, (int)min(16L, a.rows - prev * 16));
+      tile_from_lds<FW>(tl0 + ((it - 1) & 1) * TILEF, yg + prev * TILEF, lane, (int)min(16L, a.rows - prev * 16));
     tile_lds_put<FW>(tl, tr, lane, rows_valid);
     const long nxt = tile + stride;
-    if (nxt < ntiles) tile_gload<FW, EGT_NT_FFN>(tr, a.x + nxt * TILEF, lane, (int)min(16L, a.rows - nxt * 16));
+    if (nxt < ntiles) tile_gload<FW, EGT_NT_FFN>(tr, xg + nxt * TILEF, lane, (int)min(16L, a.rows - nxt * 16));
     lds_sync();
     float4 x[TW];
 #pragma unroll
@@ -237,7 +240,7 @@ __global__ void __launch_bounds__(512, 2) k_ffn_fwd(FfnArgs a) {
     prev = tile;
     if (nxt >= ntiles) {   // last tile of this wave: flush
       lds_sync();
-      tile_from_lds<FW>(tl, a.y + tile * TILEF, lane, rows_valid);
+      tile_from_lds<FW>(tl, yg + tile * TILEF, lane, rows_valid);
     }
   }
 }
@@ -308,9 +311,11 @@ __global__ void __launch_bounds__(256) k_ffn_prep_bf(FfnArgs a) {
   }
 }
 
-template <int W, int ACT, bool SPLIT>
+template <int W, int ACT, bool SPLIT, typename T>
 __global__ void __launch_bounds__(512, 2) k_ffn_fwd_bf(FfnArgs a) {
   FFN_GEO(W);
+  const T* xg = reinterpret_cast<const T*>(a.x);
+  T* yg = reinterpret_cast<T*>(a.y);
   constexpr int NS1 = (TW + 1) / 2;
   constexpr int A1F = TH * NS1 * 2 * 256, A2F = TW * TW * 2 * 256;   // slab sizes in floats (1 KiB = 256 floats per [part][lane] block)
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -330,18 +335,18 @@ __global__ void __launch_bounds__(512, 2) k_ffn_fwd_bf(FfnArgs a) {
   const long ntiles = (a.rows + 15) / 16;
   const long stride = (long)gridDim.x * 8;
   long tile = (long)blockIdx.x * 8 + wave;
-  TileRegs<FW> tr;
-  if (tile < ntiles) tile_gload<FW, EGT_NT_FFN>(tr, a.x + tile * TILEF, lane, (int)min(16L, a.rows - tile * 16));
+  typename TileIn<FW, T>::type tr;
+  if (tile < ntiles) tile_gload<FW, EGT_NT_FFN>(tr, xg + tile * TILEF, lane, (int)min(16L, a.rows - tile * 16));
   long prev = -1;
   for (int it = 0; tile < ntiles; tile += stride, ++it) {
     const int rows_valid = (int)min(16L, a.rows - tile * 16);
     float* tl = tl0 + (it & 1) * TILEF;
     lds_sync();
     if (prev >= 0)   // stream out the previous tile's y from the other buffer
-      tile_from_lds<FW>(tl0 + ((it - 1) & 1) * TILEF, a.y + prev * TILEF, lane, (int)min(16L, a.rows - prev * 16));
+      tile_from_lds<FW>(tl0 + ((it - 1) & 1) * TILEF, yg + prev * TILEF, lane, (int)min(16L, a.rows - prev * 16));
     tile_lds_put<FW>(tl, tr, lane, rows_valid);
     const long nxt = tile + stride;
-    if (nxt < ntiles) tile_gload<FW, EGT_NT_FFN>(tr, a.x + nxt * TILEF, lane, (int)min(16L, a.rows - nxt * 16));
+    if (nxt < ntiles) tile_gload<FW, EGT_NT_FFN>(tr, xg + nxt * TILEF, lane, (int)min(16L, a.rows - nxt * 16));
     lds_sync();
     float4 x[TW];
 #pragma unroll
@@ -400,7 +405,7 @@ __global__ void __launch_bounds__(512, 2) k_ffn_fwd_bf(FfnArgs a) {
     prev = tile;
     if (nxt >= ntiles) {   // last tile of this wave: flush
       lds_sync();
-      tile_from_lds<FW>(tl, a.y + tile * TILEF, lane, rows_valid);
+      tile_from_lds<FW>(tl, yg + tile * TILEF, lane, rows_valid);
     }
   }
 }
@@ -410,9 +415,12 @@ __global__ void __launch_bounds__(512, 2) k_ffn_fwd_bf(FfnArgs a) {
 // dhid = W2 . dy, dxhat = W1p . dpre: 384 of the 640 fp32 MFMAs of a tile) to the bf16 matrix pipe (144 / 48
 // MFMAs of 16 cycles); the weight-gradient contractions over the ROW axis stay exact fp32 (their operands are
 // read transposed out of the fp32 LDS tiles).
-template <int W, int ACT, int MM>
+template <int W, int ACT, int MM, typename T>
 __global__ void __launch_bounds__(256, 1) k_ffn_bwd(FfnArgs a) {
   FFN_GEO(W);
+  const T* xg = reinterpret_cast<const T*>(a.x);
+  const T* dyg = reinterpret_cast<const T*>(a.dy);
+  T* dxg = reinterpret_cast<T*>(a.dx);
   constexpr int NS1 = (TW + 1) / 2;
   constexpr bool SPLIT = MM == EGT_MM_BF16X3;
   constexpr int S1F = MM ? TH * NS1 * 2 * 256 : SLABF, S4F = MM ? TW * TW * 2 * 256 : SLABF;   // slab sizes in floats
@@ -454,25 +462,25 @@ __global__ void __launch_bounds__(256, 1) k_ffn_bwd(FfnArgs a) {
   const long ntiles = (a.rows + 15) / 16;
   const long stride = (long)gridDim.x * 4;
   long tile = (long)blockIdx.x * 4 + wave;
-  TileRegs<FW> te, td;
+  typename TileIn<FW, T>::type te, td;
   if (tile < ntiles) {
     const int rv = (int)min(16L, a.rows - tile * 16);
-    tile_gload<FW, EGT_NT_FFN>(te, a.x + tile * TILEF, lane, rv);
-    tile_gload<FW, EGT_NT_FFN>(td, a.dy + tile * TILEF, lane, rv);
+    tile_gload<FW, EGT_NT_FFN>(te, xg + tile * TILEF, lane, rv);
+    tile_gload<FW, EGT_NT_FFN>(td, dyg + tile * TILEF, lane, rv);
   }
   long prev = -1;
   for (; tile < ntiles; tile += stride) {
     const int rows_valid = (int)min(16L, a.rows - tile * 16);
     lds_sync();
-    if (prev >= 0) tile_from_lds<FW>(dt, a.dx + prev * TILEF, lane, (int)min(16L, a.rows - prev * 16));   // dx of the previous tile
+    if (prev >= 0) tile_from_lds<FW>(dt, dxg + prev * TILEF, lane, (int)min(16L, a.rows - prev * 16));   // dx of the previous tile
     lds_sync();
     tile_lds_put<FW>(et, te, lane, rows_valid);     // rows past the end are zero: they add nothing to the sums
     tile_lds_put<FW>(dt, td, lane, rows_valid);
     const long nxt = tile + stride;
     if (nxt < ntiles) {
       const int rv = (int)min(16L, a.rows - nxt * 16);
-      tile_gload<FW, EGT_NT_FFN>(te, a.x + nxt * TILEF, lane, rv);
-      tile_gload<FW, EGT_NT_FFN>(td, a.dy + nxt * TILEF, lane, rv);
+      tile_gload<FW, EGT_NT_FFN>(te, xg + nxt * TILEF, lane, rv);
+      tile_gload<FW, EGT_NT_FFN>(td, dyg + nxt * TILEF, lane, rv);
     }
     lds_sync();
     // The phases below sit behind opaque always-true guards (a.guard == 0): the uniform branches
@@ -651,7 +659,7 @@ __global__ void __launch_bounds__(256, 1) k_ffn_bwd(FfnArgs a) {
     prev = tile;
   }
   lds_sync();
-  if (prev >= 0) tile_from_lds<FW>(dt, a.dx + prev * TILEF, lane, (int)min(16L, a.rows - prev * 16));
+  if (prev >= 0) tile_from_lds<FW>(dt, dxg + prev * TILEF, lane, (int)min(16L, a.rows - prev * 16));
 
   // ---- per-workgroup partial: (wave 0 + wave 2) + (wave 1 + wave 3), a pairwise tree through two LANE-LINEAR LDS images
   //      (accumulator tile k of lane l at float4 slot k*64 + l: conflict-free b128 moves, no read-modify-write).  The
@@ -859,8 +867,23 @@ __device__ __forceinline__ void ffn8_load(const float* src, long row, bool ok, f
   }
   v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
 }
+// bf16 rows (EGT_BF16): 16 bytes, ONE access per lane
+__device__ __forceinline__ void ffn8_load(const uint16_t* src, long row, bool ok, float (&v)[8]) {
+  uint4 u = make_uint4(0u, 0u, 0u, 0u);
+  if (ok) u = *reinterpret_cast<const uint4*>(src + row * 8);
+  const float4 lo = bf4_to_f4(make_uint2(u.x, u.y)), hi = bf4_to_f4(make_uint2(u.z, u.w));
+  v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+}
+__device__ __forceinline__ void ffn8_store(float* dst, long row, float4 lo, float4 hi) {
+  *reinterpret_cast<float4*>(dst + row * 8) = lo;
+  *reinterpret_cast<float4*>(dst + row * 8 + 4) = hi;
+}
+__device__ __forceinline__ void ffn8_store(uint16_t* dst, long row, float4 lo, float4 hi) {   // rounded once, here (RNE)
+  const uint2 l = f4_to_bf4(lo), h = f4_to_bf4(hi);
+  *reinterpret_cast<uint4*>(dst + row * 8) = make_uint4(l.x, l.y, h.x, h.y);
+}
 
-template <int ACT>
+template <int ACT, typename T>   // T: storage type of x / y (float, or uint16_t = bfloat16 bits)
 __global__ void __launch_bounds__(256, 4) k_ffn8_fwd(FfnArgs a) {
   const int lane = threadIdx.x & 63;
   const long nchunk = (a.rows + 63) / 64, stride = (long)gridDim.x * 4;
@@ -868,7 +891,7 @@ __global__ void __launch_bounds__(256, 4) k_ffn8_fwd(FfnArgs a) {
     const long row = ch * 64 + lane;
     const bool ok = row < a.rows;
     float x[8], xh[8], hid[16];
-    ffn8_load(a.x, row, ok, x);
+    ffn8_load(reinterpret_cast<const T*>(a.x), row, ok, x);
     cfp w = (cfp)a.x16;
     asm volatile("" : "+s"(w));   // per-chunk copy of the base: the weight fetches stay inside the loop (272 SGPRs do not exist)
 #pragma unroll
@@ -882,17 +905,16 @@ __global__ void __launch_bounds__(256, 4) k_ffn8_fwd(FfnArgs a) {
     for (int h = 0; h < 16; ++h)
 #pragma unroll
       for (int k = 0; k < 4; ++k) y[k] = ldw2(w, F8_W2 + h * 8 + 2 * k) * splat2(hid[h]) + y[k];
-    if (ok) {
-      *reinterpret_cast<float4*>(a.y + row * 8) = make_float4(y[0][0], y[0][1], y[1][0], y[1][1]);
-      *reinterpret_cast<float4*>(a.y + row * 8 + 4) = make_float4(y[2][0], y[2][1], y[3][0], y[3][1]);
-    }
+    if (ok)
+      ffn8_store(reinterpret_cast<T*>(a.y), row, make_float4(y[0][0], y[0][1], y[1][0], y[1][1]),
+                 make_float4(y[2][0], y[2][1], y[3][0], y[3][1]));
   }
 }
 
 #ifndef F8_BWD_OCC
 #define F8_BWD_OCC 3   // waves per SIMD: 4 (128 registers) spills ~20 values per chunk
 #endif
-template <int ACT>
+template <int ACT, typename T>
 __global__ void __launch_bounds__(256, F8_BWD_OCC) k_ffn8_bwd(FfnArgs a) {
   __shared__ __attribute__((aligned(16))) float sm[4 * 2 * 16 * F8_LD];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -909,8 +931,8 @@ __global__ void __launch_bounds__(256, F8_BWD_OCC) k_ffn8_bwd(FfnArgs a) {
     const long row = ch * 64 + lane;
     const bool ok = row < a.rows;
     float xh[8], dy[8], hid[16], dp[16];
-    ffn8_load(a.x, row, ok, xh);     // rows past the end are zero: xhat = dy = dpre = 0 add nothing to the sums
-    ffn8_load(a.dy, row, ok, dy);
+    ffn8_load(reinterpret_cast<const T*>(a.x), row, ok, xh);     // rows past the end are zero: xhat = dy = dpre = 0 add nothing to the sums
+    ffn8_load(reinterpret_cast<const T*>(a.dy), row, ok, dy);
     cfp w = (cfp)a.x16;
     asm volatile("" : "+s"(w));
     const float rstd = ffn8_ln(xh, a.ln_eps);
@@ -966,10 +988,7 @@ __global__ void __launch_bounds__(256, F8_BWD_OCC) k_ffn8_bwd(FfnArgs a) {
     float o8[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) o8[c] = dy[c] + rstd * (dxh[c >> 1][c & 1] - m1 - xh[c] * m2);
-    if (ok) {
-      *reinterpret_cast<float4*>(a.dx + row * 8) = make_float4(o8[0], o8[1], o8[2], o8[3]);
-      *reinterpret_cast<float4*>(a.dx + row * 8 + 4) = make_float4(o8[4], o8[5], o8[6], o8[7]);
-    }
+    if (ok) ffn8_store(reinterpret_cast<T*>(a.dx), row, make_float4(o8[0], o8[1], o8[2], o8[3]), make_float4(o8[4], o8[5], o8[6], o8[7]));
     lds_sync();
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -1010,7 +1029,7 @@ static size_t ffn_nwg_cap(size_t W) { return W <= 16 ? 1024 : (W <= 32 ? 512 : F
 static size_t ffn_al(size_t x) { return (x + 63) & ~(size_t)63; }
 
 extern "C" int egt_ffn_supported(const egt_ffn_desc* d) {
-  if (!d || d->dtype != EGT_F32 || d->rows <= 0) return 0;
+  if (!d || (d->dtype != EGT_F32 && d->dtype != EGT_BF16) || d->rows <= 0) return 0;   // EGT_BF16: x, y, dy, dx in bf16
   if (d->matmul != EGT_MM_F32 && d->matmul != EGT_MM_BF16X3 && d->matmul != EGT_MM_BF16) return 0;
   if (d->width == 8) return d->matmul == EGT_MM_F32 && (d->activation == EGT_ACT_RELU || d->activation == EGT_ACT_ELU);   // VALU kernels: exact fp32 only
   if (d->width != 16 && d->width != 32 && d->width != 48 && d->width != 64) return 0;
@@ -1020,9 +1039,12 @@ extern "C" int egt_ffn_supported(const egt_ffn_desc* d) {
 // Every launch and workspace decision of the fused FFN is made in ONE place, plan_ffn, once per C-ABI call: the size query returns
 // its total, ffn_fill binds the workspace from it, the entry points launch from it.  Workspace, in floats (width 8 lays out as 16):
 //   [slab1 slab2 slab3 slab4 | b1p | red | part x ffn_nwg_cap | sA1 sA2 sA3 sA4 (bf16 modes) | x16 (width 8: F8_* operands)]
+// The storage dtype changes only the kernel instances (x / y / dy / dx as T): the workspace holds fp32 operands and partials in
+// both, so an EGT_BF16 descriptor has the same plan sizes as its fp32 twin.
 enum FfnFamily { FFN_ROW8, FFN_F32, FFN_BF16 };   // k_ffn8_* (one row per lane) | k_ffn_* fp32 tiles | bf16 tiles (EGT_MM_BF16X3 / _BF16)
 struct FfnPlan {
   FfnFamily fam;
+  bool bf16;   // desc.dtype == EGT_BF16: the uint16_t (bfloat16) storage instances
   int W;   // layout width
   size_t slab, b1p, red, part, sA1, sA2, sA3, sA4, x16, total;
   int part_len;                 // floats per backward workgroup partial
@@ -1032,6 +1054,7 @@ struct FfnPlan {
 static FfnPlan plan_ffn(const egt_ffn_desc* d) {
   FfnPlan P{};
   P.fam = d->width == 8 ? FFN_ROW8 : (d->matmul == EGT_MM_F32 ? FFN_F32 : FFN_BF16);
+  P.bf16 = d->dtype == EGT_BF16;
   const size_t W = P.W = d->width == 8 ? 16 : d->width, TW = W / 16, NS1 = (TW + 1) / 2;
   const size_t slab = 2 * W * W, part = 2 * slab + 3 * W;                     // slab = W*2W floats; partial = T1 | T2 | s1 | s2
   const size_t a1 = 2 * TW * NS1 * 2 * 256, a2 = TW * TW * 2 * 256;           // sA1, sA3: [TH][NS1][2][256]; sA2, sA4: [TW][TW][2][256]
@@ -1071,8 +1094,9 @@ extern "C" size_t egt_ffn_workspace_bytes(const egt_ffn_desc* d) {
 static int ffn_fill(const egt_ffn_desc* d, const egt_ffn_params* p, void* ws, FfnPlan& P, FfnArgs& a) {
   if (!d || !p || !ws) EGT_FAIL(EGT_E_NULL, "desc/params/workspace is NULL");
   if (!egt_ffn_supported(d))
-    EGT_FAIL(EGT_E_SHAPE, "fused FFN covers widths 16/32/48/64 (and 8 with exact fp32 products), fp32, relu/elu "
-                          "(got width %d, rows %lld, act %d, matmul %d)", d->width, (long long)d->rows, d->activation, d->matmul);
+    EGT_FAIL(d->dtype != EGT_F32 && d->dtype != EGT_BF16 ? EGT_E_DTYPE : EGT_E_SHAPE,
+             "fused FFN covers widths 16/32/48/64 (and 8 with exact fp32 products), fp32 or bf16 x/y, relu/elu "
+             "(got width %d, rows %lld, dtype %d, act %d, matmul %d)", d->width, (long long)d->rows, d->dtype, d->activation, d->matmul);
   if (!p->norm_gamma || !p->norm_beta || !p->lr1_kernel || !p->lr1_bias || !p->lr2_kernel || !p->lr2_bias)
     EGT_FAIL(EGT_E_NULL, "an FFN parameter pointer is NULL");
   P = plan_ffn(d);
@@ -1092,45 +1116,51 @@ static int ffn_fill(const egt_ffn_desc* d, const egt_ffn_params* p, void* ws, Ff
   return EGT_OK;
 }
 
-// one instance of the tile kernels: width W, activation ACT, products MM (the forward of the bf16 modes: k_ffn_fwd_bf, SPLIT for bf16x3)
-template <int W, int ACT, int MM>
+// one instance of the tile kernels: width W, activation ACT, products MM (the forward of the bf16 modes: k_ffn_fwd_bf, SPLIT for bf16x3),
+// storage T of x / y / dy / dx
+template <int W, int ACT, int MM, typename T>
 static void ffn_launch_tiles(const FfnPlan& P, const FfnArgs& a, bool bwd, bool prep, hipStream_t st) {
   if (prep) {
     if constexpr (MM == EGT_MM_F32) EGT_LAUNCH("k_ffn_prep", k_ffn_prep<W>, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
     else EGT_LAUNCH("k_ffn_prep", k_ffn_prep_bf<W>, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
   }
-  if (bwd) egt_launch_planned<k_ffn_bwd<W, ACT, MM>>("k_ffn_bwd", P.bwd, st, a);
-  else if constexpr (MM == EGT_MM_F32) egt_launch_planned<k_ffn_fwd<W, ACT>>("k_ffn_fwd", P.fwd, st, a);
-  else egt_launch_planned<k_ffn_fwd_bf<W, ACT, MM == EGT_MM_BF16X3>>("k_ffn_fwd", P.fwd, st, a);
+  if (bwd) egt_launch_planned<k_ffn_bwd<W, ACT, MM, T>>("k_ffn_bwd", P.bwd, st, a);
+  else if constexpr (MM == EGT_MM_F32) egt_launch_planned<k_ffn_fwd<W, ACT, T>>("k_ffn_fwd", P.fwd, st, a);
+  else egt_launch_planned<k_ffn_fwd_bf<W, ACT, MM == EGT_MM_BF16X3, T>>("k_ffn_fwd", P.fwd, st, a);
 }
-template <int W>
+template <int W, typename T>
 static void ffn_launch_w(const FfnPlan& P, const FfnArgs& a, int act, bool bwd, bool prep, hipStream_t st) {
   switch (2 * a.mm + (act == EGT_ACT_RELU)) {   // products, activation
-    case 2 * EGT_MM_F32 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_F32>(P, a, bwd, prep, st); break;
-    case 2 * EGT_MM_F32: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_F32>(P, a, bwd, prep, st); break;
-    case 2 * EGT_MM_BF16X3 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_BF16X3>(P, a, bwd, prep, st); break;
-    case 2 * EGT_MM_BF16X3: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_BF16X3>(P, a, bwd, prep, st); break;
-    case 2 * EGT_MM_BF16 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_BF16>(P, a, bwd, prep, st); break;
-    default: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_BF16>(P, a, bwd, prep, st); break;
+    case 2 * EGT_MM_F32 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_F32, T>(P, a, bwd, prep, st); break;
+    case 2 * EGT_MM_F32: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_F32, T>(P, a, bwd, prep, st); break;
+    case 2 * EGT_MM_BF16X3 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_BF16X3, T>(P, a, bwd, prep, st); break;
+    case 2 * EGT_MM_BF16X3: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_BF16X3, T>(P, a, bwd, prep, st); break;
+    case 2 * EGT_MM_BF16 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_BF16, T>(P, a, bwd, prep, st); break;
+    default: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_BF16, T>(P, a, bwd, prep, st); break;
+  }
+}
+template <typename T>
+static void ffn_launch_t(const FfnPlan& P, const FfnArgs& a, int act, bool bwd, bool prep, hipStream_t st) {
+  if (P.fam == FFN_ROW8) {
+    if (prep) EGT_LAUNCH("k_ffn_prep", k_ffn8_prep, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
+    const EgtLaunch& s = bwd ? P.bwd : P.fwd;
+    if (bwd && act == EGT_ACT_RELU) EGT_LAUNCH("k_ffn_bwd", (k_ffn8_bwd<EGT_ACT_RELU, T>), dim3(s.grid), dim3(s.block), s.lds, st, a);
+    else if (bwd) EGT_LAUNCH("k_ffn_bwd", (k_ffn8_bwd<EGT_ACT_ELU, T>), dim3(s.grid), dim3(s.block), s.lds, st, a);
+    else if (act == EGT_ACT_RELU) EGT_LAUNCH("k_ffn_fwd", (k_ffn8_fwd<EGT_ACT_RELU, T>), dim3(s.grid), dim3(s.block), s.lds, st, a);
+    else EGT_LAUNCH("k_ffn_fwd", (k_ffn8_fwd<EGT_ACT_ELU, T>), dim3(s.grid), dim3(s.block), s.lds, st, a);
+    return;
+  }
+  switch (P.W) {
+    case 16: ffn_launch_w<16, T>(P, a, act, bwd, prep, st); break;
+    case 32: ffn_launch_w<32, T>(P, a, act, bwd, prep, st); break;
+    case 48: ffn_launch_w<48, T>(P, a, act, bwd, prep, st); break;
+    default: ffn_launch_w<64, T>(P, a, act, bwd, prep, st); break;
   }
 }
 // prep (unless a backward finds its workspace prepared), then the planned family's forward / backward instance
 static void ffn_launch(const FfnPlan& P, const FfnArgs& a, int act, bool bwd, bool prep, hipStream_t st) {
-  if (P.fam == FFN_ROW8) {
-    if (prep) EGT_LAUNCH("k_ffn_prep", k_ffn8_prep, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
-    const EgtLaunch& s = bwd ? P.bwd : P.fwd;
-    if (bwd && act == EGT_ACT_RELU) EGT_LAUNCH("k_ffn_bwd", k_ffn8_bwd<EGT_ACT_RELU>, dim3(s.grid), dim3(s.block), s.lds, st, a);
-    else if (bwd) EGT_LAUNCH("k_ffn_bwd", k_ffn8_bwd<EGT_ACT_ELU>, dim3(s.grid), dim3(s.block), s.lds, st, a);
-    else if (act == EGT_ACT_RELU) EGT_LAUNCH("k_ffn_fwd", k_ffn8_fwd<EGT_ACT_RELU>, dim3(s.grid), dim3(s.block), s.lds, st, a);
-    else EGT_LAUNCH("k_ffn_fwd", k_ffn8_fwd<EGT_ACT_ELU>, dim3(s.grid), dim3(s.block), s.lds, st, a);
-    return;
-  }
-  switch (P.W) {
-    case 16: ffn_launch_w<16>(P, a, act, bwd, prep, st); break;
-    case 32: ffn_launch_w<32>(P, a, act, bwd, prep, st); break;
-    case 48: ffn_launch_w<48>(P, a, act, bwd, prep, st); break;
-    default: ffn_launch_w<64>(P, a, act, bwd, prep, st); break;
-  }
+  if (P.bf16) ffn_launch_t<uint16_t>(P, a, act, bwd, prep, st);
+  else ffn_launch_t<float>(P, a, act, bwd, prep, st);
 }
 
 extern "C" int egt_ffn_fwd(const egt_ffn_desc* desc, const egt_ffn_params* params, const void* x, void* y,

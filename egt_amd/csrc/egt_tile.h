@@ -89,20 +89,7 @@ __device__ __forceinline__ void tile_from_lds(const float* tl, float* dst, int l
 }
 
 // ---- bf16 edge tensors (desc.dtype == EGT_BF16): same tiles, 8-byte global accesses; the
-// arithmetic, the LDS tiles and everything node-side stay fp32 ----
-__device__ __forceinline__ float4 bf4_to_f4(uint2 u) {
-  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xFFFF0000u),
-                     __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xFFFF0000u));
-}
-// fp32 -> bf16 pairs on v_cvt_pk_bf16_f32 (gfx950: round to nearest even, NaN stays NaN): one
-// instruction per two elements instead of the ~14 integer ops of a software rounding
-typedef __bf16 egt_bf2 __attribute__((ext_vector_type(2)));
-typedef float egt_f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t f2_to_bf2(float lo, float hi) {
-  const egt_bf2 b = __builtin_convertvector((egt_f2){lo, hi}, egt_bf2);
-  return *reinterpret_cast<const uint32_t*>(&b);
-}
-__device__ __forceinline__ uint2 f4_to_bf4(float4 v) { return make_uint2(f2_to_bf2(v.x, v.y), f2_to_bf2(v.z, v.w)); }
+// arithmetic, the LDS tiles and everything node-side stay fp32 (conversions: egt_common.h) ----
 template <int DE, bool NT = false>
 __device__ __forceinline__ void tile_gload(TileRegs<DE>& r, const uint16_t* src, int lane, int rows_valid) {
   using G = Geo<DE>;
@@ -133,6 +120,39 @@ __device__ __forceinline__ void tile_from_lds(const float* tl, uint16_t* dst, in
 }
 template <bool BF> struct EdgeT { typedef float type; };
 template <> struct EdgeT<true> { typedef uint16_t type; };
+
+// A streamed tile kept as loaded: bf16 bits in registers (half the prefetch registers of TileRegs), widened only when it
+// is put into the fp32 LDS tile.  TileIn<DE, T>: the prefetch buffer of a tile stored as T (float: TileRegs).
+template <int DE>
+struct TileRegsBf { uint2 v[(Geo<DE>::NF4 + 63) / 64]; };
+template <int DE, typename T> struct TileIn { typedef TileRegs<DE> type; };
+template <int DE> struct TileIn<DE, uint16_t> { typedef TileRegsBf<DE> type; };
+typedef unsigned egt_nt_v2u __attribute__((ext_vector_type(2)));
+template <int DE, bool NT = false>
+__device__ __forceinline__ void tile_gload(TileRegsBf<DE>& r, const uint16_t* src, int lane, int rows_valid) {
+  using G = Geo<DE>;
+  constexpr int NI = (G::NF4 + 63) / 64;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    int f = i * 64 + lane;
+    if (G::NF4 < 64) f &= (G::NF4 - 1);
+    const int row = f / G::NSLOT;
+    const int fc = row < rows_valid ? f : f - row * G::NSLOT;
+    if (NT) {
+      const egt_nt_v2u t = __builtin_nontemporal_load(reinterpret_cast<const egt_nt_v2u*>(src + (size_t)fc * 4));
+      r.v[i] = make_uint2(t[0], t[1]);
+    } else {
+      r.v[i] = *reinterpret_cast<const uint2*>(src + (size_t)fc * 4);
+    }
+  }
+}
+template <int DE>
+__device__ __forceinline__ void tile_lds_put(float* tl, const TileRegsBf<DE>& r, int lane, int rows_valid) {
+  TileRegs<DE> w;
+#pragma unroll
+  for (int i = 0; i < (Geo<DE>::NF4 + 63) / 64; ++i) w.v[i] = bf4_to_f4(r.v[i]);
+  tile_lds_put<DE>(tl, w, lane, rows_valid);
+}
 
 template <int DE>
 __device__ __forceinline__ void tile_lds_get(const float* tl, TileRegs<DE>& r, int lane) {

@@ -2,7 +2,9 @@
     y = x + Dense_2(act(Dense_1(LayerNorm(x))))
 (lib/models/graph_xformer_model_base.py:230-258, applied per channel type by ffn_block :309-324;
 pre-norm, no cross-talk, ffn_multiplier 2).  One C-ABI call per direction (egt_ffn_fwd / egt_ffn_bwd
-in include/egt_amd.h) for widths 8/16/32/48/64, fp32, elu / relu; there is no CPU fallback."""
+in include/egt_amd.h) for widths 8/16/32/48/64, elu / relu; there is no CPU fallback.  x (and so y, dy, dx) is fp32 or
+bf16 (EGT_BF16: bf16 in HBM; parameters, their gradients and all arithmetic stay fp32, y and dx are rounded once when
+stored)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -17,17 +19,24 @@ from .functional import _f32c, _need_gpu
 _ACT = {"relu": L.ACT_RELU, "elu": L.ACT_ELU}
 # how the matrix products are evaluated (include/egt_amd.h EGT_MM_*): "f32" exact fp32 MFMA; "bf16x3" 3-term
 # bfloat16 split on the bf16 matrix pipe (per-product error 2^-16, same parity tolerances as fp32);
-# "bf16" plain bfloat16 products (rtol 2e-2).  Tensors and accumulation are fp32 in every mode.
+# "bf16" plain bfloat16 products (rtol 2e-2).  Parameters and accumulation are fp32 in every mode.
 _MM = {"f32": L.MM_F32, "bf16x3": L.MM_BF16X3, "bf16": L.MM_BF16}
+# storage dtype of x / y / dy / dx -> desc.dtype
+_DTYPE = {torch.float32: L.EGT_F32, torch.bfloat16: L.EGT_BF16}
 
 
-def _desc(rows: int, width: int, activation: str, eps: float, matmul: str = "f32") -> L.FfnDesc:
+def _desc(rows: int, width: int, activation: str, eps: float, matmul: str = "f32", dtype=torch.float32) -> L.FfnDesc:
     if activation not in _ACT:
         raise ValueError(f"fused FFN activation must be one of {sorted(_ACT)} (got {activation!r})")
     if matmul not in _MM:
         raise ValueError(f"matmul must be one of {sorted(_MM)} (got {matmul!r})")
-    return L.FfnDesc(rows=rows, width=width, dtype=L.EGT_F32, activation=_ACT[activation], ln_eps=eps,
+    if dtype not in _DTYPE:
+        raise TypeError(f"fused FFN takes fp32 or bf16 x (got {dtype})")
+    return L.FfnDesc(rows=rows, width=width, dtype=_DTYPE[dtype], activation=_ACT[activation], ln_eps=eps,
                      matmul=_MM[matmul], flags=0)
+
+
+_TORCH = {v: k for k, v in _DTYPE.items()}   # desc.dtype -> storage dtype
 
 
 def _pstruct(tensors) -> L.FfnParams:
@@ -42,7 +51,10 @@ class _FusedFFN(torch.autograd.Function):
     def forward(ctx, x, desc, *params):
         _need_gpu(x)
         lib = L.load()
-        x = _f32c(x)
+        dt = _TORCH.get(desc.dtype)
+        if x.dtype != dt:
+            raise TypeError(f"fused FFN: the descriptor stores {dt}, x is {x.dtype}")
+        x = x.contiguous()
         ctx.param_objs = params
         params = tuple(_f32c(p) for p in params)
         y = torch.empty_like(x)
@@ -59,7 +71,7 @@ class _FusedFFN(torch.autograd.Function):
         lib = L.load()
         x, *params = ctx.saved_tensors
         desc = ctx.desc
-        dy = _f32c(dy)
+        dy = dy.to(x.dtype).contiguous()   # (autograd hands back the dtype of y = x's)
         dx = torch.empty_like(x)
         from .fused import grad_sinks
         grads, rets = grad_sinks(ctx.param_objs)
@@ -76,9 +88,9 @@ def ffn(x, norm_gamma, norm_beta, lr1_kernel, lr1_bias, lr2_kernel, lr2_bias, ac
     W = x.shape[-1]
     rows = x.numel() // W
     params = (norm_gamma, norm_beta, lr1_kernel, lr1_bias, lr2_kernel, lr2_bias)
-    desc = _desc(rows, W, activation, eps, matmul)
+    desc = _desc(rows, W, activation, eps, matmul, x.dtype)
     if not L.load().egt_ffn_supported(C.byref(desc)):
-        raise ValueError(f"fused FFN covers widths 8/16/32/48/64 in fp32 (width 8: exact fp32 products only); "
+        raise ValueError(f"fused FFN covers widths 8/16/32/48/64 in fp32 or bf16 (width 8: exact fp32 products only); "
                          f"got width {W}, dtype {x.dtype}, matmul {matmul!r}")
     return _FusedFFN.apply(x, desc, *params)
 

@@ -41,15 +41,33 @@ def _desc(blk, B, N, training, seed, edge_dtype=torch.float32, seed_device=None)
                        seed_device=None if seed_device is None else seed_device[0].ptr(seed_device[1]))
 
 
+def _unsupported(blk, training):
+    """The tensor-independent conditions of the fused kernels: why they cannot run `blk` (None: they can, as far as the
+    module's attributes go).  Shared by block_supported (per call) and bf16_refusal (at construction)."""
+    if blk.edge_channel_type not in ("residual", "constrained", "bias"):
+        return f"edge_channel_type {blk.edge_channel_type!r}"
+    if blk.add_n_norm or blk.edge_activation is not None:
+        return "add_n_norm / edge_activation"
+    if blk.mha.scale_degree or blk.mha.attn_dropout > 0 or blk.mha.num_virtual_nodes > 0:
+        return "scale_degree / attn_dropout / virtual nodes"
+    if training and (blk.node_dropout > 0 or blk.edge_dropout > 0):
+        return "node / edge dropout"
+    if blk.model_width % blk.num_heads:
+        return f"model_width {blk.model_width} is not a multiple of num_heads {blk.num_heads}"
+    return None
+
+
+def _lib_covers(blk, B, N, edge_dtype) -> bool:
+    """the library's answer for this geometry (egt_block_supported)"""
+    lib = L.load()
+    if not hasattr(lib, "egt_block_fwd"):
+        return False
+    return bool(lib.egt_block_supported(C.byref(_desc(blk, B, N, False, 0, edge_dtype))))
+
+
 def block_supported(blk, h, e, attn_mask, rand_mask) -> bool:
     """Configurations the fused kernels cover (everything else composes)."""
-    if blk.edge_channel_type not in ("residual", "constrained", "bias"):
-        return False
-    if blk.add_n_norm or blk.edge_activation is not None:
-        return False
-    if blk.mha.scale_degree or blk.mha.attn_dropout > 0 or blk.mha.num_virtual_nodes > 0:
-        return False
-    if blk.training and (blk.node_dropout > 0 or blk.edge_dropout > 0):
+    if _unsupported(blk, blk.training) is not None:
         return False
     if blk.edge_channel_type == "constrained" and attn_mask is None:
         return False
@@ -57,13 +75,23 @@ def block_supported(blk, h, e, attn_mask, rand_mask) -> bool:
         return False
     if h.dtype not in (torch.float32, torch.bfloat16):
         return False
-    if blk.model_width % blk.num_heads:
-        return False
-    lib = L.load()
-    if not hasattr(lib, "egt_block_fwd"):
-        return False
-    d = _desc(blk, h.shape[0], h.shape[1], False, 0, e.dtype)
-    return bool(lib.egt_block_supported(C.byref(d)))
+    return _lib_covers(blk, h.shape[0], h.shape[1], e.dtype)
+
+
+def bf16_refusal(blk):
+    """Why the fused block cannot run `blk` with bf16 edge tensors (None: it can).  bf16 edges exist only on the fused
+    path -- the composed ops are fp32 -- so a bf16 model checks this at construction instead of failing at its first step:
+    the tensor-independent conditions of block_supported (in training mode: a model trains) and the library's answer for
+    a bf16 descriptor (N does not change what the block covers)."""
+    if blk.fused is False or blk.fused == 'off':
+        return "the fused block is switched off"
+    why = _unsupported(blk, True)
+    if why is not None:
+        return why
+    if not _lib_covers(blk, 1, 16, torch.bfloat16):
+        return (f"geometry (num_heads {blk.num_heads}, head dim {blk.model_width // blk.num_heads}, "
+                f"edge_width {blk.edge_width}) is not covered by the fused block")
+    return None
 
 
 def _edge_c(t, dtype=None):

@@ -399,6 +399,26 @@ class EGTLayerStack(nn.Module):
         self.overlap_ffn = False     # node FFN on a side stream beside the edge FFN (small per-GPU batches; see forward)
         self._side = None
 
+    def check_edge_dtype(self, dtype):
+        """Raise ValueError unless every layer runs with `dtype` edge tensors: bf16 edges run on the fused block and the
+        fused edge FFN only (no composed bf16 path, and no silent fp32 fall-back)."""
+        if dtype == torch.float32:
+            return
+        if dtype != torch.bfloat16:
+            raise ValueError(f"edge tensors are fp32 or bf16 (got {dtype})")
+        from . import fused as FZ
+        for i, blk in enumerate(self.blocks):
+            why = FZ.bf16_refusal(blk)
+            if why:
+                raise ValueError(f"bf16 edge tensors need the fused block; layer {i}: {why}")
+        if self.ffn_edge is not None:
+            import ctypes as C
+            from . import _lib as L
+            from .ffn import _desc
+            f = self.ffn_edge[0]
+            if not L.load().egt_ffn_supported(C.byref(_desc(16, f.width, f.activation, 1e-3, f.matmul, torch.bfloat16))):
+                raise ValueError(f"bf16 edge tensors: the fused FFN does not cover width {f.width} with matmul={f.matmul!r}")
+
     def keras_named_parameters(self):
         """every parameter under the reference's Keras variable name: attention sub-layers
         '<layer>_<ii>/<var>' (graph_xformer_model_base.py:337 tags), FFN sub-layers

@@ -29,16 +29,28 @@ from .layers import EGTLayerStack, KerasDense, KerasLayerNorm, LN_EPS
 from .masks import node_mask_from_features
 
 
-def _embed_desc(B, N, De, upto_hop, clip_hops, num_edge_features, num_float_features=0, mask_value=-1.0) -> L.EmbedDesc:
+# edge_dtype keyword of the models / edge_embed -> storage dtype of the edge tensor e (EGT_BF16: bf16 in HBM, fp32 math)
+EDGE_DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16}
+
+
+def _edge_dtype(edge_dtype) -> torch.dtype:
+    if edge_dtype not in EDGE_DTYPES:
+        raise ValueError(f"edge_dtype must be one of {sorted(EDGE_DTYPES)} (got {edge_dtype!r})")
+    return EDGE_DTYPES[edge_dtype]
+
+
+def _embed_desc(B, N, De, upto_hop, clip_hops, num_edge_features, num_float_features=0, mask_value=-1.0,
+                dtype=torch.float32) -> L.EmbedDesc:
     return L.EmbedDesc(B=B, N=N, De=De, upto_hop=upto_hop, clip_hops=1 if clip_hops else 0,
-                       num_edge_features=num_edge_features, dtype=L.EGT_F32, num_float_features=num_float_features,
-                       mask_value=float(mask_value), reserved=0)
+                       num_edge_features=num_edge_features, dtype=L.EGT_BF16 if dtype == torch.bfloat16 else L.EGT_F32,
+                       num_float_features=num_float_features, mask_value=float(mask_value), reserved=0)
 
 
 class _EdgeEmbed(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, fmat, adj, table, kernel, bias, clip_hops, ffeat=None, mask_value=-1.0):
-        """kernel: [upto_hop + F, De] (adj_emb rows, then the rows of the real-valued features' Dense); ffeat [B,N,N,F]"""
+    def forward(ctx, fmat, adj, table, kernel, bias, clip_hops, ffeat=None, mask_value=-1.0, e_dtype=torch.float32):
+        """kernel: [upto_hop + F, De] (adj_emb rows, then the rows of the real-valued features' Dense); ffeat [B,N,N,F];
+        e_dtype: storage of e (fp32 or bf16; the hop planes and every parameter gradient stay fp32)"""
         _need_gpu(fmat, adj, table)
         lib = L.load()
         fmat = fmat.to(torch.int32).contiguous()
@@ -48,12 +60,12 @@ class _EdgeEmbed(torch.autograd.Function):
         B, N, _ = adj.shape
         F_ = 0 if ffeat is None else ffeat.shape[-1]
         K, De = kernel.shape[0] - F_, kernel.shape[1]
-        desc = _embed_desc(B, N, De, K, clip_hops, table.shape[0] - 1, F_, mask_value)
+        desc = _embed_desc(B, N, De, K, clip_hops, table.shape[0] - 1, F_, mask_value, e_dtype)
         if not lib.egt_edge_embed_supported(C.byref(desc)):
             raise ValueError(f"edge embedding kernel does not cover upto_hop={K}, edge_width={De}, "
                              f"num_edge_features={table.shape[0] - 1}")
         hops = torch.empty(K + F_, B, N, N, dtype=torch.float32, device=adj.device)   # plane-major (unit-stride planes)
-        e = torch.empty(B, N, N, De, dtype=torch.float32, device=adj.device)
+        e = torch.empty(B, N, N, De, dtype=e_dtype, device=adj.device)
         L.check(lib.egt_edge_embed_fwd(C.byref(desc), L.ptr(fmat), L.ptr(adj), L.ptr(ffeat), L.ptr(table), L.ptr(kernel),
                                        L.ptr(bias), L.ptr(hops), L.ptr(e), L.current_stream()))
         ctx.desc = desc
@@ -66,25 +78,28 @@ class _EdgeEmbed(torch.autograd.Function):
         lib = L.load()
         fmat, hops, table, kernel, bias = ctx.saved_tensors
         desc = ctx.desc
-        de = _f32c(de)
+        de = de.to(torch.bfloat16 if desc.dtype == L.EGT_BF16 else torch.float32).contiguous()
         dt, dk, db = torch.empty_like(table), torch.empty_like(kernel), torch.empty_like(bias)
         ws = torch.empty(lib.egt_edge_embed_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=de.device)
         L.check(lib.egt_edge_embed_bwd(C.byref(desc), L.ptr(fmat), L.ptr(hops), L.ptr(de), L.ptr(dt), L.ptr(dk),
                                        L.ptr(db), L.ptr(ws), L.current_stream()))
-        return None, None, dt, dk, db, None, None, None
+        return None, None, dt, dk, db, None, None, None, None
 
 
 def edge_embed(feature_matrix, graph_matrix, fm_table, adj_kernel, adj_bias, clip_hops=True, return_hops=False,
-               float_features=None, float_kernel=None, float_bias=None, mask_value=-1.0):
+               float_features=None, float_kernel=None, float_bias=None, mask_value=-1.0, edge_dtype="f32"):
     """e0 = fm_table[feature_matrix + 1] + stack_hops(graph_matrix) @ adj_kernel + adj_bias
           [+ Dense(Masking(float_features))]  ->  [B,N,N,De].
     float_features [B,N,N,F] (F <= 4) with its Dense kernel [F,De] / bias: the real-valued edge features of the
-    CIFAR10 / MNIST models (lib/models/cifar10/dc.py:70-73); they ride as F more planes behind the hop planes."""
+    CIFAR10 / MNIST models (lib/models/cifar10/dc.py:70-73); they ride as F more planes behind the hop planes.
+    edge_dtype "bf16": e is stored in bfloat16 (the fp32 sum rounded once, to nearest even); its gradient flows back
+    in bf16 and the parameter gradients stay fp32."""
     kernel, bias = adj_kernel, adj_bias
     if float_features is not None:
         kernel = torch.cat([adj_kernel, float_kernel], dim=0)        # autograd splits the gradient rows back
         bias = adj_bias + float_bias
-    e, hops = _EdgeEmbed.apply(feature_matrix, graph_matrix, fm_table, kernel, bias, clip_hops, float_features, mask_value)
+    e, hops = _EdgeEmbed.apply(feature_matrix, graph_matrix, fm_table, kernel, bias, clip_hops, float_features, mask_value,
+                               _edge_dtype(edge_dtype))
     return (e, hops) if return_hops else e
 
 
@@ -106,10 +121,13 @@ class ZincDCTransformer(nn.Module):
                  l2_reg=0, distance_loss=0., distance_target=8, add_n_norm=False, combine_layer_repr=False,
                  node2edge_xtalk=0., edge2node_xtalk=0., node2edge_embed=False, node_normalization='layer',
                  edge_normalization='layer', global_step_layer=False, max_length=None,
-                 seed=0, ffn_matmul='f32', **unknown):
+                 seed=0, ffn_matmul='f32', edge_dtype='f32', **unknown):
         super().__init__()
         if unknown:
             raise TypeError(f"{type(self).__name__}: unknown model_config keys {sorted(unknown)}")
+        # edge_dtype (a project key, like ffn_matmul): storage of the [B,N,N,De] edge tensor between the edge embedding, the
+        # attention blocks and the edge FFNs.  "bf16" halves its HBM traffic; node tensors, parameters and math stay fp32.
+        self.edge_dtype = _edge_dtype(edge_dtype)
         unsupported = dict(readout_edges=(readout_edges, False), num_virtual_nodes=(num_virtual_nodes, 0),
                            node_dropout=(node_dropout, 0), edge_dropout=(edge_dropout, 0), l2_reg=(l2_reg, 0),
                            distance_loss=(distance_loss, 0), add_n_norm=(add_n_norm, False),
@@ -144,6 +162,8 @@ class ZincDCTransformer(nn.Module):
                                     random_mask_prob=random_mask_prob, scale_degree=scale_degree, scaler_type=scaler_type,
                                     attn_dropout=attn_dropout, edge_activation=edge_activation, seed=seed,
                                     ffn_matmul=ffn_matmul, ffn_multiplier=ffn_multiplier)
+        if self.edge_dtype == torch.bfloat16:
+            self.layers.check_edge_dtype(self.edge_dtype)   # ValueError now, not a TypeError at the first step
         self.node_norm_final = KerasLayerNorm(model_width) if do_final_norm else None
         self.mlp_out = nn.ModuleList()
         w = model_width
@@ -224,11 +244,14 @@ class ZincDCTransformer(nn.Module):
         """the parameters the reference model owns (the dead last-layer edge parameters excluded)"""
         return list(self.keras_named_parameters().values())
 
+    def _edge_key(self):
+        return "bf16" if self.edge_dtype == torch.bfloat16 else "f32"
+
     def embeddings(self, node_features, feature_matrix, graph_matrix):
         mask = node_mask_from_features(node_features)                                  # masking.py:42-43
         h = F.embedding((node_features + 1).long(), self.node_emb)                      # zinc/dc.py:66-69
         e = edge_embed(feature_matrix, graph_matrix, self.fm_emb, self.adj_emb.kernel, self.adj_emb.bias,
-                       clip_hops=self.cfg["clip_hops"])                                 # :70-73 + graph_model_base.py:97-127
+                       clip_hops=self.cfg["clip_hops"], edge_dtype=self._edge_key())   # :70-73 + graph_model_base.py:97-127
         return h, e, mask
 
     def forward(self, node_features, feature_matrix, graph_matrix, attn_mask=None, singular_vectors=None,
@@ -311,7 +334,8 @@ class Cifar10DCTransformer(ZincDCTransformer):
         fmat = torch.full(graph_matrix.shape, -1, dtype=torch.int32, device=graph_matrix.device)
         e = edge_embed(fmat, graph_matrix, self.fm_emb, self.adj_emb.kernel, self.adj_emb.bias,
                        clip_hops=self.cfg["clip_hops"], float_features=feature_matrix, float_kernel=self.edge_emb.kernel,
-                       float_bias=self.edge_emb.bias, mask_value=self.mask_value)       # :71-73 + graph_model_base.py:97-127
+                       float_bias=self.edge_emb.bias, mask_value=self.mask_value,
+                       edge_dtype=self._edge_key())                                     # :71-73 + graph_model_base.py:97-127
         return h, e, mask
 
 

@@ -90,6 +90,8 @@ def default_config(scheme: str = "zinc.svd") -> Config:
         weight_file=":", prediction_bmult=2, optimizer="adam",
         use_hipgraph=False,      # (not a reference key) forward + loss + backward of a training batch replayed from a hipGraph
                                  # captured per batch geometry: egt_amd.graph; for launch-bound per-GPU batches
+        edge_dtype="f32",        # (not a reference key) storage of the [B,N,N,De] edge tensor: "f32" or "bf16" (fp32 math,
+                                 # bf16 in HBM: BASELINE config 3); handed to the model by get_model, not part of model_config
     )
     c.update(  # BaseDCModelScheme
         model_name="dc", dataset_name="dataset",
@@ -136,6 +138,9 @@ def make_config(user: Optional[dict], scheme: Optional[str] = None) -> Config:
             if k not in c:
                 raise KeyError(f'Unknown config "{k}"')
         c.update(user)
+    from .model import EDGE_DTYPES      # the models' edge_dtype keys: one list
+    if c.edge_dtype not in EDGE_DTYPES:
+        raise ValueError(f'config "edge_dtype" must be one of {list(EDGE_DTYPES)} (got {c.edge_dtype!r})')
     return c
 
 
@@ -357,11 +362,17 @@ class ZincSVDScheme:
     def get_model_config(self):
         return model_config(self.config)
 
+    def model_kwargs(self):
+        """the model's constructor keywords: model_config plus the project keys that are not reference keys and differ from
+        their defaults (edge_dtype); a model_factory gets the same dict, so a bf16 config is never silently trained in fp32"""
+        mc = self.get_model_config()
+        return mc if self.config.edge_dtype == "f32" else dict(mc, edge_dtype=self.config.edge_dtype)
+
     def get_model(self):
         if self.model_factory is not None:
-            return self.model_factory(self.get_model_config())
+            return self.model_factory(self.model_kwargs())
         from .model import ZincDCTransformer
-        return ZincDCTransformer(**self.get_model_config())
+        return ZincDCTransformer(**self.model_kwargs())
 
     def get_optimizer(self, params):
         c = self.config
@@ -747,9 +758,9 @@ class PatternSVDScheme(ZincSVDScheme):
 
     def get_model(self):
         if self.model_factory is not None:
-            return self.model_factory(self.get_model_config())
+            return self.model_factory(self.model_kwargs())
         from .model import PatternDCTransformer
-        return PatternDCTransformer(**self.get_model_config())
+        return PatternDCTransformer(**self.model_kwargs())
 
     def get_loss(self):
         from .model import weighted_sparse_xent_loss
@@ -886,9 +897,9 @@ class Cifar10SVDScheme(ZincSVDScheme):
 
     def get_model(self):
         if self.model_factory is not None:
-            return self.model_factory(self.get_model_config())
+            return self.model_factory(self.model_kwargs())
         from .model import Cifar10DCTransformer
-        return Cifar10DCTransformer(**self.get_model_config())
+        return Cifar10DCTransformer(**self.model_kwargs())
 
     def get_loss(self):
         from .model import sparse_xent_loss

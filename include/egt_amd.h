@@ -49,9 +49,11 @@ extern "C" {
 
 /* dtype */
 #define EGT_F32 0
-#define EGT_BF16 1 /* fused block/stack only: the EDGE tensors (e, e', d e', d e and the stack's
-                      saved e_l) are bfloat16 in HBM; node tensors, parameters, gradients of
-                      parameters and all arithmetic stay fp32 */
+#define EGT_BF16 1 /* the EDGE tensors are bfloat16 in HBM; node tensors, parameters, gradients of
+                      parameters, workspaces and all arithmetic stay fp32.  Taken by the fused
+                      block/stack (e, e', d e', d e and the stack's saved e_l), the channel FFN
+                      (x, y, dy, dx) and the edge embedding (e_out, d_e; the hop planes stay
+                      fp32); every other op is fp32 only */
 
 /* egt_attn_desc.flags — the operator attributes of EGT.__init__
  * (egt_layers.py:5-16) */
@@ -365,7 +367,7 @@ int egt_pair_bwd(const egt_block_desc* desc, const egt_block_params* params, con
 typedef struct egt_ffn_desc {
   int64_t rows;
   int32_t width;
-  int32_t dtype;      /* EGT_F32 */
+  int32_t dtype;      /* EGT_F32, or EGT_BF16: x, y, dy, dx in bfloat16 (parameters and their gradients fp32) */
   int32_t activation; /* EGT_ACT_* (config.activation) */
   float ln_eps;       /* 1e-3 */
   int32_t matmul;     /* EGT_MM_* */
@@ -426,7 +428,7 @@ typedef struct egt_embed_desc {
   int32_t upto_hop;           /* 1..16 */
   int32_t clip_hops;          /* clip every hop product to [0,1] (graph_model_base.py:114-115) */
   int32_t num_edge_features;  /* embedding rows - 1 (0: no integer feature matrix; pass a zero one-row table) */
-  int32_t dtype;              /* EGT_F32 */
+  int32_t dtype;              /* EGT_F32, or EGT_BF16: e_out and d_e in bfloat16 (hop planes fp32) */
   int32_t num_float_features; /* 0..4 real-valued edge features per pair: keras Masking(mask_value) + Dense
                                  (lib/models/cifar10/dc.py:70-73); the rows of that Dense kernel are appended to
                                  adj_kernel ([upto_hop + num_float_features, De]) and its bias added to adj_bias */
