@@ -25,6 +25,7 @@ EP_LAYERNORM, EP_GATES = 0x1, 0x2
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_ELU = 0, 1, 2, 3
 # egt_block_desc.flags
 BF_GATE, BF_ATTN_MASK, BF_TRAINING, BF_CLIP, BF_NO_EDGE_LN, BF_SEED_DEVICE = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+BF_STATIC_EDGE = 0x40   # 'bias' edge channels: e is an input only (with BF_NO_EDGE_LN; De = 8 pair kernels)
 
 
 class AttnDesc(C.Structure):
@@ -142,6 +143,7 @@ _PROTOS = {
 _OPTIONAL_PROTOS = {
     "egt_block_supported": (C.c_int, [C.POINTER(BlockDesc)]),
     "egt_block_bwd_kernel": (C.c_char_p, [C.POINTER(BlockDesc)]),
+    "egt_block_launch_form": (C.c_char_p, [C.POINTER(BlockDesc)]),
     "egt_block_saved_bytes": (C.c_size_t, [C.POINTER(BlockDesc)]),
     "egt_block_workspace_bytes": (C.c_size_t, [C.POINTER(BlockDesc)]),
     "egt_block_fwd": (C.c_int, [C.POINTER(BlockDesc), C.POINTER(BlockParams)] + [_VP] * 10),

@@ -29,6 +29,7 @@
 // k=lane>>4; B: k=lane>>4, col=lane&15; D: row=4*(lane>>4)+reg, col=lane&15).
 #include "egt_common.h"
 
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
@@ -104,6 +105,12 @@ static int block_check(const egt_block_desc* d, bool report) {
   }
   if ((size_t)d->B * d->N * d->N * d->H > 0xFFFFFFFFull) BAD(EGT_E_SHAPE, "B*N*N*H exceeds the 32-bit RNG counter");
   if ((d->flags & EGT_BF_SEED_DEVICE) && !d->seed_device) BAD(EGT_E_NULL, "EGT_BF_SEED_DEVICE set but seed_device is NULL");
+  if (d->flags & EGT_BF_STATIC_EDGE) {   // the static-edge mode lives in the De = 8 pair kernels (egt_narrow.hip) and nowhere else
+    if (!(d->flags & EGT_BF_NO_EDGE_LN)) BAD(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE is only valid together with EGT_BF_NO_EDGE_LN");
+    if (d->flags & EGT_BF_ATTN_MASK) BAD(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE does not take EGT_BF_ATTN_MASK");
+    if (d->De != 8) BAD(EGT_E_SHAPE, "EGT_BF_STATIC_EDGE covers edge_width 8 (got %d)", d->De);
+    if (block_env().no_narrow_fwd || block_env().no_narrow_bwd) BAD(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE needs the De = 8 pair kernels (EGT_NO_NARROW* is set)");
+  }
   return EGT_OK;
 #undef BAD
 }
@@ -325,6 +332,18 @@ extern "C" const char* egt_block_bwd_kernel(const egt_block_desc* d) {
   return g_bwd_kernel_name[(int)plan_block(d, mask_tensor(d, nullptr)).bwd];
 }
 
+// The launch forms plan_block chose for `d` (no mask tensor), as text: "fwd=<family>/<waves>w[/half] bwd=<family>/<waves>w/tl<rows>".
+// For tests and bench lines that must not assume which form a batch reaches.  Thread-local string; NULL when `d` is not covered.
+extern "C" const char* egt_block_launch_form(const egt_block_desc* d) {
+  if (block_check(d, false)) return nullptr;
+  const BlockPlan P = plan_block(d, mask_tensor(d, nullptr));
+  static const char* const fwd_name[] = {"k_narrow_fwd", "k_block_fwd_r4", "k_block_fwd"};
+  static thread_local char buf[128];
+  snprintf(buf, sizeof buf, "fwd=%s/%dw%s bwd=%s/%dw/tl%d", fwd_name[(int)P.fwd], P.fwd == FwdKernel::tile ? 4 : P.fwd_nw,
+           P.fwd_half ? "/half" : "", g_bwd_kernel_name[(int)P.bwd], P.bwd == BwdKernel::narrow ? P.bwd_nw : 4, P.TL);
+  return buf;
+}
+
 extern "C" size_t egt_block_saved_bytes(const egt_block_desc* d) {
   if (block_check(d, false)) return 0;
   return plan_block(d, mask_tensor(d, nullptr)).saved_total * sizeof(float);
@@ -336,10 +355,12 @@ extern "C" size_t egt_block_workspace_bytes(const egt_block_desc* d) {
 }
 
 // every pointer of a parameter / gradient table (the gate's two, #2 and #3, only when the block is gated)
+// (EGT_BF_STATIC_EDGE: norm_edge, #0 and #1, and dense_edge_r, #12 and #13, are neither read nor written)
 static int check_table(const egt_block_params* t, uint32_t flags, const char* what, int layer = -1) {
   const void* const* tp = reinterpret_cast<const void* const*>(t);
   for (int i = 0; i < 14; ++i) {
     if (tp[i] || (!(flags & EGT_BF_GATE) && (i == 2 || i == 3))) continue;
+    if ((flags & EGT_BF_STATIC_EDGE) && (i < 2 || i >= 12)) continue;
     if (layer < 0) EGT_FAIL(EGT_E_NULL, "%s #%d is NULL", what, i);
     EGT_FAIL(EGT_E_NULL, "layer %d %s #%d is NULL", layer, what, i);
   }
@@ -370,6 +391,7 @@ static int fill_block(const egt_block_desc* d, const egt_block_params* p, BlockA
   a.Wqkv = (const float*)p->dense_qkv_kernel; a.bqkv = (const float*)p->dense_qkv_bias;
   a.Wo = (const float*)p->dense_mha_kernel; a.bo = (const float*)p->dense_mha_bias;
   a.Wr = (const float*)p->dense_edge_r_kernel; a.br = (const float*)p->dense_edge_r_bias;
+  if (d->flags & EGT_BF_STATIC_EDGE) a.ne_g = a.ne_b = a.Wr = a.br = nullptr;   // never read: whatever the caller left there
   return EGT_OK;
 }
 
@@ -381,6 +403,7 @@ static void bind_grads(BlockArgs& a, const egt_block_params* g) {
   a.g_Wqkv = (float*)g->dense_qkv_kernel; a.g_bqkv = (float*)g->dense_qkv_bias;
   a.g_Wo = (float*)g->dense_mha_kernel; a.g_bo = (float*)g->dense_mha_bias;
   a.g_Wr = (float*)g->dense_edge_r_kernel; a.g_br = (float*)g->dense_edge_r_bias;
+  if (a.flags & EGT_BF_STATIC_EDGE) a.g_ne_g = a.g_ne_b = a.g_Wr = a.g_br = nullptr;   // never written
 }
 
 static void bind_common(const egt_block_desc* d, const BlockPlan& P, BlockArgs& a, const void* h, const void* e,
@@ -517,12 +540,14 @@ extern "C" int egt_block_fwd(const egt_block_desc* desc, const egt_block_params*
   BlockArgs a;
   int rc = fill_block(desc, params, a);
   if (rc) return rc;
-  if (!h || !e || !h_out || !e_out || !saved || !workspace)
+  const bool se = (desc->flags & EGT_BF_STATIC_EDGE) != 0;   // e is an input only: e_out is not written (may be NULL)
+  if (!h || !e || !h_out || (!e_out && !se) || !saved || !workspace)
     EGT_FAIL(EGT_E_NULL, "h/e/h_out/e_out/saved/workspace is NULL");
   if ((desc->flags & EGT_BF_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
+  if (se && host_rand_mask(desc, rand_mask)) EGT_FAIL(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE takes the in-kernel random mask only (rand_mask must be NULL)");
   const BlockPlan P = plan_block(desc, mask_tensor(desc, rand_mask));
   bind_common(desc, P, a, h, e, key_mask, attn_mask, rand_mask, (float*)saved, (float*)workspace);
-  a.h_out = (float*)h_out; a.e_out = (float*)e_out;
+  a.h_out = (float*)h_out; a.e_out = se ? nullptr : (float*)e_out;
   a.epi = 1;
   DISPATCH_BDE(desc->De, launch_fwd<DE>(a, P, (hipStream_t)stream, false));
   EGT_HIP_LAUNCH_CHECK("egt_block_fwd");
@@ -537,9 +562,11 @@ extern "C" int egt_block_bwd(const egt_block_desc* desc, const egt_block_params*
   BlockArgs a;
   int rc = fill_block(desc, params, a);
   if (rc) return rc;
-  if (!h || !e || !saved || !d_h_out || !d_e_out || !d_h || !d_e || !grads || !workspace)
+  const bool se = (desc->flags & EGT_BF_STATIC_EDGE) != 0;   // d_e_out NULL = zeros (not read)
+  if (!h || !e || !saved || !d_h_out || (!d_e_out && !se) || !d_h || !d_e || !grads || !workspace)
     EGT_FAIL(EGT_E_NULL, "h/e/saved/d_h_out/d_e_out/d_h/d_e/grads/workspace is NULL");
   if ((desc->flags & EGT_BF_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
+  if (se && host_rand_mask(desc, rand_mask)) EGT_FAIL(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE takes the in-kernel random mask only (rand_mask must be NULL)");
   // every layer's dh' is read again after dh was written (deferred dWo contraction): no in-place dh
   if (d_h == d_h_out) EGT_FAIL(EGT_E_FLAGS, "d_h must not alias d_h_out (d_e may alias d_e_out)");
   rc = check_table(grads, desc->flags, "gradient pointer");
@@ -572,6 +599,15 @@ struct StackLayout {
   size_t h_sz, e_sz;
 };
 
+// egt_stack_* keeps a layer's e' as the next layer's input: the static-edge mode is a per-block one (egt_block_fwd / _bwd)
+static int stack_flags_check(const egt_block_desc* d, bool report) {
+  if (d && (d->flags & EGT_BF_STATIC_EDGE)) {
+    if (report) egt_set_error("egt_stack_* does not take EGT_BF_STATIC_EDGE (use egt_block_fwd / egt_block_bwd per layer)");
+    return EGT_E_FLAGS;
+  }
+  return EGT_OK;
+}
+
 static StackLayout stack_layout(const egt_block_desc* d, const BlockPlan& P, int layers) {
   StackLayout S{};
   S.h_sz = al((size_t)d->B * d->N * d->d * d->H);
@@ -586,11 +622,11 @@ static StackLayout stack_layout(const egt_block_desc* d, const BlockPlan& P, int
 }
 
 extern "C" size_t egt_stack_saved_bytes(const egt_block_desc* d, int32_t layers) {
-  if (block_check(d, false) || layers < 1) return 0;
+  if (stack_flags_check(d, false) || block_check(d, false) || layers < 1) return 0;
   return stack_layout(d, plan_block(d, mask_tensor(d, nullptr)), layers).saved_total * sizeof(float);
 }
 extern "C" size_t egt_stack_workspace_bytes(const egt_block_desc* d, int32_t layers) {
-  if (block_check(d, false) || layers < 1) return 0;
+  if (stack_flags_check(d, false) || block_check(d, false) || layers < 1) return 0;
   return stack_layout(d, plan_block(d, mask_tensor(d, nullptr)), layers).ws_total * sizeof(float);
 }
 
@@ -609,6 +645,7 @@ extern "C" int egt_stack_fwd(const egt_block_desc* desc, int32_t layers, const e
                              const void* h, const void* e, const uint8_t* key_mask,
                              const void* attn_mask, void* h_out, void* e_out, void* saved,
                              void* workspace, void* stream) {
+  if (stack_flags_check(desc, true)) return EGT_E_FLAGS;   // (before the pointer checks: a descriptor-only answer)
   if (layers < 1) EGT_FAIL(EGT_E_SHAPE, "layers must be >= 1");
   if (!params || !h || !e || !h_out || !e_out || !saved || !workspace)
     EGT_FAIL(EGT_E_NULL, "params/h/e/h_out/e_out/saved/workspace is NULL");
@@ -660,6 +697,7 @@ extern "C" int egt_stack_bwd(const egt_block_desc* desc, int32_t layers, const e
                              const void* attn_mask, const void* saved, const void* d_h_out,
                              const void* d_e_out, void* d_h, void* d_e,
                              const egt_block_params* grads, void* workspace, void* stream) {
+  if (stack_flags_check(desc, true)) return EGT_E_FLAGS;   // (before the pointer checks: a descriptor-only answer)
   if (layers < 1) EGT_FAIL(EGT_E_SHAPE, "layers must be >= 1");
   if (layers > 64) EGT_FAIL(EGT_E_SHAPE, "at most 64 layers per stack call");
   if (!params || !grads || !h || !e || !saved || !d_h_out || !d_e_out || !d_h || !d_e || !workspace)

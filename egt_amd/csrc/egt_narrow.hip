@@ -166,7 +166,16 @@ template <bool BF, int NS> __device__ __forceinline__ v4f nrw_mm(const NrwOp<BF,
 // feature sets with compile-time flags (the run-time flag tests cost scalar branches / selects in every step)
 #define NRW_F_GATED 1
 #define NRW_F_CLIP 2
+#define NRW_F_BIAS 4              // static edge tensor (EGT_BF_STATIC_EDGE, 'bias' edge channels): see below
 #define NRW_F_RUNTIME (-1)
+#define NRW_F_RUNTIME_BIAS (-2)   // gate / clip read at run time + NRW_F_BIAS
+#define NRW_BIAS(FEAT) ((FEAT) >= 0 ? ((FEAT) & NRW_F_BIAS) != 0 : (FEAT) == NRW_F_RUNTIME_BIAS)
+// NRW_F_BIAS instances: e is an input only (EGT-simple: every layer reads the embedding's e; no norm_edge, no dense_edge_r).
+// COMPILED OUT, not branched around -- forward: the LayerNorm moments (both four-row sums, the rsq), wrA / brr and the
+// dense_edge_r MFMA, the e' store (a.e_out is never touched); backward: the LayerNorm recompute and its backward (the pair sum),
+// wrA and the dH_ext MFMA (dH_ext = 0), the de' half of the [xhat | de'] operand tile, the [H_hat | 1] tile write and its four
+// reads, the R product and its partial rows.  What stays of the edge gradient is de = de' + Wp.dGE; a.de_out may be NULL (zeros:
+// a launch-uniform switch, the de' requests are not issued).
 
 // ------------------------------------------------------------------------------------ forward ---
 // Workgroup = (graph b, 16 query rows), NW waves = NW equal parts of the key range (NW = 4; 8 for launches of at most one
@@ -209,6 +218,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? NRW_FWDM_OCC : 1) k_narrow_
   const bool gated = FEAT >= 0 ? (FEAT & NRW_F_GATED) != 0 : (a.flags & EGT_BF_GATE) != 0;
   const bool clip = FEAT >= 0 ? (FEAT & NRW_F_CLIP) != 0 : (a.flags & EGT_BF_CLIP) != 0;
   const bool ln_on = (a.flags & EGT_BF_NO_EDGE_LN) == 0;
+  constexpr bool SE = NRW_BIAS(FEAT);
   const int l = lg * RG + (HR ? (p & 7) : p);
   const bool row_ok = l < N;
   const bool row_own = row_ok && (!HR || p < 8);   // the lane that writes the row's V_att / statistics
@@ -228,10 +238,10 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? NRW_FWDM_OCC : 1) k_narrow_
   float brr[2];
   v4f c2r;
   const NrwOp<MV, 2> pwA = nrw_op<MV>(a.pw[(2 * q) * 16 + p], a.pw[(2 * q + 1) * 16 + p]);
-  const NrwOp<MV, 2> wrA = nrw_op<MV>(jm < 2 ? a.Wr[(2 * q) * NRW_DE + cm] : 0.0f, jm < 2 ? a.Wr[(2 * q + 1) * NRW_DE + cm] : 0.0f);
+  const NrwOp<MV, 2> wrA = SE ? NrwOp<MV, 2>() : nrw_op<MV>(jm < 2 ? a.Wr[(2 * q) * NRW_DE + cm] : 0.0f, jm < 2 ? a.Wr[(2 * q + 1) * NRW_DE + cm] : 0.0f);
 #pragma unroll
   for (int r = 0; r < 4; ++r) c2r[r] = a.pw[16 * 16 + 4 * q + r];
-  brr[0] = a.br[2 * q]; brr[1] = a.br[2 * q + 1];
+  brr[0] = SE ? 0.0f : a.br[2 * q]; brr[1] = SE ? 0.0f : a.br[2 * q + 1];
 
   // ---- the wave's key blocks ----
   const int nblk = (N + NRW_KB - 1) / NRW_KB;
@@ -294,11 +304,13 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? NRW_FWDM_OCC : 1) k_narrow_
       const int m = m0 + kl;
       // ---- norm_edge: the pair's 8 channels sit in the quad, two per lane (two-pass moments) ----
       float x0 = ev[kk].x, x1 = ev[kk].y;
-      const float mu = ln_on ? nrw_sum4rows(x0 + x1) * 0.125f : 0.0f;
-      x0 -= mu; x1 -= mu;
-      const float var = nrw_sum4rows(fmaf(x0, x0, x1 * x1)) * 0.125f;
-      const float rstd = ln_on ? __builtin_amdgcn_rsqf(var + a.ln_eps) : 1.0f;
-      x0 *= rstd; x1 *= rstd;
+      if constexpr (!SE) {
+        const float mu = ln_on ? nrw_sum4rows(x0 + x1) * 0.125f : 0.0f;
+        x0 -= mu; x1 -= mu;
+        const float var = nrw_sum4rows(fmaf(x0, x0, x1 * x1)) * 0.125f;
+        const float rstd = ln_on ? __builtin_amdgcn_rsqf(var + a.ln_eps) : 1.0f;
+        x0 *= rstd; x1 *= rstd;
+      }
       // ---- [attention_gates | dense_edge_b]: acc[r] = column 4q + r of the pair ----
       const v4f acc = nrw_mm<MV, 2>(pwA, nrw_op<MV>(x0, x1), c2r);
       // ---- scaled QK^T, clip, + E (egt_layers.py:79-86) ----
@@ -324,15 +336,17 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? NRW_FWDM_OCC : 1) k_narrow_
       if (!(NRW_ABL & 8)) apply_masks<false>(a, kmw[kl], mr, (size_t)(((uint32_t)pair_row + (uint32_t)m) * (uint32_t)BH), q, xl[kk], gl[kk]);   // (counter mod 2^32)
       if (kl >= nv) { xl[kk][0] = -3.0e38f; xl[kk][1] = -3.0e38f; }   // past the graph's last key: probability exactly 0
       // ---- dense_edge_r + res_edge: e' = e + H_hat.Wr + br, the lane's two channels ----
-      float2 eo;
-      {
-        v4f t = {ev[kk].x + brr[0], ev[kk].y + brr[1], 0.f, 0.f};
-        t = nrw_mm<MV, 2>(wrA, nrw_op<MV>(hh[0], hh[1]), t);
-        eo.x = t[0];
-        eo.y = t[1];
+      if constexpr (!SE) {
+        float2 eo;
+        {
+          v4f t = {ev[kk].x + brr[0], ev[kk].y + brr[1], 0.f, 0.f};
+          t = nrw_mm<MV, 2>(wrA, nrw_op<MV>(hh[0], hh[1]), t);
+          eo.x = t[0];
+          eo.y = t[1];
+        }
+        if (row_ok && kl < nv && !(NRW_ABL & 1)) LD::ustore(a.e_out, ugraph + (m - hp), loff + hp * NRW_DE, eo);   // (m - hp: wave-uniform)
+        if ((NRW_ABL & 1) && eo.x == 123.456f) LD::ustore(a.e_out, ugraph + (m - hp), loff + hp * NRW_DE, eo);
       }
-      if (row_ok && kl < nv && !(NRW_ABL & 1)) LD::ustore(a.e_out, ugraph + (m - hp), loff + hp * NRW_DE, eo);   // (m - hp: wave-uniform)
-      if ((NRW_ABL & 1) && eo.x == 123.456f) LD::ustore(a.e_out, ugraph + (m - hp), loff + hp * NRW_DE, eo);
     }
     if (blk + 1 < blk1) fetch_kv(blk + 1);   // (after the logits phase: its registers are free again)
     // ---- one online-softmax step for the block, x gate, A.V: the row's state never leaves the lane ----
@@ -451,6 +465,16 @@ static_assert(16 * QS_LD <= NRW_FWD_AREA(4), "the epilogue's staging rows fit th
 // holds the epilogue the geometry allows.  Kernel instances: bf16 or fp32 edge tensors, the gated + clipped block as
 // straight-line code (NRW_F_GATED | NRW_F_CLIP) or both read at run time (NRW_F_RUNTIME).
 static bool nrw_feat_full(const BlockArgs& a) { return (a.flags & EGT_BF_GATE) && (a.flags & EGT_BF_CLIP); }
+static bool nrw_static_edge(const BlockArgs& a) { return (a.flags & EGT_BF_STATIC_EDGE) != 0; }
+// the four feature sets of a storage type: {straight-line, run-time switched} x {residual, static edge}
+#define NRW_FEAT_DISPATCH(BF, CALL)                                                                                    \
+  do {                                                                                                                 \
+    if (nrw_static_edge(a)) {                                                                                          \
+      if (nrw_feat_full(a)) { constexpr int FT = NRW_F_GATED | NRW_F_CLIP | NRW_F_BIAS; CALL; }                        \
+      else { constexpr int FT = NRW_F_RUNTIME_BIAS; CALL; }                                                            \
+    } else if (nrw_feat_full(a)) { constexpr int FT = NRW_F_GATED | NRW_F_CLIP; CALL; }                                \
+    else { constexpr int FT = NRW_F_RUNTIME; CALL; }                                                                   \
+  } while (0)
 
 size_t egt_narrow_fwd_lds(int nw) { return ((size_t)(nw == 8 ? NRW_FWD_AREA(8) : NRW_FWD_AREA(4)) + 16 * QS_LD + 80) * 4; }
 
@@ -469,8 +493,8 @@ void egt_narrow_launch_fwd(BlockArgs& a, int nw, bool half, const EgtLaunch& s, 
   { static bool reg = false; if (!reg) { reg = true; atexit([] { g_nf.report(); }); } }
   a.dbg = g_nf.attach(s.grid);
 #endif
-  if (a.bf16) { if (nrw_feat_full(a)) nrw_fwd<true, NRW_F_GATED | NRW_F_CLIP>(a, nw, half, s, st); else nrw_fwd<true, NRW_F_RUNTIME>(a, nw, half, s, st); }
-  else { if (nrw_feat_full(a)) nrw_fwd<false, NRW_F_GATED | NRW_F_CLIP>(a, nw, half, s, st); else nrw_fwd<false, NRW_F_RUNTIME>(a, nw, half, s, st); }
+  if (a.bf16) NRW_FEAT_DISPATCH(true, (nrw_fwd<true, FT>(a, nw, half, s, st)));
+  else NRW_FEAT_DISPATCH(false, (nrw_fwd<false, FT>(a, nw, half, s, st)));
 #ifdef NRW_TIMING
   g_nf.collect(s.grid, st);
 #endif
@@ -515,6 +539,8 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
   const bool gated = FEAT >= 0 ? (FEAT & NRW_F_GATED) != 0 : (a.flags & EGT_BF_GATE) != 0;
   const bool clip = FEAT >= 0 ? (FEAT & NRW_F_CLIP) != 0 : (a.flags & EGT_BF_CLIP) != 0;
   const bool ln_on = (a.flags & EGT_BF_NO_EDGE_LN) == 0;
+  constexpr bool SE = NRW_BIAS(FEAT);
+  const bool de_in = !SE || a.de_out != nullptr;   // static edge: de' may be absent (zeros) -- launch-uniform
   constexpr int AREA = NW * NRW_M_WAVE > BWD_PRO_WS ? NW * NRW_M_WAVE : BWD_PRO_WS;
   static_assert(NW * 528 <= AREA, "edge partial staging must fit the per-wave area");
   float* kt = sm + wave * NRW_M_WAVE;      // [4 u][64 lanes][4]: K[4u .. 4u+3] of (key p, head pair q)
@@ -550,7 +576,10 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
       const int lo = min(cmt * 16 + p, N - 1) * NRW_DE + 2 * q;
       const size_t pr = ugraph + (size_t)(l_begin + cli) * N;
       en[slot] = LD::uload(a.e, pr, lo);
-      dn[slot] = LD::uload(a.de_out, pr, lo);
+      // (a.de may BE a.de_out -- the stack's chain, the static-edge route's accumulator: a lane reads and writes only its own
+      //  (row, key, channel pair) element, exactly once per launch, and this request, two steps ahead of the store, touches an
+      //  element no lane has written yet; a lane of a key past N reads key N - 1's element and stores nothing)
+      if (de_in) dn[slot] = LD::uload(a.de_out, pr, lo);
       if (++cli >= ((balance && cmt == mt_last) ? t1 - cmt * nl : nl)) { cli = 0; cmt += mt_step; }
     }
   };
@@ -573,8 +602,9 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
   NrwOp<MB, 4> wdA;
   auto load_weights = [&]() __attribute__((always_inline)) {
     pwA = nrw_op<MV>(a.pw[(2 * q) * 16 + p], a.pw[(2 * q + 1) * 16 + p]);           // [gates | E] column p from channels 2q, 2q+1
-    wrA = nrw_op<MB>(jm < 2 ? a.Wr[hm * NRW_DE + 2 * q] : 0.0f,                       // dH_ext of head hm from de' channels 2q, 2q+1
-                     jm < 2 ? a.Wr[hm * NRW_DE + 2 * q + 1] : 0.0f);
+    if constexpr (!SE)
+      wrA = nrw_op<MB>(jm < 2 ? a.Wr[hm * NRW_DE + 2 * q] : 0.0f,                     // dH_ext of head hm from de' channels 2q, 2q+1
+                       jm < 2 ? a.Wr[hm * NRW_DE + 2 * q + 1] : 0.0f);
     wdA = nrw_op<MB>(jm < 2 ? a.pw[hm * 16 + 4 * q] : 0.0f, jm < 2 ? a.pw[hm * 16 + 4 * q + 1] : 0.0f,   // d ehat of channel hm from
                      jm < 2 ? a.pw[hm * 16 + 4 * q + 2] : 0.0f, jm < 2 ? a.pw[hm * 16 + 4 * q + 3] : 0.0f);  // dGE columns 4q .. 4q+3
 #pragma unroll
@@ -596,6 +626,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
   v4f accT = {0.f, 0.f, 0.f, 0.f}, accR = {0.f, 0.f, 0.f, 0.f};
   float ssum = 0.f;   // column p of dGE summed over the pairs 4 s + q of every step (the B operands of the T product): ONE register
   const float hcst = p == 8 ? 1.0f : 0.0f;   // columns 8..15 of the [H_hat | 1] operand
+  const int pa = SE ? (p & 7) : p;           // static edge: the operand tile holds xhat only -- rows 8..15 of T (dropped below) repeat rows 0..7
   request(0);
   request(1);
   for (int mt = mt_first; mt <= mt_last; mt += mt_step) {
@@ -624,23 +655,27 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
       if (!kvalid) { ev = make_float2(0.f, 0.f); dyv = make_float2(0.f, 0.f); }   // a key past N: zero tile row
       // ---- norm_edge (recompute): the pair's 8 channels sit in lanes p, p+16, p+32, p+48 ----
       float x0 = ev.x, x1 = ev.y;
-      const float mu = ln_on ? nrw_sum4rows(x0 + x1) * 0.125f : 0.0f;
-      x0 -= mu; x1 -= mu;
-      const float var = nrw_sum4rows(fmaf(x0, x0, x1 * x1)) * 0.125f;
-      const float rstd = ln_on ? __builtin_amdgcn_rsqf(var + a.ln_eps) : 1.0f;
-      x0 *= rstd; x1 *= rstd;
+      float rstd = 1.0f;
+      if constexpr (!SE) {
+        const float mu = ln_on ? nrw_sum4rows(x0 + x1) * 0.125f : 0.0f;
+        x0 -= mu; x1 -= mu;
+        const float var = nrw_sum4rows(fmaf(x0, x0, x1 * x1)) * 0.125f;
+        rstd = ln_on ? __builtin_amdgcn_rsqf(var + a.ln_eps) : 1.0f;
+        x0 *= rstd; x1 *= rstd;
+      }
       // ---- projections (acc[r] = column 4q + r) and dH_ext (dhx[j] = head 2q + j) on the matrix core ----
       const v4f acc = nrw_mm<MV, 2>(pwA, nrw_op<MV>(x0, x1), (v4f){c2r[0], c2r[1], c2r[2], c2r[3]});
-      v4f dh4;
-      if constexpr (MB) dh4 = nrw_mm<true, 2>(wrA, nrw_op_raw(kvalid ? dyraw : 0u), (v4f){0.f, 0.f, 0.f, 0.f});   // de' is bfloat16 in memory already
+      v4f dh4 = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (SE) {}   // dH_ext = 0: no dense_edge_r
+      else if constexpr (MB) dh4 = nrw_mm<true, 2>(wrA, nrw_op_raw(kvalid ? dyraw : 0u), (v4f){0.f, 0.f, 0.f, 0.f});   // de' is bfloat16 in memory already
       else dh4 = nrw_mm<false, 2>(wrA, nrw_op<false>(dyv.x, dyv.y), (v4f){0.f, 0.f, 0.f, 0.f});
       // ---- weight-gradient operand A = [xhat | de'] of the step's 16 pairs (transposed through the operand tile) ----
       float wa[4], wb1[4], wb2[4];
       *reinterpret_cast<float2*>(op + p * NRW_OPW + 2 * q) = make_float2(x0, x1);
-      *reinterpret_cast<float2*>(op + p * NRW_OPW + 8 + 2 * q) = dyv;
+      if constexpr (!SE) *reinterpret_cast<float2*>(op + p * NRW_OPW + 8 + 2 * q) = dyv;
       asm volatile("" ::: "memory");
 #pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) wa[s4] = op[(4 * s4 + q) * NRW_OPW + p];
+      for (int s4 = 0; s4 < 4; ++s4) wa[s4] = op[(4 * s4 + q) * NRW_OPW + pa];
       asm volatile("" ::: "memory");
       // ---- logits, softmax / gate backward ----
       const float* qr = qd + li * QD_LD;
@@ -707,10 +742,12 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
       for (int s4 = 0; s4 < 4; ++s4) wb1[s4] = op[(4 * s4 + q) * NRW_OPW + p];
       asm volatile("" ::: "memory");
       ssum += (wb1[0] + wb1[1]) + (wb1[2] + wb1[3]);
-      *reinterpret_cast<float2*>(op + p * NRW_OPW + 2 * q) = make_float2(hh[0], hh[1]);
-      asm volatile("" ::: "memory");
+      if constexpr (!SE) {
+        *reinterpret_cast<float2*>(op + p * NRW_OPW + 2 * q) = make_float2(hh[0], hh[1]);
+        asm volatile("" ::: "memory");
 #pragma unroll
-      for (int s4 = 0; s4 < 4; ++s4) { const float t = op[(4 * s4 + q) * NRW_OPW + p]; wb2[s4] = p < 8 ? t : hcst; }
+        for (int s4 = 0; s4 < 4; ++s4) { const float t = op[(4 * s4 + q) * NRW_OPW + p]; wb2[s4] = p < 8 ? t : hcst; }
+      }
       asm volatile("" ::: "memory");   // the next step's tile writes stay behind these reads
       // ---- d ehat = Wp'.dGE (channels 2q, 2q+1 in d4[0], d4[1]) ----
       const v4f d4 = nrw_mm<MB, 4>(wdA, nrw_op<MB>(dge[0], dge[1], dge[2], dge[3]), (v4f){0.f, 0.f, 0.f, 0.f});
@@ -737,15 +774,18 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
       {
         const NrwOp<MB, 4> oa = nrw_op<MB>(wa[0], wa[1], wa[2], wa[3]);
         accT = nrw_mm<MB, 4>(oa, nrw_op<MB>(wb1[0], wb1[1], wb1[2], wb1[3]), accT);
-        accR = nrw_mm<MB, 4>(oa, nrw_op<MB>(wb2[0], wb2[1], wb2[2], wb2[3]), accR);
+        if constexpr (!SE) accR = nrw_mm<MB, 4>(oa, nrw_op<MB>(wb2[0], wb2[1], wb2[2], wb2[3]), accR);
       }
       // ---- LayerNorm backward; de = de' + ... ----
       {
-        float m1 = d4[0] + d4[1], m2 = fmaf(d4[0], x0, d4[1] * x1);
-        if (ln_on) { nrw_sum4rows_pair(m1, m2); m1 *= 0.125f; m2 *= 0.125f; } else { m1 = 0.f; m2 = 0.f; }
         float2 o;
-        o.x = dyv.x + rstd * (d4[0] - m1 - x0 * m2);
-        o.y = dyv.y + rstd * (d4[1] - m1 - x1 * m2);
+        if constexpr (SE) { o.x = dyv.x + d4[0]; o.y = dyv.y + d4[1]; }   // de = de' + Wp.dGE, stored where de' was read
+        else {
+          float m1 = d4[0] + d4[1], m2 = fmaf(d4[0], x0, d4[1] * x1);
+          if (ln_on) { nrw_sum4rows_pair(m1, m2); m1 *= 0.125f; m2 *= 0.125f; } else { m1 = 0.f; m2 = 0.f; }
+          o.x = dyv.x + rstd * (d4[0] - m1 - x0 * m2);
+          o.y = dyv.y + rstd * (d4[1] - m1 - x1 * m2);
+        }
         if (kvalid) LD::ustore(a.de, ugraph + (size_t)l * N, loff, o);
       }
     }
@@ -790,13 +830,13 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
     for (int r4 = 0; r4 < 4; ++r4) {
       const int row = 4 * kq + r4;
       ep[row * 16 + col] = row < 8 ? accT[r4] : 0.f;                          // T = rows 0..7 of [xhat | de']^T.dGE (channels >= De: 0)
-      ep[272 + ((row + 8) & 15) * 16 + col] = row >= 8 ? accR[r4] : 0.f;      // R = rows 8..15 of [xhat | de']^T.[H_hat | 1]
+      if constexpr (!SE) ep[272 + ((row + 8) & 15) * 16 + col] = row >= 8 ? accR[r4] : 0.f;      // R = rows 8..15 of [xhat | de']^T.[H_hat | 1]
     }
     if (q == 0) ep[256 + p] = ssum;
   }
   __syncthreads();
   float* out = a.epart + (size_t)wg * 528;
-  for (int i = threadIdx.x; i < 528; i += 64 * NW) {
+  for (int i = threadIdx.x; i < (SE ? 272 : 528); i += 64 * NW) {   // (static edge: T | s, no R rows)
     float v = (sm[i] + sm[528 + i]) + (sm[2 * 528 + i] + sm[3 * 528 + i]);
     if (NW == 8) v += (sm[4 * 528 + i] + sm[5 * 528 + i]) + (sm[6 * 528 + i] + sm[7 * 528 + i]);
     out[i] = v;
@@ -853,8 +893,8 @@ void egt_narrow_launch_bwd(BlockArgs& a, int nw, const EgtLaunch& s, hipStream_t
   }
   a.dbg = g_nt_dev; a.dbg2 = g_nt_dev2;
 #endif
-  if (a.bf16) { if (nrw_feat_full(a)) nrw_bwd<true, NRW_F_GATED | NRW_F_CLIP>(a, nw, s, st); else nrw_bwd<true, NRW_F_RUNTIME>(a, nw, s, st); }
-  else { if (nrw_feat_full(a)) nrw_bwd<false, NRW_F_GATED | NRW_F_CLIP>(a, nw, s, st); else nrw_bwd<false, NRW_F_RUNTIME>(a, nw, s, st); }
+  if (a.bf16) NRW_FEAT_DISPATCH(true, (nrw_bwd<true, FT>(a, nw, s, st)));
+  else NRW_FEAT_DISPATCH(false, (nrw_bwd<false, FT>(a, nw, s, st)));
 #ifdef NRW_TIMING
   (void)hipStreamSynchronize(st);
   if (++g_nt_launch > 20) {

@@ -94,16 +94,19 @@ __device__ void prep_wfrag(const PrepLayer& a, int Dh) {
   }
 }
 
+// (ne_g / ne_b NULL -- EGT_BF_STATIC_EDGE, 'bias' edge channels -- : no norm_edge to fold, gamma = 1 and beta = 0)
 __device__ void prep_layer(const PrepLayer& a, int De, int Dh, bool gated, float* red) {
   prep_wfrag(a, Dh);
   const int DEP = ((De + 15) / 16) * 16, t = threadIdx.x;
+  const bool ln = a.ne_g != nullptr;
   for (int idx = t; idx < DEP * 16; idx += blockDim.x) {
     const int c = idx >> 4, i = idx & 15;
     float v = 0.f;
     if (c < De) {
       const int hd = col_head(i);
-      if (col_is_gate(i)) v = gated ? a.ne_g[c] * a.Wg[c * BH + hd] : 0.f;
-      else v = a.ne_g[c] * a.We[c * BH + hd];
+      const float g = ln ? a.ne_g[c] : 1.0f;
+      if (col_is_gate(i)) v = gated ? g * a.Wg[c * BH + hd] : 0.f;
+      else v = g * a.We[c * BH + hd];
     }
     a.pw[idx] = v;
   }
@@ -111,7 +114,7 @@ __device__ void prep_layer(const PrepLayer& a, int De, int Dh, bool gated, float
     const int i = t & 15, part = t >> 4, hd = col_head(i);
     const bool isg = col_is_gate(i);
     float v = 0.f;
-    if (!isg || gated) {
+    if ((!isg || gated) && ln) {
       const float* W = isg ? a.Wg : a.We;
       for (int c = part; c < De; c += 16) v = fmaf(a.ne_b[c], W[c * BH + hd], v);
     }
@@ -860,8 +863,10 @@ __global__ void __launch_bounds__(256) k_edge_param_grads(EdgeGradArgs ga) {
   constexpr int EPM = 2 * EPG_MAX_DE * 16 + 16, EU = (EPM + 255) / 256, WU = (EPG_MAX_DE * BH + 255) / 256;
   __shared__ float er[EPM], wg[EPG_MAX_DE * BH], we[EPG_MAX_DE * BH], gam[EPG_MAX_DE], bet[EPG_MAX_DE];
   const EdgeGradLayer a = ga.L[blockIdx.x];
-  const int DE = ga.De, DEP = ((DE + 15) / 16) * 16, EP = 2 * DEP * 16 + 16, t = threadIdx.x;
   const bool gated = (ga.flags & EGT_BF_GATE) != 0;
+  // EGT_BF_STATIC_EDGE: no norm_edge (gamma = 1, beta = 0, no gradient of either), no dense_edge_r -- the partials end after T | s
+  const bool se = (ga.flags & EGT_BF_STATIC_EDGE) != 0;
+  const int DE = ga.De, DEP = ((DE + 15) / 16) * 16, EP = se ? DEP * 16 + 16 : 2 * DEP * 16 + 16, t = threadIdx.x;
   {
     float e[EU], g[WU], w[WU];
 #pragma unroll
@@ -872,7 +877,7 @@ __global__ void __launch_bounds__(256) k_edge_param_grads(EdgeGradArgs ga) {
       g[u] = gated ? a.Wg[i] : 0.f;
       w[u] = a.We[i];
     }
-    const float pg = a.ne_g[min(t, DE - 1)], pb = a.ne_b[min(t, DE - 1)];
+    const float pg = se ? 1.0f : a.ne_g[min(t, DE - 1)], pb = se ? 0.0f : a.ne_b[min(t, DE - 1)];
 #pragma unroll
     for (int u = 0; u < EU; ++u) if (t + 256 * u < EP) er[t + 256 * u] = e[u];
 #pragma unroll
@@ -894,6 +899,7 @@ __global__ void __launch_bounds__(256) k_edge_param_grads(EdgeGradArgs ga) {
     if (col_is_gate(i)) { if (gated) a.g_bg[hd] = s[i]; }
     else a.g_be[hd] = s[i];
   }
+  if (se) return;
   for (int c = t; c < DE; c += 256) {
     float dg = 0.f, db = 0.f;
 #pragma unroll
@@ -1044,7 +1050,7 @@ void egt_node_launch_reduce(BlockArgs* as, int n, int nwg_bwd, int EP, hipStream
       seg(a.spart + D3, a.g_nm_g, Dh, a.spart_n, SP);
       seg(a.spart + D3 + Dh, a.g_nm_b, Dh, a.spart_n, SP);
       seg(a.sbo, a.g_bo, Dh, a.sbo_n, Dh);
-      seg(a.epart, a.ered, EP, nwg_bwd, EP);
+      seg(a.epart, a.ered, (a.flags & EGT_BF_STATIC_EDGE) ? EP / 2 + 8 : EP, nwg_bwd, EP);   // static edge: T | s only (no R part)
     }
     s.nseg = k;
     EGT_LAUNCH("k_sum_segments", k_sum_segments, dim3(nblk), dim3(32 * SUM_G), 0, st, s);

@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
@@ -18,8 +19,19 @@ _GRAD_ORDER = (("norm_edge", "gamma"), ("norm_edge", "beta"),
                ("dense_edge_r", "kernel"), ("dense_edge_r", "bias"))
 
 
-def _desc(blk, B, N, training, seed, edge_dtype=torch.float32, seed_device=None) -> L.BlockDesc:
-    flags = 0
+_NO_STATIC_EDGE = None
+
+
+def static_edge_disabled() -> bool:
+    """EGT_NO_STATIC_EDGE=1 (read once per process): 'bias' stacks keep the per-layer route through the residual kernels."""
+    global _NO_STATIC_EDGE
+    if _NO_STATIC_EDGE is None:
+        _NO_STATIC_EDGE = os.environ.get("EGT_NO_STATIC_EDGE", "") not in ("", "0")
+    return _NO_STATIC_EDGE
+
+
+def _desc(blk, B, N, training, seed, edge_dtype=torch.float32, seed_device=None, static_edge=False) -> L.BlockDesc:
+    flags = L.BF_STATIC_EDGE if static_edge else 0
     if seed_device is not None:      # egt_amd.graph.DeviceSeeds: the kernels complete the seed from HBM
         flags |= L.BF_SEED_DEVICE
     if blk.gated:
@@ -57,12 +69,27 @@ def _unsupported(blk, training):
     return None
 
 
-def _lib_covers(blk, B, N, edge_dtype) -> bool:
+def _lib_covers(blk, B, N, edge_dtype, static_edge=False) -> bool:
     """the library's answer for this geometry (egt_block_supported)"""
     lib = L.load()
     if not hasattr(lib, "egt_block_fwd"):
         return False
-    return bool(lib.egt_block_supported(C.byref(_desc(blk, B, N, False, 0, edge_dtype))))
+    return bool(lib.egt_block_supported(C.byref(_desc(blk, B, N, False, 0, edge_dtype, static_edge=static_edge))))
+
+
+def static_edge_route(blk, h, e, rand_mask) -> bool:
+    """Whether this call of a 'bias' block takes the static-edge route (EGT_BF_STATIC_EDGE): the block was opted in by its
+    EGTLayerStack (`_static_edge`), the process switch is off, the random mask is the kernels' own, and the library covers the
+    flagged descriptor.  The library's answer is kept per (B, N, dtype)."""
+    if not getattr(blk, "_static_edge", False) or blk.edge_channel_type != "bias" or rand_mask is not None:
+        return False
+    if static_edge_disabled():
+        return False
+    key = (h.shape[0], h.shape[1], e.dtype)
+    ok = blk._static_ok.get(key)
+    if ok is None:
+        ok = blk._static_ok[key] = _lib_covers(blk, h.shape[0], h.shape[1], e.dtype, static_edge=True)
+    return ok
 
 
 def block_supported(blk, h, e, attn_mask, rand_mask) -> bool:
@@ -88,6 +115,8 @@ def bf16_refusal(blk):
     why = _unsupported(blk, True)
     if why is not None:
         return why
+    if getattr(blk, "_static_edge", False) and not static_edge_disabled() and _lib_covers(blk, 1, 16, torch.bfloat16, static_edge=True):
+        return None
     if not _lib_covers(blk, 1, 16, torch.bfloat16):
         return (f"geometry (num_heads {blk.num_heads}, head dim {blk.model_width // blk.num_heads}, "
                 f"edge_width {blk.edge_width}) is not covered by the fused block")
@@ -180,6 +209,68 @@ class _FusedBlock(torch.autograd.Function):
         return (dh, de, None, None, None, None, *rets)
 
 
+class _FusedBlockStatic(torch.autograd.Function):
+    """A 'bias' block of an EGTLayerStack on the static-edge route (EGT_BF_STATIC_EDGE).  The second output IS the input e
+    (an alias: no copy, no kernel write) and the next layer consumes it, so the per-layer chain of the edge gradient is
+    kept: a layer receives the sum of all later layers' edge gradients as the gradient of that output, adds its own
+    contribution and hands the result down.  One edge read per layer forward; one read + one read-modify-write per layer
+    backward; no fills, no autograd adds.
+
+    The accumulation is in place only in a buffer this class allocated itself (tagged `_egt_edge_acc` while it travels
+    between the layers of a stack; the stack's first layer removes the tag before the gradient leaves).  A gradient tensor
+    that came from anywhere else is read, and a fresh buffer is written: a caller's tensor is never mutated."""
+
+    @staticmethod
+    def forward(ctx, h, e, key_mask, desc, first, *params):
+        _need_gpu(h, e)
+        lib = L.load()
+        h = _f32c(h); e_in = e; e = _edge_c(e)
+        key_mask = _u8c(key_mask)
+        ctx.param_objs = params
+        params = tuple(None if p is None else _f32c(p) for p in params)
+        dev = h.device
+        h_out = torch.empty_like(h)
+        saved = torch.empty(lib.egt_block_saved_bytes(C.byref(desc)), dtype=torch.uint8, device=dev)
+        ws = torch.empty(lib.egt_block_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=dev)
+        pst = _params_struct(params)
+        L.check(lib.egt_block_fwd(C.byref(desc), C.byref(pst), L.ptr(h), L.ptr(e), L.ptr(key_mask),
+                                  None, None, L.ptr(h_out), None, L.ptr(saved), L.ptr(ws), L.current_stream()))
+        ctx.desc, ctx.first = desc, first
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(h, e, key_mask, saved, *params)
+        return h_out, e_in               # (returning an input: autograd hands out an alias of it)
+
+    @staticmethod
+    def backward(ctx, dh_out, de_out):
+        lib = L.load()
+        h, e, key_mask, saved, *params = ctx.saved_tensors
+        desc = ctx.desc
+        if dh_out is None:
+            dh_out = torch.zeros_like(h)
+        dh_out = _f32c(dh_out)
+        own = (de_out is not None and getattr(de_out, "_egt_edge_acc", False) and de_out.dtype == e.dtype
+               and de_out.is_contiguous() and de_out.shape == e.shape)
+        if own:
+            de = de_out                                 # ours: de[i] = de_out[i] + contribution, in place
+        else:
+            if de_out is not None:                      # someone else's tensor: read only
+                de_out = _edge_c(de_out, e.dtype)
+            de = torch.empty_like(e)                    # (de_out None: the kernel takes NULL as zeros -- no fill)
+        dh = torch.empty_like(h)
+        grads, rets = grad_sinks(ctx.param_objs)
+        ws = torch.empty(lib.egt_block_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=h.device)
+        pst, gst = _params_struct(params), _params_struct(grads)
+        L.check(lib.egt_block_bwd(C.byref(desc), C.byref(pst), L.ptr(h), L.ptr(e), L.ptr(key_mask),
+                                  None, None, L.ptr(saved), L.ptr(dh_out), L.ptr(de_out), L.ptr(dh), L.ptr(de),
+                                  C.byref(gst), L.ptr(ws), L.current_stream()))
+        if ctx.first:
+            if own:
+                del de._egt_edge_acc                    # leaves the stack: an ordinary tensor from here on
+        else:
+            de._egt_edge_acc = True
+        return (dh, de, None, None, None, *rets)
+
+
 def _block_params(blk, e):
     """the 14 C-ABI parameters of a block.  'bias' edge channels (EGT-simple) have no norm_edge and no
     dense_edge_r: identity LN parameters and a zero update are passed instead (EGT_BF_NO_EDGE_LN)."""
@@ -198,6 +289,17 @@ def block_fused(blk, h, e, mask, attn_mask, rand_mask=None):
     training = blk.training and blk.mha.random_mask_prob > 0.0
     sdev = blk.mha.seed_device if (training and rand_mask is None) else None
     seed = blk.mha.next_seed() if (training and rand_mask is None and sdev is None) else 0
+    if static_edge_route(blk, h, e, rand_mask):
+        # no identity / zero constants here: norm_edge and dense_edge_r do not exist for the kernels either
+        desc = _desc(blk, h.shape[0], h.shape[1], training, seed, e.dtype, sdev, static_edge=True)
+        mods = blk._modules
+        params = [None if (mod in ("norm_edge", "dense_edge_r") or mods.get(mod) is None) else mods[mod]._parameters[attr]
+                  for mod, attr in _GRAD_ORDER]
+        h, hdt = _node_io(h)
+        h2, e2 = _FusedBlockStatic.apply(h, e, mask, desc, bool(getattr(blk, "_static_first", True)), *params)
+        blk.last_edge_route = "static"
+        return (h2 if hdt is None else h2.to(hdt)), e2
+    blk.last_edge_route = "per-layer-bias" if blk.edge_channel_type == "bias" else "chained-residual"
     desc = _desc(blk, h.shape[0], h.shape[1], training, seed, e.dtype, sdev)
     params = _block_params(blk, e)
     if blk.edge_channel_type != "constrained":

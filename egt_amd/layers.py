@@ -391,6 +391,14 @@ class EGTLayerStack(nn.Module):
             [EGTBlock(seed=seed * 1000 + i, model_width=model_width, edge_width=edge_width, **block_kwargs)
              for i in range(model_height)])
         ect = block_kwargs.get('edge_channel_type', 'residual')
+        # 'bias' (EGT-simple): e is computed once by the embedding and read by every layer.  The stack opts its blocks into the
+        # static-edge route of the fused block (fused.static_edge_route: taken where the library covers the flagged
+        # descriptor, De = 8); an EGTBlock called on its own keeps today's behaviour.
+        for i, blk in enumerate(self.blocks):
+            blk._static_edge = ect == 'bias'
+            blk._static_first = i == 0
+            blk._static_ok = {}
+        self.last_edge_route = None   # "static" | "per-layer-bias" | "chained-residual" | "composed" | "mixed": what the last forward ran
         # FFN.__init__ raises ValueError for a width the fused FFN kernels do not cover (at
         # construction, not at the first forward: ADVICE r1)
         self.ffn_node = nn.ModuleList([FFN(model_width, activation=activation) for _ in range(model_height)])
@@ -454,8 +462,11 @@ class EGTLayerStack(nn.Module):
         does not contain the last layer's edge FFN in the reference either (a Keras functional model keeps only
         layers on a path to its outputs)."""
         last = len(self.blocks) - 1
+        routes = set()
         for i, blk in enumerate(self.blocks):
+            blk.last_edge_route = "composed"
             h, e = blk(h, e, mask, attn_mask)                  # layer/{i}/attention
+            routes.add(blk.last_edge_route)
             edge_ffn = self.ffn_edge is not None and not (skip_last_edge_ffn and i == last)
             if self.overlap_ffn and edge_ffn and h.is_cuda:
                 # the node and the edge FFN of a layer are independent (graph_xformer_model_base.py:309-324): the node FFN
@@ -477,4 +488,5 @@ class EGTLayerStack(nn.Module):
             if edge_ffn:                                        # layer/{i}/ffn
                 e = self.ffn_edge[i](e)
             h = self.ffn_node[i](h)
+        self.last_edge_route = routes.pop() if len(routes) == 1 else "mixed"
         return h, e

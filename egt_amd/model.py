@@ -137,7 +137,11 @@ class ZincDCTransformer(nn.Module):
         bad = {k: v for k, (v, d) in unsupported.items() if v != d}
         if bad:    # the reference model applies every one of these: training "a different model without a warning" is not an option
             raise NotImplementedError(f"{type(self).__name__} covers the shipped configs; not built: {bad}")
-        if edge_channel_type not in ('residual', 'constrained'):
+        # 'bias' = EGT-Simple (configs/ablation/egt_simple): e is computed once by the embedding and never updated; no
+        # norm_edge, dense_edge_r, edge FFN or edge_norm_final (graph_xformer_model_base.py:173-190, :313, :346).  Built for the
+        # head dims the fused block covers (d <= 8): the ZINC egt_simple configs (model_width 80, d = 10) stay refused.
+        if edge_channel_type not in ('residual', 'constrained', 'bias') or \
+                (edge_channel_type == 'bias' and model_width > 8 * num_heads):
             raise NotImplementedError("edge_channel_type must be residual or constrained")
         if use_svd and use_eig:
             raise NotImplementedError("use_svd and use_eig together (no reference model class mixes both)")
@@ -214,6 +218,8 @@ class ZincDCTransformer(nn.Module):
     # the Keras functional model contains only layers on a path to the outputs: with readout_edges=False the last
     # layer's dense_edge_r / edge FFN and edge_norm_final are NOT part of the reference model
     def _dead_edge_params(self):
+        if self.cfg["edge_channel_type"] == 'bias':
+            return []                    # EGT-Simple: every layer's gate and bias projections feed h; nothing else is edge-side
         last = self.layers.blocks[-1]
         dead = [last.dense_edge_r.kernel, last.dense_edge_r.bias]
         if self.layers.ffn_edge is not None:

@@ -237,6 +237,18 @@ int egt_edge_update_bwd(const egt_edge_desc* desc, const void* d_e_out,
                                   kernel when it runs, not by the host at launch).  A captured step replays
                                   with a fresh sample by advancing that word on the device; forward and
                                   backward of one step must see the same value */
+#define EGT_BF_STATIC_EDGE 0x40u /* 'bias' edge channels as what they are: e is an INPUT only (every layer of an
+                                  EGT-simple model reads the same e, :173-190).  Only valid with EGT_BF_NO_EDGE_LN.
+                                  Forward: e_out is never written and may be NULL; the norm_edge_* and dense_edge_r_*
+                                  parameter pointers are never read and may be NULL.  Backward: d_e_out may be NULL
+                                  (= zeros; it is then not read); d_e may alias d_e_out (d_e[i] = d_e_out[i] +
+                                  contribution, in place: a lane reads and writes only its own (row, key,
+                                  channel pair) element, exactly once per launch, and the requests that run ahead
+                                  touch elements no lane has written yet); the norm_edge_* / dense_edge_r_*
+                                  gradient pointers are never written and may be NULL.  The in-kernel random mask
+                                  only (rand_mask must be NULL).  egt_block_supported() answers 1 with this flag
+                                  exactly where the De = 8 pair kernels run: De = 8, d <= 8, H = 8, fp32 or bf16
+                                  edges, no EGT_BF_ATTN_MASK; egt_stack_* refuses it (EGT_E_FLAGS) */
 
 typedef struct egt_block_desc {
   int32_t B, N, H, d, De;   /* model_width Dh = d*H                             */
@@ -273,6 +285,10 @@ int egt_block_supported(const egt_block_desc* desc);
  * "k_block_bwd_v5", "k_block_bwd_v4", "k_block_bwd_v4r", "k_narrow_bwd": DESIGN.md section 4); NULL when `desc` is not covered.
  * Static string; for tests and bench lines (the launch profiler reports every family as "k_block_bwd"). */
 const char* egt_block_bwd_kernel(const egt_block_desc* desc);
+/* The launch forms the dispatch takes for `desc` when no mask tensor is passed, as text:
+ * "fwd=<family>/<waves>w[/half] bwd=<family>/<waves>w/tl<rows per workgroup>", e.g. "fwd=k_narrow_fwd/8w/half bwd=k_narrow_bwd/8w/tl8".
+ * Thread-local string, valid until the thread's next call; NULL when `desc` is not covered.  For tests and bench lines. */
+const char* egt_block_launch_form(const egt_block_desc* desc);
 /* bytes of the forward->backward buffer (V_att, softmax row statistics, packed
  * Q/K/V, the LN-folded edge weights and the MFMA-fragment-major copies of Wqkv / Wo the forward prepares: the backward
  * must be given the `saved` buffer of ITS forward call, made with the same parameter values) and of the scratch
