@@ -137,10 +137,6 @@ _PROTOS = {
     "egt_prof_names": (C.c_int, [C.c_char_p, C.c_size_t]),
     "egt_prof_collect_graph": (C.c_int, [C.c_int]),
     "egt_prof_forget_graphs": (C.c_int, []),
-}
-# entry points added by later build stages; bound when present, listed here so the
-# "every declared symbol is exported" test sees one table
-_OPTIONAL_PROTOS = {
     "egt_block_supported": (C.c_int, [C.POINTER(BlockDesc)]),
     "egt_block_bwd_kernel": (C.c_char_p, [C.POINTER(BlockDesc)]),
     "egt_block_launch_form": (C.c_char_p, [C.POINTER(BlockDesc)]),
@@ -181,10 +177,6 @@ def load():
     for name, (res, args) in _PROTOS.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    for name, (res, args) in _OPTIONAL_PROTOS.items():
-        if hasattr(lib, name):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
     if lib.egt_abi_version() != ABI_VERSION:
         raise EGTLibraryError("ABI version mismatch")
     _lib = lib

@@ -344,16 +344,6 @@ extern "C" const char* egt_block_launch_form(const egt_block_desc* d) {
   return buf;
 }
 
-extern "C" size_t egt_block_saved_bytes(const egt_block_desc* d) {
-  if (block_check(d, false)) return 0;
-  return plan_block(d, mask_tensor(d, nullptr)).saved_total * sizeof(float);
-}
-extern "C" size_t egt_block_workspace_bytes(const egt_block_desc* d) {
-  if (block_check(d, false)) return 0;
-  const BlockPlan P = plan_block(d, mask_tensor(d, nullptr));
-  return (P.common_total + P.layer_total) * sizeof(float);
-}
-
 // every pointer of a parameter / gradient table (the gate's two, #2 and #3, only when the block is gated)
 // (EGT_BF_STATIC_EDGE: norm_edge, #0 and #1, and dense_edge_r, #12 and #13, are neither read nor written)
 static int check_table(const egt_block_params* t, uint32_t flags, const char* what, int layer = -1) {
@@ -367,12 +357,8 @@ static int check_table(const egt_block_params* t, uint32_t flags, const char* wh
   return EGT_OK;
 }
 
-static int fill_block(const egt_block_desc* d, const egt_block_params* p, BlockArgs& a) {
-  int rc = block_check(d, true);
-  if (rc) return rc;
-  if (!p) EGT_FAIL(EGT_E_NULL, "params is NULL");
-  rc = check_table(p, d->flags, "block parameter");
-  if (rc) return rc;
+// descriptor and parameters of one layer (checked by check_call / bind_chain)
+static void fill_block(const egt_block_desc* d, const egt_block_params* p, BlockArgs& a) {
   a = BlockArgs{};
   a.B = d->B; a.N = d->N; a.De = d->De; a.DK = d->d; a.Dh = d->d * d->H;
   a.flags = d->flags;
@@ -392,7 +378,6 @@ static int fill_block(const egt_block_desc* d, const egt_block_params* p, BlockA
   a.Wo = (const float*)p->dense_mha_kernel; a.bo = (const float*)p->dense_mha_bias;
   a.Wr = (const float*)p->dense_edge_r_kernel; a.br = (const float*)p->dense_edge_r_bias;
   if (d->flags & EGT_BF_STATIC_EDGE) a.ne_g = a.ne_b = a.Wr = a.br = nullptr;   // never read: whatever the caller left there
-  return EGT_OK;
 }
 
 static void bind_grads(BlockArgs& a, const egt_block_params* g) {
@@ -406,18 +391,14 @@ static void bind_grads(BlockArgs& a, const egt_block_params* g) {
   if (a.flags & EGT_BF_STATIC_EDGE) a.g_ne_g = a.g_ne_b = a.g_Wr = a.g_br = nullptr;   // never written
 }
 
-static void bind_common(const egt_block_desc* d, const BlockPlan& P, BlockArgs& a, const void* h, const void* e,
-                        const uint8_t* km, const void* M, const uint8_t* rm, float* saved, float* ws) {
-  a.h = (const float*)h; a.e = (const float*)e; a.km = km;
+// what the layers of a call share: its masks and its random-mask source (bind_layer binds a layer's own regions)
+static void bind_common(const egt_block_desc* d, BlockArgs& a, const uint8_t* km, const void* M, const uint8_t* rm) {
+  a.km = km;
   a.M = (d->flags & EGT_BF_ATTN_MASK) ? (const float*)M : nullptr;
   a.rm = nullptr; a.rng_rm = 0;
   if ((d->flags & EGT_BF_TRAINING) && d->random_mask_prob > 0.0f) {
     if (rm) a.rm = rm; else a.rng_rm = 1;
   }
-  a.v_att = saved + P.v_att; a.stats = saved + P.stats; a.qkvp = saved + P.qkvp;
-  bind_ws(P, a, ws, ws + P.common_total);
-  a.pw = saved + P.pw_sv;
-  a.wfrag = a.Dh <= 64 ? saved + P.wfrag_sv : nullptr;
   a.prep = 1;
 }
 
@@ -532,65 +513,11 @@ static void launch_bwd(BlockArgs& a, const BlockPlan& P, hipStream_t st, bool to
   else if (!below) egt_node_launch_bwd(a, nullptr, true, st);   // bottom of the chain: only dQKV -> dh is left
 }
 
-
-extern "C" int egt_block_fwd(const egt_block_desc* desc, const egt_block_params* params,
-                             const void* h, const void* e, const uint8_t* key_mask,
-                             const void* attn_mask, const uint8_t* rand_mask, void* h_out,
-                             void* e_out, void* saved, void* workspace, void* stream) {
-  BlockArgs a;
-  int rc = fill_block(desc, params, a);
-  if (rc) return rc;
-  const bool se = (desc->flags & EGT_BF_STATIC_EDGE) != 0;   // e is an input only: e_out is not written (may be NULL)
-  if (!h || !e || !h_out || (!e_out && !se) || !saved || !workspace)
-    EGT_FAIL(EGT_E_NULL, "h/e/h_out/e_out/saved/workspace is NULL");
-  if ((desc->flags & EGT_BF_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
-  if (se && host_rand_mask(desc, rand_mask)) EGT_FAIL(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE takes the in-kernel random mask only (rand_mask must be NULL)");
-  const BlockPlan P = plan_block(desc, mask_tensor(desc, rand_mask));
-  bind_common(desc, P, a, h, e, key_mask, attn_mask, rand_mask, (float*)saved, (float*)workspace);
-  a.h_out = (float*)h_out; a.e_out = se ? nullptr : (float*)e_out;
-  a.epi = 1;
-  DISPATCH_BDE(desc->De, launch_fwd<DE>(a, P, (hipStream_t)stream, false));
-  EGT_HIP_LAUNCH_CHECK("egt_block_fwd");
-  return EGT_OK;
-}
-
-extern "C" int egt_block_bwd(const egt_block_desc* desc, const egt_block_params* params,
-                             const void* h, const void* e, const uint8_t* key_mask,
-                             const void* attn_mask, const uint8_t* rand_mask, const void* saved,
-                             const void* d_h_out, const void* d_e_out, void* d_h, void* d_e,
-                             const egt_block_params* grads, void* workspace, void* stream) {
-  BlockArgs a;
-  int rc = fill_block(desc, params, a);
-  if (rc) return rc;
-  const bool se = (desc->flags & EGT_BF_STATIC_EDGE) != 0;   // d_e_out NULL = zeros (not read)
-  if (!h || !e || !saved || !d_h_out || (!d_e_out && !se) || !d_h || !d_e || !grads || !workspace)
-    EGT_FAIL(EGT_E_NULL, "h/e/saved/d_h_out/d_e_out/d_h/d_e/grads/workspace is NULL");
-  if ((desc->flags & EGT_BF_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
-  if (se && host_rand_mask(desc, rand_mask)) EGT_FAIL(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE takes the in-kernel random mask only (rand_mask must be NULL)");
-  // every layer's dh' is read again after dh was written (deferred dWo contraction): no in-place dh
-  if (d_h == d_h_out) EGT_FAIL(EGT_E_FLAGS, "d_h must not alias d_h_out (d_e may alias d_e_out)");
-  rc = check_table(grads, desc->flags, "gradient pointer");
-  if (rc) return rc;
-  const BlockPlan P = plan_block(desc, mask_tensor(desc, rand_mask));
-  bind_common(desc, P, a, h, e, key_mask, attn_mask, rand_mask, (float*)saved, (float*)workspace);
-  a.prep = 0;   // prepared by the forward, kept in `saved`
-  a.dh_out = (const float*)d_h_out; a.de_out = (const float*)d_e_out;
-  a.dh = (float*)d_h; a.de = (float*)d_e;
-  bind_grads(a, grads);
-  DISPATCH_BDE(desc->De, launch_bwd<DE>(a, P, (hipStream_t)stream, true, nullptr, nullptr, node_fused_ok(a)));
-  egt_node_launch_wgrads(&a, 1, (hipStream_t)stream);
-  egt_node_launch_reduce(&a, 1, P.nwg_bwd, P.EP, (hipStream_t)stream);  // partial sums + edge param grads
-  EGT_HIP_LAUNCH_CHECK("egt_block_bwd");
-  return EGT_OK;
-}
-
-
-// ============================================================ layer stack =====
-// The model_height loop over attention blocks (graph_xformer_model_base.py:336-339) as ONE
-// call per direction: Ly x {node_pre, block_fwd, node_post} enqueued back to back, and in
-// backward the per-workgroup partial sums of ALL layers reduced by a single launch at the end
-// (they are off the dh/de critical path).  Layer l draws its random mask from
-// seed ^ golden * (l + 1).
+// ===================================================== one call: block or layer stack =====
+// A call runs a chain of `layers` blocks.  egt_stack_* chains model_height of them; egt_block_* is the one-layer chain of the
+// same layout (stack_layout puts `blk` at offset 0 then) with the caller's seed as it is and, optionally, a host random mask.
+// The argument checks (check_call) and the binding of the chain (bind_chain) are shared; an entry point keeps its outputs /
+// incoming gradients and its launch sequence.
 static uint64_t layer_seed(uint64_t seed, int l) { return seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(l + 1)); }
 
 struct StackLayout {
@@ -621,16 +548,18 @@ static StackLayout stack_layout(const egt_block_desc* d, const BlockPlan& P, int
   return S;
 }
 
-extern "C" size_t egt_stack_saved_bytes(const egt_block_desc* d, int32_t layers) {
-  if (stack_flags_check(d, false) || block_check(d, false) || layers < 1) return 0;
-  return stack_layout(d, plan_block(d, mask_tensor(d, nullptr)), layers).saved_total * sizeof(float);
+// saved / workspace bytes of a chain of `layers` blocks (0: not covered)
+static size_t chain_bytes(const egt_block_desc* d, int layers, bool stack, bool ws) {
+  if ((stack && stack_flags_check(d, false)) || block_check(d, false) || layers < 1) return 0;
+  const StackLayout S = stack_layout(d, plan_block(d, mask_tensor(d, nullptr)), layers);
+  return (ws ? S.ws_total : S.saved_total) * sizeof(float);
 }
-extern "C" size_t egt_stack_workspace_bytes(const egt_block_desc* d, int32_t layers) {
-  if (stack_flags_check(d, false) || block_check(d, false) || layers < 1) return 0;
-  return stack_layout(d, plan_block(d, mask_tensor(d, nullptr)), layers).ws_total * sizeof(float);
-}
+extern "C" size_t egt_block_saved_bytes(const egt_block_desc* d) { return chain_bytes(d, 1, false, false); }
+extern "C" size_t egt_block_workspace_bytes(const egt_block_desc* d) { return chain_bytes(d, 1, false, true); }
+extern "C" size_t egt_stack_saved_bytes(const egt_block_desc* d, int32_t layers) { return chain_bytes(d, layers, true, false); }
+extern "C" size_t egt_stack_workspace_bytes(const egt_block_desc* d, int32_t layers) { return chain_bytes(d, layers, true, true); }
 
-// the saved / workspace regions of layer l (bind_common bound layer 0's)
+// the saved / workspace regions of layer l
 static void bind_layer(const StackLayout& S, const BlockPlan& P, int l, BlockArgs& a, float* saved, float* ws) {
   float* bs = saved + S.blk + P.saved_total * (size_t)l;
   a.v_att = bs + P.v_att; a.stats = bs + P.stats; a.qkvp = bs + P.qkvp;
@@ -641,33 +570,129 @@ static void bind_layer(const StackLayout& S, const BlockPlan& P, int l, BlockArg
   a.wfrag = a.Dh <= 64 ? bs + P.wfrag_sv : nullptr;
 }
 
+// what the four entry points hand to check_call and bind_chain
+struct ChainCall {
+  const egt_block_desc* d;
+  int layers;
+  bool stack, bwd;
+  const egt_block_params *params, *grads;   // grads: backward only
+  const void *h, *e;
+  const uint8_t* km;
+  const void* M;
+  const uint8_t* rm;                        // host random mask: block calls only
+  float *saved, *ws;
+};
+
+// The argument checks of a call, in the order the entry points have always answered in.  `ptrs_ok`: none of the tensors the
+// entry point needs (`names`) is NULL; `alias`: d_h is d_h_out.  The parameter / gradient tables of a stack call are checked
+// layer by layer in bind_chain.
+static int check_call(const ChainCall& c, bool ptrs_ok, const char* names, bool alias) {
+  const egt_block_desc* d = c.d;
+  int rc;
+  if (c.stack) {   // flags and layer count before the pointers: a descriptor-only answer
+    if ((rc = stack_flags_check(d, true))) return rc;
+    if (c.layers < 1) EGT_FAIL(EGT_E_SHAPE, "layers must be >= 1");
+    if (c.bwd && c.layers > 64) EGT_FAIL(EGT_E_SHAPE, "at most 64 layers per stack call");
+    if (!ptrs_ok) EGT_FAIL(EGT_E_NULL, "params/%s is NULL", names);
+    if ((rc = block_check(d, true))) return rc;
+  } else {
+    if ((rc = block_check(d, true))) return rc;
+    if (!c.params) EGT_FAIL(EGT_E_NULL, "params is NULL");
+    if ((rc = check_table(c.params, d->flags, "block parameter"))) return rc;
+    if (!ptrs_ok) EGT_FAIL(EGT_E_NULL, "%s is NULL", names);
+  }
+  if ((d->flags & EGT_BF_ATTN_MASK) && !c.M) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
+  if ((d->flags & EGT_BF_STATIC_EDGE) && host_rand_mask(d, c.rm))
+    EGT_FAIL(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE takes the in-kernel random mask only (rand_mask must be NULL)");
+  if (c.layers > 64) EGT_FAIL(EGT_E_SHAPE, "at most 64 layers per stack call");   // (the forward's place for it)
+  // every layer's dh' is read again after dh was written (deferred dWo contraction): no in-place dh
+  if (alias) EGT_FAIL(EGT_E_FLAGS, "d_h must not alias d_h_out (d_e may alias d_e_out)");
+  return EGT_OK;
+}
+
+// Layers 0 .. layers-1 of a call bound into as[]: seed, parameters, input / activation addresses, masks, saved and workspace
+// regions, gradient tables.  A NULL table slot is reported for the layer the direction reaches first.
+static int bind_chain(const ChainCall& c, const BlockPlan& P, BlockArgs* as) {
+  const StackLayout S = stack_layout(c.d, P, c.layers);
+  for (int i = 0; i < c.layers; ++i) {
+    const int l = c.bwd ? c.layers - 1 - i : i;
+    int rc = c.stack ? check_table(c.params + l, c.d->flags, "block parameter") : EGT_OK;   // (a block call's: check_call)
+    if (!rc && c.bwd) rc = check_table(c.grads + l, c.d->flags, "gradient pointer", c.stack ? l : -1);
+    if (rc) return rc;
+    egt_block_desc dl = *c.d;
+    if (c.stack) dl.seed = layer_seed(c.d->seed, l);
+    BlockArgs& a = as[l];
+    fill_block(&dl, c.params + l, a);
+    a.h = l == 0 ? (const float*)c.h : c.saved + S.h_act + S.h_sz * (size_t)(l - 1);
+    a.e = l == 0 ? (const float*)c.e : c.saved + S.e_act + S.e_sz * (size_t)(l - 1);
+    bind_common(&dl, a, c.km, c.M, c.rm);
+    bind_layer(S, P, l, a, c.saved, c.ws);
+    if (c.bwd) bind_grads(a, c.grads + l);
+  }
+  return EGT_OK;
+}
+
+extern "C" int egt_block_fwd(const egt_block_desc* desc, const egt_block_params* params,
+                             const void* h, const void* e, const uint8_t* key_mask,
+                             const void* attn_mask, const uint8_t* rand_mask, void* h_out,
+                             void* e_out, void* saved, void* workspace, void* stream) {
+  const bool se = desc && (desc->flags & EGT_BF_STATIC_EDGE);   // e is an input only: e_out is not written (may be NULL)
+  const ChainCall c{desc, 1, false, false, params, nullptr, h, e, key_mask, attn_mask, rand_mask, (float*)saved, (float*)workspace};
+  int rc = check_call(c, h && e && h_out && (e_out || se) && saved && workspace, "h/e/h_out/e_out/saved/workspace", false);
+  if (rc) return rc;
+  const BlockPlan P = plan_block(desc, mask_tensor(desc, rand_mask));
+  BlockArgs a;
+  if ((rc = bind_chain(c, P, &a))) return rc;
+  a.h_out = (float*)h_out; a.e_out = se ? nullptr : (float*)e_out;
+  a.epi = 1;
+  DISPATCH_BDE(desc->De, launch_fwd<DE>(a, P, (hipStream_t)stream, false));
+  EGT_HIP_LAUNCH_CHECK("egt_block_fwd");
+  return EGT_OK;
+}
+
+extern "C" int egt_block_bwd(const egt_block_desc* desc, const egt_block_params* params,
+                             const void* h, const void* e, const uint8_t* key_mask,
+                             const void* attn_mask, const uint8_t* rand_mask, const void* saved,
+                             const void* d_h_out, const void* d_e_out, void* d_h, void* d_e,
+                             const egt_block_params* grads, void* workspace, void* stream) {
+  const bool se = desc && (desc->flags & EGT_BF_STATIC_EDGE);   // d_e_out NULL = zeros (not read)
+  const ChainCall c{desc, 1, false, true, params, grads, h, e, key_mask, attn_mask, rand_mask, (float*)saved, (float*)workspace};
+  int rc = check_call(c, h && e && saved && d_h_out && (d_e_out || se) && d_h && d_e && grads && workspace,
+                      "h/e/saved/d_h_out/d_e_out/d_h/d_e/grads/workspace", d_h == d_h_out);
+  if (rc) return rc;
+  const BlockPlan P = plan_block(desc, mask_tensor(desc, rand_mask));
+  BlockArgs a;
+  if ((rc = bind_chain(c, P, &a))) return rc;
+  a.prep = 0;   // prepared by the forward, kept in `saved`
+  a.dh_out = (const float*)d_h_out; a.de_out = (const float*)d_e_out;
+  a.dh = (float*)d_h; a.de = (float*)d_e;
+  DISPATCH_BDE(desc->De, launch_bwd<DE>(a, P, (hipStream_t)stream, true, nullptr, nullptr, node_fused_ok(a)));
+  egt_node_launch_wgrads(&a, 1, (hipStream_t)stream);
+  egt_node_launch_reduce(&a, 1, P.nwg_bwd, P.EP, (hipStream_t)stream);  // partial sums + edge param grads
+  EGT_HIP_LAUNCH_CHECK("egt_block_bwd");
+  return EGT_OK;
+}
+
+
+// ============================================================ layer stack =====
+// The model_height loop over attention blocks (graph_xformer_model_base.py:336-339) as ONE
+// call per direction: Ly x {node_pre, block_fwd, node_post} enqueued back to back, and in
+// backward the per-workgroup partial sums of ALL layers reduced by a single launch at the end
+// (they are off the dh/de critical path).  Layer l draws its random mask from
+// seed ^ golden * (l + 1)  (layer_seed).
 extern "C" int egt_stack_fwd(const egt_block_desc* desc, int32_t layers, const egt_block_params* params,
                              const void* h, const void* e, const uint8_t* key_mask,
                              const void* attn_mask, void* h_out, void* e_out, void* saved,
                              void* workspace, void* stream) {
-  if (stack_flags_check(desc, true)) return EGT_E_FLAGS;   // (before the pointer checks: a descriptor-only answer)
-  if (layers < 1) EGT_FAIL(EGT_E_SHAPE, "layers must be >= 1");
-  if (!params || !h || !e || !h_out || !e_out || !saved || !workspace)
-    EGT_FAIL(EGT_E_NULL, "params/h/e/h_out/e_out/saved/workspace is NULL");
-  if (block_check(desc, true)) return block_check(desc, true);
-  if ((desc->flags & EGT_BF_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
-  if (layers > 64) EGT_FAIL(EGT_E_SHAPE, "at most 64 layers per stack call");
+  const ChainCall c{desc, layers, true, false, params, nullptr, h, e, key_mask, attn_mask, nullptr, (float*)saved, (float*)workspace};
+  int rc = check_call(c, params && h && e && h_out && e_out && saved && workspace, "h/e/h_out/e_out/saved/workspace", false);
+  if (rc) return rc;
   const BlockPlan P = plan_block(desc, mask_tensor(desc, nullptr));
-  const StackLayout S = stack_layout(desc, P, layers);
-  float* sv = (float*)saved;
   BlockArgs as[64];
-  for (int l = 0; l < layers; ++l) {
-    egt_block_desc dl = *desc;
-    dl.seed = layer_seed(desc->seed, l);
-    BlockArgs& a = as[l];
-    int rc = fill_block(&dl, params + l, a);
-    if (rc) return rc;
-    const float* hin = l == 0 ? (const float*)h : sv + S.h_act + S.h_sz * (size_t)(l - 1);
-    const float* ein = l == 0 ? (const float*)e : sv + S.e_act + S.e_sz * (size_t)(l - 1);
-    bind_common(&dl, P, a, hin, ein, key_mask, attn_mask, nullptr, sv, (float*)workspace);
-    bind_layer(S, P, l, a, sv, (float*)workspace);
-    a.h_out = l == layers - 1 ? (float*)h_out : sv + S.h_act + S.h_sz * (size_t)l;
-    a.e_out = l == layers - 1 ? (float*)e_out : sv + S.e_act + S.e_sz * (size_t)l;
+  if ((rc = bind_chain(c, P, as))) return rc;
+  for (int l = 0; l < layers; ++l) {   // a layer writes the next layer's inputs (activations kept in `saved`)
+    as[l].h_out = l == layers - 1 ? (float*)h_out : const_cast<float*>(as[l + 1].h);
+    as[l].e_out = l == layers - 1 ? (float*)e_out : const_cast<float*>(as[l + 1].e);
   }
   // edge weights of every layer in one launch; each block's epilogue then finishes the node side
   // (dense_mha + residual) and already produces the next block's packed QKV, so a layer is ONE
@@ -697,30 +722,15 @@ extern "C" int egt_stack_bwd(const egt_block_desc* desc, int32_t layers, const e
                              const void* attn_mask, const void* saved, const void* d_h_out,
                              const void* d_e_out, void* d_h, void* d_e,
                              const egt_block_params* grads, void* workspace, void* stream) {
-  if (stack_flags_check(desc, true)) return EGT_E_FLAGS;   // (before the pointer checks: a descriptor-only answer)
-  if (layers < 1) EGT_FAIL(EGT_E_SHAPE, "layers must be >= 1");
-  if (layers > 64) EGT_FAIL(EGT_E_SHAPE, "at most 64 layers per stack call");
-  if (!params || !grads || !h || !e || !saved || !d_h_out || !d_e_out || !d_h || !d_e || !workspace)
-    EGT_FAIL(EGT_E_NULL, "params/grads/h/e/saved/d_h_out/d_e_out/d_h/d_e/workspace is NULL");
-  if (block_check(desc, true)) return block_check(desc, true);
-  if ((desc->flags & EGT_BF_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "ATTN_MASK set but attn_mask is NULL");
-  if (d_h == d_h_out) EGT_FAIL(EGT_E_FLAGS, "d_h must not alias d_h_out (d_e may alias d_e_out)");
+  const ChainCall c{desc, layers, true, true, params, grads, h, e, key_mask, attn_mask, nullptr, (float*)saved, (float*)workspace};
+  int rc = check_call(c, params && grads && h && e && saved && d_h_out && d_e_out && d_h && d_e && workspace,
+                      "grads/h/e/saved/d_h_out/d_e_out/d_h/d_e/workspace", d_h == d_h_out);
+  if (rc) return rc;
   const BlockPlan P = plan_block(desc, mask_tensor(desc, nullptr));
-  const StackLayout S = stack_layout(desc, P, layers);
-  float* sv = (float*)saved;
   BlockArgs as[64];
-  for (int l = layers - 1; l >= 0; --l) {
-    egt_block_desc dl = *desc;
-    dl.seed = layer_seed(desc->seed, l);
+  if ((rc = bind_chain(c, P, as))) return rc;
+  for (int l = 0; l < layers; ++l) {
     BlockArgs& a = as[l];
-    int rc = fill_block(&dl, params + l, a);
-    if (rc) return rc;
-    rc = check_table(grads + l, desc->flags, "gradient pointer", l);
-    if (rc) return rc;
-    const float* hin = l == 0 ? (const float*)h : sv + S.h_act + S.h_sz * (size_t)(l - 1);
-    const float* ein = l == 0 ? (const float*)e : sv + S.e_act + S.e_sz * (size_t)(l - 1);
-    bind_common(&dl, P, a, hin, ein, key_mask, attn_mask, nullptr, sv, (float*)workspace);
-    bind_layer(S, P, l, a, sv, (float*)workspace);
     // d_e flows in place below the top layer; every layer keeps its own dh (the deferred dWo
     // contraction reads dh' of each layer at the end)
     auto dhbuf = [&](int ll) { return (float*)workspace + P.common_total + P.layer_total * (size_t)ll + P.dhbuf; };
@@ -728,7 +738,6 @@ extern "C" int egt_stack_bwd(const egt_block_desc* desc, int32_t layers, const e
     a.de_out = l == layers - 1 ? (const float*)d_e_out : (const float*)d_e;
     a.dh = l == 0 ? (float*)d_h : dhbuf(l);
     a.de = (float*)d_e;
-    bind_grads(a, grads + l);
   }
   bool fuse = true;
   for (int l = 0; l < layers; ++l) fuse = fuse && node_fused_ok(as[l]);

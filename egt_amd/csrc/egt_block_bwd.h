@@ -1,6 +1,8 @@
 // Backward pair kernels of the fused attention block (included by egt_block.hip, which holds the dispatch):
 // k_block_bwd_v4 (mask tensors / ragged N / bf16), k_block_bwd_v5 (LDS-DMA staged e tiles: the headline),
-// k_block_bwd_v4r (narrow edge channels, R rows per iteration) and the weight-gradient epilogue they share.
+// k_block_bwd_v4r (narrow edge channels, R rows per iteration).  Each kernel carries its OWN copy of the P3 softmax / gate backward,
+// the dK / dV / dQ block and the weight-gradient (edge-partial) epilogue.  The copies are deliberate: the kernels sit at the register
+// edge, and moving a phase into a shared helper changes their instruction streams and register counts.
 #pragma once
 // Cache-policy hints of the streamed tiles (egt_tile.h) in k_block_bwd_v5: e_l is read once (LDS-DMA, non-temporal), de' was written by
 // the launch before and de is the next launch's de' (both cached: 134 MB of the 256 MB memory-side cache at the headline batch).

@@ -30,9 +30,10 @@ def static_edge_disabled() -> bool:
     return _NO_STATIC_EDGE
 
 
-def _desc(blk, B, N, training, seed, edge_dtype=torch.float32, seed_device=None, static_edge=False) -> L.BlockDesc:
+def _flags(blk, training=False, seed_device=False, static_edge=False) -> int:
+    """egt_block_desc.flags of a block"""
     flags = L.BF_STATIC_EDGE if static_edge else 0
-    if seed_device is not None:      # egt_amd.graph.DeviceSeeds: the kernels complete the seed from HBM
+    if seed_device:                  # egt_amd.graph.DeviceSeeds: the kernels complete the seed from HBM
         flags |= L.BF_SEED_DEVICE
     if blk.gated:
         flags |= L.BF_GATE
@@ -42,20 +43,45 @@ def _desc(blk, B, N, training, seed, edge_dtype=torch.float32, seed_device=None,
         flags |= L.BF_TRAINING
     if blk.edge_channel_type == "bias":
         flags |= L.BF_NO_EDGE_LN
-    lo = hi = 0.0
     if blk.mha.clip_logits_value is not None:
         flags |= L.BF_CLIP
+    return flags
+
+
+def _edge_code(edge_dtype) -> int:
+    return L.EGT_BF16 if edge_dtype == torch.bfloat16 else L.EGT_F32
+
+
+def _desc(blk, B, N, training, seed, edge_dtype=torch.float32, seed_device=None, static_edge=False) -> L.BlockDesc:
+    lo = hi = 0.0
+    if blk.mha.clip_logits_value is not None:
         lo, hi = float(blk.mha.clip_logits_value[0]), float(blk.mha.clip_logits_value[1])
     return L.BlockDesc(B=B, N=N, H=blk.num_heads, d=blk.model_width // blk.num_heads,
-                       De=blk.edge_width, dtype=L.EGT_BF16 if edge_dtype == torch.bfloat16 else L.EGT_F32, flags=flags, clip_lo=lo, clip_hi=hi,
+                       De=blk.edge_width, dtype=_edge_code(edge_dtype), flags=_flags(blk, training, seed_device is not None, static_edge),
+                       clip_lo=lo, clip_hi=hi,
                        random_mask_prob=float(blk.mha.random_mask_prob), ln_eps=1e-3, reserved=0,
                        seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
                        seed_device=None if seed_device is None else seed_device[0].ptr(seed_device[1]))
 
 
+_LIB_ANSWERS = {}   # (entry point, B, N, H, d, De, dtype, flags) -> bool
+
+
+def _lib_covers(entry, blk, B, N, edge_dtype, static_edge=False) -> bool:
+    """The library's answer (`entry`: egt_block_supported / egt_pair_supported) for a block's geometry, asked once per
+    descriptor: the key is every descriptor field those read, built from the block's attributes as they are now."""
+    key = (entry, B, N, blk.num_heads, blk.model_width // blk.num_heads, blk.edge_width, _edge_code(edge_dtype),
+           _flags(blk, static_edge=static_edge))
+    ok = _LIB_ANSWERS.get(key)
+    if ok is None:
+        d = _desc(blk, B, N, False, 0, edge_dtype, static_edge=static_edge)
+        ok = _LIB_ANSWERS[key] = bool(getattr(L.load(), entry)(C.byref(d)))
+    return ok
+
+
 def _unsupported(blk, training):
     """The tensor-independent conditions of the fused kernels: why they cannot run `blk` (None: they can, as far as the
-    module's attributes go).  Shared by block_supported (per call) and bf16_refusal (at construction)."""
+    module's attributes go)."""
     if blk.edge_channel_type not in ("residual", "constrained", "bias"):
         return f"edge_channel_type {blk.edge_channel_type!r}"
     if blk.add_n_norm or blk.edge_activation is not None:
@@ -69,55 +95,65 @@ def _unsupported(blk, training):
     return None
 
 
-def _lib_covers(blk, B, N, edge_dtype, static_edge=False) -> bool:
-    """the library's answer for this geometry (egt_block_supported)"""
-    lib = L.load()
-    if not hasattr(lib, "egt_block_fwd"):
-        return False
-    return bool(lib.egt_block_supported(C.byref(_desc(blk, B, N, False, 0, edge_dtype, static_edge=static_edge))))
+_FLOATS = (torch.float32, torch.bfloat16)
 
 
-def static_edge_route(blk, h, e, rand_mask) -> bool:
-    """Whether this call of a 'bias' block takes the static-edge route (EGT_BF_STATIC_EDGE): the block was opted in by its
-    EGTLayerStack (`_static_edge`), the process switch is off, the random mask is the kernels' own, and the library covers the
-    flagged descriptor.  The library's answer is kept per (B, N, dtype)."""
-    if not getattr(blk, "_static_edge", False) or blk.edge_channel_type != "bias" or rand_mask is not None:
-        return False
-    if static_edge_disabled():
-        return False
-    key = (h.shape[0], h.shape[1], e.dtype)
-    ok = blk._static_ok.get(key)
-    if ok is None:
-        ok = blk._static_ok[key] = _lib_covers(blk, h.shape[0], h.shape[1], e.dtype, static_edge=True)
-    return ok
+def _covered(blk, B, N, node_dtype, edge_dtype, on_gpu, attn_mask, rand_mask, training):
+    """What the fused kernels cover of one call: (edge route of the fused block or None, whether the fused pair operator
+    covers it).  Every condition of either lives here and nowhere else."""
+    if not on_gpu or _unsupported(blk, training) is not None:
+        return None, False
+    ect = blk.edge_channel_type
+    edge_route = None
+    if (node_dtype in _FLOATS and edge_dtype in _FLOATS and (ect != "constrained" or attn_mask)
+            and _lib_covers("egt_block_supported", blk, B, N, edge_dtype)):
+        # static: the block was opted in by its EGTLayerStack (`_static_edge`), the process switch is off, the random mask is
+        # the kernels' own, and the library covers the flagged descriptor
+        static = (ect == "bias" and blk._static_edge and not rand_mask and not static_edge_disabled()
+                  and _lib_covers("egt_block_supported", blk, B, N, edge_dtype, static_edge=True))
+        edge_route = "static" if static else "per-layer-bias" if ect == "bias" else "chained-residual"
+    # the pair operator (large heads): 'residual' edge channels, gated, fp32, no mask tensor of either kind
+    pair = (ect == "residual" and blk.gated and not attn_mask and not rand_mask
+            and node_dtype == torch.float32 and edge_dtype == torch.float32
+            and _lib_covers("egt_pair_supported", blk, B, N, edge_dtype))
+    return edge_route, pair
 
 
-def block_supported(blk, h, e, attn_mask, rand_mask) -> bool:
-    """Configurations the fused kernels cover (everything else composes)."""
-    if _unsupported(blk, blk.training) is not None:
-        return False
-    if blk.edge_channel_type == "constrained" and attn_mask is None:
-        return False
-    if not (h.is_cuda and e.is_cuda) or e.dtype not in (torch.float32, torch.bfloat16):
-        return False
-    if h.dtype not in (torch.float32, torch.bfloat16):
-        return False
-    return _lib_covers(blk, h.shape[0], h.shape[1], e.dtype)
+def route_core(blk, B, N, node_dtype, edge_dtype, on_gpu, attn_mask=False, rand_mask=False, keep=False, training=None):
+    """Which route one call of `blk` takes, from plain values (`attn_mask`, `rand_mask`, `keep`: whether the call passes an
+    attention mask, a random-mask tensor, injected dropout samples): (path, edge route) with path "fused" (edge route
+    "static" | "per-layer-bias" | "chained-residual"), "fused-pair" or "composed" (edge route None).  fused=True / 'on'
+    raises RuntimeError where neither fused route covers the configuration."""
+    if blk.fused is False or blk.fused == "off":
+        return "composed", None
+    edge_route, pair = _covered(blk, B, N, node_dtype, edge_dtype, on_gpu, attn_mask, rand_mask,
+                                blk.training if training is None else training)
+    if edge_route is not None:
+        return "fused", edge_route
+    if pair and not keep:
+        return "fused-pair", None
+    if blk.fused in (True, "on") and not pair:
+        raise RuntimeError("fused EGT block requested but this configuration is not covered by it")
+    return "composed", None
+
+
+def route(blk, h, e, attn_mask=None, rand_mask=None, node_keep=None, edge_keep=None):
+    """route_core for the tensors of a call"""
+    return route_core(blk, h.shape[0], h.shape[1], h.dtype, e.dtype, h.is_cuda and e.is_cuda, attn_mask is not None,
+                      rand_mask is not None, node_keep is not None or edge_keep is not None)
 
 
 def bf16_refusal(blk):
     """Why the fused block cannot run `blk` with bf16 edge tensors (None: it can).  bf16 edges exist only on the fused
     path -- the composed ops are fp32 -- so a bf16 model checks this at construction instead of failing at its first step:
-    the tensor-independent conditions of block_supported (in training mode: a model trains) and the library's answer for
-    a bf16 descriptor (N does not change what the block covers)."""
+    the tensor-independent conditions (in training mode: a model trains) and the library's answer for a bf16 descriptor
+    (N does not change what the block covers)."""
     if blk.fused is False or blk.fused == 'off':
         return "the fused block is switched off"
     why = _unsupported(blk, True)
     if why is not None:
         return why
-    if getattr(blk, "_static_edge", False) and not static_edge_disabled() and _lib_covers(blk, 1, 16, torch.bfloat16, static_edge=True):
-        return None
-    if not _lib_covers(blk, 1, 16, torch.bfloat16):
+    if _covered(blk, 1, 16, torch.float32, torch.bfloat16, True, True, False, True)[0] is None:
         return (f"geometry (num_heads {blk.num_heads}, head dim {blk.model_width // blk.num_heads}, "
                 f"edge_width {blk.edge_width}) is not covered by the fused block")
     return None
@@ -161,56 +197,27 @@ def grad_sinks(params):
     return bufs, rets
 
 
+def _call_tensors(h, e, key_mask, attn_mask, params):
+    """the tensors of a block / stack call as the C-ABI takes them"""
+    _need_gpu(h, e)
+    attn_mask = None if attn_mask is None else _f32c(attn_mask.to(torch.float32))
+    return _f32c(h), _edge_c(e), _u8c(key_mask), attn_mask, tuple(None if p is None else _f32c(p) for p in params)
+
+
+def _scratch(nbytes, dev):
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _param_array(tensors, layers=1):
+    """`layers` egt_block_params tables (parameters or gradient sinks), layer-major"""
+    return (L.BlockParams * layers)(*[_params_struct(tensors[14 * i:14 * i + 14]) for i in range(layers)])
+
+
 class _FusedBlock(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, h, e, key_mask, attn_mask, rand_mask, desc, *params):
-        _need_gpu(h, e)
-        lib = L.load()
-        h = _f32c(h); e = _edge_c(e)
-        key_mask = _u8c(key_mask); rand_mask = _u8c(rand_mask)
-        attn_mask = None if attn_mask is None else _f32c(attn_mask.to(torch.float32))
-        ctx.param_objs = params          # the Parameter objects themselves (grad_sinks looks at their .grad in the backward)
-        params = tuple(None if p is None else _f32c(p) for p in params)
-        dev = h.device
-        h_out = torch.empty_like(h)
-        e_out = torch.empty_like(e)
-        saved = torch.empty(lib.egt_block_saved_bytes(C.byref(desc)), dtype=torch.uint8, device=dev)
-        ws = torch.empty(lib.egt_block_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=dev)
-        pst = _params_struct(params)
-        L.check(lib.egt_block_fwd(C.byref(desc), C.byref(pst), L.ptr(h), L.ptr(e), L.ptr(key_mask),
-                                  L.ptr(attn_mask), L.ptr(rand_mask), L.ptr(h_out), L.ptr(e_out),
-                                  L.ptr(saved), L.ptr(ws), L.current_stream()))
-        ctx.desc = desc
-        ctx.nparams = len(params)
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(h, e, key_mask, attn_mask, rand_mask, saved, *params)
-        return h_out, e_out
+    """One block per C-ABI call (egt_block_fwd / egt_block_bwd).
 
-    @staticmethod
-    def backward(ctx, dh_out, de_out):
-        lib = L.load()
-        h, e, key_mask, attn_mask, rand_mask, saved, *params = ctx.saved_tensors
-        desc = ctx.desc
-        dev = h.device
-        if de_out is None:
-            de_out = torch.zeros_like(e)               # 'bias': the caller continues with e itself
-        if dh_out is None:
-            dh_out = torch.zeros_like(h)
-        dh_out = _f32c(dh_out); de_out = _edge_c(de_out, e.dtype)
-        dh = torch.empty_like(h)
-        de = torch.empty_like(e)
-        grads, rets = grad_sinks(ctx.param_objs)
-        ws = torch.empty(lib.egt_block_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=dev)
-        pst, gst = _params_struct(params), _params_struct(grads)
-        L.check(lib.egt_block_bwd(C.byref(desc), C.byref(pst), L.ptr(h), L.ptr(e), L.ptr(key_mask),
-                                  L.ptr(attn_mask), L.ptr(rand_mask), L.ptr(saved), L.ptr(dh_out),
-                                  L.ptr(de_out), L.ptr(dh), L.ptr(de), C.byref(gst), L.ptr(ws),
-                                  L.current_stream()))
-        return (dh, de, None, None, None, None, *rets)
-
-
-class _FusedBlockStatic(torch.autograd.Function):
-    """A 'bias' block of an EGTLayerStack on the static-edge route (EGT_BF_STATIC_EDGE).  The second output IS the input e
+    With EGT_BF_STATIC_EDGE in `desc` (a 'bias' block of an EGTLayerStack on the static-edge route; `first`: it is the stack's
+    first layer) the second output IS the input e
     (an alias: no copy, no kernel write) and the next layer consumes it, so the per-layer chain of the edge gradient is
     kept: a layer receives the sum of all later layers' edge gradients as the gradient of that output, adds its own
     contribution and hands the result down.  One edge read per layer forward; one read + one read-modify-write per layer
@@ -221,54 +228,57 @@ class _FusedBlockStatic(torch.autograd.Function):
     that came from anywhere else is read, and a fresh buffer is written: a caller's tensor is never mutated."""
 
     @staticmethod
-    def forward(ctx, h, e, key_mask, desc, first, *params):
-        _need_gpu(h, e)
+    def forward(ctx, h, e, key_mask, attn_mask, rand_mask, desc, first, *params):
         lib = L.load()
-        h = _f32c(h); e_in = e; e = _edge_c(e)
-        key_mask = _u8c(key_mask)
-        ctx.param_objs = params
-        params = tuple(None if p is None else _f32c(p) for p in params)
+        static = bool(desc.flags & L.BF_STATIC_EDGE)     # (block_fused passes no mask tensors then)
+        ctx.param_objs = params          # the Parameter objects themselves (grad_sinks looks at their .grad in the backward)
+        e_in = e
+        h, e, key_mask, attn_mask, params = _call_tensors(h, e, key_mask, attn_mask, params)
+        rand_mask = _u8c(rand_mask)
         dev = h.device
         h_out = torch.empty_like(h)
-        saved = torch.empty(lib.egt_block_saved_bytes(C.byref(desc)), dtype=torch.uint8, device=dev)
-        ws = torch.empty(lib.egt_block_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=dev)
-        pst = _params_struct(params)
-        L.check(lib.egt_block_fwd(C.byref(desc), C.byref(pst), L.ptr(h), L.ptr(e), L.ptr(key_mask),
-                                  None, None, L.ptr(h_out), None, L.ptr(saved), L.ptr(ws), L.current_stream()))
-        ctx.desc, ctx.first = desc, first
+        e_out = None if static else torch.empty_like(e)
+        saved = _scratch(lib.egt_block_saved_bytes(C.byref(desc)), dev)
+        ws = _scratch(lib.egt_block_workspace_bytes(C.byref(desc)), dev)
+        L.check(lib.egt_block_fwd(C.byref(desc), _param_array(params), L.ptr(h), L.ptr(e), L.ptr(key_mask),
+                                  L.ptr(attn_mask), L.ptr(rand_mask), L.ptr(h_out), L.ptr(e_out),
+                                  L.ptr(saved), L.ptr(ws), L.current_stream()))
+        ctx.desc, ctx.static, ctx.first = desc, static, first
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(h, e, key_mask, saved, *params)
-        return h_out, e_in               # (returning an input: autograd hands out an alias of it)
+        ctx.save_for_backward(h, e, key_mask, attn_mask, rand_mask, saved, *params)
+        return h_out, (e_in if static else e_out)        # (returning an input: autograd hands out an alias of it)
 
     @staticmethod
     def backward(ctx, dh_out, de_out):
         lib = L.load()
-        h, e, key_mask, saved, *params = ctx.saved_tensors
+        h, e, key_mask, attn_mask, rand_mask, saved, *params = ctx.saved_tensors
         desc = ctx.desc
         if dh_out is None:
             dh_out = torch.zeros_like(h)
         dh_out = _f32c(dh_out)
-        own = (de_out is not None and getattr(de_out, "_egt_edge_acc", False) and de_out.dtype == e.dtype
+        own = (ctx.static and de_out is not None and getattr(de_out, "_egt_edge_acc", False) and de_out.dtype == e.dtype
                and de_out.is_contiguous() and de_out.shape == e.shape)
         if own:
             de = de_out                                 # ours: de[i] = de_out[i] + contribution, in place
         else:
+            if de_out is None and not ctx.static:
+                de_out = torch.zeros_like(e)            # 'bias': the caller continues with e itself
             if de_out is not None:                      # someone else's tensor: read only
                 de_out = _edge_c(de_out, e.dtype)
-            de = torch.empty_like(e)                    # (de_out None: the kernel takes NULL as zeros -- no fill)
+            de = torch.empty_like(e)                    # (static, de_out None: the kernel takes NULL as zeros -- no fill)
         dh = torch.empty_like(h)
         grads, rets = grad_sinks(ctx.param_objs)
-        ws = torch.empty(lib.egt_block_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=h.device)
-        pst, gst = _params_struct(params), _params_struct(grads)
-        L.check(lib.egt_block_bwd(C.byref(desc), C.byref(pst), L.ptr(h), L.ptr(e), L.ptr(key_mask),
-                                  None, None, L.ptr(saved), L.ptr(dh_out), L.ptr(de_out), L.ptr(dh), L.ptr(de),
-                                  C.byref(gst), L.ptr(ws), L.current_stream()))
-        if ctx.first:
-            if own:
+        ws = _scratch(lib.egt_block_workspace_bytes(C.byref(desc)), h.device)
+        L.check(lib.egt_block_bwd(C.byref(desc), _param_array(params), L.ptr(h), L.ptr(e), L.ptr(key_mask),
+                                  L.ptr(attn_mask), L.ptr(rand_mask), L.ptr(saved), L.ptr(dh_out),
+                                  L.ptr(de_out), L.ptr(dh), L.ptr(de), _param_array(grads), L.ptr(ws),
+                                  L.current_stream()))
+        if ctx.static:
+            if not ctx.first:
+                de._egt_edge_acc = True
+            elif own:
                 del de._egt_edge_acc                    # leaves the stack: an ordinary tensor from here on
-        else:
-            de._egt_edge_acc = True
-        return (dh, de, None, None, None, *rets)
+        return (dh, de, None, None, None, None, None, *rets)
 
 
 def _block_params(blk, e):
@@ -285,30 +295,30 @@ def _block_params(blk, e):
     return params
 
 
-def block_fused(blk, h, e, mask, attn_mask, rand_mask=None):
+def block_fused(blk, h, e, mask, attn_mask, rand_mask=None, edge_route=None):
+    """`edge_route`: route()'s answer for this call (asked here when the caller did not)"""
+    if edge_route is None:
+        edge_route = route(blk, h, e, attn_mask, rand_mask)[1]
+    static = edge_route == "static"
     training = blk.training and blk.mha.random_mask_prob > 0.0
     sdev = blk.mha.seed_device if (training and rand_mask is None) else None
     seed = blk.mha.next_seed() if (training and rand_mask is None and sdev is None) else 0
-    if static_edge_route(blk, h, e, rand_mask):
+    desc = _desc(blk, h.shape[0], h.shape[1], training, seed, e.dtype, sdev, static_edge=static)
+    if static:
         # no identity / zero constants here: norm_edge and dense_edge_r do not exist for the kernels either
-        desc = _desc(blk, h.shape[0], h.shape[1], training, seed, e.dtype, sdev, static_edge=True)
         mods = blk._modules
         params = [None if (mod in ("norm_edge", "dense_edge_r") or mods.get(mod) is None) else mods[mod]._parameters[attr]
                   for mod, attr in _GRAD_ORDER]
-        h, hdt = _node_io(h)
-        h2, e2 = _FusedBlockStatic.apply(h, e, mask, desc, bool(getattr(blk, "_static_first", True)), *params)
-        blk.last_edge_route = "static"
-        return (h2 if hdt is None else h2.to(hdt)), e2
-    blk.last_edge_route = "per-layer-bias" if blk.edge_channel_type == "bias" else "chained-residual"
-    desc = _desc(blk, h.shape[0], h.shape[1], training, seed, e.dtype, sdev)
-    params = _block_params(blk, e)
+    else:
+        params = _block_params(blk, e)
     if blk.edge_channel_type != "constrained":
         attn_mask = None
+    blk.last_edge_route = edge_route
     h, hdt = _node_io(h)
-    h2, e2 = _FusedBlock.apply(h, e, mask, attn_mask, rand_mask, desc, *params)
-    if blk.edge_channel_type == "bias":
+    h2, e2 = _FusedBlock.apply(h, e, mask, attn_mask, rand_mask, desc, blk._static_first, *params)
+    if blk.edge_channel_type == "bias" and not static:
         e2 = e                                         # :190 returns e0; the kernel's e' equals it (zero update)
-    return (h2 if hdt is None else h2.to(hdt)), e2
+    return (h2 if hdt is None else h2.to(hdt)), e2     # (static: e2 is autograd's alias of e, which chains the edge gradient)
 
 
 # ------------------------------------------------------------------ layer stack ---
@@ -318,17 +328,13 @@ class _FusedStack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, e, key_mask, attn_mask, desc, layers, holder, *params):
-        _need_gpu(h, e)
         lib = L.load()
-        h = _f32c(h); e = _edge_c(e)
-        key_mask = _u8c(key_mask)
-        attn_mask = None if attn_mask is None else _f32c(attn_mask.to(torch.float32))
-        params = tuple(None if p is None else _f32c(p) for p in params)
+        h, e, key_mask, attn_mask, params = _call_tensors(h, e, key_mask, attn_mask, params)
         dev = h.device
         h_out, e_out = torch.empty_like(h), torch.empty_like(e)
-        saved = torch.empty(lib.egt_stack_saved_bytes(C.byref(desc), layers), dtype=torch.uint8, device=dev)
-        ws = torch.empty(lib.egt_stack_workspace_bytes(C.byref(desc), layers), dtype=torch.uint8, device=dev)
-        parr = (L.BlockParams * layers)(*[_params_struct(params[14 * i:14 * i + 14]) for i in range(layers)])
+        saved = _scratch(lib.egt_stack_saved_bytes(C.byref(desc), layers), dev)
+        ws = _scratch(lib.egt_stack_workspace_bytes(C.byref(desc), layers), dev)
+        parr = _param_array(params, layers)
         L.check(lib.egt_stack_fwd(C.byref(desc), layers, parr, L.ptr(h), L.ptr(e), L.ptr(key_mask),
                                   L.ptr(attn_mask), L.ptr(h_out), L.ptr(e_out), L.ptr(saved), L.ptr(ws),
                                   L.current_stream()))
@@ -377,7 +383,7 @@ class _FusedStack(torch.autograd.Function):
                     for q in sp:
                         q.grad = sink[o2:o2 + q.numel()].view_as(q)
                         o2 += q.numel()
-            ws = torch.empty(lib.egt_stack_workspace_bytes(C.byref(desc), layers), dtype=torch.uint8, device=dev)
+            ws = _scratch(lib.egt_stack_workspace_bytes(C.byref(desc), layers), dev)
             L.check(lib.egt_stack_bwd(C.byref(desc), layers, ctx.parr, L.ptr(h), L.ptr(e), L.ptr(key_mask),
                                       L.ptr(attn_mask), L.ptr(saved), L.ptr(dh_out), L.ptr(de_out), L.ptr(dh),
                                       L.ptr(de), garr, L.ptr(ws), L.current_stream()))
@@ -397,9 +403,9 @@ class _FusedStack(torch.autograd.Function):
                 grads.append(v if p.dim() == 1 else v.view(p.shape))
         if ctx.holder is not None:
             ctx.holder.flat = flat
-        ws = torch.empty(lib.egt_stack_workspace_bytes(C.byref(desc), layers), dtype=torch.uint8, device=dev)
+        ws = _scratch(lib.egt_stack_workspace_bytes(C.byref(desc), layers), dev)
         parr = ctx.parr                            # the forward's struct array: same parameter tensors (kept alive by saved_tensors)
-        garr = (L.BlockParams * layers)(*[_params_struct(grads[14 * i:14 * i + 14]) for i in range(layers)])
+        garr = _param_array(grads, layers)
         L.check(lib.egt_stack_bwd(C.byref(desc), layers, parr, L.ptr(h), L.ptr(e), L.ptr(key_mask),
                                   L.ptr(attn_mask), L.ptr(saved), L.ptr(dh_out), L.ptr(de_out), L.ptr(dh),
                                   L.ptr(de), garr, L.ptr(ws), L.current_stream()))
@@ -407,14 +413,13 @@ class _FusedStack(torch.autograd.Function):
 
 
 def stack_supported(stack, h, e, attn_mask) -> bool:
+    """one egt_stack_* call runs the stack: every block takes the fused route and they share one descriptor"""
     blocks = list(stack.blocks)
-    if not blocks or not hasattr(L.load(), "egt_stack_fwd"):
+    if not blocks:
         return False
     b0 = blocks[0]
     for b in blocks:
-        if b.fused is False or b.fused == "off":
-            return False
-        if not block_supported(b, h, e, attn_mask, None):
+        if route(b, h, e, attn_mask)[0] != "fused":
             return False
         same = (b.model_width == b0.model_width and b.edge_width == b0.edge_width and
                 b.edge_channel_type == b0.edge_channel_type and b.gated == b0.gated and

@@ -176,6 +176,8 @@ class EGTBlock(nn.Module):
         self.edge_activation = edge_activation
         self.node_dropout, self.edge_dropout, self.add_n_norm = node_dropout, edge_dropout, add_n_norm
         self.fused = fused
+        # static-edge route of the fused block (fused.route): off unless an EGTLayerStack opts its 'bias' blocks in
+        self._static_edge, self._static_first = False, True
         has_edge = edge_channel_type != 'none'
         # gates exist only on the edge-carrying variants (edge_update_none passes gates=None)
         self.gated = bool(gate_attention) and has_edge
@@ -243,15 +245,13 @@ class EGTBlock(nn.Module):
         if ect == 'none':                                           # :164-171
             h, _ = self._mha_block(h, None, None, mask, attn_mask, rand_mask, node_keep)
             return h, e
-        if self._use_fused(h, e, attn_mask, rand_mask):
-            from .fused import block_fused
-            self.last_path = "fused"
-            return block_fused(self, h, e, mask, attn_mask, rand_mask)
-        if self._use_pair(h, e, attn_mask, rand_mask, node_keep, edge_keep):
+        from . import fused as FZ
+        self.last_path, edge_route = FZ.route(self, h, e, attn_mask, rand_mask, node_keep, edge_keep)
+        if self.last_path == "fused":
+            return FZ.block_fused(self, h, e, mask, attn_mask, rand_mask, edge_route)
+        if self.last_path == "fused-pair":
             from .pair import block_pair      # large heads (d = 64): fused pair operator + library GEMMs on the node side
-            self.last_path = "fused-pair"
             return block_pair(self, h, e, mask)
-        self.last_path = "composed"
         use_ln = ect in ('residual', 'constrained') and not self.add_n_norm
         ne = getattr(self, 'norm_edge', None)
         ag = getattr(self, 'attention_gates', None)
@@ -273,26 +273,6 @@ class EGTBlock(nn.Module):
         if self.add_n_norm:
             e = self.norm_edge(e)                                   # :220-221
         return h, e
-
-    def _use_pair(self, h, e, attn_mask, rand_mask, node_keep, edge_keep):
-        if self.fused is False or self.fused == 'off' or node_keep is not None or edge_keep is not None:
-            return False
-        from . import pair as PZ
-        return PZ.pair_supported(self, h, e, attn_mask, rand_mask)
-
-    def _use_fused(self, h, e, attn_mask, rand_mask):
-        if self.fused is False or self.fused == 'off':
-            return False
-        try:
-            from . import fused as FZ
-        except ImportError:
-            if self.fused in (True, 'on'):
-                raise
-            return False
-        ok = FZ.block_supported(self, h, e, attn_mask, rand_mask)
-        if not ok and self.fused in (True, 'on') and not self._use_pair(h, e, attn_mask, rand_mask, None, None):
-            raise RuntimeError("fused EGT block requested but this configuration is not covered by it")
-        return ok
 
     def keras_named_parameters(self, tag: str):
         """Parameters keyed by the reference's Keras variable names for layer
@@ -392,12 +372,10 @@ class EGTLayerStack(nn.Module):
              for i in range(model_height)])
         ect = block_kwargs.get('edge_channel_type', 'residual')
         # 'bias' (EGT-simple): e is computed once by the embedding and read by every layer.  The stack opts its blocks into the
-        # static-edge route of the fused block (fused.static_edge_route: taken where the library covers the flagged
-        # descriptor, De = 8); an EGTBlock called on its own keeps today's behaviour.
+        # static-edge route of the fused block (fused.route: taken where the library covers the flagged descriptor, De = 8);
+        # an EGTBlock called on its own keeps the per-layer route.
         for i, blk in enumerate(self.blocks):
-            blk._static_edge = ect == 'bias'
-            blk._static_first = i == 0
-            blk._static_ok = {}
+            blk._static_edge, blk._static_first = ect == 'bias', i == 0
         self.last_edge_route = None   # "static" | "per-layer-bias" | "chained-residual" | "composed" | "mixed": what the last forward ran
         # FFN.__init__ raises ValueError for a width the fused FFN kernels do not cover (at
         # construction, not at the first forward: ADVICE r1)

@@ -25,26 +25,6 @@ def _struct(ts):
     return _params_struct(full)
 
 
-def pair_supported(blk, h, e, attn_mask, rand_mask) -> bool:
-    if blk.edge_channel_type != "residual" or not blk.gated or blk.add_n_norm or blk.edge_activation is not None:
-        return False
-    if blk.mha.scale_degree or blk.mha.attn_dropout > 0 or blk.mha.num_virtual_nodes > 0:
-        return False
-    if blk.training and (blk.node_dropout > 0 or blk.edge_dropout > 0):
-        return False
-    if attn_mask is not None or rand_mask is not None:
-        return False
-    if not (h.is_cuda and e.is_cuda) or e.dtype != torch.float32 or h.dtype != torch.float32:
-        return False
-    if blk.model_width % blk.num_heads:
-        return False
-    lib = L.load()
-    if not hasattr(lib, "egt_pair_fwd"):
-        return False
-    d = _desc(blk, h.shape[0], h.shape[1], False, 0, e.dtype)
-    return bool(lib.egt_pair_supported(C.byref(d)))
-
-
 class _PairOp(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, e, key_mask, desc, *params):
@@ -87,7 +67,7 @@ class _PairOp(torch.autograd.Function):
 
 
 def block_pair(blk, h, e, mask):
-    """EGTBlock forward on the fused pair operator: torch node-side Dense layers (library GEMMs) around it
+    """EGTBlock forward on the fused pair operator (fused.route decides when): torch node-side Dense layers (library GEMMs) around it
     (mha_block, graph_xformer_model_base.py:106-145, inside edge_update_residual, :192-223)."""
     B, N = h.shape[0], h.shape[1]
     m = blk.mha

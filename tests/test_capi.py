@@ -31,8 +31,7 @@ def test_library_exports_every_declared_symbol(egt_lib):
 
 def test_ctypes_table_matches_header(egt_lib):
     from egt_amd import _lib
-    table = set(_lib._PROTOS) | set(_lib._OPTIONAL_PROTOS)
-    assert set(declared_symbols()) == table
+    assert set(declared_symbols()) == set(_lib._PROTOS)
 
 
 def test_argument_validation_without_gpu(egt_lib):

@@ -1,14 +1,20 @@
-"""Host time per eager stack step (how far the Python side runs ahead of the GPU): python tools/micro/host_time.py [B]"""
+"""Host time per eager stack step (how far the Python side runs ahead of the GPU): python tools/micro/host_time.py [B] [--layer-stack]
+(--layer-stack: a 'bias' EGTLayerStack at De = 8 instead, one block call per layer: the per-block route decision is on this path)"""
 import os, sys, time, cProfile, pstats, io
 R = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, R)
 import torch
 from egt_amd import EGTStack
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 2
+from egt_amd.layers import EGTLayerStack
+LS = "--layer-stack" in sys.argv
+argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+B = int(argv[0]) if argv else 2
+De = 8 if LS else 64
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
-st = EGTStack(model_height=10, model_width=64, edge_width=64, num_heads=8, random_mask_prob=0.1, seed=1, fused=True).to(dev).train()
-h = torch.randn(B, 64, 64, device=dev, requires_grad=True); e = torch.randn(B, 64, 64, 64, device=dev, requires_grad=True)
+kw = dict(model_height=10, model_width=64, edge_width=De, num_heads=8, random_mask_prob=0.1, seed=1, fused=True)
+st = (EGTLayerStack(edge_channel_type="bias", **kw) if LS else EGTStack(**kw)).to(dev).train()
+h = torch.randn(B, 64, 64, device=dev, requires_grad=True); e = torch.randn(B, 64, 64, De, device=dev, requires_grad=True)
 mask = torch.ones(B, 64, dtype=torch.bool, device=dev); dh = torch.randn_like(h); de = torch.randn_like(e)
 params = list(st.parameters())
 def step():
