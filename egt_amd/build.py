@@ -27,10 +27,13 @@ EXTRA_FLAGS = {"egt_ffn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "egt_narrow.hip": ["-fno-slp-vectorize"]}
 if os.environ.get("EGT_BLOCK_FLAGS"):   # experiments: extra hipcc flags for egt_block.hip
     EXTRA_FLAGS["egt_block.hip"] = os.environ["EGT_BLOCK_FLAGS"].split()
-if os.environ.get("EGT_NARROW_FLAGS"):  # e.g. -DNRW_ABL=<bits> (timing ablations of the De = 8 kernels)
+if os.environ.get("EGT_NARROW_FLAGS"):  # e.g. -DEGT_STAMPS / -DNRW_ABL=<bits> (measurement builds of the De = 8 kernels)
     EXTRA_FLAGS["egt_narrow.hip"] = EXTRA_FLAGS["egt_narrow.hip"] + os.environ["EGT_NARROW_FLAGS"].split()
-if os.environ.get("EGT_ATTN_FLAGS"):    # e.g. -DEGT_ATTN_STAMPS / -DEGT_ATTN_ABL=<bits> (measurement builds of the MFMA inner op)
+if os.environ.get("EGT_ATTN_FLAGS"):    # e.g. -DEGT_STAMPS / -DEGT_ATTN_ABL=<bits> (measurement builds of the MFMA inner op and the pair kernels)
     EXTRA_FLAGS["egt_attn_mfma.hip"] = os.environ["EGT_ATTN_FLAGS"].split()
+if os.environ.get("EGT_STAMPS") == "1":  # phase stamps (csrc/egt_stamps.h, tools/stamps.py) in every unit that stamps
+    for _s in ("egt_narrow.hip", "egt_attn_mfma.hip"):
+        EXTRA_FLAGS[_s] = EXTRA_FLAGS.get(_s, []) + ["-DEGT_STAMPS"]
 
 
 def _hipcc() -> str:

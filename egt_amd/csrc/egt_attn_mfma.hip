@@ -34,6 +34,7 @@
 #include <stdlib.h>
 
 #include "egt_common.h"
+#include "egt_stamps.h"
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 #define MFMA_(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -64,18 +65,10 @@ struct AttnMfmaArgs {
   int pack_what;   // PACK_* bits
 };
 
-// Phase stamps (-DEGT_ATTN_STAMPS via EGT_ATTN_FLAGS): s_memtime deltas of every wave of workgroup 0, summed per
-// phase, read back with egt_attn_mfma_read_stamps().  Compiled out otherwise.
-#ifdef EGT_ATTN_STAMPS
-__device__ long long g_attn_stamps[3][8][16];
-#define STAMP_DECL long long st_last = __builtin_readcyclecounter(), st_acc[16] = {}
-#define STAMP(i) do { const long long t__ = __builtin_readcyclecounter(); st_acc[i] += t__ - st_last; st_last = t__; } while (0)
-#define STAMP_OUT(k) do { if (blockIdx.x == 0 && (threadIdx.x & 63) == 0) for (int i__ = 0; i__ < 16; ++i__) g_attn_stamps[k][threadIdx.x >> 6][i__] = st_acc[i__]; } while (0)
-#else
-#define STAMP_DECL
-#define STAMP(i)
-#define STAMP_OUT(k)
-#endif
+// Phase stamps (egt_stamps.h; measurement builds only).  Slots of this unit: a kernel's compute / attention waves and the pair kernels'
+// edge waves stamp different phases (the loader waves of k_attn_mfma_fwd / _bwd_kv do not stamp)
+enum { ST_ATTN_FWD, ST_ATTN_BWD_KV, ST_PAIR_FWD_ATT, ST_PAIR_FWD_EDGE, ST_PAIR_BWD_ATT, ST_PAIR_BWD_EDGE, ST_COUNT };
+EGT_STAMP_UNIT(ST_COUNT);
 // timing ablations (results are wrong): -DEGT_ATTN_ABL=<bits>: 1 no operand DMA, 2 no pair loads / scatter, 4 no output stores,
 // 8 no MFMAs, 16 no elementwise phase (probabilities = logits)
 #ifndef EGT_ATTN_ABL
@@ -304,9 +297,6 @@ __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" :
 __device__ __forceinline__ unsigned dma_lane_off(int lane) {   // source byte offset (inside a 1 KB block) of the chunk that lands in slot `lane`
   return (unsigned)((lane >> 2) * 64 + (((lane & 3) ^ chunk_xor(lane >> 2)) << 4));
 }
-#ifndef ATTN_BWD_SWAP
-#define ATTN_BWD_SWAP 1   // k_attn_mfma_bwd_kv: operand-tile rows pair-swapped in LDS (A/B: 0)
-#endif
 #define OPS_STAGE 32768   // bytes of one operand stage: 4 heads x (two 4 KB tiles)
 #define OPS_BYTES (2 * OPS_STAGE)
 
@@ -339,7 +329,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
   const Feat<V> f(a);
   const int mtiles = NP / 16;
   const size_t arr = (size_t)a.B * AH * NP * D;
-  STAMP_DECL;
+  EGT_STAMP_DECL;
 
   if (loader) {
     // ------------------------------------------------------------------ loader waves ----
@@ -471,7 +461,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
   // operand fragment address: row ll, chunk q of the k-tile blocks of head w's tiles (+ stage, + 1024 T, + KT*1024 for V^T)
   const float* opl = sm + w * (KT * 512) + ll * 16 + ((q ^ chunk_xor(ll)) << 2);
   lds_barrier();
-  STAMP(0);
+  EGT_STAMP(0);
   for (int it = 0; it < mtiles; ++it) {
     const int m0 = 16 * it;
     const float* ops = opl + (it & 1) * (OPS_STAGE / 4);
@@ -492,7 +482,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
       if (f.M) m4[qt] = *reinterpret_cast<const float4*>(Inb + 2 * TS + qt * 4 * PT_PL + po4);
     }
     __builtin_amdgcn_sched_barrier(0);   // every LDS request of the S phase is in flight before its first MFMA
-    STAMP(1);
+    EGT_STAMP(1);
     // ---- S^T[m][l] = sum_k K[m][k] (d^-1/2 Q)[l][k]: every K register feeds the two query tiles ----
     v4f s[FQ];
 #pragma unroll
@@ -508,7 +498,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
 #pragma unroll
     for (int T = 0; T < KT; ++T) vc[T] = *reinterpret_cast<const float4*>(ops + KT * 256 + T * 256);   // V^T fragments: requested behind the S MFMAs, landed long before P.V
     __builtin_amdgcn_sched_barrier(0);
-    STAMP(2);
+    EGT_STAMP(2);
     const float kav[4] = {ka4.x, ka4.y, ka4.z, ka4.w}, kgv[4] = {kg4.x, kg4.y, kg4.z, kg4.w};
     float pa[FQ][4];
 #pragma unroll
@@ -562,7 +552,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    STAMP(3);
+    EGT_STAMP(3);
     // ---- O^T[k][l] += sum_m V^T[k][m] P^T[m][l]  (contraction order m = 4q + t): every V^T register feeds two MFMAs ----
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -572,9 +562,9 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
 #pragma unroll
         for (int qt = 0; qt < FQ; ++qt) oacc[qt][kt] = MFMA(va, pa[qt][r], oacc[qt][kt]);
       }
-    STAMP(4);
+    EGT_STAMP(4);
     lds_barrier();
-    STAMP(6);
+    EGT_STAMP(6);
   }
   // ---- finalize: O[l][k] / l_run into the (now idle) operand stages as [row][k][4 heads]; row statistics for the backward ----
 #pragma unroll
@@ -589,8 +579,8 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
     if (l < N && q == 0)
       *reinterpret_cast<float4*>(a.rowstats + (((size_t)b * N + l) * AH + h) * 4) = make_float4(mrun[qt], lrun[qt], 0.f, 0.f);
   }
-  STAMP(7);
-  STAMP_OUT(0);
+  EGT_STAMP(7);
+  EGT_STAMP_OUT(ST_ATTN_FWD);
   }
   // V_att[l][k*8 + h]: all eight waves store 16-byte pieces (the group's 4 heads of one channel), consecutive threads
   // consecutive channels (a dword store per lane and channel costs ~300 cycles each: 19 k cycles per workgroup before)
@@ -638,7 +628,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
   const size_t arr = (size_t)a.B * AH * NP * D;
   const size_t hb = ((size_t)b * AH + h) * NP * D;
   const size_t gb = (size_t)b * N * N * AH;
-  STAMP_DECL;
+  EGT_STAMP_DECL;
 
   if (loader) {
     // ------------------------------------------------------------------ loader waves ----
@@ -646,7 +636,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
     const int crow = lt >> 4, ccol = lt & 15;   // query row, key of each 16 x 16 sub-tile; the group's 4 heads (16 bytes)
     const float* Qh = a.pk + PK_QH * arr + hb;  // this loader wave feeds head h
     const float* Oh = a.pk + PK_OH * arr + hb;
-    const unsigned doff = dma_lane_off(ATTN_BWD_SWAP ? lane ^ (((lane >> 4) & 1) << 2) : lane);   // (swap: LDS row sigma <- tile row sigma ^ ((sigma >> 2) & 1), see the compute waves)
+    const unsigned doff = dma_lane_off(lane ^ (((lane >> 4) & 1) << 2));   // (operand-tile rows pair-swapped in LDS: LDS row sigma <- tile row sigma ^ ((sigma >> 2) & 1), see the compute waves)
     const unsigned ops0 = lds_addr(sm) + w * (KT * 2048);   // head w: Q tile, then dO tile
     auto dma_ops = [&](int ltile, int stage) __attribute__((always_inline)) {
       const float* qs = Qh + (size_t)ltile * 16 * D;
@@ -785,14 +775,14 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
   const int po4 = w * PT_PL + ptT_off(4 * q, mm);   // this lane's query rows 4q..4q+3 of key mm inside a sub-tile: one 16-byte access
   // operand tiles of head w (Q, then dO): row form: lane (row mm, chunk q) b128; transposed form: lane (channel mm, q):
   // rows 4q + r, dword mm & 3 of chunk mm >> 2
-  // (ATTN_BWD_SWAP: tile rows 4-7 / 12-15 pair-swapped in LDS, as in k_pair_bwd: the transposed b32 reads of a 32-lane group touch
+  // (tile rows 4-7 / 12-15 pair-swapped in LDS, as in k_pair_bwd: the transposed b32 reads of a 32-lane group touch
   //  tile rows r and 4 + r -- the same 16 banks with 16-float rows, 2-way on the 32 reads of a tile; swapped, the group covers 32 banks)
-  const float* oprow = sm + w * (KT * 512) + (ATTN_BWD_SWAP ? mm ^ ((mm >> 2) & 1) : mm) * 16 + ((q ^ chunk_xor(mm)) << 2);
+  const float* oprow = sm + w * (KT * 512) + (mm ^ ((mm >> 2) & 1)) * 16 + ((q ^ chunk_xor(mm)) << 2);
   const float* optr = sm + w * (KT * 512) + (4 * q) * 16 + (((mm >> 2) ^ chunk_xor(4 * q)) << 2) + (mm & 3);
-  const float* optr_e = optr + (ATTN_BWD_SWAP ? (q & 1) * 16 : 0);   // steps 0, 2: LDS row 4q + r + (q & 1)
-  const float* optr_o = optr - (ATTN_BWD_SWAP ? (q & 1) * 16 : 0);   // steps 1, 3: LDS row 4q + r - (q & 1)
+  const float* optr_e = optr + (q & 1) * 16;   // steps 0, 2: LDS row 4q + r + (q & 1)
+  const float* optr_o = optr - (q & 1) * 16;   // steps 1, 3: LDS row 4q + r - (q & 1)
   lds_barrier();
-  STAMP(0);
+  EGT_STAMP(0);
   for (int l0 = 0, it = 0; it < mtiles; l0 += 16, ++it) {
     const float* opr = oprow + (it & 1) * (OPS_STAGE / 4);
     const float* opt_e = optr_e + (it & 1) * (OPS_STAGE / 4);
@@ -816,7 +806,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) stc[r] = *reinterpret_cast<const float4*>(statL + (((it & 1) * 4 + w) * 16 + 4 * q + r) * 4);
     __builtin_amdgcn_sched_barrier(0);   // every LDS request of the first two phases is in flight before the first MFMA
-    STAMP(1);
+    EGT_STAMP(1);
     // ---- S[l][m] = sum_k (d^-1/2 Q)[l][k] K[m][k] ; dP[l][m] = sum_k dO[l][k] V[m][k]: every Q / dO register feeds two MFMAs ----
     v4f s[BK], dp[BK];
 #pragma unroll
@@ -837,7 +827,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    STAMP(2);
+    EGT_STAMP(2);
     float at[BK][4], da[BK][4];
 #pragma unroll
     for (int kb = 0; kb < BK; ++kb) {
@@ -877,7 +867,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
         *reinterpret_cast<float4*>(dAb[kb] + (size_t)it * mtiles * 256 + ooff) = make_float4(da[kb][0], da[kb][1], da[kb][2], da[kb][3]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    STAMP(3);
+    EGT_STAMP(3);
     // ---- dV^T[k][m] += sum_l dO[l][k] A[l][m] ; dK^T[k][m] += sum_l (d^-1/2 Q)[l][k] dA[l][m]: transposed operands from the same tiles ----
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt)
@@ -892,9 +882,9 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
           dKacc[kb][kt] = MFMA(qq, da[kb][r], dKacc[kb][kt]);
         }
       }
-    STAMP(4);
+    EGT_STAMP(4);
     lds_barrier();
-    STAMP(6);
+    EGT_STAMP(6);
   }
   // dK / dV into the (now idle) operand stages as [key][k][4 heads], dK in stage 0, dV in stage 1
 #pragma unroll
@@ -908,8 +898,8 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
         ks[OPS_STAGE / 4 + (16 * kt + r) * 4] = dVacc[kb][kt][r];
       }
   }
-  STAMP(7);
-  STAMP_OUT(1);
+  EGT_STAMP(7);
+  EGT_STAMP_OUT(ST_ATTN_BWD_KV);
   }
   // dK / dV rows of d_qkv: all eight waves store 16-byte pieces (the group's 4 heads of one channel)
   lds_barrier();
@@ -1353,11 +1343,11 @@ extern "C" int egt_pair_bwd(const egt_block_desc* desc, const egt_block_params* 
   return EGT_OK;
 }
 
-#ifdef EGT_ATTN_STAMPS
-extern "C" int egt_attn_mfma_read_stamps(long long* host, int n) {
-  long long tmp[3 * 8 * 16];
-  if (hipMemcpyFromSymbol(tmp, HIP_SYMBOL(g_attn_stamps), sizeof(tmp)) != hipSuccess) return -1;
-  for (int i = 0; i < n && i < 3 * 8 * 16; ++i) host[i] = tmp[i];
-  return 0;
-}
+#ifdef EGT_STAMPS
+static const char* const g_attn_names[] = {"setup", "top: pair loads, out stores, LDS reads", "MFMA 1 + operand reloads", "elementwise", "MFMA 2 + reloads", nullptr, "barrier", "epilogue"};
+static const EgtStampKernel g_attn_stamped[ST_COUNT] = {
+    {"k_attn_mfma_fwd (compute waves)", g_attn_names, 8},     {"k_attn_mfma_bwd_kv (compute waves)", g_attn_names, 8},
+    {"k_pair_fwd (attention waves)", g_pair_fwd_att_names, 8}, {"k_pair_fwd (edge waves)", g_pair_fwd_edge_names, 9},
+    {"k_pair_bwd (attention waves)", g_pair_bwd_att_names, 9}, {"k_pair_bwd (edge waves)", g_pair_bwd_edge_names, 10}};
+EGT_STAMP_REGISTER(g_attn_stamped);
 #endif

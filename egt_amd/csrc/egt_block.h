@@ -33,7 +33,7 @@ struct BlockArgs {
   int spart_n, sbo_n;   // how many workgroup partials the reduction finds in spart / sbo
   int wpart_n;          // ... and in wpart: the row chunks egt_node_launch_wgrads launched (stored there, read by the reduction)
   int guard;    // backward phase guards (always 0 in production, see k_block_bwd_v4)
-  unsigned* dbg; unsigned dbg_t0;   // measurement builds of egt_narrow.hip (-DNRW_TIMING): per-wave section cycle sums
+  unsigned* dbg; unsigned dbg_t0;   // unused, kept for the argument layout (with dbg2 below)
   int prep;     // node kernels: add the edge-weight preparation workgroup
   const float *nx_nm_g, *nx_nm_b, *nx_Wqkv, *nx_bqkv;   // next block (epi == 2)
   // MFMA-fragment-major copies of Wqkv / Wo (prepared by the forward beside pw, kept in `saved`): what the node-side epilogue /
@@ -59,7 +59,7 @@ struct BlockArgs {
   float *dh, *de;
   float *g_ne_g, *g_ne_b, *g_Wg, *g_bg, *g_We, *g_be, *g_nm_g, *g_nm_b, *g_Wqkv, *g_bqkv, *g_Wo,
       *g_bo, *g_Wr, *g_br;
-  unsigned* dbg2;   // -DNRW_TIMING: the node-side prologue's phase cycles (last member: the other translation units ignore it)
+  unsigned* dbg2;
 };
 
 template <int DE>

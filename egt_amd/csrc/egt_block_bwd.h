@@ -358,15 +358,11 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
 // fp32 value it replaces.
 // floats of k_block_bwd_v5's tile area: four waves x (two e buffers + de' tile + hand-off tiles), and at least the four parity-0 e
 // buffers + the node-side prologue's scratch behind them
-#ifndef V5_BALANCE
-#define V5_BALANCE 1   // k_block_bwd_v5: balanced (tile, row) ranges when the key-tile count is not a multiple of 4 (A/B: 0)
-#endif
 #define V5_AREA(DE_) ((4 * (3 * Geo<DE_>::TILE_FLOATS + 448) > 4 * Geo<DE_>::TILE_FLOATS + BWD_PRO_WS) \
                           ? 4 * (3 * Geo<DE_>::TILE_FLOATS + 448) : 4 * Geo<DE_>::TILE_FLOATS + BWD_PRO_WS)
 template <int DE, int MM, bool RAG>
 __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
   seed_from_device(a);
-#define PSTAMP(i) do {} while (0)
   constexpr bool SPLIT = MM == EGT_MM_BF16X3;
   constexpr int NS = (Geo<DE>::TILES + 1) / 2;   // 16x16x32 steps over the channel axis
   (void)SPLIT; (void)NS;
@@ -418,7 +414,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
   // ranges: a tile that straddles two ranges is shared by neighbouring waves, whose dK / dV meet in the tile's partial slot (the later
   // wave parks its sum there, the earlier one adds its own: same CU, an LDS flag -- as k_narrow_bwd does).  At least three tiles: a
   // range is then never shorter than 3/4 of a tile and no tile has more than two waves.
-  const bool balance = RAG && V5_BALANCE && ntile >= 3 && (ntile & 3) != 0;
+  const bool balance = RAG && ntile >= 3 && (ntile & 3) != 0;
   const int T_ = ntile * nl;
   const int t0 = balance ? (wave * T_) >> 2 : 0, t1 = balance ? ((wave + 1) * T_) >> 2 : 0;
   const bool have = balance ? t1 > t0 : wave < ntile;
@@ -488,12 +484,10 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
       }
     }
   }
-  PSTAMP(0);
   if (a.pro) {
     __syncthreads();
     bwd_node_prologue_finish<DE>(a, pro_ws, qd, b, l_begin, wg, proR);
   }
-  PSTAMP(1);
   // weight slabs: element (t, lane, u)
   if constexpr (MM != 0) {
     // bf16 operands.  wsA / wsB: [step s][part hi|lo][lane][8 slots], slot i <-> channel 16 (2s + (i >> 2)) + 4q + (i & 3);
@@ -533,7 +527,6 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
   for (int t = 0; t < G::TILES; ++t) { accT[t] = (v4f){0.f, 0.f, 0.f, 0.f}; accR[t] = (v4f){0.f, 0.f, 0.f, 0.f}; }
   float ssum[4] = {0.f, 0.f, 0.f, 0.f};
   __syncthreads();   // the prologue's scratch (the tile area behind the parity-0 e buffers) is dead from here
-  PSTAMP(2);
 
   for (int mt = mt_first; have && mt <= mt_last; mt += mt_step) {
     const int r0 = (balance && mt == mt_first) ? r0_first : 0;            // rows [r0, r1) of the workgroup's nl
@@ -901,11 +894,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
   // (the later wave meets it first and parks its dK / dV partial in LDS, the earlier one meets it last and adds it) -- as in
   // k_narrow_bwd.
   const int npair = (nl + R - 1) / R;
-#ifdef EGT_V4R_NO_BALANCE
-  const bool balance = false;
-#else
   const bool balance = ntile >= 4 && (ntile & 3) != 0;
-#endif
   const int TT = ntile * npair;
   const int t0 = balance ? (wave * TT) >> 2 : 0, t1 = balance ? ((wave + 1) * TT) >> 2 : 0;
   const int mt_first = balance ? t0 / npair : wave, mt_last = balance ? (t1 - 1) / npair : ntile - 1, mt_step = balance ? 1 : 4;

@@ -312,34 +312,29 @@ __device__ __forceinline__ void bwd_stage_rows(const BlockArgs& a, float* qd, in
 //              delta = sum_k dV_att*V_att into the qd statistics, dbo column sums -> sbo
 // One launch per layer on the dh critical path instead of two; dV_att / delta never touch HBM.
 // `ws`: the (still idle) per-wave tile area; `qd`: the staged [16][QD_LD] rows.
-#ifndef EGT_PRO_UNROLL
 #define EGT_PRO_UNROLL 4   // partial loads in flight per element of the dQ / dK / dV gather
-#endif
 #define BWD_PRO_WS 8192   // floats of LDS scratch the prologue needs (dQKV, xhat, d h_ln, dh' rows, partials)
-// HOIST: the loads of the dV_att step (Wo columns, V_att rows) are issued with the first round of global loads instead of
-// after the dh' rows exist: one memory round trip on the kernel's critical path instead of two (costs 20 registers across
-// the first part)
-#define NSTAMP(i) do {} while (0)
+// (Measured and not kept: the loads of the dV_att step issued with the first round of global loads -- 20 registers held across the first part.)
 // The prologue's global inputs live in this register set between `bwd_prologue_load` (every load of the step issued: ONE
 // memory round trip, which a kernel can overlap with its other start-up requests) and `bwd_prologue_compute`.
 struct BwdProRegs { float4 hx, gq[3], wq[12], wo[4]; float dho[4], gmm[4], va[4]; };
 
 #define BWD_PRO_COMMON()                                                                                   \
   constexpr int LD = 68, LD3 = 196;                                                                        \
-  const int t = ptid, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);                        \
+  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);                        \
   const int p = lane & 15, q = lane >> 4, N = a.N;                                                         \
   const size_t row0 = (size_t)b * N + l_begin;                                                             \
   const int lnrow = 4 * wave + q;    /* LayerNorm mapping: row 4*wave + q, columns p + 16 i */            \
   /* ragged last row group (N not a multiple of 16): loads are clamped to the graph's last row, the rows  \
      past the end contribute zeros to every sum and are never stored */                                   \
-  const int nv = pnv >= 0 ? pnv : min(a.TL, N - l_begin);  /* valid rows of this 16-row group (<= 16) */                          \
+  const int nv = min(a.TL, N - l_begin);  /* valid rows of this 16-row group (<= 16) */                    \
   auto rc = [&](int r) { return row0 + max(min(r, nv - 1), 0); };   /* clamped global row */               \
   const int Dh = D64 ? 64 : a.Dh;                                                                          \
   (void)LD; (void)LD3; (void)lnrow; (void)p; (void)q; (void)rc; (void)Dh
 
 // Wo columns and V_att rows of the dV_att step
 template <int DE, bool D64>
-__device__ __forceinline__ void bwd_prologue_load_wo_va(const BlockArgs& a, int b, int l_begin, BwdProRegs& R, int ptid, int pnv) {
+__device__ __forceinline__ void bwd_prologue_load_wo_va(const BlockArgs& a, int b, int l_begin, BwdProRegs& R) {
   BWD_PRO_COMMON();
   const bool iok = D64 || 16 * wave + p < Dh;   // the lane's dV_att channel exists
 #pragma unroll
@@ -350,7 +345,7 @@ __device__ __forceinline__ void bwd_prologue_load_wo_va(const BlockArgs& a, int 
 }
 // [pro == 2] every global input of the dQKV / d h_ln / LayerNorm-backward step
 template <int DE, bool D64>
-__device__ __forceinline__ void bwd_prologue_load_main(const BlockArgs& a, int b, int l_begin, BwdProRegs& R, int ptid, int pnv) {
+__device__ __forceinline__ void bwd_prologue_load_main(const BlockArgs& a, int b, int l_begin, BwdProRegs& R) {
   BWD_PRO_COMMON();
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     // ---- every global input in one round trip ----
@@ -409,8 +404,7 @@ __device__ __forceinline__ void bwd_prologue_load_main(const BlockArgs& a, int b
 }
 
 template <int DE, bool D64>
-__device__ __forceinline__ void bwd_prologue_compute(const BlockArgs& a, float* ws, float* qd, int b, int l_begin, int wg, BwdProRegs& R,
-                                                     bool wo_loaded, unsigned* tp, int ptid, int pnv) {
+__device__ __forceinline__ void bwd_prologue_compute(const BlockArgs& a, float* ws, float* qd, int b, int l_begin, int wg, BwdProRegs& R) {
   float* dqs = ws;                   // dQKV  [16][196]
   float* xs = dqs + 16 * 196;        // xhat  [16][68]
   float* dls = xs + 16 * 68;         // d h_ln
@@ -423,9 +417,7 @@ __device__ __forceinline__ void bwd_prologue_compute(const BlockArgs& a, float* 
   float (&va)[4] = R.va;
   if (a.pro == 2) {
     float4 (&gq)[3] = R.gq; float4 (&wq)[12] = R.wq; float (&dho)[4] = R.dho; float (&gmm)[4] = R.gmm; const float4 hx = R.hx;
-    NSTAMP(0);
     *reinterpret_cast<float4*>(xs + (t >> 4) * LD + (t & 15) * 4) = hx;
-    NSTAMP(1);
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
       const int i = t + u * 256, r = i / 48, pos4 = (i % 48) * 4, sx = pos4 >> 6;
@@ -464,7 +456,6 @@ __device__ __forceinline__ void bwd_prologue_compute(const BlockArgs& a, float* 
 #pragma unroll
       for (int r = 0; r < 4; ++r) dls[(4 * q + r) * LD + 16 * wave + p] = acc[r];
     }
-    NSTAMP(2);
     for (int i = t; i < nv * 48; i += 256) {   // dQKV rows out (natural channel order, [3][Dh] per row) for k_node_wgrads
       const int r = i / 48, c4 = (i % 48) * 4;
       if (D64 || (c4 & 63) < Dh)
@@ -519,10 +510,8 @@ __device__ __forceinline__ void bwd_prologue_compute(const BlockArgs& a, float* 
         make_float4(ok ? dv4.x : 0.f, ok ? dv4.y : 0.f, ok ? dv4.z : 0.f, ok ? dv4.w : 0.f);
   }
   // ---- dV_att = dh'.Wo^T for i tile = wave (contraction order c = 16 q + s), delta, dbo ----
-  NSTAMP(3);
-  if (!wo_loaded) bwd_prologue_load_wo_va<DE, D64>(a, b, l_begin, R, ptid, pnv);
+  bwd_prologue_load_wo_va<DE, D64>(a, b, l_begin, R);
   __syncthreads();
-  NSTAMP(4);
   {
     v4f acc = {0.f, 0.f, 0.f, 0.f};
     const float* ar = dhs + p * LD + 16 * q;
@@ -547,7 +536,6 @@ __device__ __forceinline__ void bwd_prologue_compute(const BlockArgs& a, float* 
       if (p < 8) dlp[(wave * 16 + row) * 8 + p] = pr;
     }
   }
-  NSTAMP(5);
   if (t < 64) {   // dbo: column sums of dh'
     float s0 = 0.f, s1 = 0.f;
 #pragma unroll
@@ -562,25 +550,24 @@ __device__ __forceinline__ void bwd_prologue_compute(const BlockArgs& a, float* 
   }
 }
 
-template <int DE, bool D64, bool HOIST>
-__device__ __forceinline__ void bwd_node_prologue_t(const BlockArgs& a, float* ws, float* qd, int b, int l_begin, int wg, unsigned* tp, int ptid, int pnv) {
+template <int DE, bool D64>
+__device__ __forceinline__ void bwd_node_prologue_t(const BlockArgs& a, float* ws, float* qd, int b, int l_begin, int wg) {
   BwdProRegs R;
-  if (HOIST) bwd_prologue_load_wo_va<DE, D64>(a, b, l_begin, R, ptid, pnv);
-  if (a.pro == 2) bwd_prologue_load_main<DE, D64>(a, b, l_begin, R, ptid, pnv);
-  bwd_prologue_compute<DE, D64>(a, ws, qd, b, l_begin, wg, R, HOIST, tp, ptid, pnv);
+  if (a.pro == 2) bwd_prologue_load_main<DE, D64>(a, b, l_begin, R);
+  bwd_prologue_compute<DE, D64>(a, ws, qd, b, l_begin, wg, R);
 }
 // The two halves on their own, for a kernel that issues the prologue's loads together with its other start-up requests (one memory
 // round trip for all of them) and runs the arithmetic later: k_block_bwd_v5.
 template <int DE>
 __device__ __forceinline__ void bwd_node_prologue_load(const BlockArgs& a, BwdProRegs& R, int b, int l_begin) {
   if (a.pro != 2) return;
-  if (a.Dh == 64) bwd_prologue_load_main<DE, true>(a, b, l_begin, R, threadIdx.x, -1);
-  else bwd_prologue_load_main<DE, false>(a, b, l_begin, R, threadIdx.x, -1);
+  if (a.Dh == 64) bwd_prologue_load_main<DE, true>(a, b, l_begin, R);
+  else bwd_prologue_load_main<DE, false>(a, b, l_begin, R);
 }
 template <int DE>
 __device__ __forceinline__ void bwd_node_prologue_finish(const BlockArgs& a, float* ws, float* qd, int b, int l_begin, int wg, BwdProRegs& R) {
-  if (a.Dh == 64) bwd_prologue_compute<DE, true>(a, ws, qd, b, l_begin, wg, R, false, nullptr, threadIdx.x, -1);
-  else bwd_prologue_compute<DE, false>(a, ws, qd, b, l_begin, wg, R, false, nullptr, threadIdx.x, -1);
+  if (a.Dh == 64) bwd_prologue_compute<DE, true>(a, ws, qd, b, l_begin, wg, R);
+  else bwd_prologue_compute<DE, false>(a, ws, qd, b, l_begin, wg, R);
 }
 // the barriers of bwd_node_prologue, for waves of a workgroup that take no part in it (a.pro is uniform)
 __device__ __forceinline__ void bwd_node_prologue_idle(const BlockArgs& a) {
@@ -588,14 +575,10 @@ __device__ __forceinline__ void bwd_node_prologue_idle(const BlockArgs& a) {
   __syncthreads();
   __syncthreads();
 }
-// ptid / pnv: the calling thread's index inside its 256-thread group and the group's valid rows -- defaults: the workgroup IS the
-// group (threadIdx.x, min(a.TL, N - l_begin)).  (A workgroup of several 256-thread groups -- round 5's twelve-wave experiment, in the git
-// history -- passes its own; every thread of the workgroup must make the call: the barriers inside are workgroup barriers.)
-template <int DE, bool HOIST = false>
-__device__ __forceinline__ void bwd_node_prologue(const BlockArgs& a, float* ws, float* qd, int b, int l_begin, int wg, unsigned* tp = nullptr,
-                                                  int ptid = -1, int pnv = -1) {
-  if (ptid < 0) ptid = threadIdx.x;
-  if (a.Dh == 64) bwd_node_prologue_t<DE, true, HOIST>(a, ws, qd, b, l_begin, wg, tp, ptid, pnv);
-  else bwd_node_prologue_t<DE, false, HOIST>(a, ws, qd, b, l_begin, wg, tp, ptid, pnv);
+// (every thread of the 256-thread workgroup must make the call: the barriers inside are workgroup barriers)
+template <int DE>
+__device__ __forceinline__ void bwd_node_prologue(const BlockArgs& a, float* ws, float* qd, int b, int l_begin, int wg) {
+  if (a.Dh == 64) bwd_node_prologue_t<DE, true>(a, ws, qd, b, l_begin, wg);
+  else bwd_node_prologue_t<DE, false>(a, ws, qd, b, l_begin, wg);
 }
 

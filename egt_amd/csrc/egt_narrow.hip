@@ -25,42 +25,14 @@
 
 #include "egt_block.h"
 #include "egt_block_dev.h"
+#include "egt_stamps.h"
 
 #define NRW_DE 8
-#ifdef NRW_TIMING   // measurement builds (EGT_NARROW_FLAGS=-DNRW_TIMING): per-wave cycle sums of the kernel's sections, printed at exit
-#define NSTMP(i) do { const unsigned tn__ = (unsigned)__builtin_amdgcn_s_memtime(); nacc[i] += tn__ - nlast; nlast = tn__; } while (0)
-#else
-#define NSTMP(i) do {} while (0)
-#endif
-#ifdef NRW_TIMING
-struct NrwTimer {   // host side of a timing build: one device record of 8 counters per wave, summed after every launch (synchronises)
-  const char* kernel; const char* const* names; int nsec;
-  unsigned* dev = nullptr; unsigned* host = nullptr; int n = 0; double sum[8] = {}; long launches = 0, waves = 0;
-  unsigned* attach(int nwg) {
-    if (n < nwg) { if (dev) (void)hipFree(dev); (void)hipMalloc(&dev, (size_t)nwg * 32 * sizeof(unsigned)); free(host); host = (unsigned*)malloc((size_t)nwg * 32 * sizeof(unsigned)); n = nwg; }
-    return dev;
-  }
-  void collect(int nwg, hipStream_t st) {
-    (void)hipStreamSynchronize(st);
-    if (++launches <= 20) return;
-    (void)hipMemcpy(host, dev, (size_t)nwg * 32 * sizeof(unsigned), hipMemcpyDeviceToHost);
-    for (int w = 0; w < nwg * 4; ++w) { for (int i = 0; i < 8; ++i) sum[i] += host[w * 8 + i]; ++waves; }
-  }
-  void report() const {
-    if (!waves) return;
-    double tot = 0; for (int i = 0; i < nsec; ++i) tot += sum[i];
-    fprintf(stderr, "[egt] %s section cycles per wave (mean over %ld waves, %ld launches; total %.0f):\n", kernel, waves, launches, tot / waves);
-    for (int i = 0; i < nsec; ++i) fprintf(stderr, "    %-30s %10.0f  (%.1f %%)\n", names[i], sum[i] / waves, 100.0 * sum[i] / tot);
-  }
-};
-#endif
+EGT_STAMP_UNIT(2);   // slot 0: k_narrow_fwd, 1: k_narrow_bwd
 #ifndef NRW_ABL          // timing ablations (measurement builds only, tools/build_variant.sh -DNRW_ABL=<bits>):
 #define NRW_ABL 0        // 1 no e' stores, 2 no e loads, 4 no K/V chunk traffic, 8 no mask hash, 16 no exp/sigmoid, 32 no epilogue
 #endif
-#ifndef NRW_KB
-#define NRW_KB 4
-#endif
-//      NRW_KB: keys per K/V chunk and per e prefetch block (one 128-byte line of a pair row)
+#define NRW_KB 4          // keys per K/V chunk and per e prefetch block (one 128-byte line of a pair row)
 #define NRW_KV_CHUNK (NRW_KB * 128)   // floats: [key][K 64 | V 64]
 
 
@@ -185,22 +157,17 @@ template <bool BF, int NS> __device__ __forceinline__ v4f nrw_mm(const NrwOp<BF,
 //      merge buffer [NW - 1][20][64] after it, then the epilogue's staging rows; [16][QS_LD] V_att rows for the epilogue.
 #define NRW_FWD_AREA(NW) ((((NW) - 1) * 20 * 64) > ((NW) * NRW_KV_CHUNK + (NW) * NRW_KB) ? (((NW) - 1) * 20 * 64) : ((NW) * NRW_KV_CHUNK + (NW) * NRW_KB))
 // Projections and dense_edge_r of a pair: two MFMAs each (4 A-operand registers).
-#ifndef NRW_FWDM_OCC
-#define NRW_FWDM_OCC 3
-#endif
 // HR ("half rows", with NW = 8): workgroup = (graph, EIGHT query rows) for launches whose 16-row grid would leave half of the CUs
 // without a workgroup (config 4 as specified: B = 16, N = 120 -> 128 workgroups of 16 rows on 256 CUs).  Lanes p < 8 and p >= 8 work on the
 // same row p & 7 and on the even / odd key of a step's key pair (a row's 64-byte segment per request instead of 32); their online-softmax
 // states are merged across the lane pair (p, p ^ 8) before the waves' key ranges are.
 template <bool BF, int FEAT, int NW, bool HR>
-__global__ void __launch_bounds__(64 * NW, NW == 4 ? NRW_FWDM_OCC : 1) k_narrow_fwd(BlockArgs a) {
+__global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 1) k_narrow_fwd(BlockArgs a) {
   static_assert(!HR || (NW == 8 && NRW_KB % 2 == 0), "half-row workgroups: eight waves, key blocks of an even size");
   constexpr int RG = HR ? 8 : 16;            // query rows per workgroup
   constexpr int KS = HR ? NRW_KB / 2 : NRW_KB;   // key steps per block
   seed_from_device(a);
-#ifdef NRW_TIMING
-  unsigned nacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nlast = (unsigned)__builtin_amdgcn_s_memtime();
-#endif
+  EGT_STAMP_DECL;
   typedef NrwLd<BF> LD;
   constexpr bool MV = NRW_MMA_BF_VALUES(BF);   // bf16 MFMAs for the value path (projections, dense_edge_r): off by default, see NRW_MMA_BF_VALUES
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -279,7 +246,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? NRW_FWDM_OCC : 1) k_narrow_
     if (a.km) kmr = (a.km[(size_t)b * N + m0 + min(lane & (NRW_KB - 1), kmax)] == 0) ? -EGT_NEG : 0.0f;
   };
   if (blk0 < blk1) { fetch_e(blk0); fetch_kv(blk0); }
-  NSTMP(0);   // lane constants, weight table, first requests
+  EGT_STAMP(0);   // lane constants, weight table, first requests
 
   // one block of keys; nv = number of real keys in it (NRW_KB except in the graph's last block)
   auto block = [&](int blk, int nv) __attribute__((always_inline)) {
@@ -398,7 +365,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? NRW_FWDM_OCC : 1) k_narrow_
       for (int k = 0; k < 8; ++k) O[2 * k + j] = fmaf(O[2 * k + j], f0, __shfl_xor(O[2 * k + j], 8) * f1);
     }
   }
-  NSTMP(1);   // key loop
+  EGT_STAMP(1);   // key loop
   // the node-side epilogue's weight fragments / bias / residual rows: requested now, landed by the time the key ranges are merged
   // (eight waves: two waves per SIMD at most, the 69 registers are there; with four waves the kernel runs three workgroups per CU at <= 128)
   const bool epi_on = a.epi && !(NRW_ABL & 32);
@@ -444,20 +411,15 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? NRW_FWDM_OCC : 1) k_narrow_
       }
     }
   }
-  NSTMP(2);   // sync + merge of the key quarters
+  EGT_STAMP(2);   // sync + merge of the key quarters
   // node-side epilogue on the 16 rows (its own lane roles: MFMA layout); its staging rows reuse the merge area
   if (epi_on) {
     if (NW == 4) fwd_node_epilogue(a, sm, qs, b, lg * RG, min(RG, N - lg * RG), N, wave, lane & 15, lane >> 4);
     else if (wave < 4) fwd_node_epilogue_finish(a, epiR, sm, qs, b, lg * RG, min(RG, N - lg * RG), N, wave, lane & 15, lane >> 4);
     else fwd_node_epilogue_idle(a);   // the epilogue is four waves' work: the others only meet its barriers
   }
-#ifdef NRW_TIMING
-  NSTMP(3);   // node-side epilogue
-  if (a.dbg && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) if (wave < 4) a.dbg[((size_t)blockIdx.x * 4 + wave) * 8 + i] = nacc[i];
-  }
-#endif
+  EGT_STAMP(3);   // node-side epilogue
+  EGT_STAMP_OUT(0);
 }
 static_assert(16 * QS_LD <= NRW_FWD_AREA(4), "the epilogue's staging rows fit the merge area");
 
@@ -478,10 +440,6 @@ static bool nrw_static_edge(const BlockArgs& a) { return (a.flags & EGT_BF_STATI
 
 size_t egt_narrow_fwd_lds(int nw) { return ((size_t)(nw == 8 ? NRW_FWD_AREA(8) : NRW_FWD_AREA(4)) + 16 * QS_LD + 80) * 4; }
 
-#ifdef NRW_TIMING
-static const char* const g_nf_names[] = {"constants + first requests", "key loop", "sync + merge", "node-side epilogue"};
-static NrwTimer g_nf{"k_narrow_fwd", g_nf_names, 4};
-#endif
 template <bool BF, int FEAT>
 static void nrw_fwd(BlockArgs& a, int nw, bool half, const EgtLaunch& s, hipStream_t st) {
   if (half) egt_launch_planned<k_narrow_fwd<BF, FEAT, 8, true>>("k_block_fwd", s, st, a);
@@ -489,15 +447,8 @@ static void nrw_fwd(BlockArgs& a, int nw, bool half, const EgtLaunch& s, hipStre
   else egt_launch_planned<k_narrow_fwd<BF, FEAT, 4, false>>("k_block_fwd", s, st, a);
 }
 void egt_narrow_launch_fwd(BlockArgs& a, int nw, bool half, const EgtLaunch& s, hipStream_t st) {
-#ifdef NRW_TIMING
-  { static bool reg = false; if (!reg) { reg = true; atexit([] { g_nf.report(); }); } }
-  a.dbg = g_nf.attach(s.grid);
-#endif
   if (a.bf16) NRW_FEAT_DISPATCH(true, (nrw_fwd<true, FT>(a, nw, half, s, st)));
   else NRW_FEAT_DISPATCH(false, (nrw_fwd<false, FT>(a, nw, half, s, st)));
-#ifdef NRW_TIMING
-  g_nf.collect(s.grid, st);
-#endif
 }
 
 // ------------------------------------------------------------------- backward, matrix-core lanes ---
@@ -523,9 +474,7 @@ void egt_narrow_launch_fwd(BlockArgs& a, int nw, bool half, const EgtLaunch& s, 
 template <bool BF, int FEAT, int NW>
 __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockArgs a) {
   seed_from_device(a);
-#ifdef NRW_TIMING
-  unsigned nacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nlast = (unsigned)__builtin_amdgcn_s_memtime();
-#endif
+  EGT_STAMP_DECL;
   typedef NrwLd<BF> LD;
   constexpr bool MV = NRW_MMA_BF_VALUES(BF), MB = NRW_MMA_BF(BF);   // bf16 MFMAs: value path (projection recompute) / gradient path
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -554,15 +503,11 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
   BwdProRegs proR;
   if (NW == 8 && wave < 4) bwd_node_prologue_load<NRW_DE>(a, proR, b, l_begin);
   bwd_stage_rows<64 * NW, NW == 4 ? 3 : 2>(a, qd, b, l_begin, nl);
-  NSTMP(0);   // staging issued
+  EGT_STAMP(0);   // staging issued
   const int ntile = (N + 15) / 16;
   // Work of a wave: key tiles w, w+NW, ... when the tile count is a multiple of NW (or < NW); otherwise the ntile x nl (tile, row)
   // steps are cut into NW CONTIGUOUS equal ranges and a tile that straddles two ranges is shared by neighbouring waves.
-#ifdef NRW_NO_BALANCE
-  const bool balance = false;
-#else
-  const bool balance = ntile >= NW && (ntile % NW) != 0;
-#endif
+  const bool balance = ntile >= NW && (ntile % NW) != 0;   // (worth 3 us per launch at config 3, three workgroups per CU)
   const int T = ntile * nl;
   const int t0 = balance ? (wave * T) / NW : 0, t1 = balance ? ((wave + 1) * T) / NW : 0;
   const int mt_first = balance ? t0 / nl : wave, mt_last = balance ? (t1 - 1) / nl : ntile - 1, mt_step = balance ? 1 : NW;
@@ -621,7 +566,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
     else bwd_node_prologue_idle(a);   // the prologue is four waves' work: the others only meet its barriers
   }
   __syncthreads();   // prologue scratch dead, qd rows complete
-  NSTMP(1);   // node-side prologue
+  EGT_STAMP(1);   // node-side prologue
   load_weights();
   v4f accT = {0.f, 0.f, 0.f, 0.f}, accR = {0.f, 0.f, 0.f, 0.f};
   float ssum = 0.f;   // column p of dGE summed over the pairs 4 s + q of every step (the B operands of the T product): ONE register
@@ -644,7 +589,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
     const MaskRegs mr{make_float2(1.f, 1.f), 0};
     const uint32_t pcol = (uint32_t)((size_t)b * N * N + mc);   // pair index of (row 0 of the graph, key mc), mod 2^32: the mask-RNG counter
     const int loff = mc * NRW_DE + 2 * q;         // the lane's element offset inside a pair row
-    NSTMP(2);   // tile set-up: weights (first tile), K / V -> LDS, first e / de' requests
+    EGT_STAMP(2);   // tile set-up: weights (first tile), K / V -> LDS, first e / de' requests
     for (int li = r0; li < r1; ++li) {
       const int l = l_begin + li;
       const uint32_t pair = pcol + (uint32_t)(l * N);
@@ -789,7 +734,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
         if (kvalid) LD::ustore(a.de, ugraph + (size_t)l * N, loff, o);
       }
     }
-    NSTMP(3);   // row loop
+    EGT_STAMP(3);   // row loop
     // ---- the tile's dK / dV: the workgroup's partial slot of key m ----
     float4* ko = reinterpret_cast<float4*>(a.dkvp + (((((size_t)b * a.NLR + lr) * N + mc) * 2 + 0) * 4 + q) * 16);
     float4* vo = reinterpret_cast<float4*>(a.dkvp + (((((size_t)b * a.NLR + lr) * N + mc) * 2 + 1) * 4 + q) * 16);
@@ -819,7 +764,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
       if (lane == 0) pflag[wave] = 1;
     }
   }
-  NSTMP(4);   // dK / dV stores, parked partials
+  EGT_STAMP(4);   // dK / dV stores, parked partials
   // ---- edge-parameter gradient partials of the workgroup: T [16][16] | s [16] | R [16][16] ----
   ssum = nrw_sum4rows(ssum);   // column p: the four lane rows hold the pairs q, 4 + q, 8 + q, 12 + q
   __syncthreads();
@@ -841,32 +786,9 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 3 : 2) k_narrow_bwd(BlockAr
     if (NW == 8) v += (sm[4 * 528 + i] + sm[5 * 528 + i]) + (sm[6 * 528 + i] + sm[7 * 528 + i]);
     out[i] = v;
   }
-#ifdef NRW_TIMING
-  NSTMP(5);   // workgroup partials (waits for the slowest wave)
-  if (a.dbg && lane == 0 && wave < 4) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a.dbg[((size_t)blockIdx.x * 4 + wave) * 8 + i] = nacc[i];
-  }
-#endif
+  EGT_STAMP(5);   // workgroup partials (waits for the slowest wave)
+  EGT_STAMP_OUT(1);
 }
-
-#ifdef NRW_TIMING
-static unsigned* g_nt_dev = nullptr;
-static unsigned* g_nt_dev2 = nullptr;
-static double g_nt2_sum[8];
-static int g_nt_n = 0;
-static double g_nt_sum[8];
-static long g_nt_launch = 0, g_nt_waves = 0;
-static void nrw_timing_report() {
-  static const char* nm[] = {"staging issue", "node-side prologue + sync", "tile set-up (K/V, first e)", "row loop", "dK/dV stores + park", "workgroup partials + sync"};
-  if (!g_nt_waves) return;
-  double tot = 0; for (int i = 0; i < 6; ++i) tot += g_nt_sum[i];
-  fprintf(stderr, "[egt] k_narrow_bwd section cycles per wave (mean over %ld waves, %ld launches; total %.0f):\n", g_nt_waves, g_nt_launch, tot / g_nt_waves);
-  for (int i = 0; i < 6; ++i) fprintf(stderr, "    %-30s %10.0f  (%.1f %%)\n", nm[i], g_nt_sum[i] / g_nt_waves, 100.0 * g_nt_sum[i] / tot);
-  fprintf(stderr, "    prologue (pro = 2 launches, per wave): load issue %.0f | first round trip -> rows in LDS %.0f | sync + LN fwd + 48 MFMA %.0f | dQKV out + sync + LN bwd + col sums %.0f | wo/va + sync %.0f | 16 MFMA + delta partials %.0f | dbo + sync + delta %.0f\n",
-          g_nt2_sum[0] / g_nt_waves, g_nt2_sum[1] / g_nt_waves, g_nt2_sum[2] / g_nt_waves, g_nt2_sum[3] / g_nt_waves, g_nt2_sum[4] / g_nt_waves, g_nt2_sum[5] / g_nt_waves, g_nt2_sum[6] / g_nt_waves);
-}
-#endif
 
 size_t egt_narrow_bwd_lds(int nw) {   // four waves: 47 KB, three workgroups per CU
   constexpr int AREA4 = 4 * NRW_M_WAVE > BWD_PRO_WS ? 4 * NRW_M_WAVE : BWD_PRO_WS, AREA8 = 8 * NRW_M_WAVE;
@@ -880,30 +802,13 @@ static void nrw_bwd(BlockArgs& a, int nw, const EgtLaunch& s, hipStream_t st) {
   else egt_launch_planned<k_narrow_bwd<BF, FEAT, 4>>("k_block_bwd", s, st, a);
 }
 void egt_narrow_launch_bwd(BlockArgs& a, int nw, const EgtLaunch& s, hipStream_t st) {
-#ifdef NRW_TIMING
-  const int nwg = s.grid;
-  if (g_nt_n < nwg) {
-    if (g_nt_dev) (void)hipFree(g_nt_dev);
-    (void)hipMalloc(&g_nt_dev, (size_t)nwg * 32 * sizeof(unsigned));
-    if (g_nt_dev2) (void)hipFree(g_nt_dev2);
-    (void)hipMalloc(&g_nt_dev2, (size_t)nwg * 32 * sizeof(unsigned));
-    (void)hipMemset(g_nt_dev2, 0, (size_t)nwg * 32 * sizeof(unsigned));
-    if (!g_nt_n) atexit(nrw_timing_report);
-    g_nt_n = nwg;
-  }
-  a.dbg = g_nt_dev; a.dbg2 = g_nt_dev2;
-#endif
   if (a.bf16) NRW_FEAT_DISPATCH(true, (nrw_bwd<true, FT>(a, nw, s, st)));
   else NRW_FEAT_DISPATCH(false, (nrw_bwd<false, FT>(a, nw, s, st)));
-#ifdef NRW_TIMING
-  (void)hipStreamSynchronize(st);
-  if (++g_nt_launch > 20) {
-    static unsigned* h = nullptr; static int hn = 0;
-    if (hn < nwg) { free(h); h = (unsigned*)malloc((size_t)nwg * 32 * sizeof(unsigned)); hn = nwg; }
-    (void)hipMemcpy(h, g_nt_dev, (size_t)nwg * 32 * sizeof(unsigned), hipMemcpyDeviceToHost);
-    for (int w = 0; w < nwg * 4; ++w) { for (int i = 0; i < 8; ++i) g_nt_sum[i] += h[w * 8 + i]; ++g_nt_waves; }
-    (void)hipMemcpy(h, g_nt_dev2, (size_t)nwg * 32 * sizeof(unsigned), hipMemcpyDeviceToHost);
-    for (int w = 0; w < nwg * 4; ++w) for (int i = 0; i < 8; ++i) g_nt2_sum[i] += h[w * 8 + i];
-  }
-#endif
 }
+
+#ifdef EGT_STAMPS
+static const char* const g_nf_names[] = {"constants + first requests", "key loop", "sync + merge", "node-side epilogue"};
+static const char* const g_nb_names[] = {"staging issue", "node-side prologue + sync", "tile set-up (K/V, first e)", "row loop", "dK/dV stores + park", "workgroup partials + sync"};
+static const EgtStampKernel g_nrw_stamped[] = {{"k_narrow_fwd", g_nf_names, 4}, {"k_narrow_bwd", g_nb_names, 6}};
+EGT_STAMP_REGISTER(g_nrw_stamped);
+#endif

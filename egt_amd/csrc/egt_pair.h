@@ -41,14 +41,8 @@ struct PairArgs {
 __device__ __forceinline__ void lds_sync_() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 // The same hand-off WITHOUT the drain: the LDS executes one wave's DS instructions in program order, so a read issued behind a write of
 // the same wave sees it and a write issued behind a read cannot overtake it -- only the compiler has to keep the order (the waits for
-// the reads' results are its own, at their first use).  PAIR_LDS_NOWAIT=0 restores the drains (A/B).
-#ifndef PAIR_LDS_NOWAIT
-#define PAIR_LDS_NOWAIT 1
-#endif
-__device__ __forceinline__ void lds_order_() {
-  if (PAIR_LDS_NOWAIT) { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
-  else lds_sync_();
-}
+// the reads' results are its own, at their first use).
+__device__ __forceinline__ void lds_order_() { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
 // the workgroup barrier of the pair kernels: nothing is scheduled across it (a plain asm barrier orders memory only: hipcc hoisted the
 // next trip's LayerNorm arithmetic above it, i.e. in front of the wait for a tile that had only just been requested)
 __device__ __forceinline__ void pair_barrier() {
@@ -60,29 +54,10 @@ __device__ __forceinline__ void pair_barrier() {
 #ifndef PAIR_ABL
 #define PAIR_ABL 0   // timing ablations of k_pair_fwd (results are wrong): 1 attention waves idle, 2 no dense_edge_r / stores, 4 no LN / projections, 8 no e requests, 16 no e' stores, 32 / 64 e loads / e' stores on the tile of trip 0 (cache hits)
 #endif
-#ifndef PAIR_BWD_NT
-#define PAIR_BWD_NT 4   // k_pair_bwd cache-policy hints: 1 e tiles non-temporal, 2 de' first read, 4 de' second read (POST).  Measured (same box, us per launch):
-                        // 0: 263.3-263.4, 1: 265.6-266.2, 4: 246.8-255.5, 5: 249.4-253.9 -> the re-read of de' (a tile nobody reads again) is non-temporal
-#endif
-#ifndef PAIR_ST_SC
-#define PAIR_ST_SC 0   // k_pair_fwd: e' stores with scope bits (1: sc1, 2: sc0 sc1 -- write-through forms that drop the line from L2); A/B
-#endif
-#ifndef PAIR_NT_ST
-#define PAIR_NT_ST 0   // k_pair_fwd: e' stores non-temporal (A/B)
-#endif
-#ifndef PAIR_STAGGER
-#define PAIR_STAGGER 0   // k_pair_fwd: 1 = a workgroup starts on the key tile of its own row block instead of every workgroup on tile `it` in lock step
-                        // (the 16 rows of a workgroup are 64 KB apart: a test for HBM channel camping) -- measured: no difference (145.1-146.2 vs 145.4-146.7 us)
-#endif
 #ifndef PAIR_BWD_ABL
 #define PAIR_BWD_ABL 0   // timing ablations of k_pair_bwd (results are wrong): 1 first reads of e / de', 2 de stores, 4 the POST re-read of de' -- on the tile of trip 0 (cache hits)
 #endif
-#ifndef PAIR_EDGE_PRIO
-#define PAIR_EDGE_PRIO 2
-#endif
-#ifndef PAIR_NT_E
-#define PAIR_NT_E 0   // 1: the forward's e tiles by non-temporal loads (read once; measured before adopting)
-#endif
+#define PAIR_EDGE_PRIO 2   // s_setprio of the edge waves
 // a wave-uniform pointer the compiler cannot prove uniform -> scalar registers (LDS-DMA takes its base address from an SGPR pair)
 __device__ __forceinline__ const float* uni_ptr(const float* p) {
   const uint64_t v = (uint64_t)(uintptr_t)p;
@@ -105,10 +80,6 @@ typedef float pr_nt_v4f __attribute__((ext_vector_type(4)));
 template <bool NT>
 __device__ __forceinline__ float4 pr_ld4(const char* p) {
   if (NT) { const pr_nt_v4f t = __builtin_nontemporal_load(reinterpret_cast<const pr_nt_v4f*>(p)); return make_float4(t[0], t[1], t[2], t[3]); }
-  return *reinterpret_cast<const float4*>(p);
-}
-__device__ __forceinline__ float4 egt_ld4_nt_(const float* p) {
-  if (PAIR_NT_E) { const pr_nt_v4f t = __builtin_nontemporal_load(reinterpret_cast<const pr_nt_v4f*>(p)); return make_float4(t[0], t[1], t[2], t[3]); }
   return *reinterpret_cast<const float4*>(p);
 }
 template <int DE> struct PairGeo { static constexpr int T = DE / 16; };
@@ -210,20 +181,16 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
   const int b = __builtin_amdgcn_readfirstlane(wg / mtiles), l0 = __builtin_amdgcn_readfirstlane((wg % mtiles) * 16);   // (the division runs on the VALU: back to scalar registers)
   const size_t arr = (size_t)a.B * AH * NP * D;
   const bool clip = (a.flags & EGT_F_CLIP) != 0;
-  // Key-tile order: trip `it` works on key tile (it + row block) mod mtiles.  The online softmax does not care about the order of the keys,
-  // HBM does: the 16 rows of a workgroup are N De 4 bytes apart (64 KB at config 5), so with every workgroup on key tile `it` in lock
-  // step the whole chip reads and writes ONE 2 KB window of every 64 KB period of the e tensor at a time (a fraction of the channels);
-  // staggered, the 32 row blocks of a graph cover the period.
-  const int tstart = PAIR_STAGGER ? (l0 >> 4) % mtiles : 0;
-  auto mt_of = [&](int it) __attribute__((always_inline)) { const int t = it + tstart; return t < mtiles ? t : t - mtiles; };
-  STAMP_DECL;
+  // Key tile of trip `it`: tile `it`.  (Measured and not kept: every workgroup starting on the key tile of its own row block, a test
+  // for HBM channel camping -- no difference, 145.1-146.2 against 145.4-146.7 us.  What is left of it is this wrap past the last tile: dead,
+  // but hipcc does not know mtiles > 0 and keeps it for trip 0's requests; taking it out changes k_pair_fwd's set-up code.)
+  auto mt_of = [&](int it) __attribute__((always_inline)) { return it < mtiles ? it : it - mtiles; };
+  EGT_STAMP_DECL;
 
   if (wv >= 4) {
     // --------------------------------------------------------------------- edge waves ----
     const int j = wv - 4, p = lane & 15, q = lane >> 4;
-#if PAIR_EDGE_PRIO
     __builtin_amdgcn_s_setprio(PAIR_EDGE_PRIO);   // the edge waves are the longer role: the SIMD's issue arbitration (priority, then age) favours them
-#endif
     for (int m = tid - 256; m < NP + 16; m += 256) {
       float ka = 0.f;
       if (m >= N) ka = KEY_OFF;
@@ -270,7 +237,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int t = 0; t < T; ++t) s.x[r][t] = egt_ld4_nt_(reinterpret_cast<const float*>(erow[r] + mo + 64 * t));
+        for (int t = 0; t < T; ++t) s.x[r][t] = *reinterpret_cast<const float4*>(erow[r] + mo + 64 * t);   // (plain loads: the non-temporal A/B switch is retired)
     };
     // LN + projections of a tile from set s -> E / G planes of stage st
     auto project = [&](const ESet& s, int st) __attribute__((always_inline)) {
@@ -334,9 +301,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
         for (int t = 0; t < T; ++t) {
           char* dst = (FULL || (rowok[r] && m < N)) ? orow[r] + mo + 64 * t : dumpl;
           const pr_nt_v4f o4 = {ov.x[r][t].x, ov.x[r][t].y, ov.x[r][t].z, ov.x[r][t].w};
-          if (PAIR_ST_SC == 1) asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(dst), "v"(o4) : "memory");
-          else if (PAIR_ST_SC == 2) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(dst), "v"(o4) : "memory");
-          else *reinterpret_cast<pr_nt_v4f*>(dst) = o4;
+          *reinterpret_cast<pr_nt_v4f*>(dst) = o4;   // (plain stores: the sc1 / sc0 sc1 write-through and non-temporal A/B switches are retired)
         }
     };
     auto update = [&](const ESet& s, int itx) __attribute__((always_inline)) { ESet ov; update_compute(s, itx, ov); update_store(ov, itx); };
@@ -360,20 +325,20 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
           asm volatile("" : "+v"(s_.x[r][t].x), "+v"(s_.x[r][t].y), "+v"(s_.x[r][t].z), "+v"(s_.x[r][t].w));
     };
     auto steady = [&](int it, ESet& done, ESet& nxt) __attribute__((always_inline)) {
-      STAMP(7);
+      EGT_STAMP(7);
       pin(nxt);
       if (!(PAIR_ABL & 2)) update(done, it - 1);
       __builtin_amdgcn_sched_barrier(0);
-      STAMP(0);
+      EGT_STAMP(0);
       // (requesting e(it+2) BEFORE the stores -- vmcnt retires in order, so that the next trip's wait for it would not cover them -- was
       //  built and measured: 159-160 us against 146-147; the order below stays)
       if (!(PAIR_ABL & 8)) eload(done, mt_of(min(it + 2, mtiles - 1)));
       __builtin_amdgcn_sched_barrier(0);
-      STAMP(1);
+      EGT_STAMP(1);
       if (!(PAIR_ABL & 4)) project(nxt, (it + 1) & 1);
-      STAMP(2);
+      EGT_STAMP(2);
       pair_barrier();           // barrier(it+1)
-      STAMP(3);
+      EGT_STAMP(3);
     };
     {   // trip 0: nothing to update yet
       eload(S2, mt_of(min(2, mtiles - 1)));
@@ -398,8 +363,8 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
       const int k = (mtiles - 1) % 3;
       if (k == 0) update(S0, mtiles - 1); else if (k == 1) update(S1, mtiles - 1); else update(S2, mtiles - 1);
     }
-    STAMP(8);
-    STAMP_OUT(0);
+    EGT_STAMP(8);
+    EGT_STAMP_OUT(ST_PAIR_FWD_EDGE);
   } else {
     // ---------------------------------------------------------------- attention waves ----
     const int w = wv, ll = lane & 15, q = lane >> 4;
@@ -447,7 +412,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
     const int lq = PR_CLAMP(l0 + ll);
     vm_wait<0>();              // (Q fragments in registers, tiles of key tile 0 landed)
     pair_barrier();             // barrier(0)
-    STAMP(7);
+    EGT_STAMP(7);
     for (int it = 0; it < mtiles; ++it) {
       const int m0 = 16 * mt_of(it);
       const bool more = it + 1 < mtiles;
@@ -479,7 +444,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
 #pragma unroll
           for (int hh = 0; hh < 2; ++hh) s[hh] = MFMA(f4get(kc[hh][Tt], u), Qr[hh][4 * Tt + u], s[hh]);
       __builtin_amdgcn_sched_barrier(0);
-      STAMP(0);
+      EGT_STAMP(0);
       // the K tiles of the next key tile: this wave was their only reader and its reads have returned (the MFMAs above consumed them)
       if (more) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); dma_tile(kdst, Kh + (size_t)mt_of(it + 1) * 16 * D); }
       const float kav[4] = {ka4.x, ka4.y, ka4.z, ka4.w}, kgv[4] = {kg4.x, kg4.y, kg4.z, kg4.w};
@@ -528,7 +493,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-      STAMP(1);
+      EGT_STAMP(1);
       if (more) vm_wait<2 * KT>(); else vm_wait<0>();   // V^T(it) landed (only the K(it+1) pieces just issued are younger)
       float4 vc[2][KT];
 #pragma unroll
@@ -543,10 +508,10 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
 #pragma unroll
           for (int hh = 0; hh < 2; ++hh) oacc[hh][kt] = MFMA(f4get(vc[hh][kt], r), pa_[hh][r], oacc[hh][kt]);
       __builtin_amdgcn_sched_barrier(0);
-      STAMP(2);
+      EGT_STAMP(2);
       if (more) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); dma_tile(vdst, VT + (size_t)mt_of(it + 1) * 16 * D); }
       pair_barrier();           // barrier(it+1)
-      STAMP(3);
+      EGT_STAMP(3);
     }
     // ---- finalize: O[l][k] / l_run into the K stage as [row][k][8 heads]; row statistics for the backward ----
 #pragma unroll
@@ -561,7 +526,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
       if (l < N && q == 0)
         *reinterpret_cast<float4*>(a.rowstats + (((size_t)b * N + l) * AH + h) * 4) = make_float4(mrun[hh], lrun[hh], 0.f, 0.f);
     }
-    STAMP_OUT(0);
+    EGT_STAMP_OUT(ST_PAIR_FWD_ATT);
   }
   // V_att[l][k * 8 + h]: 16 rows x 512 channels, consecutive threads consecutive 16-byte pieces
   pair_barrier();
@@ -607,14 +572,12 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
   const int b = __builtin_amdgcn_readfirstlane(wg / mtiles), mt0 = __builtin_amdgcn_readfirstlane(wg % mtiles), m0 = mt0 * 16;
   const size_t arr = (size_t)a.B * AH * NP * D;
   const bool clip = (a.flags & EGT_F_CLIP) != 0;
-  STAMP_DECL;
+  EGT_STAMP_DECL;
 
   if (wv >= 4) {
     // --------------------------------------------------------------------- edge waves ----
     const int j = wv - 4, p = lane & 15, q = lane >> 4;
-#if PAIR_EDGE_PRIO
     __builtin_amdgcn_s_setprio(PAIR_EDGE_PRIO);
-#endif
     {   // the prepared table (k_pair_prep) -> LDS: every edge wave writes the same values (a benign race) and reads only after its own writes
 #pragma unroll
       for (int i = 0; i < 3 * T + 1; ++i)
@@ -658,9 +621,9 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
       const char* er = rowaddr(pa.e, ltile, r, lo);
       const char* dr = rowaddr(pa.d_e_out, ltile, r, lo);
 #pragma unroll
-      for (int t = 0; t < T; ++t) s.x[r][t] = pr_ld4<(PAIR_BWD_NT & 1) != 0>(er + lo + 64 * t);
+      for (int t = 0; t < T; ++t) s.x[r][t] = pr_ld4<false>(er + lo + 64 * t);
 #pragma unroll
-      for (int t = 0; t < T; ++t) s.df[r][t] = pr_ld4<(PAIR_BWD_NT & 2) != 0>(dr + lo + 64 * t);
+      for (int t = 0; t < T; ++t) s.df[r][t] = pr_ld4<false>(dr + lo + 64 * t);
     };
     // de' of a held tile is NOT kept in registers from PRE to POST (two sets x four rows x 8 registers that the allocator does not have:
     // spill reloads wait on vmcnt(0), i.e. drain the wave's whole prefetch queue): POST reads it again -- a tile this CU streamed one
@@ -670,7 +633,8 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
       uint32_t lo;
       const char* dr = rowaddr(pa.d_e_out, ltile, r, lo, 4);
 #pragma unroll
-      for (int t = 0; t < T; ++t) s.df[r][t] = pr_ld4<(PAIR_BWD_NT & 4) != 0>(dr + lo + 64 * t);
+      // non-temporal: a tile nobody reads again.  Measured, us per launch: no hint 263.3-263.4, e tiles 265.6-266.2, this re-read 246.8-255.5, both 249.4-253.9
+      for (int t = 0; t < T; ++t) s.df[r][t] = pr_ld4<true>(dr + lo + 64 * t);
     };
     float* xs = scr + j * (2 * 16 * DE);   // [ehat tile | de' tile]: layout below
     // plane offsets (ptT_off) of the lane's rows 4 r + sk: the row enters through r (the chunk XOR, compile time) and sk (the dword):
@@ -810,27 +774,27 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
     // values of tile it+1, which PRE then turns into the held set of it+1
     auto steady = [&](int it, HSet& prev, int set) __attribute__((always_inline)) {
       float* pprev = Pl + set * 3 * TSZ;
-      STAMP(8);
+      EGT_STAMP(8);
 #pragma unroll
       for (int r = 0; r < 4; ++r) df_load(prev, r, it - 1);
       __builtin_amdgcn_sched_barrier(0);
-      STAMP(0);
+      EGT_STAMP(0);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         post(prev, set, r, it - 1, pprev);
         raw_load(prev, r, it + 1);
       }
-      STAMP(1);
+      EGT_STAMP(1);
       const float4 stn = stat_load(it + 1);
       __builtin_amdgcn_sched_barrier(0);
-      STAMP(4);
+      EGT_STAMP(4);
 #pragma unroll
       for (int r = 0; r < 4; ++r) pre(prev, set, r, it + 1, pprev);
-      STAMP(5);
+      EGT_STAMP(5);
       stat_put(stn, (it + 1) & 1);
-      STAMP(6);
+      EGT_STAMP(6);
       pair_barrier();           // barrier(it+1)
-      STAMP(7);
+      EGT_STAMP(7);
     };
     {   // trip 0: nothing to POST yet; tile 1's raw values were requested in the prologue
       if (mtiles > 1) {
@@ -873,8 +837,8 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
         for (int r = 0; r < 4; ++r) post(H0, 0, r, mtiles - 1, pl);
       }
     }
-    STAMP(9);
-    STAMP_OUT(1);
+    EGT_STAMP(9);
+    EGT_STAMP_OUT(ST_PAIR_BWD_EDGE);
     // partials of this wave -> the (now idle) other plane set: [That[DE][16] | s[16] | dWr[8][DE] | dbr[DE]]
     float* red = Pl + (mtiles & 1) * 3 * TSZ + j * (PSZ1 + PSZ2);
 #pragma unroll
@@ -956,7 +920,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
     dma_half(0, 1);
     vm_wait<0>();              // (K / V fragments in registers, both stages of query tile 0 landed)
     pair_barrier();             // barrier(0)
-    STAMP(8);
+    EGT_STAMP(8);
     for (int l0 = 0, it = 0; it < mtiles; l0 += 16, ++it) {
       float* ps = Pl + (it & 1) * 3 * TSZ;
 #pragma unroll
@@ -991,7 +955,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
             dp = MFMA(f4get(oa[Tt], u), f4get(Vr[hf][Tt], u), dp);
           }
         __builtin_amdgcn_sched_barrier(0);
-        STAMP(0);
+        EGT_STAMP(0);
         float at[4], da[4], dE4[4], dG4[4], hh4[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1023,7 +987,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
         *reinterpret_cast<float4*>(ps + 2 * TSZ + h * PT_PL + po4) = make_float4(hh4[0], hh4[1], hh4[2], hh4[3]);
         *reinterpret_cast<float4*>(dAb[hf] + (size_t)it * mtiles * 256 + ooff) = make_float4(da[0], da[1], da[2], da[3]);
         __builtin_amdgcn_sched_barrier(0);
-        STAMP(1);
+        EGT_STAMP(1);
         // ---- dV^T[k][m] += sum_l dO[l][k] A[l][m] ; dK^T[k][m] += sum_l (d^-1/2 Q)[l][k] dA[l][m] ----
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt)
@@ -1035,14 +999,14 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
             dVacc[hf][kt] = MFMA(oo, at[r], dVacc[hf][kt]);
             dKacc[hf][kt] = MFMA(qq, da[r], dKacc[hf][kt]);
           }
-        STAMP(2);
+        EGT_STAMP(2);
         // the stage is free (this wave was its only reader): the same head's tiles of the next query tile
         if (it + 1 < mtiles) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); dma_half(it + 1, hf); }
         if (hf == 1) pair_barrier();   // barrier(it+1)
-        STAMP(3);
+        EGT_STAMP(3);
       }
     }
-    STAMP_OUT(1);
+    EGT_STAMP_OUT(ST_PAIR_BWD_ATT);
     // dK / dV into the (now idle) operand stages as [key][k][8 heads]: dK in the first 32 KB, dV in the second
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
@@ -1076,3 +1040,10 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
     }
   }
 }
+
+#ifdef EGT_STAMPS   // phase names of the stamps above (nullptr: not stamped)
+static const char* const g_pair_fwd_att_names[] = {"wait K + loads + S: 32 MFMA", "DMA K + softmax / gates / H_hat", "wait V + A.V: 32 MFMA", "DMA V + barrier", nullptr, nullptr, nullptr, "(setup)"};
+static const char* const g_pair_fwd_edge_names[] = {"dense_edge_r of tile it-1", "e requests", "LN + projections", "barrier", nullptr, nullptr, nullptr, "(setup)", "last update"};
+static const char* const g_pair_bwd_att_names[] = {"wait stage + loads + S, dP: 32 MFMA", "softmax bwd + planes + dA", "dV, dK: 32 MFMA", "DMA next (+ barrier)", nullptr, nullptr, nullptr, nullptr, "(setup)"};
+static const char* const g_pair_bwd_edge_names[] = {"de' reload issue", "POST 4 rows + e, de' requests", nullptr, nullptr, "stat request", "PRE 4 rows", "stat put", "barrier", "(setup)", "last POST"};
+#endif

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Per-kernel assembly of two builds of one source, compared kernel by kernel (instructions and .amdhsa metadata; comments,
-label numbers and symbol names normalised).  A kernel that gained a trailing `float` template argument (the storage type of the
-bf16 edge change) is matched to its old name.  Prints the kernels that differ and a count line.
+"""Per-kernel assembly of two builds, compared kernel by kernel (instructions and .amdhsa metadata; comments, label numbers and
+symbol names normalised).  Kernels are matched by their demangled names.  Prints the kernels that differ and a count line.
 
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -c egt_amd/csrc/egt_ffn.hip -I egt_amd/csrc -I include \
-          -mllvm -amdgpu-mfma-vgpr-form=1 --save-temps=obj -o /tmp/new/egt_ffn.o        (and the same for the parent commit's tree)
-    python tools/cmp_kernel_asm.py /tmp/old/egt_ffn-hip-amdgcn-amd-amdhsa-gfx950.s /tmp/new/egt_ffn-hip-amdgcn-amd-amdhsa-gfx950.s [-v]
+    python tools/cmp_kernel_asm.py OLD.s NEW.s [-v] [--show 'demangled kernel name']     (hipcc --save-temps=obj leaves <unit>-hip-amdgcn-amd-amdhsa-gfx950.s)
+    python tools/cmp_kernel_asm.py --trees OLD_TREE NEW_TREE SCRATCH_DIR
+--trees: every file of build.SOURCES of each tree compiled as build.py compiles it (this tree's build.EXTRA_FLAGS, at most 8 compilations
+at a time) into SCRATCH_DIR/old and /new, one count line per translation unit; exit status 1 if any unit has differ, new-only or old unmatched above 0.
+--mnemonics (either mode): the opcode sequences only -- operands and .amdhsa metadata dropped (for a change that moves kernel-argument
+offsets; tools/kres.py compares registers, spills, scratch and LDS).
 """
-import re, subprocess, sys
+import concurrent.futures, difflib, importlib.util, os, re, subprocess, sys
 
 def funcs(path):
     out, cur, name = {}, None, None
@@ -16,21 +18,19 @@ def funcs(path):
         if m and not line.startswith('.'):
             name = m.group(1); cur = []; out[name] = cur; continue
         if name is None: continue
-        if re.match(r'^\s*\.(end_amdhsa_kernel|size)\b', line):
-            cur.append(line); 
-            if line.strip().startswith('.size'): name = None
-            continue
         cur.append(line)
+        if line.strip().startswith('.size'): name = None
     return out
 
 def norm(lines):
     res = []
     for l in lines:
-        l = re.sub(r'\.LBB\d+_(\d+)', r'.LBB_\1', l)
-        l = re.sub(r'\.Lfunc_end\d+', '.Lfunc_end', l)
-        l = re.sub(r'_Z\S+', 'SYM', l)
+        l = re.sub(r'_Z\S+', 'SYM', re.sub(r'\.Lfunc_end\d+', '.Lfunc_end', re.sub(r'\.LBB\d+_(\d+)', r'.LBB_\1', l)))
         if l.strip().startswith(';'): continue
         l = re.sub(r'\s*;.*$', '', l.rstrip('\n'))
+        if MNEMONICS:
+            if not l.strip() or (l.lstrip().startswith('.') and not l.startswith('.LBB')): continue   # directives, metadata
+            l = l.split()[0]
         res.append(l)
     return res
 
@@ -38,28 +38,41 @@ def dem(names):
     r = subprocess.run(['c++filt'], input='\n'.join(names), capture_output=True, text=True).stdout.split('\n')
     return dict(zip(names, r))
 
-a, b = funcs(sys.argv[1]), funcs(sys.argv[2])
-da, db = dem(list(a)), dem(list(b))
-ia = {v: k for k, v in da.items()}
-same = diff = 0; newonly = []
-for nb, d in db.items():
-    old = re.sub(r', float>', '>', d)
-    old = re.sub(r'<float>', '', old)
-    if old in ia:
-        if norm(a[ia[old]]) == norm(b[nb]): same += 1
+def compare(old_s, new_s, label=''):   # prints the differing kernels and the count line; returns differ + new-only + old unmatched
+    a, b = funcs(old_s), funcs(new_s)
+    da, db = dem(list(a)), dem(list(b))
+    ia = {v: k for k, v in da.items()}
+    same, diff, newonly = 0, 0, []
+    for nb, d in db.items():
+        if d not in ia: newonly.append(d)
+        elif norm(a[ia[d]]) == norm(b[nb]): same += 1
         else:
             diff += 1; print('DIFF', d)
-    else:
-        newonly.append(d)
-unmatched = [da[k] for k in a if da[k] not in {re.sub(r'<float>', '', re.sub(r', float>', '>', x)) for x in db.values()}]
-print(f'identical {same}, differ {diff}, new-only {len(newonly)}, old unmatched {len(unmatched)}')
-for x in unmatched: print('  OLD-UNMATCHED', x)
-if '-v' in sys.argv:
-    for x in newonly: print('  NEW', x)
-if '--show' in sys.argv:
-    import difflib
-    tgt = sys.argv[sys.argv.index('--show') + 1]
-    for nb, d in db.items():
-        if d == tgt:
-            old = re.sub(r'<float>', '', re.sub(r', float>', '>', d))
-            print(''.join(list(difflib.unified_diff(norm(a[ia[old]]), norm(b[nb]), n=1))[:80]))
+            if SHOW == d: print('\n'.join(list(difflib.unified_diff(norm(a[ia[d]]), norm(b[nb]), n=1, lineterm=''))[:80]))
+    unmatched = [d for d in da.values() if d not in set(db.values())]
+    print(f'{label}identical {same}, differ {diff}, new-only {len(newonly)}, old unmatched {len(unmatched)}')
+    for x in unmatched: print('  OLD-UNMATCHED', x)
+    if '-v' in sys.argv:
+        for x in newonly: print('  NEW', x)
+    return diff + len(newonly) + len(unmatched)
+
+def compile_unit(build, tree, out, src):   # as build.build() compiles it, plus --save-temps=obj; returns the device .s
+    os.makedirs(out, exist_ok=True)
+    csrc, unit = os.path.join(tree, 'egt_amd', 'csrc'), src[:-len('.hip')]
+    cmd = [build._hipcc(), f'--offload-arch={build.ARCH}', '-O3', '-std=c++17', '-fPIC', '-c', os.path.join(csrc, src), '-o', os.path.join(out, unit + '.o'),
+           '-I', csrc, '-I', os.path.join(tree, 'include'), '-Wno-unused-result', '--save-temps=obj'] + build.EXTRA_FLAGS.get(src, [])
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0: raise RuntimeError(f'hipcc failed on {tree}: {src}\n{r.stdout}')
+    return os.path.join(out, f'{unit}-hip-amdgcn-amd-amdhsa-{build.ARCH}.s')
+
+argv = sys.argv[1:]
+MNEMONICS, SHOW = '--mnemonics' in argv, argv[argv.index('--show') + 1] if '--show' in argv else None
+pos = [x for i, x in enumerate(argv) if not x.startswith('-') and (i == 0 or argv[i - 1] != '--show')]
+if '--trees' not in argv: compare(pos[0], pos[1])
+else:
+    spec = importlib.util.spec_from_file_location('egt_build', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'egt_amd', 'build.py'))
+    build = importlib.util.module_from_spec(spec); spec.loader.exec_module(build)
+    with concurrent.futures.ThreadPoolExecutor(max_workers=8) as pool:
+        asm = {(d, s): pool.submit(compile_unit, build, os.path.abspath(t), os.path.join(pos[2], d), s) for t, d in ((pos[0], 'old'), (pos[1], 'new')) for s in build.SOURCES}
+        bad = sum(compare(asm['old', s].result(), asm['new', s].result(), label=f'{s[:-4]}: ') for s in build.SOURCES)
+    sys.exit(1 if bad else 0)
