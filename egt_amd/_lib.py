@@ -88,6 +88,24 @@ class EmbedDesc(C.Structure):
                 ("num_float_features", C.c_int32), ("mask_value", C.c_float), ("reserved", C.c_int32)]
 
 
+EH_LAYERNORM = 0x1   # egt_head_desc.flags
+
+
+class HeadDesc(C.Structure):
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("De", C.c_int32), ("M0", C.c_int32), ("M1", C.c_int32),
+                ("C", C.c_int32), ("dtype", C.c_int32), ("activation", C.c_int32), ("flags", C.c_int32),
+                ("ln_eps", C.c_float), ("reserved", C.c_int32)]
+
+
+HEAD_PARAM_FIELDS = ("edge_norm_final_gamma", "edge_norm_final_beta", "mlp_out_dist_targ_0_kernel",
+                     "mlp_out_dist_targ_0_bias", "mlp_out_dist_targ_1_kernel", "mlp_out_dist_targ_1_bias",
+                     "distance_target_kernel", "distance_target_bias")
+
+
+class HeadParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in HEAD_PARAM_FIELDS]
+
+
 class EGTLibraryError(RuntimeError):
     pass
 
@@ -124,6 +142,12 @@ _PROTOS = {
     "egt_edge_embed_workspace_bytes": (C.c_size_t, [C.POINTER(EmbedDesc)]),
     "egt_edge_embed_fwd": (C.c_int, [C.POINTER(EmbedDesc)] + [_VP] * 9),
     "egt_edge_embed_bwd": (C.c_int, [C.POINTER(EmbedDesc)] + [_VP] * 8),
+    "egt_distance_target": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP]),
+    "egt_edge_head_supported": (C.c_int, [C.POINTER(HeadDesc)]),
+    "egt_edge_head_workspace_bytes": (C.c_size_t, [C.POINTER(HeadDesc)]),
+    "egt_edge_head_fwd": (C.c_int, [C.POINTER(HeadDesc), C.POINTER(HeadParams)] + [_VP] * 5),
+    "egt_edge_head_bwd": (C.c_int, [C.POINTER(HeadDesc), C.POINTER(HeadParams)] + [_VP] * 4
+                          + [C.POINTER(HeadParams)] + [_VP] * 2),
     "egt_dp_unique_id": (C.c_int, [_VP]),
     "egt_dp_init": (C.c_int, [_VP, C.c_int32, C.c_int32]),
     "egt_dp_allreduce": (C.c_int, [_VP, C.c_size_t, C.c_int32, _VP]),

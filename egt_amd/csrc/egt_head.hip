@@ -1,0 +1,694 @@
+// Distance objective of the reference's *_spe_do configs (distance_loss / distance_target): the auxiliary loss over the
+// FINAL edge channels e_L [B,N,N,De].
+//   target   lib/models/graph_model_base.py:66-76     sum of the first T clipped hop matrices, an integer in [0, T]
+//   head     graph_model_base.py:83-94, graph_xformer_model_base.py:343-372
+//            logits = Dense_t(act(Dense_1(act(Dense_0(edge_norm_final(e))))))      De -> M0 -> M1 -> C = T + 1
+//   loss     lib/base/genutil/loss_layers.py:38-67    per_graph[b] = sum_ij CE(logits, target) * (target > 0)
+// One kernel per direction.  A wave owns a 16-pair tile (tiles are cut per graph: the last tile of a graph is ragged, none
+// straddles two graphs); a tile whose 16 targets are all 0 is skipped before anything of e is loaded.  The three products run
+// on v_mfma_f32_16x16x4_f32 tiles with the LayerNorm-folded, zero-padded weights (M0 -> 32, M1 -> 16, C -> 16 columns)
+// resident in LDS; the activations of a tile go through a per-wave LDS image in [pair][feature] layout, which is the
+// A operand of the next product and -- transposed -- of the weight-gradient products of the backward.  The backward recomputes
+// the forward from e (nothing is saved).  Loss and parameter-gradient partials are per workgroup, reduced in a fixed order by
+// k_edge_head_reduce / k_edge_head_finish: no atomics, two runs are bitwise equal.
+#include "egt_common.h"
+
+typedef float v4f_h __attribute__((ext_vector_type(4)));
+#define HMFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+
+#define EH_NW 4      // waves per workgroup
+#define EH_P0 36     // LDS pitch of W0f rows / of the x1 image  (32 columns + 4: the transposed reads stay conflict-free)
+#define EH_P1 20     // LDS pitch of W1 / Wt rows, of the x2 and d_logits images (16 columns + 4)
+
+// LDS hand-offs inside one wavefront: DS operations of a wave complete in order (egt_tile.h lds_sync)
+__device__ __forceinline__ void eh_sync() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// geometry of one instance: DET = 16-column tiles of the (zero-padded) edge width
+template <int DET>
+struct EhGeo {
+  static constexpr int DEP = 16 * DET;                     // padded De
+  static constexpr int PE = DEP + 4;                       // pitch of the e image
+  static constexpr int W0 = 0;                             // [DEP][EH_P0]   gamma-folded
+  static constexpr int W1 = W0 + DEP * EH_P0;              // [32][EH_P1]
+  static constexpr int WT = W1 + 32 * EH_P1;               // [16][EH_P1]
+  static constexpr int B0 = WT + 16 * EH_P1;               // [32]           beta-folded
+  static constexpr int B1 = B0 + 32;                       // [16]
+  static constexpr int BT = B1 + 16;                       // [16]
+  static constexpr int IMG = BT + 16;                      // floats of the prepared weight image
+  // per-wave activations
+  static constexpr int XE = 0;                             // [16][PE]
+  static constexpr int X1 = XE + 16 * PE;                  // [16][EH_P0]
+  static constexpr int X2 = X1 + 16 * EH_P0;               // [16][EH_P1]
+  static constexpr int DL = X2 + 16 * EH_P1;               // [16][EH_P1]
+  static constexpr int RS = DL + 16 * EH_P1;               // [16] rstd
+  static constexpr int WAVE = RS + 16;
+  // gradient image of a workgroup / of the reduction (dense)
+  static constexpr int G0 = 0;                             // dW0f [DEP][32]
+  static constexpr int G1 = G0 + DEP * 32;                 // dW1  [32][16]
+  static constexpr int GT = G1 + 32 * 16;                  // dWt  [16][16]
+  static constexpr int GB0 = GT + 16 * 16;                 // [32]
+  static constexpr int GB1 = GB0 + 32;                     // [16]
+  static constexpr int GBT = GB1 + 16;                     // [16]
+  static constexpr int PG = GBT + 16;
+};
+static inline int eh_det(int De) { return De <= 16 ? 1 : De / 16; }
+static inline int eh_img(int det) { return 16 * det * EH_P0 + 32 * EH_P1 + 16 * EH_P1 + 64; }
+static inline int eh_pg(int det) { return 16 * det * 32 + 32 * 16 + 16 * 16 + 64; }
+
+// ---- weight image: gamma folded into W0, beta into b0, everything zero-padded to the tile widths (one wave) ----
+__global__ void __launch_bounds__(64) k_edge_head_prep(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                       const float* __restrict__ W0, const float* __restrict__ b0,
+                                                       const float* __restrict__ W1, const float* __restrict__ b1,
+                                                       const float* __restrict__ Wt, const float* __restrict__ bt,
+                                                       float* __restrict__ img, int De, int DEP, int M0, int M1, int C, int ln) {
+  const int oW1 = DEP * EH_P0, oWT = oW1 + 32 * EH_P1, oB0 = oWT + 16 * EH_P1, oB1 = oB0 + 32, oBT = oB1 + 16;
+  for (int i = threadIdx.x; i < DEP * EH_P0; i += 64) {
+    const int k = i / EH_P0, j = i % EH_P0;
+    img[i] = (k < De && j < M0) ? (ln ? gamma[k] : 1.f) * W0[k * M0 + j] : 0.f;
+  }
+  for (int i = threadIdx.x; i < 32 * EH_P1; i += 64) {
+    const int k = i / EH_P1, j = i % EH_P1;
+    img[oW1 + i] = (k < M0 && j < M1) ? W1[k * M1 + j] : 0.f;
+  }
+  for (int i = threadIdx.x; i < 16 * EH_P1; i += 64) {
+    const int k = i / EH_P1, j = i % EH_P1;
+    img[oWT + i] = (k < M1 && j < C) ? Wt[k * C + j] : 0.f;
+  }
+  for (int j = threadIdx.x; j < 32; j += 64) {
+    float s = 0.f;
+    if (j < M0) {
+      s = b0[j];
+      if (ln)
+        for (int k = 0; k < De; ++k) s = fmaf(beta[k], W0[k * M0 + j], s);
+    }
+    img[oB0 + j] = s;
+  }
+  for (int j = threadIdx.x; j < 16; j += 64) {
+    img[oB1 + j] = j < M1 ? b1[j] : 0.f;
+    img[oBT + j] = j < C ? bt[j] : 0.f;
+  }
+}
+
+// ---- MFMA products on LDS images; lane (i = lane & 15, q = lane >> 4); D: row 4 q + r, column i ----
+// acc += A[16 x K] . B[K x 16]: A rows at A[i * pa + k] (one 16-byte read = 4 contraction steps, the contraction index of step s
+// is 16 g + 4 q + s on both sides), B at B[k * pb + i]
+template <int K>
+__device__ __forceinline__ v4f_h eh_mm_nn(const float* A, int pa, const float* B, int pb, int i, int q, v4f_h acc) {
+#pragma unroll
+  for (int g = 0; g < K / 16; ++g) {
+    const v4f_h a4 = *reinterpret_cast<const v4f_h*>(A + i * pa + 16 * g + 4 * q);
+    const float* bp = B + (16 * g + 4 * q) * pb + i;
+    acc = HMFMA(a4[0], bp[0], acc);
+    acc = HMFMA(a4[1], bp[pb], acc);
+    acc = HMFMA(a4[2], bp[2 * pb], acc);
+    acc = HMFMA(a4[3], bp[3 * pb], acc);
+  }
+  return acc;
+}
+// acc += A[16 x K] . W^T: B[k][column] = W[column * pw + k] (the backward through a Dense kernel)
+template <int K>
+__device__ __forceinline__ v4f_h eh_mm_nt(const float* A, int pa, const float* W, int pw, int i, int q, v4f_h acc) {
+#pragma unroll
+  for (int g = 0; g < K / 16; ++g) {
+    const v4f_h a4 = *reinterpret_cast<const v4f_h*>(A + i * pa + 16 * g + 4 * q);
+    const v4f_h b4 = *reinterpret_cast<const v4f_h*>(W + i * pw + 16 * g + 4 * q);
+    acc = HMFMA(a4[0], b4[0], acc);
+    acc = HMFMA(a4[1], b4[1], acc);
+    acc = HMFMA(a4[2], b4[2], acc);
+    acc = HMFMA(a4[3], b4[3], acc);
+  }
+  return acc;
+}
+// acc += X^T . Y over the 16 pairs of the tile: A[row][k] = X[k * px + row], B[k][column] = Y[k * py + column]
+__device__ __forceinline__ v4f_h eh_mm_tn(const float* X, int px, const float* Y, int py, int i, int q, v4f_h acc) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc = HMFMA(X[(4 * q + s) * px + i], Y[(4 * q + s) * py + i], acc);
+  return acc;
+}
+
+__device__ __forceinline__ float eh_act(float x, int act) {
+  return act == EGT_ACT_ELU ? (x > 0.f ? x : expm1f(x)) : fmaxf(x, 0.f);
+}
+// act'(x) from y = act(x): elu' = 1 (x > 0) or exp(x) = y + 1; relu' = [y > 0]
+__device__ __forceinline__ float eh_dact(float y, int act) {
+  return y > 0.f ? 1.f : (act == EGT_ACT_ELU ? y + 1.f : 0.f);
+}
+__device__ __forceinline__ float eh_sum_q(float v) { return sum_xor32(sum_xor16(v)); }
+
+// a 4-channel slot of e as loaded (bf16: the raw bits, widened only when the slot goes into the LDS image, so that a
+// prefetched tile stays in flight)
+__device__ __forceinline__ float4 eh_ld_raw(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ uint2 eh_ld_raw(const uint16_t* p) { return *reinterpret_cast<const uint2*>(p); }
+__device__ __forceinline__ float4 eh_widen(float4 v) { return v; }
+__device__ __forceinline__ float4 eh_widen(uint2 v) { return bf4_to_f4(v); }
+template <typename T> struct EhRaw { typedef float4 type; };
+template <> struct EhRaw<uint16_t> { typedef uint2 type; };
+__device__ __forceinline__ void eh_zero(float4& v) { v = make_float4(0.f, 0.f, 0.f, 0.f); }
+__device__ __forceinline__ void eh_zero(uint2& v) { v = make_uint2(0u, 0u); }
+__device__ __forceinline__ void eh_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
+__device__ __forceinline__ void eh_st4(uint16_t* p, float4 v) { *reinterpret_cast<uint2*>(p) = f4_to_bf4(v); }
+
+// grid = B * G workgroups; workgroup (b, g) owns the tiles [g * chunk, (g + 1) * chunk) of graph b, wave w every EH_NW-th of them.
+// BWD == false: loss_part[b * G + g] = the workgroup's share of per_graph[b].
+// BWD == true:  de = d per_graph / d e (zeros on skipped tiles), part[(b * G + g) * PG ..] = the workgroup's parameter gradients
+template <int DET, typename T, bool BWD>
+__global__ void __launch_bounds__(EH_NW * 64) k_edge_head(const T* __restrict__ e, const uint8_t* __restrict__ target,
+                                                          const float* __restrict__ img, const float* __restrict__ sgrad,
+                                                          T* __restrict__ de, float* __restrict__ loss_part,
+                                                          float* __restrict__ part, int N, int G, int chunk, int De, int C, int act,
+                                                          int ln, float eps) {
+  using Z = EhGeo<DET>;
+  constexpr int PE = Z::PE;
+  __shared__ __attribute__((aligned(16))) float wsm[Z::IMG];
+  __shared__ __attribute__((aligned(16))) float asm_[EH_NW * Z::WAVE];
+  __shared__ float lsm[EH_NW];
+  static_assert(EH_NW * Z::WAVE >= Z::PG, "the gradient image is reduced in the activation area");
+  const int b = blockIdx.x / G, g = blockIdx.x % G;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4;
+  const int NN = N * N, TPG = (NN + 15) / 16;
+  const int t0 = g * chunk, t1 = min(TPG, t0 + chunk);
+  for (int k = threadIdx.x; k < Z::IMG; k += EH_NW * 64) wsm[k] = img[k];
+  float* const my = asm_ + wave * Z::WAVE;
+  for (int k = lane; k < Z::WAVE; k += 64) my[k] = 0.f;   // (the pad columns of the e image stay 0)
+  __syncthreads();
+  float* const XE = my + Z::XE;
+  float* const X1 = my + Z::X1;
+  float* const X2 = my + Z::X2;
+  float* const DL = my + Z::DL;
+  float* const RS = my + Z::RS;
+  const float* const W0 = wsm + Z::W0;
+  const float* const W1 = wsm + Z::W1;
+  const float* const WT = wsm + Z::WT;
+  const float sb = BWD ? sgrad[b] : 0.f;
+  const int C4 = De >> 2, NF4 = 4 * De;   // 16-byte (fp32) slots per row / per tile
+  const float inv_de = 1.0f / (float)De;
+
+  float lossacc = 0.f;
+  v4f_h gW0[DET][2], gW1[2], gWt;
+  float gb0[2] = {0.f, 0.f}, gb1 = 0.f, gbt = 0.f;
+#pragma unroll
+  for (int a = 0; a < DET; ++a) gW0[a][0] = gW0[a][1] = (v4f_h){0.f, 0.f, 0.f, 0.f};
+  gW1[0] = gW1[1] = gWt = (v4f_h){0.f, 0.f, 0.f, 0.f};
+
+  for (int t = t0 + wave; t < t1; t += EH_NW) {
+    const int valid = min(16, NN - 16 * t);
+    const size_t p0 = (size_t)b * NN + (size_t)16 * t;       // first pair of the tile
+    const int my_t = lane < valid ? (int)target[p0 + lane] : 0;
+    const T* et = e + p0 * De;
+    if (__ballot(my_t != 0) == 0ull) {                         // nothing to learn here: no e load, no arithmetic
+      if (BWD) {
+        T* dt = de + p0 * De;
+        for (int f = lane; f < NF4; f += 64)
+          if (f / C4 < valid) eh_st4(dt + (size_t)f * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+      }
+      continue;
+    }
+    // ---- e tile -> LDS image (rows >= valid: zeros) ----
+    for (int f = lane; f < NF4; f += 64) {
+      const int row = f / C4, c4 = f % C4;
+      const float4 v = row < valid ? eh_widen(eh_ld_raw(et + (size_t)f * 4)) : make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(XE + row * PE + 4 * c4) = v;
+    }
+    eh_sync();
+    // ---- edge_norm_final: two-pass moments; 4 lanes per row ----
+    if (ln) {
+      const int row = lane >> 2, pt = lane & 3;
+      float s = 0.f;
+      for (int c4 = pt; c4 < C4; c4 += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
+        s += (v.x + v.y) + (v.z + v.w);
+      }
+      s += lane_xor<1>(s); s += lane_xor<2>(s);
+      const float mu = s * inv_de;
+      float vs = 0.f;
+      for (int c4 = pt; c4 < C4; c4 += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
+        const float a0 = v.x - mu, a1 = v.y - mu, a2 = v.z - mu, a3 = v.w - mu;
+        vs = fmaf(a0, a0, vs); vs = fmaf(a1, a1, vs); vs = fmaf(a2, a2, vs); vs = fmaf(a3, a3, vs);
+      }
+      vs += lane_xor<1>(vs); vs += lane_xor<2>(vs);
+      const float rstd = rsqrtf(vs * inv_de + eps);
+      for (int c4 = pt; c4 < C4; c4 += 4) {
+        float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
+        v.x = (v.x - mu) * rstd; v.y = (v.y - mu) * rstd; v.z = (v.z - mu) * rstd; v.w = (v.w - mu) * rstd;
+        *reinterpret_cast<float4*>(XE + row * PE + 4 * c4) = v;
+      }
+      if (pt == 0) RS[row] = rstd;
+      eh_sync();
+    }
+    // ---- x1 = act(ehat . W0f + b0f) ----
+    v4f_h a1[2], a2;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      const float bb = wsm[Z::B0 + 16 * ct + i];
+      v4f_h acc = (v4f_h){bb, bb, bb, bb};
+      acc = eh_mm_nn<Z::DEP>(XE, PE, W0 + 16 * ct, EH_P0, i, q, acc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[r] = eh_act(acc[r], act);
+        X1[(4 * q + r) * EH_P0 + 16 * ct + i] = acc[r];
+      }
+      a1[ct] = acc;
+    }
+    eh_sync();
+    // ---- x2 = act(x1 . W1 + b1) ----
+    {
+      const float bb = wsm[Z::B1 + i];
+      v4f_h acc = (v4f_h){bb, bb, bb, bb};
+      acc = eh_mm_nn<32>(X1, EH_P0, W1, EH_P1, i, q, acc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[r] = eh_act(acc[r], act);
+        X2[(4 * q + r) * EH_P1 + i] = acc[r];
+      }
+      a2 = acc;
+    }
+    eh_sync();
+    // ---- logits, max-subtracted log-sum-exp over the C real columns, gather, mask ----
+    v4f_h z;
+    {
+      const float bb = wsm[Z::BT + i];
+      z = (v4f_h){bb, bb, bb, bb};
+      z = eh_mm_nn<16>(X2, EH_P1, WT, EH_P1, i, q, z);
+    }
+    v4f_h dl;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int tr = __shfl(my_t, 4 * q + r, 64);
+      const bool real = i < C;
+      const float m = row_max16(real ? z[r] : -INFINITY);
+      const float ex = real ? expf(z[r] - m) : 0.f;
+      const float se = row_sum16(ex);
+      const float zt = row_sum16(i == tr ? z[r] : 0.f);
+      if (!BWD) {
+        if (i == 0 && tr > 0) lossacc += (m + logf(se)) - zt;
+      } else {
+        dl[r] = (tr > 0 && real) ? (ex / se - (i == tr ? 1.f : 0.f)) * sb : 0.f;
+      }
+    }
+    if (!BWD) continue;
+
+    // ================= backward of the tile =================
+    gbt += (dl[0] + dl[1]) + (dl[2] + dl[3]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) DL[(4 * q + r) * EH_P1 + i] = dl[r];
+    eh_sync();
+    gWt = eh_mm_tn(X2, EH_P1, DL, EH_P1, i, q, gWt);                                   // dWt += x2^T . dl
+    v4f_h d2 = eh_mm_nt<16>(DL, EH_P1, WT, EH_P1, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});  // dx2 = dl . Wt^T
+#pragma unroll
+    for (int r = 0; r < 4; ++r) d2[r] *= eh_dact(a2[r], act);
+    gb1 += (d2[0] + d2[1]) + (d2[2] + d2[3]);
+    eh_sync();                                                                         // x2 has been read
+#pragma unroll
+    for (int r = 0; r < 4; ++r) X2[(4 * q + r) * EH_P1 + i] = d2[r];
+    eh_sync();
+    v4f_h d1[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      gW1[ct] = eh_mm_tn(X1 + 16 * ct, EH_P0, X2, EH_P1, i, q, gW1[ct]);               // dW1 += x1^T . dx2pre
+      d1[ct] = eh_mm_nt<16>(X2, EH_P1, W1 + 16 * ct * EH_P1, EH_P1, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+      for (int r = 0; r < 4; ++r) d1[ct][r] *= eh_dact(a1[ct][r], act);
+      gb0[ct] += (d1[ct][0] + d1[ct][1]) + (d1[ct][2] + d1[ct][3]);
+    }
+    eh_sync();                                                                         // x1 has been read
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) X1[(4 * q + r) * EH_P0 + 16 * ct + i] = d1[ct][r];
+    eh_sync();
+    v4f_h ge[DET];
+#pragma unroll
+    for (int a = 0; a < DET; ++a) {
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+        gW0[a][ct] = eh_mm_tn(XE + 16 * a, PE, X1 + 16 * ct, EH_P0, i, q, gW0[a][ct]);  // dW0f += ehat^T . dx1pre
+      ge[a] = eh_mm_nt<32>(X1, EH_P0, W0 + 16 * a * EH_P0, EH_P0, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});   // dehat = dx1pre . W0f^T
+    }
+    // ---- LayerNorm backward per row: de = rstd (g - mean(g) - ehat mean(g ehat)) ----
+    if (ln) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 4 * q + r;
+        float eh[DET], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int a = 0; a < DET; ++a) {
+          eh[a] = XE[row * PE + 16 * a + i];
+          s1 += ge[a][r];
+          s2 = fmaf(ge[a][r], eh[a], s2);
+        }
+        s1 = row_sum16(s1) * inv_de;
+        s2 = row_sum16(s2) * inv_de;
+        const float rstd = RS[row];
+#pragma unroll
+        for (int a = 0; a < DET; ++a) ge[a][r] = rstd * (ge[a][r] - s1 - eh[a] * s2);
+      }
+    }
+    eh_sync();                                                                         // ehat has been read
+#pragma unroll
+    for (int a = 0; a < DET; ++a)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (16 * a + i < De) XE[(4 * q + r) * PE + 16 * a + i] = ge[a][r];
+    eh_sync();
+    {
+      T* dt = de + p0 * De;
+      for (int f = lane; f < NF4; f += 64) {
+        const int row = f / C4, c4 = f % C4;
+        if (row < valid) eh_st4(dt + (size_t)f * 4, *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4));
+      }
+    }
+    eh_sync();   // the image is free for the next tile (its pad columns are untouched)
+  }
+
+  // ---- workgroup partials, waves added in index order ----
+  if (!BWD) {
+    const float l = eh_sum_q(lossacc);   // (lanes i == 0 carry the rows)
+    if (lane == 0) lsm[wave] = l;
+    __syncthreads();
+    if (threadIdx.x == 0) loss_part[blockIdx.x] = ((lsm[0] + lsm[1]) + lsm[2]) + lsm[3];
+    return;
+  }
+  gb0[0] = eh_sum_q(gb0[0]); gb0[1] = eh_sum_q(gb0[1]); gb1 = eh_sum_q(gb1); gbt = eh_sum_q(gbt);
+  __syncthreads();   // every wave is done with its activation image
+  float* const red = asm_;
+  for (int w = 0; w < EH_NW; ++w) {
+    if (wave == w) {
+      const bool first = w == 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int a = 0; a < DET; ++a)
+#pragma unroll
+          for (int ct = 0; ct < 2; ++ct) {
+            float* p = red + Z::G0 + (16 * a + 4 * q + r) * 32 + 16 * ct + i;
+            *p = (first ? 0.f : *p) + gW0[a][ct][r];
+          }
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+          float* p = red + Z::G1 + (16 * ct + 4 * q + r) * 16 + i;
+          *p = (first ? 0.f : *p) + gW1[ct][r];
+        }
+        float* p = red + Z::GT + (4 * q + r) * 16 + i;
+        *p = (first ? 0.f : *p) + gWt[r];
+      }
+      if (q == 0) {
+        float* p = red + Z::GB0 + i;
+        p[0] = (first ? 0.f : p[0]) + gb0[0];
+        p[16] = (first ? 0.f : p[16]) + gb0[1];
+        p = red + Z::GB1 + i;
+        *p = (first ? 0.f : *p) + gb1;
+        p = red + Z::GBT + i;
+        *p = (first ? 0.f : *p) + gbt;
+      }
+    }
+    __syncthreads();
+  }
+  float* out = part + (size_t)blockIdx.x * Z::PG;
+  for (int k = threadIdx.x; k < Z::PG; k += EH_NW * 64) out[k] = red[k];
+}
+
+// per_graph[b] = sum_g loss_part[b][g], in index order
+__global__ void __launch_bounds__(64) k_edge_head_loss(const float* __restrict__ loss_part, float* __restrict__ per_graph, int B,
+                                                       int G) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  float s = 0.f;
+  for (int g = 0; g < G; ++g) s += loss_part[(size_t)b * G + g];
+  per_graph[b] = s;
+}
+
+// red[k] = sum over the workgroups' partials in a fixed order: 4 contiguous segments of workgroups per element, then the 4
+__global__ void __launch_bounds__(256) k_edge_head_reduce(const float* __restrict__ part, float* __restrict__ red, int nwg, int PG) {
+  __shared__ float sm[4][64];
+  const int k = blockIdx.x * 64 + (threadIdx.x & 63), sg = threadIdx.x >> 6;
+  const int per = (nwg + 3) / 4, w0 = sg * per, w1 = min(nwg, w0 + per);
+  float s = 0.f;
+  if (k < PG)
+    for (int w = w0; w < w1; ++w) s += part[(size_t)w * PG + k];
+  sm[sg][threadIdx.x & 63] = s;
+  __syncthreads();
+  if (sg == 0 && k < PG) red[k] = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+}
+
+// the reduced (folded, padded) gradients -> the eight parameter gradients: W0f = gamma (.) W0, b0f = b0 + beta . W0
+// (so W0 collects gamma[k] dW0f[k][j] + beta[k] db0f[j])
+__global__ void __launch_bounds__(256) k_edge_head_finish(const float* __restrict__ red, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, const float* __restrict__ W0, float* __restrict__ d_gamma,
+                                                          float* __restrict__ d_beta, float* __restrict__ d_W0,
+                                                          float* __restrict__ d_b0, float* __restrict__ d_W1,
+                                                          float* __restrict__ d_b1, float* __restrict__ d_Wt,
+                                                          float* __restrict__ d_bt, int De, int DEP, int M0, int M1, int C, int ln) {
+  const int oG1 = DEP * 32, oGT = oG1 + 512, oB0 = oGT + 256, oB1 = oB0 + 32, oBT = oB1 + 16;
+  const int tid = threadIdx.x;
+  for (int x = tid; x < De * M0; x += 256) {
+    const int k = x / M0, j = x % M0;
+    d_W0[x] = ln ? fmaf(gamma[k], red[k * 32 + j], beta[k] * red[oB0 + j]) : red[k * 32 + j];
+  }
+  if (ln)
+    for (int k = tid; k < De; k += 256) {
+      float sg = 0.f, sbt = 0.f;
+      for (int j = 0; j < M0; ++j) {
+        const float w = W0[k * M0 + j];
+        sg = fmaf(red[k * 32 + j], w, sg);
+        sbt = fmaf(red[oB0 + j], w, sbt);
+      }
+      d_gamma[k] = sg;
+      d_beta[k] = sbt;
+    }
+  for (int x = tid; x < M0 * M1; x += 256) d_W1[x] = red[oG1 + (x / M1) * 16 + x % M1];
+  for (int x = tid; x < M1 * C; x += 256) d_Wt[x] = red[oGT + (x / C) * 16 + x % C];
+  for (int j = tid; j < M0; j += 256) d_b0[j] = red[oB0 + j];
+  for (int j = tid; j < M1; j += 256) d_b1[j] = red[oB1 + j];
+  for (int j = tid; j < C; j += 256) d_bt[j] = red[oBT + j];
+}
+
+// ---- distance target: target = round(sum_{k=1..T} hop_k), hop_1 = A, hop_k = clip(A . hop_{k-1}, 0, 1) ----
+// k_hop_chain's scheme (egt_embed.hip): a workgroup owns CT column tiles of one graph, keeps the zero-padded adjacency
+// ([R16][R16 + 4]) and its column block of the current hop ([R16][16 CT + 4]) in LDS, and walks the hops without another global
+// read; the running sum stays in the MFMA tiles' registers.  Sums of 0/1 products are exact in any order.
+#define DT_NW 8
+#define DT_MAXT 8
+__global__ void __launch_bounds__(DT_NW * 64) k_dist_target(const float* __restrict__ adj, uint8_t* __restrict__ target, int N, int T,
+                                                            int NB, int CT) {
+  extern __shared__ __attribute__((aligned(16))) float dsm[];
+  const int RT = (N + 15) / 16, R16 = RT * 16, PA = R16 + 4, PH = 16 * CT + 4;
+  float* As = dsm;
+  float* Hs = As + R16 * PA;
+  const int b = blockIdx.x / NB, c0 = (blockIdx.x % NB) * CT * 16;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, kq = lane >> 4;
+  const float* A = adj + (size_t)b * N * N;
+  for (int x = threadIdx.x; x < R16 * PA; x += DT_NW * 64) {
+    const int r = x / PA, c = x % PA;
+    As[x] = (r < N && c < N) ? A[(size_t)r * N + c] : 0.f;
+  }
+  for (int x = threadIdx.x; x < R16 * PH; x += DT_NW * 64) {
+    const int r = x / PH, c = c0 + x % PH;
+    Hs[x] = (r < N && c < N && (x % PH) < 16 * CT) ? A[(size_t)r * N + c] : 0.f;
+  }
+  __syncthreads();
+  const int ntile = RT * CT;
+  v4f_h sum[DT_MAXT];
+#pragma unroll
+  for (int ti = 0; ti < DT_MAXT; ++ti) {
+    sum[ti] = (v4f_h){0.f, 0.f, 0.f, 0.f};
+    const int t = wave + DT_NW * ti;
+    if (t < ntile)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sum[ti][r] = Hs[(16 * (t / CT) + 4 * kq + r) * PH + 16 * (t % CT) + m];   // hop 1
+  }
+  for (int k = 2; k <= T; ++k) {
+    v4f_h acc[DT_MAXT];
+#pragma unroll
+    for (int ti = 0; ti < DT_MAXT; ++ti) {
+      acc[ti] = (v4f_h){0.f, 0.f, 0.f, 0.f};
+      const int t = wave + DT_NW * ti;
+      if (t < ntile) {
+        const float* ap = As + (16 * (t / CT) + m) * PA + 4 * kq;
+        const float* bp = Hs + (4 * kq) * PH + 16 * (t % CT) + m;
+        v4f_h c = acc[ti];
+        for (int g = 0; g < RT; ++g) {
+          const v4f_h a4 = *reinterpret_cast<const v4f_h*>(ap + 16 * g);
+          const float* bg = bp + 16 * g * PH;
+          c = HMFMA(a4[0], bg[0], c);
+          c = HMFMA(a4[1], bg[PH], c);
+          c = HMFMA(a4[2], bg[2 * PH], c);
+          c = HMFMA(a4[3], bg[3 * PH], c);
+        }
+        acc[ti] = c;
+      }
+    }
+    __syncthreads();   // every wave has read the old plane
+#pragma unroll
+    for (int ti = 0; ti < DT_MAXT; ++ti) {
+      const int t = wave + DT_NW * ti;
+      if (t < ntile)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float x = fminf(fmaxf(acc[ti][r], 0.f), 1.f);
+          Hs[(16 * (t / CT) + 4 * kq + r) * PH + 16 * (t % CT) + m] = x;
+          sum[ti][r] += x;
+        }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int ti = 0; ti < DT_MAXT; ++ti) {
+    const int t = wave + DT_NW * ti;
+    if (t < ntile)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * (t / CT) + 4 * kq + r, col = c0 + 16 * (t % CT) + m;
+        if (row < N && col < N) target[((size_t)b * N + row) * N + col] = (uint8_t)(int)fminf(fmaxf(rintf(sum[ti][r]), 0.f), 255.f);
+      }
+  }
+}
+
+// =================================== host ===================================
+#define DT_MAX_N 192   // the adjacency ([R16][R16 + 4] fp32) plus one column tile of a hop must fit the 160 KB of LDS
+
+extern "C" int egt_distance_target(const float* adj, int32_t B, int32_t N, int32_t T, uint8_t* target, void* stream) {
+  if (B < 1 || N < 1 || (long)B * N * N > 2147483647L) EGT_FAIL(EGT_E_SHAPE, "distance target: B, N >= 1 and B*N*N inside 32 bits (got B=%d N=%d)", B, N);
+  if (N > DT_MAX_N) EGT_FAIL(EGT_E_SHAPE, "distance target: N <= %d (the graph's adjacency stays in LDS); got %d", DT_MAX_N, N);
+  if (T < 1 || T > 255) EGT_FAIL(EGT_E_SHAPE, "distance target: 1 <= T <= 255 (got %d)", T);
+  if (!adj || !target) EGT_FAIL(EGT_E_NULL, "adj/target is NULL");
+  const int RT = (N + 15) / 16, R16 = RT * 16;
+  int ct = (int)((long)RT * B / 256);
+  ct = ct < 1 ? 1 : (ct > RT ? RT : ct);
+  auto lds_of = [&](int c) { return (size_t)(R16 * (R16 + 4) + R16 * (16 * c + 4)) * sizeof(float); };
+  while (ct > 1 && (RT * ct > DT_NW * DT_MAXT || lds_of(ct) > 160 * 1024)) --ct;
+  if (RT * ct > DT_NW * DT_MAXT || lds_of(ct) > 160 * 1024) EGT_FAIL(EGT_E_SHAPE, "distance target: N=%d does not fit", N);
+  const int NB = (RT + ct - 1) / ct;
+  EGT_MAX_LDS_ONCE(k_dist_target);
+  EGT_LAUNCH("k_dist_target", k_dist_target, dim3((unsigned)(B * NB)), dim3(DT_NW * 64), lds_of(ct), (hipStream_t)stream, adj, target,
+             N, T, NB, ct);
+  EGT_HIP_LAUNCH_CHECK("egt_distance_target");
+  return EGT_OK;
+}
+
+static int head_check(const egt_head_desc* d) {
+  if (!d) EGT_FAIL(EGT_E_NULL, "desc is NULL");
+  if ((d->flags & ~(int32_t)EGT_EH_LAYERNORM) != 0 || d->reserved != 0)
+    EGT_FAIL(EGT_E_FLAGS, "edge head: unknown flag bits 0x%x / reserved %d", (unsigned)d->flags, d->reserved);
+  if (d->dtype != EGT_F32 && d->dtype != EGT_BF16) EGT_FAIL(EGT_E_DTYPE, "edge head: e is fp32 or bf16 (dtype %d)", d->dtype);
+  if (d->B < 1 || d->N < 1 || (long)d->B * d->N * d->N > 2147483647L)
+    EGT_FAIL(EGT_E_SHAPE, "edge head: B, N >= 1 and B*N*N inside 32-bit indexing (B=%d N=%d)", d->B, d->N);
+  if (!(d->De == 8 || d->De == 16 || d->De == 32 || d->De == 48 || d->De == 64))
+    EGT_FAIL(EGT_E_SHAPE, "edge head covers De in {8,16,32,48,64} (got %d)", d->De);
+  if (!((d->M0 == 24 && d->M1 == 12) || (d->M0 == 32 && d->M1 == 16)))
+    EGT_FAIL(EGT_E_SHAPE, "edge head covers (M0, M1) in {(24,12), (32,16)}: model widths 48 / 64 (got %d, %d)", d->M0, d->M1);
+  if (d->C < 2 || d->C > 16) EGT_FAIL(EGT_E_SHAPE, "edge head covers 2 <= C <= 16 classes (got %d)", d->C);
+  if (d->activation != EGT_ACT_ELU && d->activation != EGT_ACT_RELU)
+    EGT_FAIL(EGT_E_SHAPE, "edge head activation is EGT_ACT_ELU or EGT_ACT_RELU (got %d)", d->activation);
+  return EGT_OK;
+}
+extern "C" int egt_edge_head_supported(const egt_head_desc* d) { return head_check(d) == EGT_OK ? 1 : 0; }
+
+// workgroups per graph: about four workgroups per CU over the batch, at least 8 tiles each (the 13 KB weight image is
+// loaded once per workgroup)
+static int head_chunks(const egt_head_desc* d) {
+  const int tpg = (d->N * d->N + 15) / 16;
+  int g = 1024 / d->B;
+  const int cap = tpg / 8;
+  g = g > cap ? cap : g;
+  return g < 1 ? 1 : g;
+}
+// workspace (floats): weight image | loss partials [B G] | gradient partials [B G][PG] | reduced gradients [PG]
+extern "C" size_t egt_edge_head_workspace_bytes(const egt_head_desc* d) {
+  if (head_check(d) != EGT_OK) return 0;
+  const int det = eh_det(d->De);
+  const size_t nwg = (size_t)d->B * head_chunks(d);
+  return sizeof(float) * ((size_t)eh_img(det) + nwg + nwg * eh_pg(det) + eh_pg(det));
+}
+
+static int head_params_check(const egt_head_desc* d, const egt_head_params* p, const char* what) {
+  if (!p) EGT_FAIL(EGT_E_NULL, "edge head: %s is NULL", what);
+  if ((d->flags & EGT_EH_LAYERNORM) && (!p->edge_norm_final_gamma || !p->edge_norm_final_beta))
+    EGT_FAIL(EGT_E_NULL, "edge head: EGT_EH_LAYERNORM set but %s gamma/beta is NULL", what);
+  if (!p->mlp_out_dist_targ_0_kernel || !p->mlp_out_dist_targ_0_bias || !p->mlp_out_dist_targ_1_kernel ||
+      !p->mlp_out_dist_targ_1_bias || !p->distance_target_kernel || !p->distance_target_bias)
+    EGT_FAIL(EGT_E_NULL, "edge head: a kernel / bias pointer of %s is NULL", what);
+  return EGT_OK;
+}
+
+static void head_prep(const egt_head_desc* d, const egt_head_params* p, float* img, hipStream_t st) {
+  EGT_LAUNCH("k_edge_head_prep", k_edge_head_prep, dim3(1), dim3(64), 0, st, (const float*)p->edge_norm_final_gamma,
+             (const float*)p->edge_norm_final_beta, (const float*)p->mlp_out_dist_targ_0_kernel,
+             (const float*)p->mlp_out_dist_targ_0_bias, (const float*)p->mlp_out_dist_targ_1_kernel,
+             (const float*)p->mlp_out_dist_targ_1_bias, (const float*)p->distance_target_kernel,
+             (const float*)p->distance_target_bias, img, d->De, 16 * eh_det(d->De), d->M0, d->M1, d->C,
+             (d->flags & EGT_EH_LAYERNORM) ? 1 : 0);
+}
+
+template <int DET, typename T, bool BWD>
+static void head_launch(const egt_head_desc* d, const void* e, const uint8_t* target, const float* img, const float* s, void* de,
+                        float* loss_part, float* part, hipStream_t st) {
+  const int G = head_chunks(d), tpg = (d->N * d->N + 15) / 16, chunk = (tpg + G - 1) / G;
+  EGT_LAUNCH(BWD ? "k_edge_head_bwd" : "k_edge_head_fwd", (k_edge_head<DET, T, BWD>), dim3((unsigned)(d->B * G)), dim3(EH_NW * 64),
+             0, st, (const T*)e, target, img, s, (T*)de, loss_part, part, d->N, G, chunk, d->De, d->C, d->activation,
+             (d->flags & EGT_EH_LAYERNORM) ? 1 : 0, d->ln_eps);
+}
+template <bool BWD>
+static void head_dispatch(const egt_head_desc* d, const void* e, const uint8_t* target, const float* img, const float* s, void* de,
+                          float* loss_part, float* part, hipStream_t st) {
+  const bool bf = d->dtype == EGT_BF16;
+  switch (eh_det(d->De)) {
+#define EH_CASE(DET_)                                                                              \
+  case DET_:                                                                                       \
+    if (bf) head_launch<DET_, uint16_t, BWD>(d, e, target, img, s, de, loss_part, part, st);        \
+    else head_launch<DET_, float, BWD>(d, e, target, img, s, de, loss_part, part, st);              \
+    break;
+    EH_CASE(1) EH_CASE(2) EH_CASE(3) EH_CASE(4)
+#undef EH_CASE
+  }
+}
+
+extern "C" int egt_edge_head_fwd(const egt_head_desc* d, const egt_head_params* params, const void* e, const uint8_t* target,
+                                 float* per_graph_loss, void* workspace, void* stream) {
+  int rc = head_check(d);
+  if (rc) return rc;
+  if ((rc = head_params_check(d, params, "params"))) return rc;
+  if (!e || !target || !per_graph_loss || !workspace) EGT_FAIL(EGT_E_NULL, "edge head: e/target/per_graph_loss/workspace is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  const int det = eh_det(d->De), G = head_chunks(d);
+  float* img = (float*)workspace;
+  float* loss_part = img + eh_img(det);
+  head_prep(d, params, img, st);
+  head_dispatch<false>(d, e, target, img, nullptr, nullptr, loss_part, nullptr, st);
+  EGT_LAUNCH("k_edge_head_finish", k_edge_head_loss, dim3((unsigned)((d->B + 63) / 64)), dim3(64), 0, st, (const float*)loss_part,
+             per_graph_loss, d->B, G);
+  EGT_HIP_LAUNCH_CHECK("egt_edge_head_fwd");
+  return EGT_OK;
+}
+
+extern "C" int egt_edge_head_bwd(const egt_head_desc* d, const egt_head_params* params, const void* e, const uint8_t* target,
+                                 const float* d_per_graph, void* d_e, const egt_head_params* grads, void* workspace,
+                                 void* stream) {
+  int rc = head_check(d);
+  if (rc) return rc;
+  if ((rc = head_params_check(d, params, "params"))) return rc;
+  if ((rc = head_params_check(d, grads, "grads"))) return rc;
+  if (!e || !target || !d_per_graph || !d_e || !workspace) EGT_FAIL(EGT_E_NULL, "edge head: e/target/d_per_graph/d_e/workspace is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  const int det = eh_det(d->De), G = head_chunks(d), nwg = d->B * G, PG = eh_pg(det);
+  const int ln = (d->flags & EGT_EH_LAYERNORM) ? 1 : 0;
+  float* img = (float*)workspace;
+  float* part = img + eh_img(det) + nwg;
+  float* red = part + (size_t)nwg * PG;
+  head_prep(d, params, img, st);
+  head_dispatch<true>(d, e, target, img, d_per_graph, d_e, nullptr, part, st);
+  EGT_LAUNCH("k_edge_head_finish", k_edge_head_reduce, dim3((unsigned)((PG + 63) / 64)), dim3(256), 0, st, (const float*)part, red,
+             nwg, PG);
+  EGT_LAUNCH("k_edge_head_finish", k_edge_head_finish, dim3(1), dim3(256), 0, st, (const float*)red,
+             (const float*)params->edge_norm_final_gamma, (const float*)params->edge_norm_final_beta,
+             (const float*)params->mlp_out_dist_targ_0_kernel,
+             (float*)grads->edge_norm_final_gamma, (float*)grads->edge_norm_final_beta, (float*)grads->mlp_out_dist_targ_0_kernel,
+             (float*)grads->mlp_out_dist_targ_0_bias, (float*)grads->mlp_out_dist_targ_1_kernel,
+             (float*)grads->mlp_out_dist_targ_1_bias, (float*)grads->distance_target_kernel, (float*)grads->distance_target_bias,
+             d->De, 16 * det, d->M0, d->M1, d->C, ln);
+  EGT_HIP_LAUNCH_CHECK("egt_edge_head_bwd");
+  return EGT_OK;
+}

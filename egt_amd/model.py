@@ -130,13 +130,28 @@ class ZincDCTransformer(nn.Module):
         self.edge_dtype = _edge_dtype(edge_dtype)
         unsupported = dict(readout_edges=(readout_edges, False), num_virtual_nodes=(num_virtual_nodes, 0),
                            node_dropout=(node_dropout, 0), edge_dropout=(edge_dropout, 0), l2_reg=(l2_reg, 0),
-                           distance_loss=(distance_loss, 0), add_n_norm=(add_n_norm, False),
+                           add_n_norm=(add_n_norm, False),
                            combine_layer_repr=(combine_layer_repr, False), node2edge_xtalk=(node2edge_xtalk, 0),
                            edge2node_xtalk=(edge2node_xtalk, 0), node2edge_embed=(node2edge_embed, False),
                            node_normalization=(node_normalization, 'layer'), edge_normalization=(edge_normalization, 'layer'))
         bad = {k: v for k, (v, d) in unsupported.items() if v != d}
         if bad:    # the reference model applies every one of these: training "a different model without a warning" is not an option
             raise NotImplementedError(f"{type(self).__name__} covers the shipped configs; not built: {bad}")
+        # distance objective (the *_spe_do configs): built for the head geometries of the shipped model widths (egt_amd/head.py)
+        self.distance_loss = float(distance_loss)
+        if self.distance_loss > 0:
+            why = {}
+            if edge_channel_type not in ('residual', 'constrained'):
+                why["edge_channel_type"] = edge_channel_type
+            if list(mlp_layers) != [.5, .25]:
+                why["mlp_layers"] = list(mlp_layers)
+            if model_width not in (48, 64):
+                why["model_width"] = model_width
+            if not (isinstance(distance_target, int) and 1 <= distance_target <= 15):
+                why["distance_target"] = distance_target
+            if why:
+                raise NotImplementedError(f"{type(self).__name__} covers the shipped configs; not built: distance_loss="
+                                          f"{distance_loss} with {why}")
         # 'bias' = EGT-Simple (configs/ablation/egt_simple): e is computed once by the embedding and never updated; no
         # norm_edge, dense_edge_r, edge FFN or edge_norm_final (graph_xformer_model_base.py:173-190, :313, :346).  Built for the
         # head dims the fused block covers (d <= 8): the ZINC egt_simple configs (model_width 80, d = 10) stay refused.
@@ -149,7 +164,7 @@ class ZincDCTransformer(nn.Module):
                         upto_hop=upto_hop, clip_hops=clip_hops, mlp_layers=list(mlp_layers), activation=activation,
                         do_final_norm=do_final_norm, num_node_features=num_node_features,
                         num_edge_features=num_edge_features, num_targets=num_targets, ffn_multiplier=ffn_multiplier,
-                        edge_channel_type=edge_channel_type,
+                        edge_channel_type=edge_channel_type, distance_target=distance_target,
                         use_svd=bool(use_svd), num_svd_features=num_svd_features, sel_svd_features=sel_svd_features,
                         transform_svd=bool(transform_svd), use_eig=bool(use_eig), num_eig_features=num_eig_features,
                         sel_eig_features=sel_eig_features, transform_eig=bool(transform_eig), random_neg=bool(random_neg))
@@ -175,6 +190,15 @@ class ZincDCTransformer(nn.Module):
             self.mlp_out.append(KerasDense(w, round(f * model_width)))
             w = round(f * model_width)
         self.target = KerasDense(w, num_targets)
+        self.dist_head = None
+        if self.distance_loss > 0:
+            from .head import DistanceHead
+            try:   # the library decides the coverage (egt_edge_head_supported), with the edge dtype the model runs in
+                self.dist_head = DistanceHead(edge_width, model_width, distance_target, mlp_layers, activation, do_final_norm,
+                                              self.edge_dtype)
+            except NotImplementedError as ex:
+                raise NotImplementedError(f"{type(self).__name__} covers the shipped configs; not built: distance_loss="
+                                          f"{distance_loss} ({ex})") from None
 
     # ---- positional encodings: node_emb_add = Add()([node embedding, PE embedding]) (graph_xformer_model_base.py:390-399) ----
     def positional(self, h, singular_vectors=None, eigen_vectors=None, pe_signs=None):
@@ -220,6 +244,8 @@ class ZincDCTransformer(nn.Module):
     def _dead_edge_params(self):
         if self.cfg["edge_channel_type"] == 'bias':
             return []                    # EGT-Simple: every layer's gate and bias projections feed h; nothing else is edge-side
+        if self.dist_head is not None:
+            return []                    # the distance objective reads the final edge channels: the whole edge side is live
         last = self.layers.blocks[-1]
         dead = [last.dense_edge_r.kernel, last.dense_edge_r.bias]
         if self.layers.ffn_edge is not None:
@@ -244,6 +270,8 @@ class ZincDCTransformer(nn.Module):
         for i, m in enumerate(self.mlp_out):
             out[f"mlp_out_{i}/kernel"], out[f"mlp_out_{i}/bias"] = m.kernel, m.bias
         out["target/kernel"], out["target/bias"] = self.target.kernel, self.target.bias
+        if self.dist_head is not None:
+            out.update(self.dist_head.keras_named_parameters())
         return out
 
     def trainable_parameters(self):
@@ -260,11 +288,22 @@ class ZincDCTransformer(nn.Module):
                        clip_hops=self.cfg["clip_hops"], edge_dtype=self._edge_key())   # :70-73 + graph_model_base.py:97-127
         return h, e, mask
 
+    def distance_aux(self, e, graph_matrix):
+        """{"distance_loss": per_graph [B]}: the distance objective on the final edge channels (graph_model_base.py:66-94)"""
+        from .head import distance_target
+        return {"distance_loss": self.dist_head(e, distance_target(graph_matrix, self.cfg["distance_target"]))}
+
+    def _aux(self, y, e, graph_matrix, return_aux):
+        if not return_aux:
+            return y
+        return y, (self.distance_aux(e, graph_matrix) if self.dist_head is not None else {})
+
     def forward(self, node_features, feature_matrix, graph_matrix, attn_mask=None, singular_vectors=None,
-                eigen_vectors=None, pe_signs=None):
+                eigen_vectors=None, pe_signs=None, return_aux=False):
         h, e, mask = self.embeddings(node_features, feature_matrix, graph_matrix)
         h = self.positional(h, singular_vectors, eigen_vectors, pe_signs)
-        h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask), skip_last_edge_ffn=True)   # :336-341
+        h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask),
+                           skip_last_edge_ffn=self.dist_head is None)                   # :336-341
         if self.node_norm_final is not None:
             h = self.node_norm_final(h)                                                 # :343-345
         m = mask.to(h.dtype)[..., None]
@@ -272,7 +311,7 @@ class ZincDCTransformer(nn.Module):
         for lyr in self.mlp_out:                                                        # mlp_out, :354-372
             x = lyr(x)
             x = F.elu(x) if self.cfg["activation"] == 'elu' else torch.relu(x)
-        return self.target(x)                                                           # zinc/dc.py:116-117
+        return self._aux(self.target(x), e, graph_matrix, return_aux)                   # zinc/dc.py:116-117
 
 
 class PatternDCTransformer(ZincDCTransformer):
@@ -294,11 +333,11 @@ class PatternDCTransformer(ZincDCTransformer):
         return out
 
     def forward(self, node_features, graph_matrix, attn_mask=None, return_mask=False, singular_vectors=None,
-                eigen_vectors=None, pe_signs=None):
+                eigen_vectors=None, pe_signs=None, return_aux=False):
         fmat = torch.full(graph_matrix.shape, -1, dtype=torch.int32, device=graph_matrix.device)
         h, e, mask = self.embeddings(node_features, fmat, graph_matrix)
         h = self.positional(h, singular_vectors, eigen_vectors, pe_signs)
-        h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask), skip_last_edge_ffn=True)
+        h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask), skip_last_edge_ffn=self.dist_head is None)
         if self.node_norm_final is not None:
             h = self.node_norm_final(h)
         x = h
@@ -306,7 +345,7 @@ class PatternDCTransformer(ZincDCTransformer):
             x = lyr(x)
             x = F.elu(x) if self.cfg["activation"] == 'elu' else torch.relu(x)
         y = self.target(x)                                                                # logits [B,N,C]
-        return (y, mask) if return_mask else y
+        return self._aux((y, mask) if return_mask else y, e, graph_matrix, return_aux)
 
 
 class Cifar10DCTransformer(ZincDCTransformer):

@@ -386,7 +386,24 @@ class ZincSVDScheme:
         return mae_loss
 
     def get_metrics(self):                           # :41-42
-        return ["mae"]
+        return ["mae"] + self._distance_metrics()
+
+    # ---- distance objective (the *_spe_do configs; graph_model_base.py:66-94, loss_layers.py:38-67) ----
+    def _distance_on(self):
+        return float(self.config.get("distance_loss") or 0.) > 0
+
+    def _distance_metrics(self):
+        return ["distance_loss"] if self._distance_on() else []
+
+    def _aux_kwargs(self):
+        """the model returns (prediction, {"distance_loss": per_graph [B]}) when the objective is on"""
+        return dict(return_aux=True) if self._distance_on() else {}
+
+    def _add_distance(self, loss, aux):
+        """loss + distance_loss * mean_b per_graph and the metric `distance_loss` as (sum of per_graph, graphs); the
+        per-graph sums stay on the device"""
+        pg = aux["distance_loss"]
+        return loss + self.config.distance_loss * pg.mean(), (pg.sum().detach(), pg.numel())
 
     def load_model(self):
         self.model = self.get_model()
@@ -549,10 +566,16 @@ class ZincSVDScheme:
     def batch_loss(self, batch):
         """(loss, metric sums) of one batch: scheme-specific"""
         nf, fm, adj, tgt = self._batch(batch)
-        y = self.model(nf, fm, adj, **self._pe(batch))
+        y = self.model(nf, fm, adj, **self._pe(batch), **self._aux_kwargs())
+        if self._distance_on():
+            y, aux = y
         loss = self.loss_fn(y, tgt)
         sabs = (y - tgt).abs().sum().detach()
-        return loss, dict(mae=(sabs, tgt.numel()), loss=(sabs, tgt.numel()))      # (the MAE loss IS the mae metric)
+        if not self._distance_on():
+            return loss, dict(mae=(sabs, tgt.numel()), loss=(sabs, tgt.numel()))  # (the MAE loss IS the mae metric)
+        loss, dm = self._add_distance(loss, aux)
+        n = y.shape[0]
+        return loss, dict(mae=(sabs, tgt.numel()), distance_loss=dm, loss=(loss.detach() * n, n))
 
     def _graphed_loss(self, batch):
         """config.use_hipgraph: forward + loss + backward of a training batch as ONE hipGraph launch.  A graph is captured
@@ -569,9 +592,9 @@ class ZincSVDScheme:
 
             def fn():
                 self.flat.zero(); self.flat.rebind()
-                loss, _ = self.batch_loss(static)
+                loss, ms = self.batch_loss(static)
                 loss.backward()
-                return loss.detach()
+                return loss.detach(), ms
             # one graph (with its own static batch and activation pool) per padded geometry: keep the most recently used
             # MAX_GRAPHS of them -- a dataset padded to each batch's longest graph meets dozens of geometries
             while len(self._graphs) >= self.MAX_GRAPHS:
@@ -581,9 +604,9 @@ class ZincSVDScheme:
             self._graphs[key] = self._graphs.pop(key)          # most recently used last
             for k, v in moved.items():
                 ent[0][k].copy_(v, non_blocking=True)
-        loss = ent[1].replay()
+        loss, ms = ent[1].replay()
         self.flat.rebind()                           # .grad = this buffer's views, whichever graph ran last
-        return loss
+        return loss, ms
 
     def train_step(self, batch):
         c = self.config
@@ -594,14 +617,15 @@ class ZincSVDScheme:
             self.stop_training |= stop
         self.model.train()
         if self._use_graph:
-            loss = self._graphed_loss(batch)
+            loss, ms = self._graphed_loss(batch)
         else:
             if self.flat is not None:
                 self.flat.zero(); self.flat.rebind()
             else:
                 self.optimizer.zero_grad(set_to_none=True)
-            loss, _ = self.batch_loss(batch)
+            loss, ms = self.batch_loss(batch)
             loss.backward()
+        self._step_metrics = ms if self._distance_on() else None   # (metric sums, counts) of the step: train_model's epoch means
         if self.flat is not None:
             # a rank's slice of a short last batch can be one graph smaller than another's: weight by graph counts, so that
             # every graph of the GLOBAL batch counts once (the Keras loss is a mean over the global batch)
@@ -643,10 +667,14 @@ class ZincSVDScheme:
             if self.stop_training:
                 break
             losses = []
+            msum = {}                                # distance objective: training sums of every metric but the loss
             for i, b in enumerate(self.trainset):
                 if c.steps_per_epoch is not None and i >= c.steps_per_epoch:
                     break
                 losses.append(self.train_step(b))
+                for k, (sm, cnt) in (getattr(self, "_step_metrics", None) or {}).items():
+                    if k != "loss":
+                        a = msum.setdefault(k, [0.0, 0.0]); a[0] += float(sm); a[1] += float(cnt)
                 if self.stop_training:
                     break
             loss_mean = float(np.mean(losses)) if losses else math.nan
@@ -656,7 +684,18 @@ class ZincSVDScheme:
                 torch.distributed.all_reduce(t)
                 loss_mean = float(t[0] / t[1]) if float(t[1]) > 0 else math.nan
             logs = dict(loss=loss_mean)
-            if self.LOSS_METRIC is not None:
+            if self._distance_on():
+                # the loss carries the distance term: the base metric is no longer the loss; training means from the metric sums
+                keys = [k for k in (self.LOSS_METRIC, "distance_loss") if k is not None]
+                if c.distributed and _dist_on():
+                    t = torch.tensor([x for k in keys for x in msum.get(k, [0.0, 0.0])], dtype=torch.float64,
+                                     device=self.device if torch.distributed.get_backend() == "nccl" else "cpu")
+                    torch.distributed.all_reduce(t)
+                    msum = {k: [float(t[2 * i]), float(t[2 * i + 1])] for i, k in enumerate(keys)}
+                for k in keys:
+                    sm, cnt = msum.get(k, [0.0, 0.0])
+                    logs[k] = sm / cnt if cnt > 0 else math.nan
+            elif self.LOSS_METRIC is not None:
                 logs[self.LOSS_METRIC] = logs["loss"]
             if self.valset is not None:
                 v = self.evaluate(self.valset, c.validation_steps)
@@ -769,19 +808,24 @@ class PatternSVDScheme(ZincSVDScheme):
     LOSS_METRIC = "xent"
 
     def get_metrics(self):
-        return ["xent", "acc"]
+        return ["xent", "acc"] + self._distance_metrics()
 
     def batch_loss(self, batch):
         from .model import class_weights_from_sizes
         dev = self.device
         mv = (lambda t: t.to(dev)) if dev is not None else (lambda t: t)
         nf, adj, tgt = mv(batch["node_features"]), mv(batch["graph_matrix"]), mv(batch["target"])
-        out = self.model(nf, adj, return_mask=True, **self._pe(batch))
+        out = self.model(nf, adj, return_mask=True, **self._pe(batch), **self._aux_kwargs())
+        if self._distance_on():
+            out, aux = out
         logits, mask = out
         if getattr(self, "_class_w", None) is None or self._class_w.device != logits.device:
             self._class_w = class_weights_from_sizes(self.config.class_sizes, device=logits.device)   # once: a host -> device copy cannot be captured
         w = self._class_w
         loss = self.loss_fn(logits, tgt, mask, w)
+        dm = None
+        if self._distance_on():
+            loss, dm = self._add_distance(loss, aux)
         m = mask.to(logits.dtype)
         hit = ((logits.argmax(-1) == tgt).to(logits.dtype) * m).sum().detach()
         # Keras feeds the mask as sample_weight: the metrics are means over the REAL nodes (losses.py:108-118)
@@ -791,7 +835,10 @@ class PatternSVDScheme(ZincSVDScheme):
         # its compiled-loss Mean metric, which LossesContainer updates with sample_weight = the batch dimension (number of graphs):
         # N is padded per batch, so a slot-weighted epoch mean would differ from the reference's `loss` / `val_loss`
         graphs = torch.full((), float(m.shape[0]), device=m.device, dtype=m.dtype)   # (a fill kernel: capturable, unlike a host -> device copy)
-        return loss, dict(xent=(xs, m.sum()), acc=(hit, m.sum()), loss=(loss.detach() * graphs, graphs))
+        ms = dict(xent=(xs, m.sum()), acc=(hit, m.sum()), loss=(loss.detach() * graphs, graphs))
+        if dm is not None:
+            ms["distance_loss"] = dm
+        return loss, ms
 
 
     @torch.no_grad()
@@ -852,13 +899,13 @@ class PatternEigScheme(PatternSVDScheme):
     SCHEME = "pattern.eig"
 
     def get_metrics(self):
-        return ["acc"]
+        return ["acc"] + self._distance_metrics()
 
     LOSS_METRIC = None       # its only metric is the accuracy
 
     def batch_loss(self, batch):
         loss, ms = super().batch_loss(batch)
-        return loss, dict(acc=ms["acc"], loss=ms["loss"])
+        return loss, {k: v for k, v in ms.items() if k != "xent"}
 
 
 class SyntheticPattern:
@@ -908,14 +955,20 @@ class Cifar10SVDScheme(ZincSVDScheme):
     LOSS_METRIC = "xent"
 
     def get_metrics(self):
-        return ["xent", "acc"]     # (the reference lists ['acc', xent]; the loss is the x-ent)
+        return ["xent", "acc"] + self._distance_metrics()     # (the reference lists ['acc', xent]; the loss is the x-ent)
 
     def batch_loss(self, batch):
         nf, fm, adj, tgt = self._batch(batch)
-        logits = self.model(nf, fm, adj, **self._pe(batch))
-        loss = self.loss_fn(logits, tgt)
+        logits = self.model(nf, fm, adj, **self._pe(batch), **self._aux_kwargs())
+        if self._distance_on():
+            logits, aux = logits
+        loss = xent = self.loss_fn(logits, tgt)
         n = tgt.numel()
-        return loss, dict(xent=(loss.detach() * n, n), acc=((logits.argmax(-1) == tgt).sum().detach(), n), loss=(loss.detach() * n, n))
+        ms = dict(xent=(xent.detach() * n, n), acc=((logits.argmax(-1) == tgt).sum().detach(), n))
+        if self._distance_on():
+            loss, ms["distance_loss"] = self._add_distance(loss, aux)
+        ms["loss"] = (loss.detach() * n, n)
+        return loss, ms
 
 
     def do_evaluations_on_split(self, split):        # schemes/cifar10/svd.py:45-53

@@ -461,6 +461,46 @@ int egt_edge_embed_bwd(const egt_embed_desc* desc, const int32_t* feature_matrix
                        const void* d_e, void* d_fm_table, void* d_adj_kernel, void* d_adj_bias,
                        void* workspace, void* stream);
 
+/* ---- distance objective (the reference's *_spe_do configs: distance_loss / distance_target) ----
+ *   target    = round(sum_{k=1..T} hop_k), hop_1 = A, hop_k = clip(A . hop_{k-1}, 0, 1)     lib/models/graph_model_base.py:66-76
+ *   logits    = Dense_t(act(Dense_1(act(Dense_0(edge_norm_final(e))))))   De -> M0 -> M1 -> C = T + 1   :83-94
+ *   per_graph = sum over the pairs of a graph of CE(logits, target) * (target > 0)           lib/base/genutil/loss_layers.py:38-67
+ * e [B,N,N,De] is the FINAL edge tensor (fp32, or bf16 with EGT_BF16; parameters, their gradients and the arithmetic are
+ * fp32).  egt_distance_target: adj [B,N,N] fp32 -> target [B,N,N] uint8, N <= 192 (the graph's adjacency stays in LDS).
+ * Covered: De in {8,16,32,48,64}, (M0, M1) in {(24,12), (32,16)}, 2 <= C <= 16, EGT_ACT_ELU / EGT_ACT_RELU, B*N*N < 2^31.
+ * The backward recomputes the forward from e; d_per_graph [B] fp32 is the upstream gradient of per_graph_loss.  Kernels in
+ * Keras layout [in, out].  No atomics: two calls on the same inputs give the same bits.  `workspace`
+ * (egt_edge_head_workspace_bytes) is scratch: nothing is carried from the forward to the backward. */
+#define EGT_EH_LAYERNORM 0x1 /* edge_norm_final (eps = ln_eps) before the head; off: gamma / beta may be NULL */
+typedef struct egt_head_desc {
+  int32_t B, N, De, M0, M1, C;
+  int32_t dtype;      /* EGT_F32 or EGT_BF16: storage of e and d_e */
+  int32_t activation; /* EGT_ACT_ELU or EGT_ACT_RELU (config.activation) */
+  int32_t flags;      /* EGT_EH_LAYERNORM */
+  float ln_eps;
+  int32_t reserved;   /* 0 */
+} egt_head_desc;
+
+typedef struct egt_head_params {
+  void* edge_norm_final_gamma;      /* [De] */
+  void* edge_norm_final_beta;       /* [De] */
+  void* mlp_out_dist_targ_0_kernel; /* [De, M0] */
+  void* mlp_out_dist_targ_0_bias;   /* [M0] */
+  void* mlp_out_dist_targ_1_kernel; /* [M0, M1] */
+  void* mlp_out_dist_targ_1_bias;   /* [M1] */
+  void* distance_target_kernel;     /* [M1, C] */
+  void* distance_target_bias;       /* [C] */
+} egt_head_params;
+
+int egt_distance_target(const float* adj, int32_t B, int32_t N, int32_t T, uint8_t* target, void* stream);
+int egt_edge_head_supported(const egt_head_desc* desc);
+size_t egt_edge_head_workspace_bytes(const egt_head_desc* desc);
+int egt_edge_head_fwd(const egt_head_desc* desc, const egt_head_params* params, const void* e, const uint8_t* target,
+                      float* per_graph_loss /* [B] */, void* workspace, void* stream);
+int egt_edge_head_bwd(const egt_head_desc* desc, const egt_head_params* params, const void* e, const uint8_t* target,
+                      const float* d_per_graph /* [B] */, void* d_e, const egt_head_params* grads, void* workspace,
+                      void* stream);
+
 /* ---- batch data parallelism: the gradient all-reduce on RCCL -------------------
  * Replaces what tf.distribute.MirroredStrategy does for the reference
  * (lib/training/training_base.py:230-247): one synchronous all-reduce of every
