@@ -106,6 +106,23 @@ class HeadParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in HEAD_PARAM_FIELDS]
 
 
+NH_LAYERNORM = 0x1   # egt_node_head_desc.flags
+
+
+class NodeHeadDesc(C.Structure):
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("W", C.c_int32), ("M0", C.c_int32), ("M1", C.c_int32),
+                ("C", C.c_int32), ("activation", C.c_int32), ("flags", C.c_int32), ("ln_eps", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+NODE_HEAD_PARAM_FIELDS = ("node_norm_final_gamma", "node_norm_final_beta", "mlp_out_0_kernel", "mlp_out_0_bias",
+                          "mlp_out_1_kernel", "mlp_out_1_bias", "target_kernel", "target_bias")
+
+
+class NodeHeadParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in NODE_HEAD_PARAM_FIELDS]
+
+
 class EGTLibraryError(RuntimeError):
     pass
 
@@ -148,6 +165,11 @@ _PROTOS = {
     "egt_edge_head_fwd": (C.c_int, [C.POINTER(HeadDesc), C.POINTER(HeadParams)] + [_VP] * 5),
     "egt_edge_head_bwd": (C.c_int, [C.POINTER(HeadDesc), C.POINTER(HeadParams)] + [_VP] * 4
                           + [C.POINTER(HeadParams)] + [_VP] * 2),
+    "egt_node_head_supported": (C.c_int, [C.POINTER(NodeHeadDesc)]),
+    "egt_node_head_workspace_bytes": (C.c_size_t, [C.POINTER(NodeHeadDesc)]),
+    "egt_node_head_fwd": (C.c_int, [C.POINTER(NodeHeadDesc), C.POINTER(NodeHeadParams)] + [_VP] * 7),
+    "egt_node_head_bwd": (C.c_int, [C.POINTER(NodeHeadDesc), C.POINTER(NodeHeadParams)] + [_VP] * 6
+                          + [C.POINTER(NodeHeadParams)] + [_VP] * 2),
     "egt_dp_unique_id": (C.c_int, [_VP]),
     "egt_dp_init": (C.c_int, [_VP, C.c_int32, C.c_int32]),
     "egt_dp_allreduce": (C.c_int, [_VP, C.c_size_t, C.c_int32, _VP]),

@@ -466,6 +466,315 @@ __global__ void __launch_bounds__(256) k_edge_head_finish(const float* __restric
   for (int j = tid; j < C; j += 256) d_bt[j] = red[oBT + j];
 }
 
+// ---- node-classification head (the PATTERN / CLUSTER readout: sbm_pattern/dc.py, sbm_cluster/dc.py) ----
+//   z = Dense_t(act(Dense_1(act(Dense_0(node_norm_final(h))))))                   W -> M0 -> M1 -> C
+//   stats = (sum mask w[y] CE(z, y), sum mask [argmax z == y], sum mask)          lib/base/genutil/losses.py:41-118
+// The edge head's tile with another row source and epilogue: the rows are the R = B N flattened (graph, node) slots of h,
+// workgroup g owns the tiles [g chunk, (g + 1) chunk); a tile whose 16 rows are all masked is skipped before h is loaded, and
+// the target of a masked row is never used as a class.  The weight image, the products and the parameter-gradient route
+// (per-workgroup partials -> k_edge_head_reduce -> k_edge_head_finish) are the edge head's.
+// BWD == false: stat_part[3 g ..] = the workgroup's (loss, hits, rows); hits and rows are integers (stored as their bit patterns).
+// BWD == true:  dh = sgrad[0] d stats[0] / d h (exact zeros on masked rows), part[g * PG ..] = the parameter gradients.
+template <int DET, bool BWD>
+__global__ void __launch_bounds__(EH_NW * 64) k_node_head(const float* __restrict__ h, const int32_t* __restrict__ target,
+                                                          const uint8_t* __restrict__ mask, const float* __restrict__ cw,
+                                                          const float* __restrict__ img, const float* __restrict__ sgrad,
+                                                          float* __restrict__ dh, float* __restrict__ stat_part,
+                                                          float* __restrict__ part, int R, int chunk, int W, int C, int act, int ln,
+                                                          float eps) {
+  using Z = EhGeo<DET>;
+  constexpr int PE = Z::PE;
+  __shared__ __attribute__((aligned(16))) float wsm[Z::IMG];
+  __shared__ __attribute__((aligned(16))) float asm_[EH_NW * Z::WAVE];
+  __shared__ float lsm[EH_NW];
+  __shared__ int csm[2 * EH_NW];
+  __shared__ float cws[16];
+  static_assert(EH_NW * Z::WAVE >= Z::PG, "the gradient image is reduced in the activation area");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4;
+  const int TPG = (R >> 4) + ((R & 15) != 0);
+  const int t0 = min(TPG, (int)blockIdx.x * chunk), t1 = min(TPG, t0 + chunk);
+  for (int k = threadIdx.x; k < Z::IMG; k += EH_NW * 64) wsm[k] = img[k];
+  if (threadIdx.x < 16) cws[threadIdx.x] = (int)threadIdx.x < C ? cw[threadIdx.x] : 0.f;
+  float* const my = asm_ + wave * Z::WAVE;
+  for (int k = lane; k < Z::WAVE; k += 64) my[k] = 0.f;
+  __syncthreads();
+  float* const XE = my + Z::XE;
+  float* const X1 = my + Z::X1;
+  float* const X2 = my + Z::X2;
+  float* const DL = my + Z::DL;
+  float* const RS = my + Z::RS;
+  const float* const W0 = wsm + Z::W0;
+  const float* const W1 = wsm + Z::W1;
+  const float* const WT = wsm + Z::WT;
+  const float sb = BWD ? sgrad[0] : 0.f;
+  const int C4 = W >> 2, NF4 = 4 * W;   // 16-byte slots per row / per tile
+  const float inv_w = 1.0f / (float)W;
+
+  float lossacc = 0.f;
+  int hits = 0, rows = 0;
+  v4f_h gW0[DET][2], gW1[2], gWt;
+  float gb0[2] = {0.f, 0.f}, gb1 = 0.f, gbt = 0.f;
+#pragma unroll
+  for (int a = 0; a < DET; ++a) gW0[a][0] = gW0[a][1] = (v4f_h){0.f, 0.f, 0.f, 0.f};
+  gW1[0] = gW1[1] = gWt = (v4f_h){0.f, 0.f, 0.f, 0.f};
+
+  for (int t = t0 + wave; t < t1; t += EH_NW) {
+    const size_t r0 = (size_t)16 * t;                           // first row of the tile
+    const int valid = (int)min((size_t)16, (size_t)R - r0);
+    const bool lv = lane < valid && mask[r0 + lane] != 0;
+    const unsigned long long lvm = __ballot(lv);                // bit r: row r of the tile is a real node
+    if (lvm == 0ull) {                                          // nothing to learn here: no h load, no arithmetic
+      if (BWD) {
+        float* dt = dh + r0 * W;
+        for (int f = lane; f < NF4; f += 64)
+          if (f / C4 < valid) eh_st4(dt + (size_t)f * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+      }
+      continue;
+    }
+    const int my_t = lv ? target[r0 + lane] : -1;               // a masked row has no class
+    const float* ht = h + r0 * W;
+    // ---- h tile -> LDS image (rows >= valid: zeros) ----
+    for (int f = lane; f < NF4; f += 64) {
+      const int row = f / C4, c4 = f % C4;
+      const float4 v = row < valid ? eh_ld_raw(ht + (size_t)f * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(XE + row * PE + 4 * c4) = v;
+    }
+    eh_sync();
+    // ---- node_norm_final: two-pass moments; 4 lanes per row ----
+    if (ln) {
+      const int row = lane >> 2, pt = lane & 3;
+      float s = 0.f;
+      for (int c4 = pt; c4 < C4; c4 += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
+        s += (v.x + v.y) + (v.z + v.w);
+      }
+      s += lane_xor<1>(s); s += lane_xor<2>(s);
+      const float mu = s * inv_w;
+      float vs = 0.f;
+      for (int c4 = pt; c4 < C4; c4 += 4) {
+        const float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
+        const float a0 = v.x - mu, a1 = v.y - mu, a2 = v.z - mu, a3 = v.w - mu;
+        vs = fmaf(a0, a0, vs); vs = fmaf(a1, a1, vs); vs = fmaf(a2, a2, vs); vs = fmaf(a3, a3, vs);
+      }
+      vs += lane_xor<1>(vs); vs += lane_xor<2>(vs);
+      const float rstd = rsqrtf(vs * inv_w + eps);
+      for (int c4 = pt; c4 < C4; c4 += 4) {
+        float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
+        v.x = (v.x - mu) * rstd; v.y = (v.y - mu) * rstd; v.z = (v.z - mu) * rstd; v.w = (v.w - mu) * rstd;
+        *reinterpret_cast<float4*>(XE + row * PE + 4 * c4) = v;
+      }
+      if (pt == 0) RS[row] = rstd;
+      eh_sync();
+    }
+    // ---- x1 = act(hhat . W0f + b0f) ----
+    v4f_h a1[2], a2;
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      const float bb = wsm[Z::B0 + 16 * ct + i];
+      v4f_h acc = (v4f_h){bb, bb, bb, bb};
+      acc = eh_mm_nn<Z::DEP>(XE, PE, W0 + 16 * ct, EH_P0, i, q, acc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[r] = eh_act(acc[r], act);
+        X1[(4 * q + r) * EH_P0 + 16 * ct + i] = acc[r];
+      }
+      a1[ct] = acc;
+    }
+    eh_sync();
+    // ---- x2 = act(x1 . W1 + b1) ----
+    {
+      const float bb = wsm[Z::B1 + i];
+      v4f_h acc = (v4f_h){bb, bb, bb, bb};
+      acc = eh_mm_nn<32>(X1, EH_P0, W1, EH_P1, i, q, acc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        acc[r] = eh_act(acc[r], act);
+        X2[(4 * q + r) * EH_P1 + i] = acc[r];
+      }
+      a2 = acc;
+    }
+    eh_sync();
+    // ---- logits; max-subtracted log-sum-exp over the C real columns, class weight, gather, arg-max (lowest index wins) ----
+    v4f_h z;
+    {
+      const float bb = wsm[Z::BT + i];
+      z = (v4f_h){bb, bb, bb, bb};
+      z = eh_mm_nn<16>(X2, EH_P1, WT, EH_P1, i, q, z);
+    }
+    v4f_h dl;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int tr = __shfl(my_t, 4 * q + r, 64);
+      const bool live = (lvm >> (4 * q + r)) & 1ull;
+      const bool real = i < C;
+      const float m = row_max16(real ? z[r] : -INFINITY);
+      const float ex = real ? expf(z[r] - m) : 0.f;
+      const float se = row_sum16(ex);
+      const float zt = row_sum16(i == tr ? z[r] : 0.f);
+      const float wt = live ? cws[min(max(tr, 0), 15)] : 0.f;
+      if (!BWD) {
+        const float am = -row_max16((real && z[r] == m) ? -(float)i : -16.f);
+        if (i == 0 && live) {
+          lossacc += wt * ((m + logf(se)) - zt);
+          hits += am == (float)tr ? 1 : 0;
+          rows += 1;
+        }
+      } else {
+        dl[r] = (live && real) ? (ex / se - (i == tr ? 1.f : 0.f)) * (wt * sb) : 0.f;
+      }
+    }
+    if (!BWD) continue;
+
+    // ================= backward of the tile =================
+    gbt += (dl[0] + dl[1]) + (dl[2] + dl[3]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) DL[(4 * q + r) * EH_P1 + i] = dl[r];
+    eh_sync();
+    gWt = eh_mm_tn(X2, EH_P1, DL, EH_P1, i, q, gWt);                                   // dWt += x2^T . dl
+    v4f_h d2 = eh_mm_nt<16>(DL, EH_P1, WT, EH_P1, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});  // dx2 = dl . Wt^T
+#pragma unroll
+    for (int r = 0; r < 4; ++r) d2[r] *= eh_dact(a2[r], act);
+    gb1 += (d2[0] + d2[1]) + (d2[2] + d2[3]);
+    eh_sync();                                                                         // x2 has been read
+#pragma unroll
+    for (int r = 0; r < 4; ++r) X2[(4 * q + r) * EH_P1 + i] = d2[r];
+    eh_sync();
+    v4f_h d1[2];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+      gW1[ct] = eh_mm_tn(X1 + 16 * ct, EH_P0, X2, EH_P1, i, q, gW1[ct]);               // dW1 += x1^T . dx2pre
+      d1[ct] = eh_mm_nt<16>(X2, EH_P1, W1 + 16 * ct * EH_P1, EH_P1, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+      for (int r = 0; r < 4; ++r) d1[ct][r] *= eh_dact(a1[ct][r], act);
+      gb0[ct] += (d1[ct][0] + d1[ct][1]) + (d1[ct][2] + d1[ct][3]);
+    }
+    eh_sync();                                                                         // x1 has been read
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) X1[(4 * q + r) * EH_P0 + 16 * ct + i] = d1[ct][r];
+    eh_sync();
+    v4f_h gh[DET];
+#pragma unroll
+    for (int a = 0; a < DET; ++a) {
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct)
+        gW0[a][ct] = eh_mm_tn(XE + 16 * a, PE, X1 + 16 * ct, EH_P0, i, q, gW0[a][ct]);  // dW0f += hhat^T . dx1pre
+      gh[a] = eh_mm_nt<32>(X1, EH_P0, W0 + 16 * a * EH_P0, EH_P0, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});   // dhhat = dx1pre . W0f^T
+    }
+    // ---- LayerNorm backward per row: dh = rstd (g - mean(g) - hhat mean(g hhat)) ----
+    if (ln) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 4 * q + r;
+        float hh[DET], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int a = 0; a < DET; ++a) {
+          hh[a] = XE[row * PE + 16 * a + i];
+          s1 += gh[a][r];
+          s2 = fmaf(gh[a][r], hh[a], s2);
+        }
+        s1 = row_sum16(s1) * inv_w;
+        s2 = row_sum16(s2) * inv_w;
+        const float rstd = RS[row];
+#pragma unroll
+        for (int a = 0; a < DET; ++a) gh[a][r] = rstd * (gh[a][r] - s1 - hh[a] * s2);
+      }
+    }
+    eh_sync();                                                                         // hhat has been read
+#pragma unroll
+    for (int a = 0; a < DET; ++a)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) XE[(4 * q + r) * PE + 16 * a + i] = gh[a][r];
+    eh_sync();
+    {
+      float* dt = dh + r0 * W;
+      for (int f = lane; f < NF4; f += 64) {
+        const int row = f / C4, c4 = f % C4;
+        if (row < valid) {
+          const bool on = (lvm >> row) & 1ull;                                         // a masked row gets exact zeros
+          eh_st4(dt + (size_t)f * 4, on ? *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f));
+        }
+      }
+    }
+    eh_sync();   // the image is free for the next tile (its pad columns are untouched)
+  }
+
+  // ---- workgroup partials, waves added in index order ----
+  if (!BWD) {
+    const float l = eh_sum_q(lossacc);   // (lanes i == 0 carry the rows)
+    hits += __shfl_xor(hits, 16, 64); hits += __shfl_xor(hits, 32, 64);
+    rows += __shfl_xor(rows, 16, 64); rows += __shfl_xor(rows, 32, 64);
+    if (lane == 0) { lsm[wave] = l; csm[2 * wave] = hits; csm[2 * wave + 1] = rows; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float* o = stat_part + (size_t)blockIdx.x * 3;
+      o[0] = ((lsm[0] + lsm[1]) + lsm[2]) + lsm[3];
+      o[1] = __int_as_float(csm[0] + csm[2] + csm[4] + csm[6]);
+      o[2] = __int_as_float(csm[1] + csm[3] + csm[5] + csm[7]);
+    }
+    return;
+  }
+  gb0[0] = eh_sum_q(gb0[0]); gb0[1] = eh_sum_q(gb0[1]); gb1 = eh_sum_q(gb1); gbt = eh_sum_q(gbt);
+  __syncthreads();   // every wave is done with its activation image
+  float* const red = asm_;
+  for (int w = 0; w < EH_NW; ++w) {
+    if (wave == w) {
+      const bool first = w == 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int a = 0; a < DET; ++a)
+#pragma unroll
+          for (int ct = 0; ct < 2; ++ct) {
+            float* p = red + Z::G0 + (16 * a + 4 * q + r) * 32 + 16 * ct + i;
+            *p = (first ? 0.f : *p) + gW0[a][ct][r];
+          }
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+          float* p = red + Z::G1 + (16 * ct + 4 * q + r) * 16 + i;
+          *p = (first ? 0.f : *p) + gW1[ct][r];
+        }
+        float* p = red + Z::GT + (4 * q + r) * 16 + i;
+        *p = (first ? 0.f : *p) + gWt[r];
+      }
+      if (q == 0) {
+        float* p = red + Z::GB0 + i;
+        p[0] = (first ? 0.f : p[0]) + gb0[0];
+        p[16] = (first ? 0.f : p[16]) + gb0[1];
+        p = red + Z::GB1 + i;
+        *p = (first ? 0.f : *p) + gb1;
+        p = red + Z::GBT + i;
+        *p = (first ? 0.f : *p) + gbt;
+      }
+    }
+    __syncthreads();
+  }
+  float* out = part + (size_t)blockIdx.x * Z::PG;
+  for (int k = threadIdx.x; k < Z::PG; k += EH_NW * 64) out[k] = red[k];
+}
+
+// stats = the workgroups' (loss, hits, rows) added in a fixed order: 64 contiguous segments, then the 64; the two counts in integers
+__global__ void __launch_bounds__(64) k_node_head_stats(const float* __restrict__ stat_part, float* __restrict__ stats, int G) {
+  __shared__ float ls[64];
+  __shared__ long long hs[64], rs[64];
+  const int per = (G + 63) / 64, w0 = threadIdx.x * per, w1 = min(G, w0 + per);
+  float l = 0.f;
+  long long hh = 0, rr = 0;
+  for (int w = w0; w < w1; ++w) {
+    l += stat_part[3 * (size_t)w];
+    hh += __float_as_int(stat_part[3 * (size_t)w + 1]);
+    rr += __float_as_int(stat_part[3 * (size_t)w + 2]);
+  }
+  ls[threadIdx.x] = l; hs[threadIdx.x] = hh; rs[threadIdx.x] = rr;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    l = 0.f; hh = 0; rr = 0;
+    for (int k = 0; k < 64; ++k) { l += ls[k]; hh += hs[k]; rr += rs[k]; }
+    stats[0] = l; stats[1] = (float)hh; stats[2] = (float)rr;
+  }
+}
+
 // ---- distance target: target = round(sum_{k=1..T} hop_k), hop_1 = A, hop_k = clip(A . hop_{k-1}, 0, 1) ----
 // k_hop_chain's scheme (egt_embed.hip): a workgroup owns CT column tiles of one graph, keeps the zero-padded adjacency
 // ([R16][R16 + 4]) and its column block of the current hop ([R16][16 CT + 4]) in LDS, and walks the hops without another global
@@ -690,5 +999,121 @@ extern "C" int egt_edge_head_bwd(const egt_head_desc* d, const egt_head_params* 
              (float*)grads->mlp_out_dist_targ_1_bias, (float*)grads->distance_target_kernel, (float*)grads->distance_target_bias,
              d->De, 16 * det, d->M0, d->M1, d->C, ln);
   EGT_HIP_LAUNCH_CHECK("egt_edge_head_bwd");
+  return EGT_OK;
+}
+
+// =================================== node-classification head: host ===================================
+static int node_head_check(const egt_node_head_desc* d) {
+  if (!d) EGT_FAIL(EGT_E_NULL, "desc is NULL");
+  if ((d->flags & ~(int32_t)EGT_NH_LAYERNORM) != 0 || d->reserved != 0)
+    EGT_FAIL(EGT_E_FLAGS, "node head: unknown flag bits 0x%x / reserved %d", (unsigned)d->flags, d->reserved);
+  if (d->B < 1 || d->N < 1 || (long)d->B * d->N > 2147483647L)
+    EGT_FAIL(EGT_E_SHAPE, "node head: B, N >= 1 and B*N inside 32-bit indexing (B=%d N=%d)", d->B, d->N);
+  if (!(d->W == 16 || d->W == 32 || d->W == 48 || d->W == 64))
+    EGT_FAIL(EGT_E_SHAPE, "node head covers W in {16,32,48,64} (got %d)", d->W);
+  if (!((d->M0 == 24 && d->M1 == 12) || (d->M0 == 32 && d->M1 == 16)))
+    EGT_FAIL(EGT_E_SHAPE, "node head covers (M0, M1) in {(24,12), (32,16)}: model widths 48 / 64 (got %d, %d)", d->M0, d->M1);
+  if (d->C < 2 || d->C > 16) EGT_FAIL(EGT_E_SHAPE, "node head covers 2 <= C <= 16 classes (got %d)", d->C);
+  if (d->activation != EGT_ACT_ELU && d->activation != EGT_ACT_RELU)
+    EGT_FAIL(EGT_E_SHAPE, "node head activation is EGT_ACT_ELU or EGT_ACT_RELU (got %d)", d->activation);
+  return EGT_OK;
+}
+extern "C" int egt_node_head_supported(const egt_node_head_desc* d) { return node_head_check(d) == EGT_OK ? 1 : 0; }
+
+// workgroups: one 16-row tile per wave and pass, so at least 4 tiles each; at most 1024 (the weight image is loaded once per
+// workgroup, and every workgroup leaves one gradient partial)
+static int node_head_tiles(const egt_node_head_desc* d) { return (int)(((long)d->B * d->N + 15) / 16); }
+static int node_head_groups(const egt_node_head_desc* d) {
+  int g = node_head_tiles(d) / EH_NW;
+  g = g > 1024 ? 1024 : g;
+  return g < 1 ? 1 : g;
+}
+// workspace (floats): weight image | stat partials [G][3] | gradient partials [G][PG] | reduced gradients [PG]
+extern "C" size_t egt_node_head_workspace_bytes(const egt_node_head_desc* d) {
+  if (node_head_check(d) != EGT_OK) return 0;
+  const int det = d->W / 16;
+  const size_t G = (size_t)node_head_groups(d);
+  return sizeof(float) * ((size_t)eh_img(det) + 3 * G + G * eh_pg(det) + eh_pg(det));
+}
+
+static int node_head_params_check(const egt_node_head_desc* d, const egt_node_head_params* p, const char* what) {
+  if (!p) EGT_FAIL(EGT_E_NULL, "node head: %s is NULL", what);
+  if ((d->flags & EGT_NH_LAYERNORM) && (!p->node_norm_final_gamma || !p->node_norm_final_beta))
+    EGT_FAIL(EGT_E_NULL, "node head: EGT_NH_LAYERNORM set but %s gamma/beta is NULL", what);
+  if (!p->mlp_out_0_kernel || !p->mlp_out_0_bias || !p->mlp_out_1_kernel || !p->mlp_out_1_bias || !p->target_kernel ||
+      !p->target_bias)
+    EGT_FAIL(EGT_E_NULL, "node head: a kernel / bias pointer of %s is NULL", what);
+  return EGT_OK;
+}
+
+static void node_head_prep(const egt_node_head_desc* d, const egt_node_head_params* p, float* img, hipStream_t st) {
+  EGT_LAUNCH("k_node_head_prep", k_edge_head_prep, dim3(1), dim3(64), 0, st, (const float*)p->node_norm_final_gamma,
+             (const float*)p->node_norm_final_beta, (const float*)p->mlp_out_0_kernel, (const float*)p->mlp_out_0_bias,
+             (const float*)p->mlp_out_1_kernel, (const float*)p->mlp_out_1_bias, (const float*)p->target_kernel,
+             (const float*)p->target_bias, img, d->W, d->W, d->M0, d->M1, d->C, (d->flags & EGT_NH_LAYERNORM) ? 1 : 0);
+}
+
+template <bool BWD>
+static void node_head_dispatch(const egt_node_head_desc* d, const float* h, const int32_t* target, const uint8_t* mask,
+                               const float* cw, const float* img, const float* s, float* dh, float* stat_part, float* part,
+                               hipStream_t st) {
+  const int G = node_head_groups(d), tiles = node_head_tiles(d), chunk = (tiles + G - 1) / G;
+  const int R = d->B * d->N, ln = (d->flags & EGT_NH_LAYERNORM) ? 1 : 0;
+  switch (d->W / 16) {
+#define NH_CASE(DET_)                                                                                                          \
+  case DET_:                                                                                                                   \
+    EGT_LAUNCH(BWD ? "k_node_head_bwd" : "k_node_head_fwd", (k_node_head<DET_, BWD>), dim3((unsigned)G), dim3(EH_NW * 64), 0, st, \
+               h, target, mask, cw, img, s, dh, stat_part, part, R, chunk, d->W, d->C, d->activation, ln, d->ln_eps);           \
+    break;
+    NH_CASE(1) NH_CASE(2) NH_CASE(3) NH_CASE(4)
+#undef NH_CASE
+  }
+}
+
+extern "C" int egt_node_head_fwd(const egt_node_head_desc* d, const egt_node_head_params* params, const float* h,
+                                 const int32_t* target, const uint8_t* mask, const float* class_weights, float* stats,
+                                 void* workspace, void* stream) {
+  int rc = node_head_check(d);
+  if (rc) return rc;
+  if ((rc = node_head_params_check(d, params, "params"))) return rc;
+  if (!h || !target || !mask || !class_weights || !stats || !workspace)
+    EGT_FAIL(EGT_E_NULL, "node head: h/target/mask/class_weights/stats/workspace is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  const int det = d->W / 16, G = node_head_groups(d);
+  float* img = (float*)workspace;
+  float* stat_part = img + eh_img(det);
+  node_head_prep(d, params, img, st);
+  node_head_dispatch<false>(d, h, target, mask, class_weights, img, nullptr, nullptr, stat_part, nullptr, st);
+  EGT_LAUNCH("k_node_head_finish", k_node_head_stats, dim3(1), dim3(64), 0, st, (const float*)stat_part, stats, G);
+  EGT_HIP_LAUNCH_CHECK("egt_node_head_fwd");
+  return EGT_OK;
+}
+
+extern "C" int egt_node_head_bwd(const egt_node_head_desc* d, const egt_node_head_params* params, const float* h,
+                                 const int32_t* target, const uint8_t* mask, const float* class_weights, const float* d_loss,
+                                 float* d_h, const egt_node_head_params* grads, void* workspace, void* stream) {
+  int rc = node_head_check(d);
+  if (rc) return rc;
+  if ((rc = node_head_params_check(d, params, "params"))) return rc;
+  if ((rc = node_head_params_check(d, grads, "grads"))) return rc;
+  if (!h || !target || !mask || !class_weights || !d_loss || !d_h || !workspace)
+    EGT_FAIL(EGT_E_NULL, "node head: h/target/mask/class_weights/d_loss/d_h/workspace is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  const int det = d->W / 16, G = node_head_groups(d), PG = eh_pg(det);
+  const int ln = (d->flags & EGT_NH_LAYERNORM) ? 1 : 0;
+  float* img = (float*)workspace;
+  float* part = img + eh_img(det) + 3 * (size_t)G;
+  float* red = part + (size_t)G * PG;
+  node_head_prep(d, params, img, st);
+  node_head_dispatch<true>(d, h, target, mask, class_weights, img, d_loss, d_h, nullptr, part, st);
+  EGT_LAUNCH("k_node_head_finish", k_edge_head_reduce, dim3((unsigned)((PG + 63) / 64)), dim3(256), 0, st, (const float*)part, red,
+             G, PG);
+  EGT_LAUNCH("k_node_head_finish", k_edge_head_finish, dim3(1), dim3(256), 0, st, (const float*)red,
+             (const float*)params->node_norm_final_gamma, (const float*)params->node_norm_final_beta,
+             (const float*)params->mlp_out_0_kernel, (float*)grads->node_norm_final_gamma, (float*)grads->node_norm_final_beta,
+             (float*)grads->mlp_out_0_kernel, (float*)grads->mlp_out_0_bias, (float*)grads->mlp_out_1_kernel,
+             (float*)grads->mlp_out_1_bias, (float*)grads->target_kernel, (float*)grads->target_bias, d->W, d->W, d->M0, d->M1,
+             d->C, ln);
+  EGT_HIP_LAUNCH_CHECK("egt_node_head_bwd");
   return EGT_OK;
 }

@@ -299,6 +299,12 @@ SPECS: Dict[str, DatasetSpec] = {
     # datasets/sbm_pattern.py:7-79 (no edge features; a class per node)
     "sbm_pattern": DatasetSpec("SBM_PATTERN", _graph_fields(np.int32, (), None, (), "targets/node_labels", np.int32, (None,), ("L",), 0),
                                None, -1, None, dict(num_features=2, sparse=True)),
+    # datasets/sbm_cluster.py (as SBM_PATTERN: seven node-feature values, six classes; eigen defaults 20 features)
+    "sbm_cluster": DatasetSpec("SBM_CLUSTER", _graph_fields(np.int32, (), None, (), "targets/node_labels", np.int32, (None,), ("L",), 0),
+                               None, -1, None, dict(num_features=20, sparse=True)),
+    # datasets/zinc_full.py (as ZINC; the 250k-molecule set)
+    "zinc_full": DatasetSpec("ZINC_full", _graph_fields(np.int32, (), np.int32, (), "targets/value", np.float32, (1,), (1,), 0.0),
+                             40, -1, (), dict(num_features=8, sparse=False)),
     # datasets/cifar10.py:7-84 (5 real node features, 1 real edge feature, a class per graph)
     "cifar10": DatasetSpec("CIFAR10", _graph_fields(np.float32, (5,), np.float32, (1,), "targets/label", np.int32, (), (), 0),
                            150, -1.0, (1,)),
@@ -582,10 +588,11 @@ class CreateTargets:
 def dataset_for_scheme(scheme: str, dataset_path: str, max_shuffle_len=10000, num_svd_features=16, num_eig_features=8,
                        use_svd=False, use_eig=True, splits=("training", "validation"), **kw) -> GraphDataset:
     """what ``get_dataset()`` builds for the schemes egt_amd.training runs: dataset class + dataset_config
-    (scheme_base.py:62-69,125-133,167-171; schemes/{zinc,pattern,cifar10}/svd.py) and the excluded features
+    (scheme_base.py:62-69,125-133,167-171; schemes/{zinc,zinc_full,pattern,cluster,cifar10,mnist}/svd.py) and the excluded features
     (scheme_base.py:95-98,135-139)."""
     name, lvl = scheme.split(".")
-    dataset = {"zinc": "zinc", "pattern": "sbm_pattern", "cifar10": "cifar10", "mnist": "mnist"}[name]
+    dataset = {"zinc": "zinc", "pattern": "sbm_pattern", "cifar10": "cifar10", "mnist": "mnist", "cluster": "sbm_cluster",
+               "zinc_full": "zinc_full"}[name]
     level = {"svd": "svd", "eig": "eigen", "mat": "matrix"}[lvl]
     args = dict(dataset_path=dataset_path, max_length=None, max_shuffle_len=max_shuffle_len, splits=splits)
     if level == "svd":

@@ -8,7 +8,8 @@ Pair-sized work runs in the HIP kernels through the C-ABI: the edge-channel inpu
 (egt_edge_embed_fwd/bwd: hop stacking + adj_emb + fm_emb), every attention block (egt_block_*) and
 every channel FFN (egt_ffn_*), the node mask producer (egt_node_mask_from_features).  Node-sized
 [B,N,Dh] pieces (embedding lookup, final LayerNorm, masked mean pooling, the MLP head, the loss) are
-torch ops.  Parameters carry the reference's Keras variable names (keras_named_parameters) so a
+torch ops -- except the training step of the node-classification models, whose readout + loss is one fused op
+(classification_loss -> egt_amd.node_head).  Parameters carry the reference's Keras variable names (keras_named_parameters) so a
 weight file of the reference loads unchanged.
 
 Reference (relative to /root/reference/): lib/models/zinc/dc.py:17-120,
@@ -347,6 +348,49 @@ class PatternDCTransformer(ZincDCTransformer):
         y = self.target(x)                                                                # logits [B,N,C]
         return self._aux((y, mask) if return_mask else y, e, graph_matrix, return_aux)
 
+    def head_params(self):
+        """(gamma, beta, mlp_out kernels / biases ..., target kernel, target bias): the readout's parameters in the order
+        egt_amd.node_head takes them (gamma / beta None without node_norm_final)"""
+        n = self.node_norm_final
+        mid = [t for m in self.mlp_out for t in (m.kernel, m.bias)]
+        return (None if n is None else n.gamma, None if n is None else n.beta, *mid, self.target.kernel, self.target.bias)
+
+    def node_head_fused(self, h) -> bool:
+        """whether the readout + loss of a training step run in the fused kernels: the tensors are on the GPU, the library
+        covers the geometry (egt_node_head_supported) and EGT_NO_NODE_HEAD is not set"""
+        from .node_head import node_head_disabled, node_head_supported
+        if not h.is_cuda or h.dtype != torch.float32 or len(self.mlp_out) != 2 or node_head_disabled():
+            return False
+        return node_head_supported(h.shape[0], h.shape[1], h.shape[2], self.mlp_out[0].kernel.shape[1],
+                                   self.mlp_out[1].kernel.shape[1], self.target.kernel.shape[1], self.cfg["activation"],
+                                   self.node_norm_final is not None)
+
+    def classification_loss(self, node_features, graph_matrix, target, class_weights, attn_mask=None, singular_vectors=None,
+                            eigen_vectors=None, pe_signs=None, return_aux=False):
+        """The training step's end of the model: embeddings, positional encodings and layers as in `forward`, then the
+        readout, the class-weighted sparse cross-entropy and the metric sums as ONE op (egt_amd.node_head: the fused kernels
+        where they cover the geometry, the composed head otherwise) -- no logits tensor.  Returns (loss, stats, aux):
+        stats = [sum mask w[y] CE, sum mask [argmax == y], sum mask], loss = stats[0] / (B N) (Keras SUM_OVER_BATCH_SIZE
+        counts the padded slots: weighted_sparse_xent_loss), aux as `forward(return_aux=True)` returns it."""
+        from .node_head import node_head_composed, node_head_loss
+        fmat = torch.full(graph_matrix.shape, -1, dtype=torch.int32, device=graph_matrix.device)
+        h, e, mask = self.embeddings(node_features, fmat, graph_matrix)
+        h = self.positional(h, singular_vectors, eigen_vectors, pe_signs)
+        h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask), skip_last_edge_ffn=self.dist_head is None)
+        head = node_head_loss if self.node_head_fused(h) else node_head_composed
+        stats = head(h, target, mask, class_weights, self.head_params(), self.cfg["activation"])
+        loss = stats[0] / (h.shape[0] * h.shape[1])
+        aux = self.distance_aux(e, graph_matrix) if (return_aux and self.dist_head is not None) else {}
+        return loss, stats, aux
+
+
+class ClusterDCTransformer(PatternDCTransformer):
+    """lib.models.sbm_cluster.dc.DCSVDTransformer for the cluster.svd / cluster.eig schemes: the PATTERN model with seven
+    node-feature values (0 = unlabelled, 1..6 = the labelled seed node of a community) and six target classes."""
+
+    def __init__(self, num_node_features=7, num_target_labels=6, **kw):
+        super().__init__(num_node_features=num_node_features, num_target_labels=num_target_labels, **kw)
+
 
 class Cifar10DCTransformer(ZincDCTransformer):
     """lib.models.cifar10.dc.DCSVDTransformer for scheme cifar10.svd (use_svd false; the MNIST model has the same
@@ -382,6 +426,14 @@ class Cifar10DCTransformer(ZincDCTransformer):
                        float_bias=self.edge_emb.bias, mask_value=self.mask_value,
                        edge_dtype=self._edge_key())                                     # :71-73 + graph_model_base.py:97-127
         return h, e, mask
+
+
+class MnistDCTransformer(Cifar10DCTransformer):
+    """lib.models.mnist.dc.DCSVDTransformer for scheme mnist.svd: the CIFAR10 model with three node features (grey level +
+    x, y of a superpixel)."""
+
+    def __init__(self, num_node_features=3, **kw):
+        super().__init__(num_node_features=num_node_features, **kw)
 
 
 def sparse_xent_loss(logits, y_true):

@@ -18,7 +18,7 @@ Reference (relative to /root/reference/):
 
 Data: ``load_data`` opens ``config.dataset_path`` through egt_amd.data (a PackedStore ``.npz``, or the
 reference's ``.h5`` where h5py exists) or takes any iterable of batches in the reference's input format
-(``SyntheticZinc`` / ``SyntheticPattern`` / ``SyntheticCifar10`` generate such batches; the datasets themselves are
+(``SyntheticZinc`` / ``SyntheticPattern`` / ``SyntheticCifar10`` / ``SyntheticCluster`` / ``SyntheticMnist`` generate such batches; the datasets themselves are
 not in this image).  Weight files are ``.npz`` keyed by the reference's Keras variable names instead of ``.h5``.
 """
 from __future__ import annotations
@@ -64,6 +64,9 @@ def read_config_from_file(config_file):          # training_base.py:15-17
 def save_config_to_file(config, config_file):    # :19-21
     with open(config_file, "w") as fp:
         return json.dump(config, fp, indent="\t")
+
+
+CLUSTER_CLASS_SIZES = (19695, 19222, 19559, 19417, 19801, 20139)     # schemes/cluster/svd.py:18, eig.py:17
 
 
 def default_config(scheme: str = "zinc.svd") -> Config:
@@ -122,12 +125,22 @@ def default_config(scheme: str = "zinc.svd") -> Config:
         c.update(dataset_name="sbm_pattern", class_sizes=[979220, 209900], rlr_monitor="val_xent", save_best_monitor="val_xent")
     elif scheme == "pattern.eig":   # SBMPDCEig (schemes/pattern/eig.py:16-22): the monitors stay at the base default (val_loss)
         c.update(dataset_name="sbm_pattern", class_sizes=[979220, 209900])
+    elif scheme == "cluster.svd":   # SBMCDCSVD (schemes/cluster/svd.py:14-22)
+        c.update(dataset_name="sbm_cluster", class_sizes=list(CLUSTER_CLASS_SIZES), rlr_monitor="val_xent", save_best_monitor="val_xent")
+    elif scheme == "cluster.eig":   # SBMCDCEig (schemes/cluster/eig.py:13-19): the monitors stay at the base default
+        c.update(dataset_name="sbm_cluster", class_sizes=list(CLUSTER_CLASS_SIZES))
+    elif scheme == "mnist.svd":     # MNISTDCSVD (schemes/mnist/svd.py:14-20): no num_virtual_nodes key (the model has no VNModel)
+        c.update(dataset_name="mnist", save_best_monitor="val_xent")
+    elif scheme in ("zinc_full.svd", "zinc_full.eig"):   # ZincFullDCSVD / ZincFullDCEig (schemes/zinc_full/{svd,eig}.py:14-24)
+        c.update(dataset_name="zinc_full", dataset_path="datasets/ZINC_full/ZINC_full.h5", num_virtual_nodes=0,
+                 rlr_monitor="val_mae", save_best_monitor="val_mae")
     else:                         # ZincDCSVD (schemes/zinc/svd.py:13-21), ZincDCEig (schemes/zinc/eig.py:14-22)
         c.update(dataset_name="zinc", num_virtual_nodes=0, rlr_monitor="val_mae", save_best_monitor="val_mae")
     return c
 
 
-SCHEMES = ("zinc.svd", "zinc.eig", "pattern.svd", "pattern.eig", "cifar10.svd")
+SCHEMES = ("zinc.svd", "zinc.eig", "pattern.svd", "pattern.eig", "cifar10.svd", "cluster.svd", "cluster.eig", "mnist.svd",
+           "zinc_full.svd", "zinc_full.eig")
 
 
 def make_config(user: Optional[dict], scheme: Optional[str] = None) -> Config:
@@ -149,6 +162,8 @@ def model_config(c: Config) -> dict:
     mc = _model_config_common(c)
     if "num_virtual_nodes" in c:           # the ZINC scheme adds these two (zinc/svd.py:30-34)
         mc.update(readout_edges=False, num_virtual_nodes=c.num_virtual_nodes)
+    elif c.dataset_name == "mnist":        # the MNIST scheme adds the first only (mnist/svd.py:29-32)
+        mc.update(readout_edges=False)
     return mc
 
 
@@ -811,35 +826,28 @@ class PatternSVDScheme(ZincSVDScheme):
         return ["xent", "acc"] + self._distance_metrics()
 
     def batch_loss(self, batch):
+        """the model's classification_loss: layers, then readout + class-weighted loss + metric sums as one op (the fused node
+        head where the library covers the geometry, egt_amd.node_head); stats = [sum w xent, hits, real nodes]"""
         from .model import class_weights_from_sizes
         dev = self.device
         mv = (lambda t: t.to(dev)) if dev is not None else (lambda t: t)
         nf, adj, tgt = mv(batch["node_features"]), mv(batch["graph_matrix"]), mv(batch["target"])
-        out = self.model(nf, adj, return_mask=True, **self._pe(batch), **self._aux_kwargs())
-        if self._distance_on():
-            out, aux = out
-        logits, mask = out
-        if getattr(self, "_class_w", None) is None or self._class_w.device != logits.device:
-            self._class_w = class_weights_from_sizes(self.config.class_sizes, device=logits.device)   # once: a host -> device copy cannot be captured
-        w = self._class_w
-        loss = self.loss_fn(logits, tgt, mask, w)
+        if getattr(self, "_class_w", None) is None or self._class_w.device != adj.device:
+            self._class_w = class_weights_from_sizes(self.config.class_sizes, device=adj.device)   # once: a host -> device copy cannot be captured
+        loss, stats, aux = self.model.classification_loss(nf, adj, tgt, self._class_w, **self._pe(batch), **self._aux_kwargs())
         dm = None
         if self._distance_on():
             loss, dm = self._add_distance(loss, aux)
-        m = mask.to(logits.dtype)
-        hit = ((logits.argmax(-1) == tgt).to(logits.dtype) * m).sum().detach()
+        st = stats.detach()
         # Keras feeds the mask as sample_weight: the metrics are means over the REAL nodes (losses.py:108-118)
-        logp = torch.log_softmax(logits.detach(), -1).gather(-1, tgt.clamp(min=0).long()[..., None])[..., 0]
-        xs = (-(logp) * w[tgt.clamp(min=0).long()] * m).sum()
         # `loss` of a batch is a mean over its padded (graph, node) slots (Keras SUM_OVER_BATCH_SIZE); the EPOCH figure Keras reports is
         # its compiled-loss Mean metric, which LossesContainer updates with sample_weight = the batch dimension (number of graphs):
         # N is padded per batch, so a slot-weighted epoch mean would differ from the reference's `loss` / `val_loss`
-        graphs = torch.full((), float(m.shape[0]), device=m.device, dtype=m.dtype)   # (a fill kernel: capturable, unlike a host -> device copy)
-        ms = dict(xent=(xs, m.sum()), acc=(hit, m.sum()), loss=(loss.detach() * graphs, graphs))
+        graphs = torch.full((), float(nf.shape[0]), device=st.device, dtype=st.dtype)   # (a fill kernel: capturable, unlike a host -> device copy)
+        ms = dict(xent=(st[0], st[2]), acc=(st[1], st[2]), loss=(loss.detach() * graphs, graphs))
         if dm is not None:
             ms["distance_loss"] = dm
         return loss, ms
-
 
     @torch.no_grad()
     def do_evaluations_on_split(self, split):        # SBMPATTERNEval (schemes/pattern/_eval.py:9-111)
@@ -1010,8 +1018,144 @@ class SyntheticCifar10:
                        target=cls.to(self.device))
 
 
+class ClusterSVDScheme(PatternSVDScheme):
+    """lib.training.schemes.cluster.svd.SCHEME (SBMCDCSVD): six-class node classification on SBM_CLUSTER with the
+    class-weighted sparse cross-entropy, metrics xent + acc, monitors val_xent; report of schemes/cluster/_eval.py."""
+    SCHEME = "cluster.svd"
+
+    def get_model(self):
+        if self.model_factory is not None:
+            return self.model_factory(self.model_kwargs())
+        from .model import ClusterDCTransformer
+        return ClusterDCTransformer(**self.model_kwargs())
+
+    @torch.no_grad()
+    def do_evaluations_on_split(self, split):        # SBMCLUSTEREval (schemes/cluster/_eval.py:10-95)
+        from sklearn.metrics import recall_score, accuracy_score, confusion_matrix
+        self.model.eval()
+        dev = self.device
+        mv = (lambda t: t.to(dev)) if dev is not None else (lambda t: t)
+        targs, preds = [], []
+        for b in getattr(self, split):
+            nf = mv(b["node_features"])
+            logits = self.model(nf, mv(b["graph_matrix"]), **self._pe(b))
+            keep = (nf >= 0).reshape(-1).cpu().numpy()                                   # collate_fn: node_features >= 0
+            targs.append(b["target"].reshape(-1).cpu().numpy()[keep])
+            preds.append(logits.argmax(-1).reshape(-1).cpu().numpy()[keep])              # (arg-max of the softmax = of the logits)
+        targs = np.concatenate(targs) if targs else np.zeros(0, dtype=np.int64)   # (a rank without a share of a tiny split)
+        preds = np.concatenate(preds) if preds else np.zeros(0, dtype=np.int64)
+        if self.config.distributed and _dist_on():   # the split is sharded: gather every rank's nodes
+            box = [None] * torch.distributed.get_world_size()
+            torch.distributed.all_gather_object(box, (targs, preds))
+            targs, preds = np.concatenate([x[0] for x in box]), np.concatenate([x[1] for x in box])
+        preds = preds.astype(targs.dtype)
+        classes = (np.eye(targs.max() + 1)[targs]).sum(0)
+
+        def accuracy_sbm(t, c):                      # :11-26 (mean per-class recall over the classes of the confusion matrix)
+            cm = confusion_matrix(t, c).astype(np.float32)
+            per = [cm[r, r] / float((t == r).sum()) if (t == r).sum() else 0.0 for r in range(cm.shape[0])]
+            return float(np.sum(per)) / cm.shape[0]
+
+        micro_rec = recall_score(targs, preds, average="micro")
+        macro_rec = recall_score(targs, preds, average="macro")
+        acc = accuracy_score(targs, preds)
+        wacc = accuracy_sbm(targs, preds)
+        self._report(split, [f"Accuracy = {acc:0.5%}", f"Micro Recall = {micro_rec:0.5%}", f"Macro Recall = {macro_rec:0.5%}",
+                             f"Weighted Accuracy = {wacc:0.5%}"])
+        self.print(f"Binned classes:{classes}")      # (the reference prints this line and does not write it to the file)
+
+
+class ClusterEigScheme(ClusterSVDScheme):
+    """lib.training.schemes.cluster.eig.SCHEME (SBMCDCEig): CLUSTER with eigenvector encodings; metric acc
+    (schemes/cluster/eig.py:43-45), monitors at the base default."""
+    SCHEME = "cluster.eig"
+
+    def get_metrics(self):
+        return ["acc"] + self._distance_metrics()
+
+    LOSS_METRIC = None       # its only metric is the accuracy
+
+    def batch_loss(self, batch):
+        loss, ms = super().batch_loss(batch)
+        return loss, {k: v for k, v in ms.items() if k != "xent"}
+
+
+class SyntheticCluster:
+    """Batches in the CLUSTER input format (lib/data/datasets/sbm_cluster.py): node_features [B,N] int in 0..6 (padding -1),
+    graph_matrix [B,N,N] 0/1, target [B,N] int class per node (0 on padded slots).  Six planted communities, denser inside
+    than between; ONE labelled seed node per community carries the feature 1..6 (its class + 1), every other node 0."""
+
+    def __init__(self, n_graphs=512, batch_size=128, nodes=(40, 190), seed=0, pad_multiple=1, device="cpu"):
+        g = torch.Generator().manual_seed(seed)
+        self.n = torch.randint(nodes[0], nodes[1] + 1, (n_graphs,), generator=g)
+        self.seed, self.batch_size, self.pad_multiple, self.device = seed, batch_size, pad_multiple, device
+
+    def __len__(self):
+        return (len(self.n) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        for b in range(len(self)):
+            ns = self.n[b * self.batch_size:(b + 1) * self.batch_size]
+            g = torch.Generator().manual_seed(self.seed * 100003 + b)
+            B, N = len(ns), int(ns.max())
+            N = (N + self.pad_multiple - 1) // self.pad_multiple * self.pad_multiple
+            real = torch.arange(N)[None, :] < ns[:, None]
+            cls = torch.randint(0, 6, (B, N), generator=g) * real
+            pr = torch.where(cls[:, :, None] == cls[:, None, :], torch.tensor(0.55), torch.tensor(0.06))
+            adj = (torch.rand(B, N, N, generator=g) < pr).float()
+            adj = ((adj + adj.transpose(1, 2)) > 0).float() * (real[:, :, None] & real[:, None, :]).float() * (1 - torch.eye(N))[None]
+            # the seed of community k: the real node of class k with the highest random score (none when the class is empty)
+            score = torch.rand(B, N, generator=g) * real + 1e-3 * real
+            nf = torch.zeros(B, N, dtype=torch.long)
+            for k in range(6):
+                sk = score * (cls == k) * real
+                idx = sk.argmax(1)
+                has = sk.max(1).values > 0
+                nf[torch.arange(B)[has], idx[has]] = k + 1
+            nf[~real] = -1
+            yield dict(node_features=nf.int().to(self.device), graph_matrix=adj.to(self.device), target=cls.to(self.device))
+
+
+class MnistSVDScheme(Cifar10SVDScheme):
+    """lib.training.schemes.mnist.svd.SCHEME (MNISTDCSVD): the CIFAR10 protocol around the MNIST model (three node
+    features, no num_virtual_nodes key); reports accuracy + crossentropy (schemes/mnist/svd.py:45-53)."""
+    SCHEME = "mnist.svd"
+
+    def get_model(self):
+        if self.model_factory is not None:
+            return self.model_factory(self.model_kwargs())
+        from .model import MnistDCTransformer
+        return MnistDCTransformer(**self.model_kwargs())
+
+
+class SyntheticMnist(SyntheticCifar10):
+    """Batches in the MNIST superpixel-graph input format (lib/data/datasets/mnist.py): SyntheticCifar10 with node_features
+    [B,N,3] (grey level + x,y) and 40..75 nodes."""
+
+    def __init__(self, n_graphs=512, batch_size=128, nodes=(40, 75), seed=0, pad_multiple=1, device="cpu"):
+        super().__init__(n_graphs, batch_size, nodes, seed, pad_multiple, device)
+
+    def __iter__(self):
+        for b in super().__iter__():
+            yield dict(b, node_features=b["node_features"][..., [0, 3, 4]].contiguous())   # the class-dependent channel + x,y
+
+
+class ZincFullSVDScheme(ZincSVDScheme):
+    """lib.training.schemes.zinc_full.svd.SCHEME (ZincFullDCSVD): the ZINC model and report on the ZINC-full set."""
+    SCHEME = "zinc_full.svd"
+
+
+class ZincFullEigScheme(ZincSVDScheme):
+    """lib.training.schemes.zinc_full.eig.SCHEME (ZincFullDCEig)."""
+    SCHEME = "zinc_full.eig"
+
+
 def import_scheme(name: str):
     """lib/training/importer.py:3-11."""
+    new = {"cluster.svd": ClusterSVDScheme, "cluster.eig": ClusterEigScheme, "mnist.svd": MnistSVDScheme,
+           "zinc_full.svd": ZincFullSVDScheme, "zinc_full.eig": ZincFullEigScheme}
+    if name in new:
+        return new[name]
     if name == "cifar10.svd":
         return Cifar10SVDScheme
     if name == "zinc.svd":
@@ -1048,7 +1192,8 @@ def main(argv=None):
     c = scheme.config
     bs = c.batch_size
     name = config["scheme"].split(".")[0]
-    data = {"pattern": SyntheticPattern, "cifar10": SyntheticCifar10}.get(name, SyntheticZinc)
+    data = {"pattern": SyntheticPattern, "cifar10": SyntheticCifar10, "cluster": SyntheticCluster,
+            "mnist": SyntheticMnist}.get(name, SyntheticZinc)
 
     def mk(n, seed):
         d = data(n, bs, seed=seed)

@@ -501,6 +501,46 @@ int egt_edge_head_bwd(const egt_head_desc* desc, const egt_head_params* params, 
                       const float* d_per_graph /* [B] */, void* d_e, const egt_head_params* grads, void* workspace,
                       void* stream);
 
+/* ---- node-classification head (the PATTERN / CLUSTER readout and its class-weighted loss) ----
+ *   z     = Dense_t(act(Dense_1(act(Dense_0(node_norm_final(h))))))   W -> M0 -> M1 -> C     lib/models/sbm_pattern/dc.py:51-58
+ *   stats = { sum_rows mask w[y] CE(z, y),  sum_rows mask [argmax_c z == y],  sum_rows mask }  lib/base/genutil/losses.py:41-118
+ * over the R = B*N rows of h [B,N,W] fp32; target [B,N] int32, mask [B,N] uint8 (the node mask), class_weights [C] fp32.
+ * The target of a masked row is never read as a class (any value there has no effect); on an arg-max tie the lowest class
+ * wins.  No logits tensor is written.  The backward recomputes the forward from h; d_loss is a DEVICE pointer to the upstream
+ * gradient of stats[0] (no host read: the step stays capturable); d_h gets exact zeros on masked rows.
+ * Covered: W in {16,32,48,64}, (M0, M1) in {(24,12), (32,16)}, 2 <= C <= 16, EGT_ACT_ELU / EGT_ACT_RELU, B*N < 2^31.
+ * Kernels in Keras layout [in, out].  No atomics: two calls on the same inputs give the same bits.  `workspace`
+ * (egt_node_head_workspace_bytes) is scratch: nothing is carried from the forward to the backward. */
+#define EGT_NH_LAYERNORM 0x1 /* node_norm_final (eps = ln_eps) before the head; off: gamma / beta may be NULL */
+typedef struct egt_node_head_desc {
+  int32_t B, N, W, M0, M1, C;
+  int32_t activation; /* EGT_ACT_ELU or EGT_ACT_RELU (config.activation) */
+  int32_t flags;      /* EGT_NH_LAYERNORM */
+  float ln_eps;
+  int32_t reserved;   /* 0 */
+} egt_node_head_desc;
+
+typedef struct egt_node_head_params {
+  void* node_norm_final_gamma; /* [W] */
+  void* node_norm_final_beta;  /* [W] */
+  void* mlp_out_0_kernel;      /* [W, M0] */
+  void* mlp_out_0_bias;        /* [M0] */
+  void* mlp_out_1_kernel;      /* [M0, M1] */
+  void* mlp_out_1_bias;        /* [M1] */
+  void* target_kernel;         /* [M1, C] */
+  void* target_bias;           /* [C] */
+} egt_node_head_params;
+
+int egt_node_head_supported(const egt_node_head_desc* desc);
+size_t egt_node_head_workspace_bytes(const egt_node_head_desc* desc);
+int egt_node_head_fwd(const egt_node_head_desc* desc, const egt_node_head_params* params, const float* h,
+                      const int32_t* target, const uint8_t* mask, const float* class_weights, float* stats /* [3] */,
+                      void* workspace, void* stream);
+int egt_node_head_bwd(const egt_node_head_desc* desc, const egt_node_head_params* params, const float* h,
+                      const int32_t* target, const uint8_t* mask, const float* class_weights,
+                      const float* d_loss /* device, [1] */, float* d_h, const egt_node_head_params* grads, void* workspace,
+                      void* stream);
+
 /* ---- batch data parallelism: the gradient all-reduce on RCCL -------------------
  * Replaces what tf.distribute.MirroredStrategy does for the reference
  * (lib/training/training_base.py:230-247): one synchronous all-reduce of every
