@@ -159,6 +159,10 @@ _PROTOS = {
     "egt_edge_embed_workspace_bytes": (C.c_size_t, [C.POINTER(EmbedDesc)]),
     "egt_edge_embed_fwd": (C.c_int, [C.POINTER(EmbedDesc)] + [_VP] * 9),
     "egt_edge_embed_bwd": (C.c_int, [C.POINTER(EmbedDesc)] + [_VP] * 8),
+    "egt_edge_embed_vn_supported": (C.c_int, [C.POINTER(EmbedDesc), C.c_int32]),
+    "egt_edge_embed_vn_workspace_bytes": (C.c_size_t, [C.POINTER(EmbedDesc), C.c_int32]),
+    "egt_edge_embed_vn_fwd": (C.c_int, [C.POINTER(EmbedDesc), C.c_int32] + [_VP] * 10),
+    "egt_edge_embed_vn_bwd": (C.c_int, [C.POINTER(EmbedDesc), C.c_int32] + [_VP] * 9),
     "egt_distance_target": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP]),
     "egt_edge_head_supported": (C.c_int, [C.POINTER(HeadDesc)]),
     "egt_edge_head_workspace_bytes": (C.c_size_t, [C.POINTER(HeadDesc)]),

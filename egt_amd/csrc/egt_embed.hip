@@ -200,10 +200,62 @@ __global__ void __launch_bounds__(256) k_edge_embed_fwd(const int32_t* __restric
   embed_store4(e + pair * De + 4 * c4, acc);
 }
 
+// the same embedding with the border of nv virtual nodes (lib/base/graph_layers/virtual_nodes.py:86-99) in ONE write of the
+// [B,N',N',De] tensor, N' = nv + N:   interior (nv + l, nv + m) = e0[l,m];   virtual row (i, nv + m) = vn[i] (padded columns
+// too: the reference tiles over the whole axis);   virtual column (nv + l, j) = vn[j];   box (i, j) = 0.5 (vn[i] + vn[j]).
+// thread = (pair', 4 channels), pair' = (row, column) of the bordered matrix of graph blockIdx.x / bpg (32-bit index math:
+// N' N' De / 4 < 2^31).  Interior threads run k_edge_embed_fwd's table + FMA chain in its order (bit-identical values); border
+// threads read the virtual table staged beside W and the table.  The hop planes keep the interior pitch N.
+template <int KMAX, typename T>
+__global__ void __launch_bounds__(256) k_edge_embed_vn_fwd(const int32_t* __restrict__ fmat, const float* __restrict__ hops,
+                                                           const float* __restrict__ table, const float* __restrict__ W,
+                                                           const float* __restrict__ bias, const float* __restrict__ vn,
+                                                           T* __restrict__ e, long pairs, int N, int nv, int De, int K, int V,
+                                                           unsigned bpg) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* Ws = sm;                 // [K][De]
+  float* Ts = Ws + K * De;        // [V][De] (+ bias folded in)
+  float* Vs = Ts + V * De;        // [nv][De]
+  for (int i = threadIdx.x; i < K * De; i += 256) Ws[i] = W[i];
+  for (int i = threadIdx.x; i < V * De; i += 256) Ts[i] = table[i] + bias[i % De];
+  for (int i = threadIdx.x; i < nv * De; i += 256) Vs[i] = vn[i];
+  __syncthreads();
+  const unsigned C4 = De / 4, NV = nv + N;
+  const unsigned b = blockIdx.x / bpg;
+  const unsigned t = (blockIdx.x % bpg) * 256u + threadIdx.x;
+  const unsigned pv = t / C4, c4 = t % C4;
+  if (pv >= NV * NV) return;
+  const unsigned r = pv / NV, c = pv % NV;
+  float4 acc;
+  if (r >= (unsigned)nv && c >= (unsigned)nv) {
+    const long pair = ((long)b * N + (r - nv)) * N + (c - nv);
+    int f = fmat[pair] + 1;
+    f = min(max(f, 0), V - 1);
+    acc = *reinterpret_cast<const float4*>(Ts + f * De + 4 * c4);
+    const float* hp = hops + pair;
+#pragma unroll 4
+    for (int k = 0; k < K; ++k) {
+      const float hv = hp[(size_t)k * pairs];
+      const float4 w = *reinterpret_cast<const float4*>(Ws + k * De + 4 * c4);
+      acc.x = fmaf(hv, w.x, acc.x); acc.y = fmaf(hv, w.y, acc.y);
+      acc.z = fmaf(hv, w.z, acc.z); acc.w = fmaf(hv, w.w, acc.w);
+    }
+  } else {
+    const float4 vr = *reinterpret_cast<const float4*>(Vs + min(r, (unsigned)nv - 1) * De + 4 * c4);
+    const float4 vc = *reinterpret_cast<const float4*>(Vs + min(c, (unsigned)nv - 1) * De + 4 * c4);
+    if (r < (unsigned)nv && c < (unsigned)nv)
+      acc = make_float4(0.5f * (vr.x + vc.x), 0.5f * (vr.y + vc.y), 0.5f * (vr.z + vc.z), 0.5f * (vr.w + vc.w));
+    else
+      acc = r < (unsigned)nv ? vr : vc;
+  }
+  embed_store4(e + ((size_t)b * NV * NV + pv) * De + 4 * c4, acc);
+}
+
 // backward: dW[k,c] = sum_pairs hops[pair,k] de[pair,c];  dtable[v,c] = sum_{fmat+1 == v} de[pair,c];  dbias = sum de
 // block = PL pair lanes x C4P channel quads (C4P = De/4 rounded up to a power of two, PL = 256 / C4P: narrow edge
 // channels get more pair lanes instead of idle threads); each thread owns 4 channels and walks its pairs; the
 // (K + V) x 4 accumulators per thread are reduced over the pair lanes in LDS; one partial per workgroup
+// (k_edge_embed_vn_bwd below is this kernel with another row walk over de: a fix here belongs there too)
 #define EMB_PPB 2048   // pairs per workgroup
 template <int K_, int V_, typename T>   // T: storage of de (float or bfloat16 bits); the sums stay fp32
 __global__ void __launch_bounds__(256) k_edge_embed_bwd(const int32_t* __restrict__ fmat, const float* __restrict__ hops,
@@ -251,6 +303,107 @@ __global__ void __launch_bounds__(256) k_edge_embed_bwd(const int32_t* __restric
     float s = 0.f;
     for (int j = 0; j < PL; ++j) s += sm[(size_t)j * R + i];   // fixed order: bit-reproducible
     out[i] = s;
+  }
+}
+
+// the same contraction over the INTERIOR of the bordered gradient de [B,N',N',De] (N' = nv + N): pair (b, l, m) sits at row
+// q = (b N' + nv + l) N' + nv + m of de; q follows the pair walk (one division per thread, before the loop).  A kernel of its
+// own, not a switch in k_edge_embed_bwd: that kernel's instances stay instruction for instruction what they were.
+// (Its twin: everything but the walk of q is k_edge_embed_bwd's text, and a fix to either belongs in both.)
+template <int K_, int V_, typename T>
+__global__ void __launch_bounds__(256) k_edge_embed_vn_bwd(const int32_t* __restrict__ fmat, const float* __restrict__ hops,
+                                                           const T* __restrict__ de, float* __restrict__ part, long pairs,
+                                                           int De, int C4P, int N, int nv) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];   // [PL pair lanes][(K+V)][De]
+  const int C4 = De / 4;
+  const int PL = 256 / C4P;
+  const int c4 = threadIdx.x % C4P, pl = threadIdx.x / C4P;
+  float4 aw[K_], at[V_];
+#pragma unroll
+  for (int k = 0; k < K_; ++k) aw[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int v = 0; v < V_; ++v) at[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+  const long p0 = (long)blockIdx.x * EMB_PPB;
+  const long p1 = min(pairs, p0 + EMB_PPB);
+  if (c4 < C4) {
+    long q = 0;
+    int l = 0, m = 0;
+    if (p0 + pl < p1) {
+      const long row = (p0 + pl) / N, NV = nv + N;
+      m = (int)((p0 + pl) % N); l = (int)(row % N);
+      q = ((row / N) * NV + nv + l) * NV + nv + m;
+    }
+    for (long pair = p0 + pl; pair < p1; pair += PL) {
+      const float4 d = embed_load4(de + q * De + 4 * c4);
+      m += PL; q += PL;
+      while (m >= N) {   // next interior row: past the nv virtual columns; next graph: past its nv virtual rows too
+        m -= N; q += nv;
+        if (++l == N) { l = 0; q += (long)nv * (nv + N); }
+      }
+      const float* hp = hops + pair;
+      int f = fmat[pair] + 1;
+      f = min(max(f, 0), V_ - 1);
+#pragma unroll
+      for (int k = 0; k < K_; ++k) {
+        const float hv = hp[(size_t)k * pairs];
+        aw[k].x = fmaf(hv, d.x, aw[k].x); aw[k].y = fmaf(hv, d.y, aw[k].y);
+        aw[k].z = fmaf(hv, d.z, aw[k].z); aw[k].w = fmaf(hv, d.w, aw[k].w);
+      }
+#pragma unroll
+      for (int v = 0; v < V_; ++v) {   // branch-free one-hot accumulate (static register indexing)
+        const float s = (f == v) ? 1.0f : 0.0f;
+        at[v].x = fmaf(s, d.x, at[v].x); at[v].y = fmaf(s, d.y, at[v].y);
+        at[v].z = fmaf(s, d.z, at[v].z); at[v].w = fmaf(s, d.w, at[v].w);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K_; ++k) *reinterpret_cast<float4*>(sm + ((size_t)pl * (K_ + V_) + k) * De + 4 * c4) = aw[k];
+#pragma unroll
+    for (int v = 0; v < V_; ++v) *reinterpret_cast<float4*>(sm + ((size_t)pl * (K_ + V_) + K_ + v) * De + 4 * c4) = at[v];
+  }
+  __syncthreads();
+  const int R = (K_ + V_) * De;
+  float* out = part + (size_t)blockIdx.x * R;
+  for (int i = threadIdx.x; i < R; i += 256) {
+    float s = 0.f;
+    for (int j = 0; j < PL; ++j) s += sm[(size_t)j * R + i];   // fixed order: bit-reproducible
+    out[i] = s;
+  }
+}
+
+// gradient of the virtual table: the border of de (O(nv N) rows per graph), one workgroup per (graph b, virtual node j):
+//   part[b][j][c] = sum_{m<N} de[b,j,nv+m,c] + sum_{l<N} de[b,nv+l,j,c] + 0.5 sum_{i<nv} (de[b,j,i,c] + de[b,i,j,c])
+// items 0 .. N'-1 walk row j (its first nv elements are the box: weight 0.5), N' .. N'+N-1 column j below the box,
+// N'+N .. N'+N+nv-1 column j of the box (the transpose term).  Every border element is read by one workgroup, the off-diagonal
+// box elements (nv (nv - 1) per graph) by two.  block = PL item lanes x C4P channel quads, reduced over the lanes in a fixed
+// order; k_edge_embed_bwd_reduce then sums the B partials (K = nv, V = 0).
+template <typename T>
+__global__ void __launch_bounds__(256) k_edge_embed_vn_border_bwd(const T* __restrict__ de, float* __restrict__ part, int N, int nv,
+                                                                  int De, int C4P) {
+  __shared__ __attribute__((aligned(16))) float sm[1024];   // [PL][De], PL De <= 256 * 4
+  const int C4 = De / 4, PL = 256 / C4P, NV = nv + N;
+  const int c4 = threadIdx.x % C4P, pl = threadIdx.x / C4P;
+  const int b = blockIdx.x / nv, j = blockIdx.x % nv;
+  const T* g = de + (size_t)b * NV * NV * De;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (c4 < C4) {
+    for (int it = pl; it < NV + N + nv; it += PL) {
+      size_t row;   // (row, column) of the border element, as one index
+      float w = 1.0f;
+      if (it < NV) { row = (size_t)j * NV + it; w = it < nv ? 0.5f : 1.0f; }
+      else if (it < NV + N) row = (size_t)(nv + it - NV) * NV + j;
+      else { row = (size_t)(it - NV - N) * NV + j; w = 0.5f; }
+      const float4 d = embed_load4(g + row * De + 4 * c4);
+      acc.x = fmaf(w, d.x, acc.x); acc.y = fmaf(w, d.y, acc.y);
+      acc.z = fmaf(w, d.z, acc.z); acc.w = fmaf(w, d.w, acc.w);
+    }
+    *reinterpret_cast<float4*>(sm + pl * De + 4 * c4) = acc;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < De; i += 256) {
+    float s = 0.f;
+    for (int p = 0; p < PL; ++p) s += sm[p * De + i];   // fixed order: bit-reproducible
+    part[(size_t)blockIdx.x * De + i] = s;
   }
 }
 
@@ -312,17 +465,11 @@ extern "C" size_t egt_edge_embed_workspace_bytes(const egt_embed_desc* d) {
   return (size_t)embed_nparts(d) * (d->upto_hop + d->num_float_features + d->num_edge_features + 1) * d->De * sizeof(float);
 }
 
-extern "C" int egt_edge_embed_fwd(const egt_embed_desc* d, const int32_t* feature_matrix, const void* graph_matrix,
-                                  const void* float_features, const void* fm_table, const void* adj_kernel,
-                                  const void* adj_bias, void* hops, void* e_out, void* stream) {
-  int rc = embed_check(d);
-  if (rc) return rc;
-  if (!feature_matrix || !graph_matrix || !fm_table || !adj_kernel || !adj_bias || !hops || !e_out)
-    EGT_FAIL(EGT_E_NULL, "feature_matrix/graph_matrix/fm_table/adj_kernel/adj_bias/hops/e_out is NULL");
-  hipStream_t st = (hipStream_t)stream;
+// the hop planes and the real-valued feature planes behind them: hops [upto_hop + num_float_features, B, N, N]
+static void embed_planes(const egt_embed_desc* d, const void* graph_matrix, const void* float_features, void* hops,
+                         hipStream_t st) {
   const long pairs = (long)d->B * d->N * d->N;
-  if (d->num_float_features > 0 && !float_features) EGT_FAIL(EGT_E_NULL, "num_float_features set but float_features is NULL");
-  const int KH = d->upto_hop, K = KH + d->num_float_features, V = d->num_edge_features + 1, T2 = (d->N + 31) / 32;
+  const int KH = d->upto_hop, K = KH + d->num_float_features, T2 = (d->N + 31) / 32;
   // one launch for all planes when the adjacency and one column block fit in LDS (N <= ~180), else a launch per hop
   int CT = 0;
   {
@@ -351,6 +498,20 @@ extern "C" int egt_edge_embed_fwd(const egt_embed_desc* d, const int32_t* featur
   if (d->num_float_features > 0)
     EGT_LAUNCH("k_feature_planes", k_feature_planes, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st,
                (const float*)float_features, (float*)hops + (size_t)KH * pairs, pairs, d->num_float_features, d->mask_value);
+}
+
+extern "C" int egt_edge_embed_fwd(const egt_embed_desc* d, const int32_t* feature_matrix, const void* graph_matrix,
+                                  const void* float_features, const void* fm_table, const void* adj_kernel,
+                                  const void* adj_bias, void* hops, void* e_out, void* stream) {
+  int rc = embed_check(d);
+  if (rc) return rc;
+  if (!feature_matrix || !graph_matrix || !fm_table || !adj_kernel || !adj_bias || !hops || !e_out)
+    EGT_FAIL(EGT_E_NULL, "feature_matrix/graph_matrix/fm_table/adj_kernel/adj_bias/hops/e_out is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  const long pairs = (long)d->B * d->N * d->N;
+  if (d->num_float_features > 0 && !float_features) EGT_FAIL(EGT_E_NULL, "num_float_features set but float_features is NULL");
+  const int K = d->upto_hop + d->num_float_features, V = d->num_edge_features + 1;
+  embed_planes(d, graph_matrix, float_features, hops, st);
   const long threads = pairs * (d->De / 4);
   const size_t lds = (size_t)(K + V) * d->De * sizeof(float);
   if (d->dtype == EGT_BF16)
@@ -367,7 +528,7 @@ extern "C" int egt_edge_embed_fwd(const egt_embed_desc* d, const int32_t* featur
 
 template <int K_, typename T>
 static void launch_embed_bwd(const egt_embed_desc* d, const int32_t* fmat, const float* hops, const T* de, float* part,
-                             hipStream_t st) {
+                             hipStream_t st, int nv = 0) {   // nv > 0: de is the bordered [B,nv+N,nv+N,De] gradient
   const long pairs = (long)d->B * d->N * d->N;
   const int nparts = embed_nparts(d);
   int c4p = 1;
@@ -376,8 +537,14 @@ static void launch_embed_bwd(const egt_embed_desc* d, const int32_t* fmat, const
 #define EB(V_)                                                                                                      \
   do {                                                                                                              \
     const size_t lds = (size_t)(256 / c4p) * (K_ + V_) * d->De * sizeof(float);                                     \
-    EGT_MAX_LDS_ONCE((k_edge_embed_bwd<K_, V_, T>)); \
-    EGT_LAUNCH("k_edge_embed_bwd", (k_edge_embed_bwd<K_, V_, T>), dim3(nparts), dim3(256), lds, st, fmat, hops, de, part, pairs, d->De, c4p); \
+    if (nv > 0) {                                                                                                   \
+      EGT_MAX_LDS_ONCE((k_edge_embed_vn_bwd<K_, V_, T>));                                                           \
+      EGT_LAUNCH("k_edge_embed_vn_bwd", (k_edge_embed_vn_bwd<K_, V_, T>), dim3(nparts), dim3(256), lds, st, fmat, hops, de, part, \
+                 pairs, d->De, c4p, d->N, nv);                                                                      \
+    } else {                                                                                                        \
+      EGT_MAX_LDS_ONCE((k_edge_embed_bwd<K_, V_, T>));                                                              \
+      EGT_LAUNCH("k_edge_embed_bwd", (k_edge_embed_bwd<K_, V_, T>), dim3(nparts), dim3(256), lds, st, fmat, hops, de, part, pairs, d->De, c4p); \
+    }                                                                                                               \
   } while (0)
   switch (d->num_edge_features + 1) {
     case 1: EB(1); break; case 2: EB(2); break; case 3: EB(3); break; case 4: EB(4); break;
@@ -386,14 +553,10 @@ static void launch_embed_bwd(const egt_embed_desc* d, const int32_t* fmat, const
 #undef EB
 }
 
-extern "C" int egt_edge_embed_bwd(const egt_embed_desc* d, const int32_t* feature_matrix, const void* hops,
-                                  const void* d_e, void* d_fm_table, void* d_adj_kernel, void* d_adj_bias,
-                                  void* workspace, void* stream) {
-  int rc = embed_check(d);
-  if (rc) return rc;
-  if (!feature_matrix || !hops || !d_e || !d_fm_table || !d_adj_kernel || !d_adj_bias || !workspace)
-    EGT_FAIL(EGT_E_NULL, "feature_matrix/hops/d_e/d_fm_table/d_adj_kernel/d_adj_bias/workspace is NULL");
-  hipStream_t st = (hipStream_t)stream;
+// the three gradients of the plain embedding from d_e [B,N,N,De] (nv = 0) or from the interior of the bordered
+// [B,nv+N,nv+N,De] gradient
+static void embed_bwd_interior(const egt_embed_desc* d, int nv, const int32_t* feature_matrix, const void* hops, const void* d_e,
+                               void* d_fm_table, void* d_adj_kernel, void* d_adj_bias, void* workspace, hipStream_t st) {
   const float* h = (const float*)hops;
   float* part = (float*)workspace;
   const int KT = d->upto_hop + d->num_float_features;   // hop planes + real-valued feature planes
@@ -401,8 +564,8 @@ extern "C" int egt_edge_embed_bwd(const egt_embed_desc* d, const int32_t* featur
   switch (KT) {
 #define C(K_)                                                                                   \
   case K_:                                                                                      \
-    if (bf) launch_embed_bwd<K_, uint16_t>(d, feature_matrix, h, (const uint16_t*)d_e, part, st); \
-    else launch_embed_bwd<K_, float>(d, feature_matrix, h, (const float*)d_e, part, st);         \
+    if (bf) launch_embed_bwd<K_, uint16_t>(d, feature_matrix, h, (const uint16_t*)d_e, part, st, nv); \
+    else launch_embed_bwd<K_, float>(d, feature_matrix, h, (const float*)d_e, part, st, nv);         \
     break;
     C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16) C(17) C(18) C(19) C(20)
 #undef C
@@ -413,6 +576,88 @@ extern "C" int egt_edge_embed_bwd(const egt_embed_desc* d, const int32_t* featur
              (float*)d_adj_bias);
   EGT_LAUNCH("k_edge_embed_bwd_reduce", k_edge_embed_bias_grad, dim3(1), dim3(64), 0, st, (const float*)d_fm_table,
              d->num_edge_features + 1, d->De, (float*)d_adj_bias);
+}
+
+extern "C" int egt_edge_embed_bwd(const egt_embed_desc* d, const int32_t* feature_matrix, const void* hops,
+                                  const void* d_e, void* d_fm_table, void* d_adj_kernel, void* d_adj_bias,
+                                  void* workspace, void* stream) {
+  int rc = embed_check(d);
+  if (rc) return rc;
+  if (!feature_matrix || !hops || !d_e || !d_fm_table || !d_adj_kernel || !d_adj_bias || !workspace)
+    EGT_FAIL(EGT_E_NULL, "feature_matrix/hops/d_e/d_fm_table/d_adj_kernel/d_adj_bias/workspace is NULL");
+  embed_bwd_interior(d, 0, feature_matrix, hops, d_e, d_fm_table, d_adj_kernel, d_adj_bias, workspace, (hipStream_t)stream);
   EGT_HIP_LAUNCH_CHECK("egt_edge_embed_bwd");
+  return EGT_OK;
+}
+
+// ---- the embedding bordered with nv virtual nodes (VNModel, lib/models/graph_model_base.py:212-246) ----
+#define EMB_MAX_VN 16
+extern "C" int egt_edge_embed_vn_supported(const egt_embed_desc* d, int32_t nv) {
+  if (nv < 1 || nv > EMB_MAX_VN || !egt_edge_embed_supported(d)) return 0;
+  const long NV = (long)nv + d->N;
+  return NV * NV * (d->De / 4) < (1l << 31) && ((NV * NV * (d->De / 4) + 255) / 256) * d->B < (1l << 31) &&
+         (long)d->B * nv < (1l << 31);
+}
+extern "C" size_t egt_edge_embed_vn_workspace_bytes(const egt_embed_desc* d, int32_t nv) {
+  if (!egt_edge_embed_vn_supported(d, nv)) return 0;
+  return egt_edge_embed_workspace_bytes(d) + (size_t)d->B * nv * d->De * sizeof(float);
+}
+static int embed_vn_check(const egt_embed_desc* d, int32_t nv) {
+  int rc = embed_check(d);
+  if (rc) return rc;
+  if (nv < 1 || nv > EMB_MAX_VN) EGT_FAIL(EGT_E_SHAPE, "num_virtual_nodes must be in 1..%d (got %d)", EMB_MAX_VN, nv);
+  if (!egt_edge_embed_vn_supported(d, nv)) EGT_FAIL(EGT_E_SHAPE, "bordered edge embedding: (nv + N)^2 De / 4 must stay below 2^31 per graph");
+  return EGT_OK;
+}
+
+extern "C" int egt_edge_embed_vn_fwd(const egt_embed_desc* d, int32_t nv, const int32_t* feature_matrix, const void* graph_matrix,
+                                     const void* float_features, const void* fm_table, const void* adj_kernel,
+                                     const void* adj_bias, const void* vn_table, void* hops, void* e_out, void* stream) {
+  int rc = embed_vn_check(d, nv);
+  if (rc) return rc;
+  if (!feature_matrix || !graph_matrix || !fm_table || !adj_kernel || !adj_bias || !vn_table || !hops || !e_out)
+    EGT_FAIL(EGT_E_NULL, "feature_matrix/graph_matrix/fm_table/adj_kernel/adj_bias/vn_table/hops/e_out is NULL");
+  if (d->num_float_features > 0 && !float_features) EGT_FAIL(EGT_E_NULL, "num_float_features set but float_features is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  const long pairs = (long)d->B * d->N * d->N, NV = (long)nv + d->N;
+  const int K = d->upto_hop + d->num_float_features, V = d->num_edge_features + 1;
+  embed_planes(d, graph_matrix, float_features, hops, st);
+  const unsigned bpg = (unsigned)((NV * NV * (d->De / 4) + 255) / 256);   // workgroups per graph
+  const size_t lds = (size_t)(K + V + nv) * d->De * sizeof(float);
+  if (d->dtype == EGT_BF16)
+    EGT_LAUNCH("k_edge_embed_vn_fwd", (k_edge_embed_vn_fwd<16, uint16_t>), dim3(bpg * (unsigned)d->B), dim3(256), lds, st,
+               feature_matrix, (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias,
+               (const float*)vn_table, (uint16_t*)e_out, pairs, d->N, nv, d->De, K, V, bpg);
+  else
+    EGT_LAUNCH("k_edge_embed_vn_fwd", (k_edge_embed_vn_fwd<16, float>), dim3(bpg * (unsigned)d->B), dim3(256), lds, st,
+               feature_matrix, (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias,
+               (const float*)vn_table, (float*)e_out, pairs, d->N, nv, d->De, K, V, bpg);
+  EGT_HIP_LAUNCH_CHECK("egt_edge_embed_vn_fwd");
+  return EGT_OK;
+}
+
+extern "C" int egt_edge_embed_vn_bwd(const egt_embed_desc* d, int32_t nv, const int32_t* feature_matrix, const void* hops,
+                                     const void* d_e, void* d_fm_table, void* d_adj_kernel, void* d_adj_bias, void* d_vn_table,
+                                     void* workspace, void* stream) {
+  int rc = embed_vn_check(d, nv);
+  if (rc) return rc;
+  if (!feature_matrix || !hops || !d_e || !d_fm_table || !d_adj_kernel || !d_adj_bias || !d_vn_table || !workspace)
+    EGT_FAIL(EGT_E_NULL, "feature_matrix/hops/d_e/d_fm_table/d_adj_kernel/d_adj_bias/d_vn_table/workspace is NULL");
+  hipStream_t st = (hipStream_t)stream;
+  embed_bwd_interior(d, nv, feature_matrix, hops, d_e, d_fm_table, d_adj_kernel, d_adj_bias, workspace, st);
+  // the border: one partial per (graph, virtual node) behind the interior partials, summed over the graphs in a fixed order
+  float* vpart = (float*)((char*)workspace + egt_edge_embed_workspace_bytes(d));
+  int c4p = 1;
+  while (c4p < d->De / 4) c4p *= 2;
+  if (d->dtype == EGT_BF16)
+    EGT_LAUNCH("k_edge_embed_vn_border_bwd", k_edge_embed_vn_border_bwd<uint16_t>, dim3((unsigned)(d->B * nv)), dim3(256), 0, st,
+               (const uint16_t*)d_e, vpart, d->N, nv, d->De, c4p);
+  else
+    EGT_LAUNCH("k_edge_embed_vn_border_bwd", k_edge_embed_vn_border_bwd<float>, dim3((unsigned)(d->B * nv)), dim3(256), 0, st,
+               (const float*)d_e, vpart, d->N, nv, d->De, c4p);
+  const int R = nv * d->De;
+  EGT_LAUNCH("k_edge_embed_bwd_reduce", k_edge_embed_bwd_reduce, dim3((R + 63) / 64), dim3(256), 0, st, (const float*)vpart, d->B,
+             nv, 0, d->De, (float*)d_vn_table, (float*)nullptr, (float*)nullptr);   // V = 0: no table / bias part
+  EGT_HIP_LAUNCH_CHECK("egt_edge_embed_vn_bwd");
   return EGT_OK;
 }

@@ -9,7 +9,8 @@ Pair-sized work runs in the HIP kernels through the C-ABI: the edge-channel inpu
 every channel FFN (egt_ffn_*), the node mask producer (egt_node_mask_from_features).  Node-sized
 [B,N,Dh] pieces (embedding lookup, final LayerNorm, masked mean pooling, the MLP head, the loss) are
 torch ops -- except the training step of the node-classification models, whose readout + loss is one fused op
-(classification_loss -> egt_amd.node_head).  Parameters carry the reference's Keras variable names (keras_named_parameters) so a
+(classification_loss -> egt_amd.node_head).  num_virtual_nodes > 0 (ZINC / CIFAR10): the embedding kernel writes e with its border of
+virtual edge embeddings (egt_edge_embed_vn_fwd/bwd), the virtual node rows join h as a torch cat, the readout takes them.  Parameters carry the reference's Keras variable names (keras_named_parameters) so a
 weight file of the reference loads unchanged.
 
 Reference (relative to /root/reference/): lib/models/zinc/dc.py:17-120,
@@ -49,9 +50,10 @@ def _embed_desc(B, N, De, upto_hop, clip_hops, num_edge_features, num_float_feat
 
 class _EdgeEmbed(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, fmat, adj, table, kernel, bias, clip_hops, ffeat=None, mask_value=-1.0, e_dtype=torch.float32):
+    def forward(ctx, fmat, adj, table, kernel, bias, clip_hops, ffeat=None, mask_value=-1.0, e_dtype=torch.float32, vn=None):
         """kernel: [upto_hop + F, De] (adj_emb rows, then the rows of the real-valued features' Dense); ffeat [B,N,N,F];
-        e_dtype: storage of e (fp32 or bf16; the hop planes and every parameter gradient stay fp32)"""
+        e_dtype: storage of e (fp32 or bf16; the hop planes and every parameter gradient stay fp32); vn [nv,De]: the virtual
+        edge table -- e comes out bordered, [B,nv+N,nv+N,De] (egt_edge_embed_vn_*)"""
         _need_gpu(fmat, adj, table)
         lib = L.load()
         fmat = fmat.to(torch.int32).contiguous()
@@ -66,10 +68,20 @@ class _EdgeEmbed(torch.autograd.Function):
             raise ValueError(f"edge embedding kernel does not cover upto_hop={K}, edge_width={De}, "
                              f"num_edge_features={table.shape[0] - 1}")
         hops = torch.empty(K + F_, B, N, N, dtype=torch.float32, device=adj.device)   # plane-major (unit-stride planes)
-        e = torch.empty(B, N, N, De, dtype=e_dtype, device=adj.device)
-        L.check(lib.egt_edge_embed_fwd(C.byref(desc), L.ptr(fmat), L.ptr(adj), L.ptr(ffeat), L.ptr(table), L.ptr(kernel),
-                                       L.ptr(bias), L.ptr(hops), L.ptr(e), L.current_stream()))
-        ctx.desc = desc
+        nv = 0 if vn is None else int(vn.shape[0])
+        if vn is None:
+            e = torch.empty(B, N, N, De, dtype=e_dtype, device=adj.device)
+            L.check(lib.egt_edge_embed_fwd(C.byref(desc), L.ptr(fmat), L.ptr(adj), L.ptr(ffeat), L.ptr(table), L.ptr(kernel),
+                                           L.ptr(bias), L.ptr(hops), L.ptr(e), L.current_stream()))
+        else:
+            vn = _f32c(vn)
+            if vn.dim() != 2 or vn.shape[1] != De or not lib.egt_edge_embed_vn_supported(C.byref(desc), nv):
+                raise ValueError(f"bordered edge embedding kernel does not cover a virtual edge table {tuple(vn.shape)} "
+                                 f"(1..16 rows of edge_width={De})")
+            e = torch.empty(B, nv + N, nv + N, De, dtype=e_dtype, device=adj.device)
+            L.check(lib.egt_edge_embed_vn_fwd(C.byref(desc), nv, L.ptr(fmat), L.ptr(adj), L.ptr(ffeat), L.ptr(table),
+                                              L.ptr(kernel), L.ptr(bias), L.ptr(vn), L.ptr(hops), L.ptr(e), L.current_stream()))
+        ctx.desc, ctx.nv = desc, nv
         ctx.save_for_backward(fmat, hops, table, kernel, bias)
         ctx.mark_non_differentiable(hops)
         return e, hops
@@ -81,32 +93,43 @@ class _EdgeEmbed(torch.autograd.Function):
         desc = ctx.desc
         de = de.to(torch.bfloat16 if desc.dtype == L.EGT_BF16 else torch.float32).contiguous()
         dt, dk, db = torch.empty_like(table), torch.empty_like(kernel), torch.empty_like(bias)
+        if ctx.nv:
+            dvn = torch.empty(ctx.nv, desc.De, dtype=torch.float32, device=de.device)
+            ws = torch.empty(lib.egt_edge_embed_vn_workspace_bytes(C.byref(desc), ctx.nv), dtype=torch.uint8, device=de.device)
+            L.check(lib.egt_edge_embed_vn_bwd(C.byref(desc), ctx.nv, L.ptr(fmat), L.ptr(hops), L.ptr(de), L.ptr(dt), L.ptr(dk),
+                                              L.ptr(db), L.ptr(dvn), L.ptr(ws), L.current_stream()))
+            return None, None, dt, dk, db, None, None, None, None, dvn
         ws = torch.empty(lib.egt_edge_embed_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=de.device)
         L.check(lib.egt_edge_embed_bwd(C.byref(desc), L.ptr(fmat), L.ptr(hops), L.ptr(de), L.ptr(dt), L.ptr(dk),
                                        L.ptr(db), L.ptr(ws), L.current_stream()))
-        return None, None, dt, dk, db, None, None, None, None
+        return None, None, dt, dk, db, None, None, None, None, None
 
 
 def edge_embed(feature_matrix, graph_matrix, fm_table, adj_kernel, adj_bias, clip_hops=True, return_hops=False,
-               float_features=None, float_kernel=None, float_bias=None, mask_value=-1.0, edge_dtype="f32"):
+               float_features=None, float_kernel=None, float_bias=None, mask_value=-1.0, edge_dtype="f32",
+               virtual_edge_table=None):
     """e0 = fm_table[feature_matrix + 1] + stack_hops(graph_matrix) @ adj_kernel + adj_bias
           [+ Dense(Masking(float_features))]  ->  [B,N,N,De].
     float_features [B,N,N,F] (F <= 4) with its Dense kernel [F,De] / bias: the real-valued edge features of the
     CIFAR10 / MNIST models (lib/models/cifar10/dc.py:70-73); they ride as F more planes behind the hop planes.
     edge_dtype "bf16": e is stored in bfloat16 (the fp32 sum rounded once, to nearest even); its gradient flows back
-    in bf16 and the parameter gradients stay fp32."""
+    in bf16 and the parameter gradients stay fp32.
+    virtual_edge_table [nv,De] (1 <= nv <= 16): e0 bordered with the virtual nodes' edge embeddings as rows, columns and the
+    corner box 0.5 (vn[i] + vn[j]) (VirtualEdgeEmbedding, virtual_nodes.py:86-99) -> [B,nv+N,nv+N,De], written by one kernel;
+    the table's gradient is fp32."""
     kernel, bias = adj_kernel, adj_bias
     if float_features is not None:
         kernel = torch.cat([adj_kernel, float_kernel], dim=0)        # autograd splits the gradient rows back
         bias = adj_bias + float_bias
     e, hops = _EdgeEmbed.apply(feature_matrix, graph_matrix, fm_table, kernel, bias, clip_hops, float_features, mask_value,
-                               _edge_dtype(edge_dtype))
+                               _edge_dtype(edge_dtype), virtual_edge_table)
     return (e, hops) if return_hops else e
 
 
 class ZincDCTransformer(nn.Module):
     """DCSVDTransformer for zinc.svd without SVD features; constructor kwargs are the reference's
     model_config keys (scheme_base.py:37-60, zinc/svd.py:27-35) with its defaults."""
+    HAS_VIRTUAL_NODES = True      # the reference class derives from VNModel (zinc/dc.py, cifar10/dc.py)
 
     def __init__(self, model_width=64, edge_width=64, num_heads=8, model_height=10, gate_attention=True,
                  edge_channel_type='residual', upto_hop=16, clip_hops=True, random_mask_prob=0.1,
@@ -129,7 +152,7 @@ class ZincDCTransformer(nn.Module):
         # edge_dtype (a project key, like ffn_matmul): storage of the [B,N,N,De] edge tensor between the edge embedding, the
         # attention blocks and the edge FFNs.  "bf16" halves its HBM traffic; node tensors, parameters and math stay fp32.
         self.edge_dtype = _edge_dtype(edge_dtype)
-        unsupported = dict(readout_edges=(readout_edges, False), num_virtual_nodes=(num_virtual_nodes, 0),
+        unsupported = dict(readout_edges=(readout_edges, False),
                            node_dropout=(node_dropout, 0), edge_dropout=(edge_dropout, 0), l2_reg=(l2_reg, 0),
                            add_n_norm=(add_n_norm, False),
                            combine_layer_repr=(combine_layer_repr, False), node2edge_xtalk=(node2edge_xtalk, 0),
@@ -138,6 +161,17 @@ class ZincDCTransformer(nn.Module):
         bad = {k: v for k, (v, d) in unsupported.items() if v != d}
         if bad:    # the reference model applies every one of these: training "a different model without a warning" is not an option
             raise NotImplementedError(f"{type(self).__name__} covers the shipped configs; not built: {bad}")
+        # virtual nodes (VNModel, graph_model_base.py:212-281): nv learned node embeddings in front of h, e bordered with nv
+        # learned edge embeddings, the graph-level readout taken from the virtual nodes (zinc/dc.py:105-110)
+        nv = self.num_virtual_nodes = int(num_virtual_nodes)
+        if nv and not self.HAS_VIRTUAL_NODES:
+            raise NotImplementedError(f"{type(self).__name__}: num_virtual_nodes={nv} (the reference model has no VNModel)")
+        if nv < 0 or nv > 16:
+            raise NotImplementedError(f"{type(self).__name__} covers the shipped configs; not built: num_virtual_nodes={nv} "
+                                      f"(the bordered edge embedding takes 1..16)")
+        if nv and float(distance_loss) > 0:   # the reference crops the border before the head; no shipped config combines them
+            raise NotImplementedError(f"{type(self).__name__} covers the shipped configs; not built: distance_loss={distance_loss} "
+                                      f"together with num_virtual_nodes={nv}")
         # distance objective (the *_spe_do configs): built for the head geometries of the shipped model widths (egt_amd/head.py)
         self.distance_loss = float(distance_loss)
         if self.distance_loss > 0:
@@ -172,6 +206,9 @@ class ZincDCTransformer(nn.Module):
         self.node_emb = nn.Parameter(torch.empty(num_node_features + 1, model_width).uniform_(-0.05, 0.05))   # keras 'uniform'
         self.fm_emb = nn.Parameter(torch.empty(num_edge_features + 1, edge_width).uniform_(-0.05, 0.05))
         self.adj_emb = KerasDense(upto_hop, edge_width)
+        if nv:                                                                           # virtual_nodes.py:31-37, :76-82
+            self.virtual_node_emb = nn.Parameter(torch.empty(nv, model_width).uniform_(-0.05, 0.05))
+            self.virtual_edge_emb = nn.Parameter(torch.empty(nv, edge_width).uniform_(-0.05, 0.05))
         if use_svd and transform_svd:
             self.svd_emb = KerasDense(2 * sel_svd_features, model_width)                # graph_model_base.py:343-345
         if use_eig and transform_eig:
@@ -181,12 +218,14 @@ class ZincDCTransformer(nn.Module):
                                     edge_channel_type=edge_channel_type, clip_logits_value=clip_logits_value,
                                     random_mask_prob=random_mask_prob, scale_degree=scale_degree, scaler_type=scaler_type,
                                     attn_dropout=attn_dropout, edge_activation=edge_activation, seed=seed,
+                                    # the operator reads num_virtual_nodes in its degree scaler only (egt_layers.py:123-136)
+                                    num_virtual_nodes=nv if scale_degree else 0,
                                     ffn_matmul=ffn_matmul, ffn_multiplier=ffn_multiplier)
         if self.edge_dtype == torch.bfloat16:
             self.layers.check_edge_dtype(self.edge_dtype)   # ValueError now, not a TypeError at the first step
         self.node_norm_final = KerasLayerNorm(model_width) if do_final_norm else None
         self.mlp_out = nn.ModuleList()
-        w = model_width
+        w = max(nv, 1) * model_width                  # GetVirtualNodes -> Flatten: [B, nv Dh] (zinc/dc.py:105-108)
         for f in mlp_layers:
             self.mlp_out.append(KerasDense(w, round(f * model_width)))
             w = round(f * model_width)
@@ -234,11 +273,28 @@ class ZincDCTransformer(nn.Module):
 
     def edge_mask(self, graph_matrix, attn_mask):
         """'constrained' edge channels: M = the adjacency tiled over the heads (AdjMatModel.get_edge_mask,
-        graph_model_base.py:131-142) unless the caller passes its own."""
+        graph_model_base.py:131-142), ones to and from the virtual nodes (VNModel.get_edge_mask, :248-268), unless the
+        caller passes its own."""
         if attn_mask is None and self.cfg["edge_channel_type"] == 'constrained':
             from .masks import constrained_edge_mask
-            return constrained_edge_mask(graph_matrix, self.cfg["num_heads"])
+            return constrained_edge_mask(graph_matrix, self.cfg["num_heads"], self.num_virtual_nodes)
         return attn_mask
+
+    def with_virtual_nodes(self, h):
+        """[B,N,Dh] -> [B,nv+N,Dh]: the virtual-node embeddings in front of every graph's nodes, AFTER the positional
+        encodings were added to the real nodes (VNModel.combine_node_embeddings, graph_model_base.py:227-235)"""
+        if not self.num_virtual_nodes:
+            return h
+        return torch.cat([self.virtual_node_emb.to(h.dtype)[None].expand(h.shape[0], -1, -1), h], dim=1)
+
+    def graph_readout(self, h, mask):
+        """[B,N',Dh] -> [B, .]: the virtual nodes' rows flattened (GetVirtualNodes -> Flatten, zinc/dc.py:105-108), or the
+        masked mean over the nodes (node_glob_avg_pool, :109) in a model without virtual nodes"""
+        nv = self.num_virtual_nodes
+        if nv:
+            return h[:, :nv].reshape(h.shape[0], nv * h.shape[2])
+        m = mask.to(h.dtype)[..., None]
+        return (h * m).sum(dim=1) / m.sum(dim=1)
 
     # the Keras functional model contains only layers on a path to the outputs: with readout_edges=False the last
     # layer's dense_edge_r / edge FFN and edge_norm_final are NOT part of the reference model
@@ -264,6 +320,9 @@ class ZincDCTransformer(nn.Module):
             out["node_emb/embeddings"] = self.node_emb
         if isinstance(self.fm_emb, nn.Parameter):
             out["fm_emb/embeddings"] = self.fm_emb
+        if self.num_virtual_nodes:
+            out["virtual_node_embedding/virtual_node_embeddings"] = self.virtual_node_emb
+            out["virtual_edge_embedding/virtual_edge_embeddings"] = self.virtual_edge_emb
         out.update({k: v for k, v in self.layers.keras_named_parameters().items() if id(v) not in dead})
         if self.node_norm_final is not None:
             out["node_norm_final/gamma"] = self.node_norm_final.gamma
@@ -282,11 +341,16 @@ class ZincDCTransformer(nn.Module):
     def _edge_key(self):
         return "bf16" if self.edge_dtype == torch.bfloat16 else "f32"
 
+    def _virtual_edge_table(self):
+        return self.virtual_edge_emb if self.num_virtual_nodes else None
+
     def embeddings(self, node_features, feature_matrix, graph_matrix):
-        mask = node_mask_from_features(node_features)                                  # masking.py:42-43
+        """h [B,N,Dh] (real nodes: the virtual ones join after the positional encodings), e and mask with the virtual nodes"""
+        mask = node_mask_from_features(node_features, self.num_virtual_nodes)           # masking.py:42-43, virtual_nodes.py:47-50
         h = F.embedding((node_features + 1).long(), self.node_emb)                      # zinc/dc.py:66-69
         e = edge_embed(feature_matrix, graph_matrix, self.fm_emb, self.adj_emb.kernel, self.adj_emb.bias,
-                       clip_hops=self.cfg["clip_hops"], edge_dtype=self._edge_key())   # :70-73 + graph_model_base.py:97-127
+                       clip_hops=self.cfg["clip_hops"], edge_dtype=self._edge_key(),   # :70-73 + graph_model_base.py:97-127
+                       virtual_edge_table=self._virtual_edge_table())
         return h, e, mask
 
     def distance_aux(self, e, graph_matrix):
@@ -302,13 +366,12 @@ class ZincDCTransformer(nn.Module):
     def forward(self, node_features, feature_matrix, graph_matrix, attn_mask=None, singular_vectors=None,
                 eigen_vectors=None, pe_signs=None, return_aux=False):
         h, e, mask = self.embeddings(node_features, feature_matrix, graph_matrix)
-        h = self.positional(h, singular_vectors, eigen_vectors, pe_signs)
+        h = self.with_virtual_nodes(self.positional(h, singular_vectors, eigen_vectors, pe_signs))
         h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask),
                            skip_last_edge_ffn=self.dist_head is None)                   # :336-341
         if self.node_norm_final is not None:
             h = self.node_norm_final(h)                                                 # :343-345
-        m = mask.to(h.dtype)[..., None]
-        x = (h * m).sum(dim=1) / m.sum(dim=1)                                           # node_glob_avg_pool, zinc/dc.py:109
+        x = self.graph_readout(h, mask)                                                 # zinc/dc.py:105-110
         for lyr in self.mlp_out:                                                        # mlp_out, :354-372
             x = lyr(x)
             x = F.elu(x) if self.cfg["activation"] == 'elu' else torch.relu(x)
@@ -319,6 +382,7 @@ class PatternDCTransformer(ZincDCTransformer):
     """lib.models.sbm_pattern.dc.DCSVDTransformer for scheme pattern.svd (use_svd false): integer node features
     (3 values), the adjacency hop embedding as the ONLY edge-channel input (no feature matrix), per-node readout
     `mlp_out -> Dense(num_target_labels)` (sbm_pattern/dc.py:51-58).  edge_width 8 in the shipped configs."""
+    HAS_VIRTUAL_NODES = False
 
     def __init__(self, num_node_features=3, num_target_labels=2, edge_width=8, model_height=16, **kw):
         kw.pop("num_edge_features", None); kw.pop("num_targets", None)
@@ -418,19 +482,22 @@ class Cifar10DCTransformer(ZincDCTransformer):
 
     def embeddings(self, node_features, feature_matrix, graph_matrix):
         from .masks import node_mask_from_masking
-        mask = node_mask_from_masking(node_features, self.mask_value)                   # keras Masking, cifar10/dc.py:68
-        h = self.node_emb(node_features * mask[..., None].to(node_features.dtype))      # Masking zeroes the padded rows
+        nv = self.num_virtual_nodes
+        mask = node_mask_from_masking(node_features, self.mask_value, nv)               # keras Masking, cifar10/dc.py:68
+        h = self.node_emb(node_features * mask[:, nv:, None].to(node_features.dtype))   # Masking zeroes the padded rows
         fmat = torch.full(graph_matrix.shape, -1, dtype=torch.int32, device=graph_matrix.device)
         e = edge_embed(fmat, graph_matrix, self.fm_emb, self.adj_emb.kernel, self.adj_emb.bias,
                        clip_hops=self.cfg["clip_hops"], float_features=feature_matrix, float_kernel=self.edge_emb.kernel,
                        float_bias=self.edge_emb.bias, mask_value=self.mask_value,
-                       edge_dtype=self._edge_key())                                     # :71-73 + graph_model_base.py:97-127
+                       edge_dtype=self._edge_key(),                                     # :71-73 + graph_model_base.py:97-127
+                       virtual_edge_table=self._virtual_edge_table())
         return h, e, mask
 
 
 class MnistDCTransformer(Cifar10DCTransformer):
     """lib.models.mnist.dc.DCSVDTransformer for scheme mnist.svd: the CIFAR10 model with three node features (grey level +
     x, y of a superpixel)."""
+    HAS_VIRTUAL_NODES = False     # lib/models/mnist/dc.py has no VNModel
 
     def __init__(self, num_node_features=3, **kw):
         super().__init__(num_node_features=num_node_features, **kw)

@@ -460,6 +460,22 @@ int egt_edge_embed_fwd(const egt_embed_desc* desc, const int32_t* feature_matrix
 int egt_edge_embed_bwd(const egt_embed_desc* desc, const int32_t* feature_matrix, const void* hops,
                        const void* d_e, void* d_fm_table, void* d_adj_kernel, void* d_adj_bias,
                        void* workspace, void* stream);
+/* The same embedding bordered with nv virtual nodes (VNModel, lib/models/graph_model_base.py:212-246;
+ * VirtualEdgeEmbedding, lib/base/graph_layers/virtual_nodes.py:86-99), N' = nv + N, written once:
+ *   e_out[b, nv+l, nv+m] = e0[b,l,m]              e_out[b, i, nv+m] = vn[i]   (every m < N, padded columns too)
+ *   e_out[b, nv+l, j]    = vn[j]                  e_out[b, i, j]    = 0.5 (vn[i] + vn[j])
+ * desc->N stays the number of real (padded) nodes; `hops` is unchanged ([K+F,B,N,N]).  vn_table / d_vn_table [nv,De] fp32;
+ * e_out / d_e [B,N',N',De] in desc->dtype.  Covered: 1 <= nv <= 16 on a desc egt_edge_embed_supported accepts, with
+ * N' N' De / 4 < 2^31.  The backward reads the interior of d_e for the three gradients above and its border for d_vn_table;
+ * no atomics: two calls on the same inputs give the same bits. */
+int egt_edge_embed_vn_supported(const egt_embed_desc* desc, int32_t nv);
+size_t egt_edge_embed_vn_workspace_bytes(const egt_embed_desc* desc, int32_t nv);
+int egt_edge_embed_vn_fwd(const egt_embed_desc* desc, int32_t nv, const int32_t* feature_matrix, const void* graph_matrix,
+                          const void* float_features, const void* fm_table, const void* adj_kernel, const void* adj_bias,
+                          const void* vn_table, void* hops, void* e_out, void* stream);
+int egt_edge_embed_vn_bwd(const egt_embed_desc* desc, int32_t nv, const int32_t* feature_matrix, const void* hops,
+                          const void* d_e, void* d_fm_table, void* d_adj_kernel, void* d_adj_bias, void* d_vn_table,
+                          void* workspace, void* stream);
 
 /* ---- distance objective (the reference's *_spe_do configs: distance_loss / distance_target) ----
  *   target    = round(sum_{k=1..T} hop_k), hop_1 = A, hop_k = clip(A . hop_{k-1}, 0, 1)     lib/models/graph_model_base.py:66-76
