@@ -778,13 +778,14 @@ __global__ void __launch_bounds__(64) k_node_head_stats(const float* __restrict_
 // ---- distance target: target = round(sum_{k=1..T} hop_k), hop_1 = A, hop_k = clip(A . hop_{k-1}, 0, 1) ----
 // k_hop_chain's scheme (egt_embed.hip): a workgroup owns CT column tiles of one graph, keeps the zero-padded adjacency
 // ([R16][R16 + 4]) and its column block of the current hop ([R16][16 CT + 4]) in LDS, and walks the hops without another global
-// read; the running sum stays in the MFMA tiles' registers.  Sums of 0/1 products are exact in any order.
+// read; the running sum stays in the MFMA tiles' registers.  Sums of 0/1 products are exact in any order.  HP: the hop plane's row
+// padding (4 floats against bank conflicts; 0 where the padded plane does not fit next to the adjacency: R16 = 192).
 #define DT_NW 8
 #define DT_MAXT 8
 __global__ void __launch_bounds__(DT_NW * 64) k_dist_target(const float* __restrict__ adj, uint8_t* __restrict__ target, int N, int T,
-                                                            int NB, int CT) {
+                                                            int NB, int CT, int HP) {
   extern __shared__ __attribute__((aligned(16))) float dsm[];
-  const int RT = (N + 15) / 16, R16 = RT * 16, PA = R16 + 4, PH = 16 * CT + 4;
+  const int RT = (N + 15) / 16, R16 = RT * 16, PA = R16 + 4, PH = 16 * CT + HP;
   float* As = dsm;
   float* Hs = As + R16 * PA;
   const int b = blockIdx.x / NB, c0 = (blockIdx.x % NB) * CT * 16;
@@ -857,7 +858,7 @@ __global__ void __launch_bounds__(DT_NW * 64) k_dist_target(const float* __restr
 }
 
 // =================================== host ===================================
-#define DT_MAX_N 192   // the adjacency ([R16][R16 + 4] fp32) plus one column tile of a hop must fit the 160 KB of LDS
+#define DT_MAX_N 192   // the adjacency ([R16][R16 + 4] fp32) plus one column tile of a hop ([R16][16], unpadded at this size) fill the 160 KB of LDS
 
 extern "C" int egt_distance_target(const float* adj, int32_t B, int32_t N, int32_t T, uint8_t* target, void* stream) {
   if (B < 1 || N < 1 || (long)B * N * N > 2147483647L) EGT_FAIL(EGT_E_SHAPE, "distance target: B, N >= 1 and B*N*N inside 32 bits (got B=%d N=%d)", B, N);
@@ -867,13 +868,17 @@ extern "C" int egt_distance_target(const float* adj, int32_t B, int32_t N, int32
   const int RT = (N + 15) / 16, R16 = RT * 16;
   int ct = (int)((long)RT * B / 256);
   ct = ct < 1 ? 1 : (ct > RT ? RT : ct);
-  auto lds_of = [&](int c) { return (size_t)(R16 * (R16 + 4) + R16 * (16 * c + 4)) * sizeof(float); };
+  int hp = 4;
+  auto lds_of = [&](int c) { return (size_t)(R16 * (R16 + 4) + R16 * (16 * c + hp)) * sizeof(float); };
   while (ct > 1 && (RT * ct > DT_NW * DT_MAXT || lds_of(ct) > 160 * 1024)) --ct;
+  if (lds_of(ct) > 160 * 1024) hp = 0;   // N in 177..192: one unpadded column tile (165888 bytes with the padding, 162816 without)
+                                          // (PH = 16 then: the hop-1 load and the B-operand reads bg[k * PH] hit LDS bank conflicts; B = 64, T = 8
+                                          //  on one MI355X: 151 us at N = 176, 187 us at N = 192 -- 1.24x for 1.30x the MFMA work, so they do not show)
   if (RT * ct > DT_NW * DT_MAXT || lds_of(ct) > 160 * 1024) EGT_FAIL(EGT_E_SHAPE, "distance target: N=%d does not fit", N);
   const int NB = (RT + ct - 1) / ct;
   EGT_MAX_LDS_ONCE(k_dist_target);
   EGT_LAUNCH("k_dist_target", k_dist_target, dim3((unsigned)(B * NB)), dim3(DT_NW * 64), lds_of(ct), (hipStream_t)stream, adj, target,
-             N, T, NB, ct);
+             N, T, NB, ct, hp);
   EGT_HIP_LAUNCH_CHECK("egt_distance_target");
   return EGT_OK;
 }

@@ -23,6 +23,20 @@
  *     crosses this boundary.
  *   - kernels are stateless and re-entrant; safe from several host threads on
  *     different streams.
+ *
+ * Buffer contract (held by tests/test_memcontract_gpu.py, entry point by entry point)
+ *   - a buffer has EXACTLY the byte count its tensor shape or its *_bytes() query states: no call reads or writes a byte
+ *     before its first or past its last, whatever the launch geometry; pointers are aligned as torch allocates tensors
+ *     (512 bytes; anything less is outside this contract).
+ *   - every output, and every gradient sink behind a non-NULL pointer, is written in full by the call -- padded rows, masked
+ *     rows and unused parameter rows included -- unless the entry point's comment names the exception (the "reserved" slot of
+ *     rowstats after a forward; the "gradient outputs are scratch" pointers of EGT_BF_NO_EDGE_LN).
+ *   - a workspace is scratch: its contents on entry do not matter and the results do not depend on them.  What travels
+ *     from a forward to its backward: `saved` of block / stack, rowstats, `hops`, and a workspace handed over under
+ *     EGT_ATTN_WS_SHARED (MFMA inner op, pair operator) or EGT_FFN_WS_PREPARED.  `const` inputs are never written.
+ *   - the aliasings allowed, all of them: d_e may alias d_e_out (egt_block_bwd, egt_stack_bwd, egt_pair_bwd; in place under
+ *     EGT_BF_STATIC_EDGE), dx may alias dy (egt_ffn_bwd), d_e_base may alias d_e (egt_edge_proj_bwd_acc).  The result is
+ *     bit-identical to the call on separate buffers.  Nothing else may overlap (d_h must NOT alias d_h_out).
  */
 #ifndef EGT_AMD_H_
 #define EGT_AMD_H_
