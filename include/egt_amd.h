@@ -26,8 +26,14 @@
  *
  * Buffer contract (held by tests/test_memcontract_gpu.py, entry point by entry point)
  *   - a buffer has EXACTLY the byte count its tensor shape or its *_bytes() query states: no call reads or writes a byte
- *     before its first or past its last, whatever the launch geometry; pointers are aligned as torch allocates tensors
- *     (512 bytes; anything less is outside this contract).
+ *     before its first or past its last, whatever the launch geometry (one exception, reads only: next item).
+ *   - alignment.  Tensors, masks, targets, seeds, saved buffers and workspaces: as torch allocates tensors (512 bytes;
+ *     anything less is outside this contract).  Parameter tensors (every member of a *_params struct, and the parameter
+ *     pointers of egt_edge_* and egt_edge_embed*) and gradient sinks (the d_* / grads counterparts of those): the alignment of
+ *     their element, 4 bytes -- they may be views of one flat buffer at any float offset, and the results are bit-identical
+ *     to the call on 512-byte-aligned copies.  For an unaligned parameter a call may READ, and never write, the bytes
+ *     between the enclosing 16-byte boundary and the parameter's first byte (the node kernels load from the pointer rounded
+ *     down and commit from the true one); a gradient sink is written from its first byte to its last and nowhere else.
  *   - every output, and every gradient sink behind a non-NULL pointer, is written in full by the call -- padded rows, masked
  *     rows and unused parameter rows included -- unless the entry point's comment names the exception (the "reserved" slot of
  *     rowstats after a forward; the "gradient outputs are scratch" pointers of EGT_BF_NO_EDGE_LN).

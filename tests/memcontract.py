@@ -7,13 +7,25 @@ allocator gives every tensor) and has EXACTLY the byte count the header / the si
 graph's slice of the buffer (ceil(bytes / B) rounded up to 512) and at least 4 KiB, so a write that is off by one row, tile,
 partial slot or graph lands in memory the test owns.  Guards hold a seeded pseudo-random byte pattern.
 
-Runner: every tensor of a case lives in an arena (inputs and parameters too: the pointer alignment is the same in every run).
+A shifted arena (`shift` bytes, a multiple of the element size) starts its payload that many bytes past the 512-aligned address:
+same byte count, guards still directly adjacent on both sides (the leading one grows by `shift`).  That is how a parameter
+tensor or a gradient sink reaches the C ABI from one flat buffer: aligned to its element and to nothing more.
+
+Runner: every tensor of a case lives in an arena (inputs and parameters too).
   run Z   outputs, carried buffers and scratch prefilled with 0x00
   run P   ... with 0xFF (NaN as fp32 and bf16, 255 as uint8); carried buffers (forward -> backward) are poisoned before the
           first step only, plain scratch again before every step
   run A   one run per aliasing the header allows (Z prefill)
-and check(): guards bit-identical after every step, const inputs bit-identical to their snapshot, run P finite, Z == P and
-Z == A bit for bit."""
+  run U-* cases with buffers of a pointer class (PARAM: filled from an nn.Parameter, SINK: from its .grad) only; P prefill.
+          The i-th such buffer of the case, in table order, is shifted by 4 (1 + i mod 3) bytes where the run shifts it:
+          U-sinks  the SINK buffers (the layout FlatGradAllReduce(direct=True) produces)
+          U-all    PARAM and SINK buffers
+          U-mixed  half of each class -- its j-th buffer when j mod 4 is 0 or 3 -- so that one call sees aligned and
+                   unaligned pointers together, neighbours of both kinds (dense_qkv.kernel and dense_mha.kernel, which
+                   the node kernels test separately, land on different sides in every row of the tables)
+and check(): guards bit-identical after every step, const inputs bit-identical to their snapshot, runs P and U-* finite,
+Z == P, Z == A and Z == U-* bit for bit (alignment changes how operands reach LDS and registers, never the order of the
+arithmetic)."""
 from __future__ import annotations
 
 import zlib
@@ -39,30 +51,31 @@ class GuardError(AssertionError):
 
 
 class Arena:
-    def __init__(self, name, nbytes, device="cpu", graphs=1, seed=0):
-        self.name, self.nbytes = name, int(nbytes)
+    def __init__(self, name, nbytes, device="cpu", graphs=1, seed=0, shift=0):
+        assert 0 <= shift < ALIGN
+        self.name, self.nbytes, self.shift = name, int(nbytes), int(shift)
         g = self.g = guard_bytes(self.nbytes, graphs)
-        raw = torch.empty(2 * g + self.nbytes + ALIGN, dtype=torch.uint8, device=device)
+        raw = torch.empty(2 * g + shift + self.nbytes + ALIGN, dtype=torch.uint8, device=device)
         skip = (-raw.data_ptr()) % ALIGN            # 0 for torch's device allocations; host memory is only 64-byte aligned
-        self.buf = raw[skip:skip + 2 * g + self.nbytes]
-        self.offset = g                             # of the payload inside buf
+        self.buf = raw[skip:skip + 2 * g + shift + self.nbytes]
+        self.offset = g + shift                     # of the payload inside buf: the leading guard grows by the shift
         gen = torch.Generator().manual_seed((zlib.crc32(name.encode()) ^ seed) & 0x7FFFFFFF)
-        pat = torch.randint(0, 256, (2 * g,), generator=gen, dtype=torch.uint8).to(device)
-        self._ref = (pat[:g].clone(), pat[g:].clone())
+        pat = torch.randint(0, 256, (2 * g + shift,), generator=gen, dtype=torch.uint8).to(device)
+        self._ref = (pat[:self.offset].clone(), pat[self.offset:].clone())
         self.before.copy_(self._ref[0])
         self.after.copy_(self._ref[1])
 
     @property
     def before(self):
-        return self.buf[:self.g]
+        return self.buf[:self.offset]
 
     @property
     def after(self):
-        return self.buf[self.g + self.nbytes:]
+        return self.buf[self.offset + self.nbytes:]
 
     @property
     def payload(self):
-        return self.buf[self.g:self.g + self.nbytes]
+        return self.buf[self.offset:self.offset + self.nbytes]
 
     def view(self, dtype, shape):
         return self.payload.view(dtype).view(*shape)
@@ -75,7 +88,7 @@ class Arena:
             if not torch.equal(cur, ref):
                 idx = (cur != ref).nonzero().flatten()
                 lo, hi = int(idx[0]), int(idx[-1])
-                out.append((side, self.g - hi, self.g - lo) if side == "before" else (side, lo, hi))
+                out.append((side, self.offset - hi, self.offset - lo) if side == "before" else (side, lo, hi))
         return out
 
     def check(self, when=""):
@@ -86,6 +99,7 @@ class Arena:
 
 # ---------------------------------------------------------------------------------------------------------- cases -----
 IN, OUT, CARRIED, SCRATCH, INOUT = "in", "out", "carried", "scratch", "inout"
+PARAM, SINK = "param", "sink"           # pointer classes: held to element alignment (4 bytes), not to torch's 512
 
 
 class Buf:
@@ -96,6 +110,8 @@ class Buf:
             SCRATCH  plain workspace: prefilled before every step
             INOUT    read-modify-write argument (`init`): not const, compared between runs
     graphs  B, for the guard size
+    ptr     PARAM (the Python side fills it from an nn.Parameter), SINK (from its .grad) or None (activations, masks, targets,
+            seeds, saved buffers, workspaces: the 512-byte contract)
     exempt  (header sentence, mask_fn or None): elements excluded from "finite in P" and "Z == P" (mask_fn(view) -> bool tensor of
             the excluded elements; None = the whole buffer)
     compare CARRIED buffers only: also an output of the contract (rowstats)
@@ -103,8 +119,9 @@ class Buf:
     rmw     {step index: (header sentence, mask_fn)}: the documented read-modify-write exceptions to `const`"""
 
     def __init__(self, name, role, init=None, dtype=None, shape=None, nbytes=None, graphs=1, exempt=None, compare=None,
-                 const_after=None, rmw=None):
-        self.name, self.role, self.init, self.graphs = name, role, init, graphs
+                 const_after=None, rmw=None, ptr=None):
+        assert ptr is None or (ptr, role) in ((PARAM, IN), (SINK, OUT))
+        self.name, self.role, self.init, self.graphs, self.ptr = name, role, init, graphs, ptr
         if init is not None:
             init = init.contiguous()
             self.init, dtype, shape = init, init.dtype, tuple(init.shape)
@@ -135,12 +152,30 @@ def _bytes(t):
     return t.contiguous().view(-1).view(torch.uint8)
 
 
-def run(case, fill, device, alias=None, sync=None, check_rc=None):
+U_RUNS = ("sinks", "all", "mixed")
+
+
+def tagged(case):
+    return [b for b in case.bufs if b.ptr is not None]
+
+
+def shifts(case, which):
+    """{buffer name: bytes} of run U-`which` (see the module's docstring)"""
+    out, seen = {}, {PARAM: 0, SINK: 0}
+    for i, b in enumerate(tagged(case)):
+        j, seen[b.ptr] = seen[b.ptr], seen[b.ptr] + 1
+        if {"sinks": b.ptr == SINK, "all": True, "mixed": j % 4 in (0, 3)}[which]:
+            out[b.name] = 4 * (1 + i % 3)
+            assert out[b.name] % b.esize == 0
+    return out
+
+
+def run(case, fill, device, alias=None, sync=None, check_rc=None, shift=None):
     """Execute the case's steps once.  Returns {name: clone of the typed payload} of every compared buffer."""
-    alias = alias or {}
+    alias, shift = alias or {}, shift or {}
     arenas, views = {}, {}
     for b in case.bufs:
-        a = arenas[b.name] = Arena(f"{case.name}:{b.name}", b.nbytes, device, b.graphs)
+        a = arenas[b.name] = Arena(f"{case.name}:{b.name}", b.nbytes, device, b.graphs, shift=shift.get(b.name, 0))
         if b.init is not None:
             a.payload.copy_(_bytes(b.init).to(device))
         else:
@@ -162,7 +197,8 @@ def run(case, fill, device, alias=None, sync=None, check_rc=None):
             check_rc(rc)
         if sync is not None:
             sync()
-        when = f" by step {i} of case '{case.name}' (prefill 0x{fill:02X}{', aliased ' + str(alias) if alias else ''})"
+        when = (f" by step {i} of case '{case.name}' (prefill 0x{fill:02X}{', aliased ' + str(alias) if alias else ''}"
+                f"{', shifted ' + str(shift) if shift else ''})")
         for a in arenas.values():
             a.check(when)
         for name, s in list(snap.items()):
@@ -223,8 +259,9 @@ def assert_same_bits(case, ref, got, names=("Z", "P")):
                                  f"(first: {r.flatten()[idx[0]].item()!r} vs {g.flatten()[idx[0]].item()!r})")
 
 
-def check(case, device, sync=None, check_rc=None):
-    """Runs Z, P and every A of the case and asserts the contract; returns run Z's outputs (for the oracle / wrapper checks)."""
+def check(case, device, sync=None, check_rc=None, u_runs=U_RUNS):
+    """Runs Z, P, every A and (where the case has buffers of a pointer class) the U runs of the case and asserts the contract;
+    returns run Z's outputs (for the oracle / wrapper checks)."""
     z = run(case, ZERO, device, sync=sync, check_rc=check_rc)
     p = run(case, POISON, device, sync=sync, check_rc=check_rc)
     assert_finite(case, p)
@@ -232,6 +269,10 @@ def check(case, device, sync=None, check_rc=None):
     for al in case.aliases:
         a = run(case, ZERO, device, alias=al, sync=sync, check_rc=check_rc)
         assert_same_bits(case, z, a, names=("Z", f"A {al}"))
+    for which in (u_runs if tagged(case) else ()):
+        u = run(case, POISON, device, sync=sync, check_rc=check_rc, shift=shifts(case, which))
+        assert_same_bits(case, z, u, names=("Z", f"U-{which}"))
+        assert_finite(case, u, f"U-{which}")
     return z
 
 
@@ -360,8 +401,8 @@ def _block_bufs(row, inp, layers, saved_bytes, ws_bytes):
             if static and i in STATIC_NULL:
                 continue
             t = inp["params"][l][i]
-            bufs.append(Buf(f"p{l}.{f}", IN, t))
-            bufs.append(Buf(f"g{l}.{f}", OUT, dtype=torch.float32, shape=t.shape))
+            bufs.append(Buf(f"p{l}.{f}", IN, t, ptr=PARAM))
+            bufs.append(Buf(f"g{l}.{f}", OUT, dtype=torch.float32, shape=t.shape, ptr=SINK))
     bufs += [Buf("h_out", OUT, dtype=torch.float32, shape=inp["h"].shape, graphs=B),
              Buf("d_h", OUT, dtype=torch.float32, shape=inp["h"].shape, graphs=B),
              Buf("d_e", OUT, dtype=edt, shape=inp["e"].shape, graphs=B),
@@ -574,7 +615,7 @@ def pair_case(lib, B, N, real, shared):
     p = C.byref(desc)
     bufs = [Buf(k, IN, t, graphs=B) for k, t in inp.items()]
     for f, t in params.items():
-        bufs += [Buf("p." + f, IN, t), Buf("g." + f, OUT, dtype=torch.float32, shape=t.shape)]
+        bufs += [Buf("p." + f, IN, t, ptr=PARAM), Buf("g." + f, OUT, dtype=torch.float32, shape=t.shape, ptr=SINK)]
     bufs += [Buf("v_att", OUT, dtype=torch.float32, shape=(B, N, d * H), graphs=B),
              Buf("e_out", OUT, dtype=torch.float32, shape=inp["e"].shape, graphs=B),
              Buf("d_qkv", OUT, dtype=torch.float32, shape=inp["qkv"].shape, graphs=B),
@@ -608,6 +649,9 @@ def pair_case(lib, B, N, real, shared):
 
 
 # -------------------------------------------------------------------------------------------------- edge ops -----
+EDGE_PARAMS = ("gamma", "beta", "Wg", "bg", "We", "be", "Wr", "br")
+
+
 def _edge_inputs(De, name):
     g = _gen(name)
     r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float32)
@@ -630,15 +674,15 @@ def edge_proj_case(lib, De, ln, gates, acc):
     desc = L.EdgeDesc(rows=rows, De=De, H=8, dtype=L.EGT_F32, flags=(L.EP_LAYERNORM if ln else 0) | (L.EP_GATES if gates else 0),
                       act=L.ACT_ELU if act else L.ACT_NONE, act_alpha=0.0, ln_eps=1e-3, reserved=0)
     p = C.byref(desc)
-    bufs = [Buf(k, IN, t, graphs=shape[0]) for k, t in inp.items()]
+    bufs = [Buf(k, IN, t, graphs=shape[0], ptr=PARAM if k in EDGE_PARAMS else None) for k, t in inp.items()]
     bufs += [Buf("E_out", OUT, dtype=torch.float32, shape=(*shape, 8), graphs=2), Buf("d_e", OUT, dtype=torch.float32, shape=(*shape, De), graphs=2),
-             Buf("d_We", OUT, dtype=torch.float32, shape=(De, 8)), Buf("d_be", OUT, dtype=torch.float32, shape=(8,)),
+             Buf("d_We", OUT, dtype=torch.float32, shape=(De, 8), ptr=SINK), Buf("d_be", OUT, dtype=torch.float32, shape=(8,), ptr=SINK),
              Buf("ws", SCRATCH, nbytes=lib.egt_edge_proj_bwd_workspace_bytes(p), graphs=2)]
     if ln:
-        bufs += [Buf("d_gamma", OUT, dtype=torch.float32, shape=(De,)), Buf("d_beta", OUT, dtype=torch.float32, shape=(De,))]
+        bufs += [Buf("d_gamma", OUT, dtype=torch.float32, shape=(De,), ptr=SINK), Buf("d_beta", OUT, dtype=torch.float32, shape=(De,), ptr=SINK)]
     if gates:
-        bufs += [Buf("G_out", OUT, dtype=torch.float32, shape=(*shape, 8), graphs=2), Buf("d_Wg", OUT, dtype=torch.float32, shape=(De, 8)),
-                 Buf("d_bg", OUT, dtype=torch.float32, shape=(8,))]
+        bufs += [Buf("G_out", OUT, dtype=torch.float32, shape=(*shape, 8), graphs=2), Buf("d_Wg", OUT, dtype=torch.float32, shape=(De, 8), ptr=SINK),
+                 Buf("d_bg", OUT, dtype=torch.float32, shape=(8,), ptr=SINK)]
 
     def fwd(v):
         return lib.egt_edge_proj_fwd(p, *[_ptr(v, k) for k in ("e", "gamma", "beta", "Wg", "bg", "We", "be", "G_out", "E_out")], _stream())
@@ -678,9 +722,9 @@ def edge_update_case(lib, De):
     desc = L.EdgeDesc(rows=shape[0] * shape[1] * shape[2], De=De, H=8, dtype=L.EGT_F32, flags=0, act=L.ACT_NONE, act_alpha=0.0, ln_eps=1e-3,
                       reserved=0)
     p = C.byref(desc)
-    bufs = [Buf(k, IN, t, graphs=2) for k, t in inp.items()]
+    bufs = [Buf(k, IN, t, graphs=2, ptr=PARAM if k in EDGE_PARAMS else None) for k, t in inp.items()]
     bufs += [Buf("e_out", OUT, dtype=torch.float32, shape=(*shape, De), graphs=2), Buf("d_h_hat", OUT, dtype=torch.float32, shape=(*shape, 8), graphs=2),
-             Buf("d_Wr", OUT, dtype=torch.float32, shape=(8, De)), Buf("d_br", OUT, dtype=torch.float32, shape=(De,)),
+             Buf("d_Wr", OUT, dtype=torch.float32, shape=(8, De), ptr=SINK), Buf("d_br", OUT, dtype=torch.float32, shape=(De,), ptr=SINK),
              Buf("ws", SCRATCH, nbytes=lib.egt_edge_update_bwd_workspace_bytes(p), graphs=2)]
 
     def fwd(v):
@@ -717,7 +761,7 @@ def ffn_case(lib, W, rows, bf16, matmul, prepared):
     bufs = [Buf("x", IN, inp["x"]), Buf("dy", IN, inp["dy"]), Buf("y", OUT, dtype=sdt, shape=(rows, W)), Buf("dx", OUT, dtype=sdt, shape=(rows, W)),
             Buf("ws", CARRIED if prepared else SCRATCH, nbytes=lib.egt_ffn_workspace_bytes(p))]
     for f, t in params.items():
-        bufs += [Buf("p." + f, IN, t), Buf("g." + f, OUT, dtype=torch.float32, shape=t.shape)]
+        bufs += [Buf("p." + f, IN, t, ptr=PARAM), Buf("g." + f, OUT, dtype=torch.float32, shape=t.shape, ptr=SINK)]
 
     def fwd(v):
         return lib.egt_ffn_fwd(p, C.byref(_struct(L.FfnParams, L.FFN_PARAM_FIELDS, v, "p.")), _ptr(v, "x"), _ptr(v, "y"), _ptr(v, "ws"), _stream())
@@ -742,6 +786,7 @@ EMBED_TABLE = [(2, 19, 8, 4, 4, 0), (3, 37, 64, 16, 5, 0), (1, 21, 48, 1, 4, 0),
                (176, 37, 8, 3, 4, 0),         # two column tiles per k_hop_chain workgroup
                (1, 200, 8, 3, 4, 0)]          # k_hop_first / k_hop_step
 VN_TABLE = [(nv, De) for nv in (1, 3, 16) for De in (8, 64)]
+EMBED_PARAMS = ("fm_table", "adj_kernel", "adj_bias", "vn_table")
 
 
 def embed_case(lib, B, N, De, K, V, F, bf16, nv=0):
@@ -769,12 +814,13 @@ def embed_case(lib, B, N, De, K, V, F, bf16, nv=0):
                        num_float_features=F, mask_value=-1.0, reserved=0)
     p = C.byref(desc)
     ws = lib.egt_edge_embed_vn_workspace_bytes(p, nv) if nv else lib.egt_edge_embed_workspace_bytes(p)
-    bufs = [Buf(k, IN, t, graphs=B if t.shape[0] == B and t.dim() > 2 else 1) for k, t in inp.items()]
+    bufs = [Buf(k, IN, t, graphs=B if t.shape[0] == B and t.dim() > 2 else 1, ptr=PARAM if k in EMBED_PARAMS else None)
+            for k, t in inp.items()]
     bufs += [Buf("hops", CARRIED, dtype=torch.float32, shape=(K + F, B, N, N), graphs=K + F, const_after=0),
              Buf("e_out", OUT, dtype=sdt, shape=(B, NO, NO, De), graphs=B), Buf("ws", SCRATCH, nbytes=ws, graphs=B)]
     assert bufs[-3].nbytes == lib.egt_edge_embed_hops_bytes(p)
-    for k in ("fm_table", "adj_kernel", "adj_bias") + (("vn_table",) if nv else ()):
-        bufs.append(Buf("d_" + k, OUT, dtype=torch.float32, shape=inp[k].shape))
+    for k in EMBED_PARAMS[:4 if nv else 3]:
+        bufs.append(Buf("d_" + k, OUT, dtype=torch.float32, shape=inp[k].shape, ptr=SINK))
     fin = ("feature_matrix", "graph_matrix", "float_features", "fm_table", "adj_kernel", "adj_bias")
 
     def fwd(v):
@@ -823,7 +869,7 @@ def edge_head_case(lib, De, M0, M1, bf16):
     p = C.byref(desc)
     bufs = [Buf(k, IN, t, graphs=B) for k, t in inp.items()]
     for f, t in params.items():
-        bufs += [Buf("p." + f, IN, t), Buf("g." + f, OUT, dtype=torch.float32, shape=t.shape)]
+        bufs += [Buf("p." + f, IN, t, ptr=PARAM), Buf("g." + f, OUT, dtype=torch.float32, shape=t.shape, ptr=SINK)]
     bufs += [Buf("per_graph_loss", OUT, dtype=torch.float32, shape=(B,)), Buf("d_e", OUT, dtype=sdt, shape=(B, N, N, De), graphs=B),
              Buf("ws", SCRATCH, nbytes=lib.egt_edge_head_workspace_bytes(p), graphs=B)]
 
@@ -867,7 +913,7 @@ def node_head_case(lib, W, Cc):
     p = C.byref(desc)
     bufs = [Buf(k, IN, t) for k, t in inp.items()]
     for f, t in params.items():
-        bufs += [Buf("p." + f, IN, t), Buf("g." + f, OUT, dtype=torch.float32, shape=t.shape)]
+        bufs += [Buf("p." + f, IN, t, ptr=PARAM), Buf("g." + f, OUT, dtype=torch.float32, shape=t.shape, ptr=SINK)]
     bufs += [Buf("stats", OUT, dtype=torch.float32, shape=(3,)), Buf("d_h", OUT, dtype=torch.float32, shape=(B, N, W), graphs=B),
              Buf("ws", SCRATCH, nbytes=lib.egt_node_head_workspace_bytes(p), graphs=B)]
     args = ("h", "target", "mask", "class_weights")

@@ -218,3 +218,82 @@ def test_bound_flat_gradients_match_the_adopted_views(N, De, gpu, egt_lib):
     seeds.detach()
     st.unbind_flat_gradients()
     assert all(p.grad is None for p in st.parameters())
+
+
+# ---- whole models, every sink off 16 bytes ----------------------------------------------------------------------------
+_WHOLE = {}         # kind -> (model, step, plain gradients, route): built and run with plain autograd gradients once
+
+
+def _whole_model(kind, gpu):
+    """One forward + backward of a small two-layer model (B = 4, N <= 24, random mask off) -> (model, step, plain .grad clones)"""
+    if kind in _WHOLE:
+        return _WHOLE[kind]
+    from egt_amd import training as T
+    torch.manual_seed(21)
+    if kind == "zinc":          # the distance objective on: block / FFN / edge-embedding sinks and the eight of the fused edge head
+        from egt_amd import ZincDCTransformer, mae_loss
+        model = ZincDCTransformer(model_width=48, edge_width=48, model_height=2, upto_hop=4, random_mask_prob=0.0,
+                                  distance_loss=0.5, distance_target=3).to(gpu).train()
+        b = {k: v.to(gpu) for k, v in next(iter(T.SyntheticZinc(4, 4, nodes=(13, 23), seed=2))).items()}
+
+        def step():
+            pred, aux = model(b["node_features"], b["feature_matrix"], b["graph_matrix"], return_aux=True)
+            (mae_loss(pred, b["target"]) + 0.5 * aux["distance_loss"].mean()).backward()
+            return type(aux["distance_loss"].grad_fn).__name__
+    else:                       # PATTERN: the fused node-classification head
+        from egt_amd import PatternDCTransformer, class_weights_from_sizes
+        model = PatternDCTransformer(model_width=64, edge_width=8, model_height=2, upto_hop=4, random_mask_prob=0.0).to(gpu).train()
+        b = {k: v.to(gpu) for k, v in next(iter(T.SyntheticPattern(4, 4, nodes=(13, 23), seed=2))).items()}
+        w = class_weights_from_sizes([979220, 209900], device=gpu)
+
+        def step():
+            loss, stats, _ = model.classification_loss(b["node_features"], b["graph_matrix"], b["target"], w)
+            loss.backward()
+            return type(stats.grad_fn).__name__
+    assert b["graph_matrix"].shape[0] == 4 and b["graph_matrix"].shape[1] <= 24
+    with torch.no_grad():       # (fresh norm parameters are ones / zeros: make every gradient depend on them)
+        for p in model.parameters():
+            if p.dim() == 1:
+                p.add_(0.2 * torch.randn_like(p))
+    params = model.trainable_parameters()
+    assert all(p.grad is None and not getattr(p, "_egt_direct_grad", False) for p in params)
+    route = step()
+    assert route == {"zinc": "_FusedHeadBackward", "pattern": "_FusedNodeHeadBackward"}[kind]       # the fused heads, not composed ones
+    plain = [torch.zeros_like(p) if p.grad is None else p.grad.detach().clone() for p in params]    # (None: the step does not reach it)
+    assert all(bool(torch.isfinite(g).all()) for g in plain) and sum(bool(g.abs().max() > 0) for g in plain) >= len(plain) - 2
+    _WHOLE[kind] = (model, step, plain, route)
+    return _WHOLE[kind]
+
+
+@pytest.mark.parametrize("dummy", [1, 2, 3])
+@pytest.mark.parametrize("kind", ["zinc", "pattern"])
+def test_whole_model_gradients_land_in_sinks_off_16_bytes(kind, dummy, gpu, egt_lib):
+    """FlatGradAllReduce([dummy] + params, direct=True) with an unused parameter of 1, 2 or 3 floats in front: every sink of
+    every fused call (block / stack, FFN, edge embedding, the edge and node heads) is a view that is aligned to its element
+    only.  Each view must hold the plain .grad (value equality: accumulating into the zeroed buffer turns -0 into +0) and
+    the floats around it must stay zero."""
+    from egt_amd.dp import FlatGradAllReduce
+    model, step, plain, route = _whole_model(kind, gpu)
+    params = model.trainable_parameters()
+    pad, tail = torch.nn.Parameter(torch.zeros(dummy, device=gpu)), torch.nn.Parameter(torch.zeros(3, device=gpu))
+    fa = FlatGradAllReduce([pad] + params + [tail], direct=True)          # (the tail: three unused floats behind the last sink)
+    assert fa.flat.data_ptr() % 512 == 0 and fa.flat.numel() == dummy + sum(p.numel() for p in params) + 3
+    off, spans, residues = dummy, [], set()
+    for p in params:
+        assert p.grad.data_ptr() == fa.flat.data_ptr() + 4 * off and p.grad.is_contiguous()
+        residues.add(off % 4)
+        spans.append((off, off + p.numel()))
+        off += p.numel()
+    assert residues - {0}, "no sink is off 16 bytes"
+    assert step() == route
+    torch.cuda.synchronize()
+    for p, (lo, hi), want in zip(params, spans, plain):
+        assert p.grad.data_ptr() == fa.flat.data_ptr() + 4 * lo, "the backward replaced a bound view"
+        got = fa.flat[lo:hi].view_as(want)
+        assert torch.equal(got, want), (f"parameter {tuple(p.shape)} at float offset {lo} (residue {lo % 4}): "
+                                        f"{int((got != want).sum())}/{want.numel()} elements differ from the plain .grad")
+    # the floats before and after each view: the views are packed, so a spill lands in a neighbour (compared above), in the
+    # dummy in front of the first or in the unused tail behind the last
+    assert bool((fa.flat[:dummy] == 0).all()), "floats in front of the first sink were written (a pointer rounded down?)"
+    assert bool((fa.flat[off:] == 0).all()), "floats behind the last sink were written (a vector store across its end?)"
+    assert torch.equal(fa.flat, torch.cat([torch.zeros(dummy, device=gpu)] + [g.flatten() for g in plain] + [torch.zeros(3, device=gpu)]))

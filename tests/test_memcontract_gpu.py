@@ -1,8 +1,11 @@
 """The buffer contract of include/egt_amd.h ("Buffer contract"), entry point by entry point, through the C ABI itself (the
 Python wrappers allocate their own buffers, which cannot be guarded).  tests/memcontract.py holds the harness and the case
 table: every tensor of a call sits in a guarded arena of exactly the stated byte count, and each case runs with outputs /
-scratch prefilled with 0x00 (run Z), with 0xFF (run P: NaN as fp32 and bf16) and once per allowed aliasing (run A).  Asserted:
-guards untouched, const inputs untouched, run P finite, Z == P == A bit for bit.  So that a case cannot be bit-stable and wrong,
+scratch prefilled with 0x00 (run Z), with 0xFF (run P: NaN as fp32 and bf16) and once per allowed aliasing (run A).  Parameter
+tensors and gradient sinks are held to element alignment only: three more poisoned runs put them 4, 8 or 12 bytes past the
+512-byte boundary (U-sinks: the sinks, as FlatGradAllReduce(direct=True) lays them out; U-all: parameters too; U-mixed: half of
+each, so one call sees both kinds).  Asserted: guards untouched, const inputs untouched, runs P and U finite, Z == P == A == U
+bit for bit.  So that a case cannot be bit-stable and wrong,
 run Z is also held to the fp64 oracle (inner op, block, stack, FFN: the suite's FWD / BWD tolerances; bf16 storage: the suite's
 bf16_stack_tol) or, where tests/cases.py has no oracle, to the Python wrapper's result on the same inputs, bit for bit (the
 parity tests tie that result to the oracle).
@@ -14,7 +17,7 @@ where those pointers are NULL.
 
 The block and stack tables run again in two child processes (the plan's switches are read once per process): the full-size
 launch geometry (EGT_BWD_TL=16 EGT_FWD_ROWS=16: dkvp / epart sizes follow nwg_bwd) and EGT_NO_NARROW=1 (De = 8 on r4 / v4r;
-without the static-edge cases, which block_check refuses there)."""
+without the static-edge cases, which block_check refuses there).  Of the U runs the children make U-all."""
 import os
 import subprocess
 import sys
@@ -46,7 +49,7 @@ def _check(case, gpu):
     from egt_amd import _lib as L
     sup = case.claims.get("supported")
     assert sup is None or sup() == 1, f"{case.name}: the library does not cover the case"
-    return M.check(case, gpu, sync=torch.cuda.synchronize, check_rc=L.check)
+    return M.check(case, gpu, sync=torch.cuda.synchronize, check_rc=L.check, u_runs=("all",) if os.environ.get(CHILD) else M.U_RUNS)
 
 
 def _hold_to_oracle(case, z, layers=1):
