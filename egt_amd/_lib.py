@@ -123,6 +123,14 @@ class NodeHeadParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in NODE_HEAD_PARAM_FIELDS]
 
 
+def params_struct(cls, fields, tensors):
+    """A parameter struct of the C-ABI (`cls`, its `fields` in order) filled with the tensors' device pointers (None -> NULL)."""
+    st = cls()
+    for name, t in zip(fields, tensors):
+        setattr(st, name, None if t is None else t.data_ptr())
+    return st
+
+
 class EGTLibraryError(RuntimeError):
     pass
 

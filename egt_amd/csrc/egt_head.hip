@@ -12,6 +12,7 @@
 // the forward from e (nothing is saved).  Loss and parameter-gradient partials are per workgroup, reduced in a fixed order by
 // k_edge_head_reduce / k_edge_head_finish: no atomics, two runs are bitwise equal.
 #include "egt_common.h"
+#include <cstring>
 
 typedef float v4f_h __attribute__((ext_vector_type(4)));
 #define HMFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
@@ -151,6 +152,241 @@ __device__ __forceinline__ void eh_zero(uint2& v) { v = make_uint2(0u, 0u); }
 __device__ __forceinline__ void eh_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ void eh_st4(uint16_t* p, float4 v) { *reinterpret_cast<uint2*>(p) = f4_to_bf4(v); }
 
+// ---- the 16-row tile of both heads: set-up, forward, backward from d_logits, workgroup partials ----
+// A wave's view of the workgroup's LDS and of its rows: `width` is the real row width (De / W), DET gives the padded one.
+template <int DET>
+struct EhTile {
+  float *XE, *X1, *X2, *DL, *RS;        // the wave's activation images
+  const float *wsm, *W0, *W1, *WT;      // the weight image
+  int lane, wave, i, q;
+  int width, C4, NF4;                   // 16-byte (fp32) slots per row / per tile
+  float inv;                            // 1 / width
+};
+// the parameter-gradient accumulators of a wave
+template <int DET>
+struct EhGrad {
+  v4f_h W0[DET][2], W1[2], Wt;
+  float b0[2], b1, bt;
+};
+template <int DET>
+__device__ __forceinline__ void eh_zero(EhGrad<DET>& g) {
+#pragma unroll
+  for (int a = 0; a < DET; ++a) g.W0[a][0] = g.W0[a][1] = (v4f_h){0.f, 0.f, 0.f, 0.f};
+  g.W1[0] = g.W1[1] = g.Wt = (v4f_h){0.f, 0.f, 0.f, 0.f};
+  g.b0[0] = g.b0[1] = g.b1 = g.bt = 0.f;
+}
+
+// weight image -> wsm, the per-wave activation area zeroed (the pad columns of the row image stay 0); ends on a workgroup barrier
+template <int DET>
+__device__ __forceinline__ EhTile<DET> eh_setup(float* wsm, float* asm_, const float* __restrict__ img, int width) {
+  using Z = EhGeo<DET>;
+  EhTile<DET> L;
+  L.lane = threadIdx.x & 63, L.wave = threadIdx.x >> 6, L.i = L.lane & 15, L.q = L.lane >> 4;
+  for (int k = threadIdx.x; k < Z::IMG; k += EH_NW * 64) wsm[k] = img[k];
+  float* const my = asm_ + L.wave * Z::WAVE;
+  for (int k = L.lane; k < Z::WAVE; k += 64) my[k] = 0.f;
+  __syncthreads();
+  L.XE = my + Z::XE, L.X1 = my + Z::X1, L.X2 = my + Z::X2, L.DL = my + Z::DL, L.RS = my + Z::RS;
+  L.wsm = wsm, L.W0 = wsm + Z::W0, L.W1 = wsm + Z::W1, L.WT = wsm + Z::WT;
+  L.width = width, L.C4 = width >> 2, L.NF4 = 4 * width;
+  L.inv = 1.0f / (float)width;
+  return L;
+}
+
+// `valid` rows of `src` -> the XE image (rows >= valid: zeros), the optional LayerNorm (rstd -> RS), the three products.
+// a1 / a2: the activations x1 / x2 (also left in X1 / X2), z: the logits
+template <int DET, typename T>
+__device__ __forceinline__ void eh_tile_fwd(const EhTile<DET>& L, const T* src, int valid, int act, int ln, float eps,
+                                            v4f_h (&a1)[2], v4f_h& a2, v4f_h& z) {
+  using Z = EhGeo<DET>;
+  constexpr int PE = Z::PE;
+  const int lane = L.lane, i = L.i, q = L.q, C4 = L.C4;
+  float* const XE = L.XE;
+  for (int f = lane; f < L.NF4; f += 64) {
+    const int row = f / C4, c4 = f % C4;
+    const float4 v = row < valid ? eh_widen(eh_ld_raw(src + (size_t)f * 4)) : make_float4(0.f, 0.f, 0.f, 0.f);
+    *reinterpret_cast<float4*>(XE + row * PE + 4 * c4) = v;
+  }
+  eh_sync();
+  // ---- LayerNorm: two-pass moments; 4 lanes per row ----
+  if (ln) {
+    const int row = lane >> 2, pt = lane & 3;
+    float s = 0.f;
+    for (int c4 = pt; c4 < C4; c4 += 4) {
+      const float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
+      s += (v.x + v.y) + (v.z + v.w);
+    }
+    s += lane_xor<1>(s); s += lane_xor<2>(s);
+    const float mu = s * L.inv;
+    float vs = 0.f;
+    for (int c4 = pt; c4 < C4; c4 += 4) {
+      const float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
+      const float d0 = v.x - mu, d1 = v.y - mu, d2 = v.z - mu, d3 = v.w - mu;
+      vs = fmaf(d0, d0, vs); vs = fmaf(d1, d1, vs); vs = fmaf(d2, d2, vs); vs = fmaf(d3, d3, vs);
+    }
+    vs += lane_xor<1>(vs); vs += lane_xor<2>(vs);
+    const float rstd = rsqrtf(vs * L.inv + eps);
+    for (int c4 = pt; c4 < C4; c4 += 4) {
+      float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
+      v.x = (v.x - mu) * rstd; v.y = (v.y - mu) * rstd; v.z = (v.z - mu) * rstd; v.w = (v.w - mu) * rstd;
+      *reinterpret_cast<float4*>(XE + row * PE + 4 * c4) = v;
+    }
+    if (pt == 0) L.RS[row] = rstd;
+    eh_sync();
+  }
+  // ---- x1 = act(xhat . W0f + b0f) ----
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct) {
+    const float bb = L.wsm[Z::B0 + 16 * ct + i];
+    v4f_h acc = (v4f_h){bb, bb, bb, bb};
+    acc = eh_mm_nn<Z::DEP>(XE, PE, L.W0 + 16 * ct, EH_P0, i, q, acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      acc[r] = eh_act(acc[r], act);
+      L.X1[(4 * q + r) * EH_P0 + 16 * ct + i] = acc[r];
+    }
+    a1[ct] = acc;
+  }
+  eh_sync();
+  // ---- x2 = act(x1 . W1 + b1) ----
+  {
+    const float bb = L.wsm[Z::B1 + i];
+    v4f_h acc = (v4f_h){bb, bb, bb, bb};
+    acc = eh_mm_nn<32>(L.X1, EH_P0, L.W1, EH_P1, i, q, acc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      acc[r] = eh_act(acc[r], act);
+      L.X2[(4 * q + r) * EH_P1 + i] = acc[r];
+    }
+    a2 = acc;
+  }
+  eh_sync();
+  // ---- logits ----
+  {
+    const float bb = L.wsm[Z::BT + i];
+    z = (v4f_h){bb, bb, bb, bb};
+    z = eh_mm_nn<16>(L.X2, EH_P1, L.WT, EH_P1, i, q, z);
+  }
+}
+
+// The backward of a tile from its d_logits: the parameter gradients are added to g, the gradient of the tile's rows is left in
+// the XE image (behind a wave sync, for the kernel's store)
+template <int DET>
+__device__ __forceinline__ void eh_tile_bwd(const EhTile<DET>& L, v4f_h dl, const v4f_h (&a1)[2], v4f_h a2, int act, int ln,
+                                            EhGrad<DET>& g) {
+  using Z = EhGeo<DET>;
+  constexpr int PE = Z::PE;
+  const int i = L.i, q = L.q;
+  float *const XE = L.XE, *const X1 = L.X1, *const X2 = L.X2, *const DL = L.DL;
+  g.bt += (dl[0] + dl[1]) + (dl[2] + dl[3]);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) DL[(4 * q + r) * EH_P1 + i] = dl[r];
+  eh_sync();
+  g.Wt = eh_mm_tn(X2, EH_P1, DL, EH_P1, i, q, g.Wt);                                    // dWt += x2^T . dl
+  v4f_h d2 = eh_mm_nt<16>(DL, EH_P1, L.WT, EH_P1, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});   // dx2 = dl . Wt^T
+#pragma unroll
+  for (int r = 0; r < 4; ++r) d2[r] *= eh_dact(a2[r], act);
+  g.b1 += (d2[0] + d2[1]) + (d2[2] + d2[3]);
+  eh_sync();                                                                           // x2 has been read
+#pragma unroll
+  for (int r = 0; r < 4; ++r) X2[(4 * q + r) * EH_P1 + i] = d2[r];
+  eh_sync();
+  v4f_h d1[2];
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct) {
+    g.W1[ct] = eh_mm_tn(X1 + 16 * ct, EH_P0, X2, EH_P1, i, q, g.W1[ct]);               // dW1 += x1^T . dx2pre
+    d1[ct] = eh_mm_nt<16>(X2, EH_P1, L.W1 + 16 * ct * EH_P1, EH_P1, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});
+#pragma unroll
+    for (int r = 0; r < 4; ++r) d1[ct][r] *= eh_dact(a1[ct][r], act);
+    g.b0[ct] += (d1[ct][0] + d1[ct][1]) + (d1[ct][2] + d1[ct][3]);
+  }
+  eh_sync();                                                                           // x1 has been read
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) X1[(4 * q + r) * EH_P0 + 16 * ct + i] = d1[ct][r];
+  eh_sync();
+  v4f_h gx[DET];
+#pragma unroll
+  for (int a = 0; a < DET; ++a) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+      g.W0[a][ct] = eh_mm_tn(XE + 16 * a, PE, X1 + 16 * ct, EH_P0, i, q, g.W0[a][ct]);  // dW0f += xhat^T . dx1pre
+    gx[a] = eh_mm_nt<32>(X1, EH_P0, L.W0 + 16 * a * EH_P0, EH_P0, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});   // dxhat = dx1pre . W0f^T
+  }
+  // ---- LayerNorm backward per row: dx = rstd (g - mean(g) - xhat mean(g xhat)) ----
+  if (ln) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = 4 * q + r;
+      float xh[DET], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int a = 0; a < DET; ++a) {
+        xh[a] = XE[row * PE + 16 * a + i];
+        s1 += gx[a][r];
+        s2 = fmaf(gx[a][r], xh[a], s2);
+      }
+      s1 = row_sum16(s1) * L.inv;
+      s2 = row_sum16(s2) * L.inv;
+      const float rstd = L.RS[row];
+#pragma unroll
+      for (int a = 0; a < DET; ++a) gx[a][r] = rstd * (gx[a][r] - s1 - xh[a] * s2);
+    }
+  }
+  eh_sync();                                                                           // xhat has been read
+#pragma unroll
+  for (int a = 0; a < DET; ++a)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (16 * a + i < L.width) XE[(4 * q + r) * PE + 16 * a + i] = gx[a][r];           // (width 8: the pad columns stay 0)
+  eh_sync();
+}
+
+// the waves' parameter gradients added in index order in the (now free) activation area -> part[blockIdx.x * PG ..]
+template <int DET>
+__device__ __forceinline__ void eh_wg_partials(const EhTile<DET>& L, EhGrad<DET>& g, float* red, float* __restrict__ part) {
+  using Z = EhGeo<DET>;
+  static_assert(EH_NW * Z::WAVE >= Z::PG, "the gradient image is reduced in the activation area");
+  const int i = L.i, q = L.q;
+  g.b0[0] = eh_sum_q(g.b0[0]); g.b0[1] = eh_sum_q(g.b0[1]); g.b1 = eh_sum_q(g.b1); g.bt = eh_sum_q(g.bt);
+  __syncthreads();   // every wave is done with its activation image
+  for (int w = 0; w < EH_NW; ++w) {
+    if (L.wave == w) {
+      const bool first = w == 0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int a = 0; a < DET; ++a)
+#pragma unroll
+          for (int ct = 0; ct < 2; ++ct) {
+            float* p = red + Z::G0 + (16 * a + 4 * q + r) * 32 + 16 * ct + i;
+            *p = (first ? 0.f : *p) + g.W0[a][ct][r];
+          }
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+          float* p = red + Z::G1 + (16 * ct + 4 * q + r) * 16 + i;
+          *p = (first ? 0.f : *p) + g.W1[ct][r];
+        }
+        float* p = red + Z::GT + (4 * q + r) * 16 + i;
+        *p = (first ? 0.f : *p) + g.Wt[r];
+      }
+      if (q == 0) {
+        float* p = red + Z::GB0 + i;
+        p[0] = (first ? 0.f : p[0]) + g.b0[0];
+        p[16] = (first ? 0.f : p[16]) + g.b0[1];
+        p = red + Z::GB1 + i;
+        *p = (first ? 0.f : *p) + g.b1;
+        p = red + Z::GBT + i;
+        *p = (first ? 0.f : *p) + g.bt;
+      }
+    }
+    __syncthreads();
+  }
+  float* out = part + (size_t)blockIdx.x * Z::PG;
+  for (int k = threadIdx.x; k < Z::PG; k += EH_NW * 64) out[k] = red[k];
+}
+
+// ---- edge head: the rows are the pairs of a graph ----
 // grid = B * G workgroups; workgroup (b, g) owns the tiles [g * chunk, (g + 1) * chunk) of graph b, wave w every EH_NW-th of them.
 // BWD == false: loss_part[b * G + g] = the workgroup's share of per_graph[b].
 // BWD == true:  de = d per_graph / d e (zeros on skipped tiles), part[(b * G + g) * PG ..] = the workgroup's parameter gradients
@@ -165,39 +401,21 @@ __global__ void __launch_bounds__(EH_NW * 64) k_edge_head(const T* __restrict__ 
   __shared__ __attribute__((aligned(16))) float wsm[Z::IMG];
   __shared__ __attribute__((aligned(16))) float asm_[EH_NW * Z::WAVE];
   __shared__ float lsm[EH_NW];
-  static_assert(EH_NW * Z::WAVE >= Z::PG, "the gradient image is reduced in the activation area");
   const int b = blockIdx.x / G, g = blockIdx.x % G;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4;
   const int NN = N * N, TPG = (NN + 15) / 16;
   const int t0 = g * chunk, t1 = min(TPG, t0 + chunk);
-  for (int k = threadIdx.x; k < Z::IMG; k += EH_NW * 64) wsm[k] = img[k];
-  float* const my = asm_ + wave * Z::WAVE;
-  for (int k = lane; k < Z::WAVE; k += 64) my[k] = 0.f;   // (the pad columns of the e image stay 0)
-  __syncthreads();
-  float* const XE = my + Z::XE;
-  float* const X1 = my + Z::X1;
-  float* const X2 = my + Z::X2;
-  float* const DL = my + Z::DL;
-  float* const RS = my + Z::RS;
-  const float* const W0 = wsm + Z::W0;
-  const float* const W1 = wsm + Z::W1;
-  const float* const WT = wsm + Z::WT;
+  const EhTile<DET> L = eh_setup<DET>(wsm, asm_, img, De);
+  const int lane = L.lane, i = L.i, q = L.q, C4 = L.C4, NF4 = L.NF4;
   const float sb = BWD ? sgrad[b] : 0.f;
-  const int C4 = De >> 2, NF4 = 4 * De;   // 16-byte (fp32) slots per row / per tile
-  const float inv_de = 1.0f / (float)De;
 
   float lossacc = 0.f;
-  v4f_h gW0[DET][2], gW1[2], gWt;
-  float gb0[2] = {0.f, 0.f}, gb1 = 0.f, gbt = 0.f;
-#pragma unroll
-  for (int a = 0; a < DET; ++a) gW0[a][0] = gW0[a][1] = (v4f_h){0.f, 0.f, 0.f, 0.f};
-  gW1[0] = gW1[1] = gWt = (v4f_h){0.f, 0.f, 0.f, 0.f};
+  EhGrad<DET> gr;
+  eh_zero(gr);
 
-  for (int t = t0 + wave; t < t1; t += EH_NW) {
+  for (int t = t0 + L.wave; t < t1; t += EH_NW) {
     const int valid = min(16, NN - 16 * t);
     const size_t p0 = (size_t)b * NN + (size_t)16 * t;       // first pair of the tile
     const int my_t = lane < valid ? (int)target[p0 + lane] : 0;
-    const T* et = e + p0 * De;
     if (__ballot(my_t != 0) == 0ull) {                         // nothing to learn here: no e load, no arithmetic
       if (BWD) {
         T* dt = de + p0 * De;
@@ -206,74 +424,9 @@ __global__ void __launch_bounds__(EH_NW * 64) k_edge_head(const T* __restrict__ 
       }
       continue;
     }
-    // ---- e tile -> LDS image (rows >= valid: zeros) ----
-    for (int f = lane; f < NF4; f += 64) {
-      const int row = f / C4, c4 = f % C4;
-      const float4 v = row < valid ? eh_widen(eh_ld_raw(et + (size_t)f * 4)) : make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(XE + row * PE + 4 * c4) = v;
-    }
-    eh_sync();
-    // ---- edge_norm_final: two-pass moments; 4 lanes per row ----
-    if (ln) {
-      const int row = lane >> 2, pt = lane & 3;
-      float s = 0.f;
-      for (int c4 = pt; c4 < C4; c4 += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
-        s += (v.x + v.y) + (v.z + v.w);
-      }
-      s += lane_xor<1>(s); s += lane_xor<2>(s);
-      const float mu = s * inv_de;
-      float vs = 0.f;
-      for (int c4 = pt; c4 < C4; c4 += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
-        const float a0 = v.x - mu, a1 = v.y - mu, a2 = v.z - mu, a3 = v.w - mu;
-        vs = fmaf(a0, a0, vs); vs = fmaf(a1, a1, vs); vs = fmaf(a2, a2, vs); vs = fmaf(a3, a3, vs);
-      }
-      vs += lane_xor<1>(vs); vs += lane_xor<2>(vs);
-      const float rstd = rsqrtf(vs * inv_de + eps);
-      for (int c4 = pt; c4 < C4; c4 += 4) {
-        float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
-        v.x = (v.x - mu) * rstd; v.y = (v.y - mu) * rstd; v.z = (v.z - mu) * rstd; v.w = (v.w - mu) * rstd;
-        *reinterpret_cast<float4*>(XE + row * PE + 4 * c4) = v;
-      }
-      if (pt == 0) RS[row] = rstd;
-      eh_sync();
-    }
-    // ---- x1 = act(ehat . W0f + b0f) ----
-    v4f_h a1[2], a2;
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      const float bb = wsm[Z::B0 + 16 * ct + i];
-      v4f_h acc = (v4f_h){bb, bb, bb, bb};
-      acc = eh_mm_nn<Z::DEP>(XE, PE, W0 + 16 * ct, EH_P0, i, q, acc);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[r] = eh_act(acc[r], act);
-        X1[(4 * q + r) * EH_P0 + 16 * ct + i] = acc[r];
-      }
-      a1[ct] = acc;
-    }
-    eh_sync();
-    // ---- x2 = act(x1 . W1 + b1) ----
-    {
-      const float bb = wsm[Z::B1 + i];
-      v4f_h acc = (v4f_h){bb, bb, bb, bb};
-      acc = eh_mm_nn<32>(X1, EH_P0, W1, EH_P1, i, q, acc);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[r] = eh_act(acc[r], act);
-        X2[(4 * q + r) * EH_P1 + i] = acc[r];
-      }
-      a2 = acc;
-    }
-    eh_sync();
-    // ---- logits, max-subtracted log-sum-exp over the C real columns, gather, mask ----
-    v4f_h z;
-    {
-      const float bb = wsm[Z::BT + i];
-      z = (v4f_h){bb, bb, bb, bb};
-      z = eh_mm_nn<16>(X2, EH_P1, WT, EH_P1, i, q, z);
-    }
+    v4f_h a1[2], a2, z;
+    eh_tile_fwd<DET>(L, e + p0 * De, valid, act, ln, eps, a1, a2, z);
+    // ---- max-subtracted log-sum-exp over the C real columns, gather, mask ----
     v4f_h dl;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -290,125 +443,25 @@ __global__ void __launch_bounds__(EH_NW * 64) k_edge_head(const T* __restrict__ 
       }
     }
     if (!BWD) continue;
-
-    // ================= backward of the tile =================
-    gbt += (dl[0] + dl[1]) + (dl[2] + dl[3]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) DL[(4 * q + r) * EH_P1 + i] = dl[r];
-    eh_sync();
-    gWt = eh_mm_tn(X2, EH_P1, DL, EH_P1, i, q, gWt);                                   // dWt += x2^T . dl
-    v4f_h d2 = eh_mm_nt<16>(DL, EH_P1, WT, EH_P1, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});  // dx2 = dl . Wt^T
-#pragma unroll
-    for (int r = 0; r < 4; ++r) d2[r] *= eh_dact(a2[r], act);
-    gb1 += (d2[0] + d2[1]) + (d2[2] + d2[3]);
-    eh_sync();                                                                         // x2 has been read
-#pragma unroll
-    for (int r = 0; r < 4; ++r) X2[(4 * q + r) * EH_P1 + i] = d2[r];
-    eh_sync();
-    v4f_h d1[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      gW1[ct] = eh_mm_tn(X1 + 16 * ct, EH_P0, X2, EH_P1, i, q, gW1[ct]);               // dW1 += x1^T . dx2pre
-      d1[ct] = eh_mm_nt<16>(X2, EH_P1, W1 + 16 * ct * EH_P1, EH_P1, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-      for (int r = 0; r < 4; ++r) d1[ct][r] *= eh_dact(a1[ct][r], act);
-      gb0[ct] += (d1[ct][0] + d1[ct][1]) + (d1[ct][2] + d1[ct][3]);
-    }
-    eh_sync();                                                                         // x1 has been read
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) X1[(4 * q + r) * EH_P0 + 16 * ct + i] = d1[ct][r];
-    eh_sync();
-    v4f_h ge[DET];
-#pragma unroll
-    for (int a = 0; a < DET; ++a) {
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-        gW0[a][ct] = eh_mm_tn(XE + 16 * a, PE, X1 + 16 * ct, EH_P0, i, q, gW0[a][ct]);  // dW0f += ehat^T . dx1pre
-      ge[a] = eh_mm_nt<32>(X1, EH_P0, W0 + 16 * a * EH_P0, EH_P0, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});   // dehat = dx1pre . W0f^T
-    }
-    // ---- LayerNorm backward per row: de = rstd (g - mean(g) - ehat mean(g ehat)) ----
-    if (ln) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 4 * q + r;
-        float eh[DET], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int a = 0; a < DET; ++a) {
-          eh[a] = XE[row * PE + 16 * a + i];
-          s1 += ge[a][r];
-          s2 = fmaf(ge[a][r], eh[a], s2);
-        }
-        s1 = row_sum16(s1) * inv_de;
-        s2 = row_sum16(s2) * inv_de;
-        const float rstd = RS[row];
-#pragma unroll
-        for (int a = 0; a < DET; ++a) ge[a][r] = rstd * (ge[a][r] - s1 - eh[a] * s2);
-      }
-    }
-    eh_sync();                                                                         // ehat has been read
-#pragma unroll
-    for (int a = 0; a < DET; ++a)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (16 * a + i < De) XE[(4 * q + r) * PE + 16 * a + i] = ge[a][r];
-    eh_sync();
+    eh_tile_bwd<DET>(L, dl, a1, a2, act, ln, gr);
     {
-      T* dt = de + p0 * De;
+      T* dt = de + p0 * De;                                    // (a target-0 row of a live tile stores what was computed: dl = 0 there)
       for (int f = lane; f < NF4; f += 64) {
         const int row = f / C4, c4 = f % C4;
-        if (row < valid) eh_st4(dt + (size_t)f * 4, *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4));
+        if (row < valid) eh_st4(dt + (size_t)f * 4, *reinterpret_cast<const float4*>(L.XE + row * PE + 4 * c4));
       }
     }
     eh_sync();   // the image is free for the next tile (its pad columns are untouched)
   }
 
-  // ---- workgroup partials, waves added in index order ----
-  if (!BWD) {
+  if (!BWD) {   // the workgroup's loss, waves added in index order
     const float l = eh_sum_q(lossacc);   // (lanes i == 0 carry the rows)
-    if (lane == 0) lsm[wave] = l;
+    if (lane == 0) lsm[L.wave] = l;
     __syncthreads();
     if (threadIdx.x == 0) loss_part[blockIdx.x] = ((lsm[0] + lsm[1]) + lsm[2]) + lsm[3];
     return;
   }
-  gb0[0] = eh_sum_q(gb0[0]); gb0[1] = eh_sum_q(gb0[1]); gb1 = eh_sum_q(gb1); gbt = eh_sum_q(gbt);
-  __syncthreads();   // every wave is done with its activation image
-  float* const red = asm_;
-  for (int w = 0; w < EH_NW; ++w) {
-    if (wave == w) {
-      const bool first = w == 0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int a = 0; a < DET; ++a)
-#pragma unroll
-          for (int ct = 0; ct < 2; ++ct) {
-            float* p = red + Z::G0 + (16 * a + 4 * q + r) * 32 + 16 * ct + i;
-            *p = (first ? 0.f : *p) + gW0[a][ct][r];
-          }
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-          float* p = red + Z::G1 + (16 * ct + 4 * q + r) * 16 + i;
-          *p = (first ? 0.f : *p) + gW1[ct][r];
-        }
-        float* p = red + Z::GT + (4 * q + r) * 16 + i;
-        *p = (first ? 0.f : *p) + gWt[r];
-      }
-      if (q == 0) {
-        float* p = red + Z::GB0 + i;
-        p[0] = (first ? 0.f : p[0]) + gb0[0];
-        p[16] = (first ? 0.f : p[16]) + gb0[1];
-        p = red + Z::GB1 + i;
-        *p = (first ? 0.f : *p) + gb1;
-        p = red + Z::GBT + i;
-        *p = (first ? 0.f : *p) + gbt;
-      }
-    }
-    __syncthreads();
-  }
-  float* out = part + (size_t)blockIdx.x * Z::PG;
-  for (int k = threadIdx.x; k < Z::PG; k += EH_NW * 64) out[k] = red[k];
+  eh_wg_partials<DET>(L, gr, asm_, part);
 }
 
 // per_graph[b] = sum_g loss_part[b][g], in index order
@@ -469,9 +522,9 @@ __global__ void __launch_bounds__(256) k_edge_head_finish(const float* __restric
 // ---- node-classification head (the PATTERN / CLUSTER readout: sbm_pattern/dc.py, sbm_cluster/dc.py) ----
 //   z = Dense_t(act(Dense_1(act(Dense_0(node_norm_final(h))))))                   W -> M0 -> M1 -> C
 //   stats = (sum mask w[y] CE(z, y), sum mask [argmax z == y], sum mask)          lib/base/genutil/losses.py:41-118
-// The edge head's tile with another row source and epilogue: the rows are the R = B N flattened (graph, node) slots of h,
+// The same tile with another row source and epilogue: the rows are the R = B N flattened (graph, node) slots of h,
 // workgroup g owns the tiles [g chunk, (g + 1) chunk); a tile whose 16 rows are all masked is skipped before h is loaded, and
-// the target of a masked row is never used as a class.  The weight image, the products and the parameter-gradient route
+// the target of a masked row is never used as a class.  The weight image and the parameter-gradient route
 // (per-workgroup partials -> k_edge_head_reduce -> k_edge_head_finish) are the edge head's.
 // BWD == false: stat_part[3 g ..] = the workgroup's (loss, hits, rows); hits and rows are integers (stored as their bit patterns).
 // BWD == true:  dh = sgrad[0] d stats[0] / d h (exact zeros on masked rows), part[g * PG ..] = the parameter gradients.
@@ -489,36 +542,19 @@ __global__ void __launch_bounds__(EH_NW * 64) k_node_head(const float* __restric
   __shared__ float lsm[EH_NW];
   __shared__ int csm[2 * EH_NW];
   __shared__ float cws[16];
-  static_assert(EH_NW * Z::WAVE >= Z::PG, "the gradient image is reduced in the activation area");
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4;
   const int TPG = (R >> 4) + ((R & 15) != 0);
   const int t0 = min(TPG, (int)blockIdx.x * chunk), t1 = min(TPG, t0 + chunk);
-  for (int k = threadIdx.x; k < Z::IMG; k += EH_NW * 64) wsm[k] = img[k];
   if (threadIdx.x < 16) cws[threadIdx.x] = (int)threadIdx.x < C ? cw[threadIdx.x] : 0.f;
-  float* const my = asm_ + wave * Z::WAVE;
-  for (int k = lane; k < Z::WAVE; k += 64) my[k] = 0.f;
-  __syncthreads();
-  float* const XE = my + Z::XE;
-  float* const X1 = my + Z::X1;
-  float* const X2 = my + Z::X2;
-  float* const DL = my + Z::DL;
-  float* const RS = my + Z::RS;
-  const float* const W0 = wsm + Z::W0;
-  const float* const W1 = wsm + Z::W1;
-  const float* const WT = wsm + Z::WT;
+  const EhTile<DET> L = eh_setup<DET>(wsm, asm_, img, W);
+  const int lane = L.lane, i = L.i, q = L.q, C4 = L.C4, NF4 = L.NF4;
   const float sb = BWD ? sgrad[0] : 0.f;
-  const int C4 = W >> 2, NF4 = 4 * W;   // 16-byte slots per row / per tile
-  const float inv_w = 1.0f / (float)W;
 
   float lossacc = 0.f;
   int hits = 0, rows = 0;
-  v4f_h gW0[DET][2], gW1[2], gWt;
-  float gb0[2] = {0.f, 0.f}, gb1 = 0.f, gbt = 0.f;
-#pragma unroll
-  for (int a = 0; a < DET; ++a) gW0[a][0] = gW0[a][1] = (v4f_h){0.f, 0.f, 0.f, 0.f};
-  gW1[0] = gW1[1] = gWt = (v4f_h){0.f, 0.f, 0.f, 0.f};
+  EhGrad<DET> gr;
+  eh_zero(gr);
 
-  for (int t = t0 + wave; t < t1; t += EH_NW) {
+  for (int t = t0 + L.wave; t < t1; t += EH_NW) {
     const size_t r0 = (size_t)16 * t;                           // first row of the tile
     const int valid = (int)min((size_t)16, (size_t)R - r0);
     const bool lv = lane < valid && mask[r0 + lane] != 0;
@@ -532,75 +568,9 @@ __global__ void __launch_bounds__(EH_NW * 64) k_node_head(const float* __restric
       continue;
     }
     const int my_t = lv ? target[r0 + lane] : -1;               // a masked row has no class
-    const float* ht = h + r0 * W;
-    // ---- h tile -> LDS image (rows >= valid: zeros) ----
-    for (int f = lane; f < NF4; f += 64) {
-      const int row = f / C4, c4 = f % C4;
-      const float4 v = row < valid ? eh_ld_raw(ht + (size_t)f * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(XE + row * PE + 4 * c4) = v;
-    }
-    eh_sync();
-    // ---- node_norm_final: two-pass moments; 4 lanes per row ----
-    if (ln) {
-      const int row = lane >> 2, pt = lane & 3;
-      float s = 0.f;
-      for (int c4 = pt; c4 < C4; c4 += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
-        s += (v.x + v.y) + (v.z + v.w);
-      }
-      s += lane_xor<1>(s); s += lane_xor<2>(s);
-      const float mu = s * inv_w;
-      float vs = 0.f;
-      for (int c4 = pt; c4 < C4; c4 += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
-        const float a0 = v.x - mu, a1 = v.y - mu, a2 = v.z - mu, a3 = v.w - mu;
-        vs = fmaf(a0, a0, vs); vs = fmaf(a1, a1, vs); vs = fmaf(a2, a2, vs); vs = fmaf(a3, a3, vs);
-      }
-      vs += lane_xor<1>(vs); vs += lane_xor<2>(vs);
-      const float rstd = rsqrtf(vs * inv_w + eps);
-      for (int c4 = pt; c4 < C4; c4 += 4) {
-        float4 v = *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4);
-        v.x = (v.x - mu) * rstd; v.y = (v.y - mu) * rstd; v.z = (v.z - mu) * rstd; v.w = (v.w - mu) * rstd;
-        *reinterpret_cast<float4*>(XE + row * PE + 4 * c4) = v;
-      }
-      if (pt == 0) RS[row] = rstd;
-      eh_sync();
-    }
-    // ---- x1 = act(hhat . W0f + b0f) ----
-    v4f_h a1[2], a2;
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      const float bb = wsm[Z::B0 + 16 * ct + i];
-      v4f_h acc = (v4f_h){bb, bb, bb, bb};
-      acc = eh_mm_nn<Z::DEP>(XE, PE, W0 + 16 * ct, EH_P0, i, q, acc);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[r] = eh_act(acc[r], act);
-        X1[(4 * q + r) * EH_P0 + 16 * ct + i] = acc[r];
-      }
-      a1[ct] = acc;
-    }
-    eh_sync();
-    // ---- x2 = act(x1 . W1 + b1) ----
-    {
-      const float bb = wsm[Z::B1 + i];
-      v4f_h acc = (v4f_h){bb, bb, bb, bb};
-      acc = eh_mm_nn<32>(X1, EH_P0, W1, EH_P1, i, q, acc);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc[r] = eh_act(acc[r], act);
-        X2[(4 * q + r) * EH_P1 + i] = acc[r];
-      }
-      a2 = acc;
-    }
-    eh_sync();
-    // ---- logits; max-subtracted log-sum-exp over the C real columns, class weight, gather, arg-max (lowest index wins) ----
-    v4f_h z;
-    {
-      const float bb = wsm[Z::BT + i];
-      z = (v4f_h){bb, bb, bb, bb};
-      z = eh_mm_nn<16>(X2, EH_P1, WT, EH_P1, i, q, z);
-    }
+    v4f_h a1[2], a2, z;
+    eh_tile_fwd<DET>(L, h + r0 * W, valid, act, ln, eps, a1, a2, z);
+    // ---- max-subtracted log-sum-exp over the C real columns, class weight, gather, arg-max (lowest index wins) ----
     v4f_h dl;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -624,88 +594,25 @@ __global__ void __launch_bounds__(EH_NW * 64) k_node_head(const float* __restric
       }
     }
     if (!BWD) continue;
-
-    // ================= backward of the tile =================
-    gbt += (dl[0] + dl[1]) + (dl[2] + dl[3]);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) DL[(4 * q + r) * EH_P1 + i] = dl[r];
-    eh_sync();
-    gWt = eh_mm_tn(X2, EH_P1, DL, EH_P1, i, q, gWt);                                   // dWt += x2^T . dl
-    v4f_h d2 = eh_mm_nt<16>(DL, EH_P1, WT, EH_P1, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});  // dx2 = dl . Wt^T
-#pragma unroll
-    for (int r = 0; r < 4; ++r) d2[r] *= eh_dact(a2[r], act);
-    gb1 += (d2[0] + d2[1]) + (d2[2] + d2[3]);
-    eh_sync();                                                                         // x2 has been read
-#pragma unroll
-    for (int r = 0; r < 4; ++r) X2[(4 * q + r) * EH_P1 + i] = d2[r];
-    eh_sync();
-    v4f_h d1[2];
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      gW1[ct] = eh_mm_tn(X1 + 16 * ct, EH_P0, X2, EH_P1, i, q, gW1[ct]);               // dW1 += x1^T . dx2pre
-      d1[ct] = eh_mm_nt<16>(X2, EH_P1, W1 + 16 * ct * EH_P1, EH_P1, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-      for (int r = 0; r < 4; ++r) d1[ct][r] *= eh_dact(a1[ct][r], act);
-      gb0[ct] += (d1[ct][0] + d1[ct][1]) + (d1[ct][2] + d1[ct][3]);
-    }
-    eh_sync();                                                                         // x1 has been read
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) X1[(4 * q + r) * EH_P0 + 16 * ct + i] = d1[ct][r];
-    eh_sync();
-    v4f_h gh[DET];
-#pragma unroll
-    for (int a = 0; a < DET; ++a) {
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-        gW0[a][ct] = eh_mm_tn(XE + 16 * a, PE, X1 + 16 * ct, EH_P0, i, q, gW0[a][ct]);  // dW0f += hhat^T . dx1pre
-      gh[a] = eh_mm_nt<32>(X1, EH_P0, W0 + 16 * a * EH_P0, EH_P0, i, q, (v4f_h){0.f, 0.f, 0.f, 0.f});   // dhhat = dx1pre . W0f^T
-    }
-    // ---- LayerNorm backward per row: dh = rstd (g - mean(g) - hhat mean(g hhat)) ----
-    if (ln) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 4 * q + r;
-        float hh[DET], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int a = 0; a < DET; ++a) {
-          hh[a] = XE[row * PE + 16 * a + i];
-          s1 += gh[a][r];
-          s2 = fmaf(gh[a][r], hh[a], s2);
-        }
-        s1 = row_sum16(s1) * inv_w;
-        s2 = row_sum16(s2) * inv_w;
-        const float rstd = RS[row];
-#pragma unroll
-        for (int a = 0; a < DET; ++a) gh[a][r] = rstd * (gh[a][r] - s1 - hh[a] * s2);
-      }
-    }
-    eh_sync();                                                                         // hhat has been read
-#pragma unroll
-    for (int a = 0; a < DET; ++a)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) XE[(4 * q + r) * PE + 16 * a + i] = gh[a][r];
-    eh_sync();
+    eh_tile_bwd<DET>(L, dl, a1, a2, act, ln, gr);
     {
       float* dt = dh + r0 * W;
       for (int f = lane; f < NF4; f += 64) {
         const int row = f / C4, c4 = f % C4;
         if (row < valid) {
           const bool on = (lvm >> row) & 1ull;                                         // a masked row gets exact zeros
-          eh_st4(dt + (size_t)f * 4, on ? *reinterpret_cast<const float4*>(XE + row * PE + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f));
+          eh_st4(dt + (size_t)f * 4, on ? *reinterpret_cast<const float4*>(L.XE + row * PE + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f));
         }
       }
     }
     eh_sync();   // the image is free for the next tile (its pad columns are untouched)
   }
 
-  // ---- workgroup partials, waves added in index order ----
-  if (!BWD) {
+  if (!BWD) {   // the workgroup's (loss, hits, rows), waves added in index order
     const float l = eh_sum_q(lossacc);   // (lanes i == 0 carry the rows)
     hits += __shfl_xor(hits, 16, 64); hits += __shfl_xor(hits, 32, 64);
     rows += __shfl_xor(rows, 16, 64); rows += __shfl_xor(rows, 32, 64);
-    if (lane == 0) { lsm[wave] = l; csm[2 * wave] = hits; csm[2 * wave + 1] = rows; }
+    if (lane == 0) { lsm[L.wave] = l; csm[2 * L.wave] = hits; csm[2 * L.wave + 1] = rows; }
     __syncthreads();
     if (threadIdx.x == 0) {
       float* o = stat_part + (size_t)blockIdx.x * 3;
@@ -715,43 +622,7 @@ __global__ void __launch_bounds__(EH_NW * 64) k_node_head(const float* __restric
     }
     return;
   }
-  gb0[0] = eh_sum_q(gb0[0]); gb0[1] = eh_sum_q(gb0[1]); gb1 = eh_sum_q(gb1); gbt = eh_sum_q(gbt);
-  __syncthreads();   // every wave is done with its activation image
-  float* const red = asm_;
-  for (int w = 0; w < EH_NW; ++w) {
-    if (wave == w) {
-      const bool first = w == 0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int a = 0; a < DET; ++a)
-#pragma unroll
-          for (int ct = 0; ct < 2; ++ct) {
-            float* p = red + Z::G0 + (16 * a + 4 * q + r) * 32 + 16 * ct + i;
-            *p = (first ? 0.f : *p) + gW0[a][ct][r];
-          }
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-          float* p = red + Z::G1 + (16 * ct + 4 * q + r) * 16 + i;
-          *p = (first ? 0.f : *p) + gW1[ct][r];
-        }
-        float* p = red + Z::GT + (4 * q + r) * 16 + i;
-        *p = (first ? 0.f : *p) + gWt[r];
-      }
-      if (q == 0) {
-        float* p = red + Z::GB0 + i;
-        p[0] = (first ? 0.f : p[0]) + gb0[0];
-        p[16] = (first ? 0.f : p[16]) + gb0[1];
-        p = red + Z::GB1 + i;
-        *p = (first ? 0.f : *p) + gb1;
-        p = red + Z::GBT + i;
-        *p = (first ? 0.f : *p) + gbt;
-      }
-    }
-    __syncthreads();
-  }
-  float* out = part + (size_t)blockIdx.x * Z::PG;
-  for (int k = threadIdx.x; k < Z::PG; k += EH_NW * 64) out[k] = red[k];
+  eh_wg_partials<DET>(L, gr, asm_, part);
 }
 
 // stats = the workgroups' (loss, hits, rows) added in a fixed order: 64 contiguous segments, then the 64; the two counts in integers
@@ -883,6 +754,50 @@ extern "C" int egt_distance_target(const float* adj, int32_t B, int32_t N, int32
   return EGT_OK;
 }
 
+// ---- what the two heads share on the host: one shape of the MLP, one block of the eight parameter pointers ----
+struct EhShape {
+  const char *who, *ln_flag;   // "edge head" / "node head" (the prefix of every message) and the name of its LayerNorm flag
+  int width, det, M0, M1, C, act, ln;
+  float eps;
+};
+struct EhParams { float* p[8]; };   // gamma, beta, W0, b0, W1, b1, Wt, bt: the order of egt_head_params and of egt_node_head_params
+static_assert(sizeof(egt_head_params) == sizeof(EhParams) && sizeof(egt_node_head_params) == sizeof(EhParams),
+              "both parameter structs are eight pointers");
+
+static int eh_mlp_check(const char* who, int M0, int M1, int C, int act) {
+  if (!((M0 == 24 && M1 == 12) || (M0 == 32 && M1 == 16)))
+    EGT_FAIL(EGT_E_SHAPE, "%s covers (M0, M1) in {(24,12), (32,16)}: model widths 48 / 64 (got %d, %d)", who, M0, M1);
+  if (C < 2 || C > 16) EGT_FAIL(EGT_E_SHAPE, "%s covers 2 <= C <= 16 classes (got %d)", who, C);
+  if (act != EGT_ACT_ELU && act != EGT_ACT_RELU)
+    EGT_FAIL(EGT_E_SHAPE, "%s activation is EGT_ACT_ELU or EGT_ACT_RELU (got %d)", who, act);
+  return EGT_OK;
+}
+// P: egt_head_params or egt_node_head_params (`what`: "params" / "grads")
+template <typename P>
+static int eh_params(const EhShape& s, const P* p, const char* what, EhParams* out) {
+  if (!p) EGT_FAIL(EGT_E_NULL, "%s: %s is NULL", s.who, what);
+  memcpy(out, p, sizeof(EhParams));
+  if (s.ln && (!out->p[0] || !out->p[1])) EGT_FAIL(EGT_E_NULL, "%s: %s set but %s gamma/beta is NULL", s.who, s.ln_flag, what);
+  for (int k = 2; k < 8; ++k)
+    if (!out->p[k]) EGT_FAIL(EGT_E_NULL, "%s: a kernel / bias pointer of %s is NULL", s.who, what);
+  return EGT_OK;
+}
+static void eh_prep(const char* label, const EhShape& s, const EhParams& P, float* img, hipStream_t st) {
+  float* const* p = P.p;
+  EGT_LAUNCH(label, k_edge_head_prep, dim3(1), dim3(64), 0, st, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], img, s.width,
+             16 * s.det, s.M0, s.M1, s.C, s.ln);
+}
+// the workgroups' gradient partials -> the eight gradients of G
+static void eh_reduce_finish(const char* label, const EhShape& s, const EhParams& P, const EhParams& G, const float* part, float* red,
+                             int nwg, hipStream_t st) {
+  const int PG = eh_pg(s.det);
+  float* const* g = G.p;
+  EGT_LAUNCH(label, k_edge_head_reduce, dim3((unsigned)((PG + 63) / 64)), dim3(256), 0, st, part, red, nwg, PG);
+  EGT_LAUNCH(label, k_edge_head_finish, dim3(1), dim3(256), 0, st, red, P.p[0], P.p[1], P.p[2],
+             g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], s.width, 16 * s.det, s.M0, s.M1, s.C, s.ln);
+}
+
+// =================================== edge head: host ===================================
 static int head_check(const egt_head_desc* d) {
   if (!d) EGT_FAIL(EGT_E_NULL, "desc is NULL");
   if ((d->flags & ~(int32_t)EGT_EH_LAYERNORM) != 0 || d->reserved != 0)
@@ -892,12 +807,11 @@ static int head_check(const egt_head_desc* d) {
     EGT_FAIL(EGT_E_SHAPE, "edge head: B, N >= 1 and B*N*N inside 32-bit indexing (B=%d N=%d)", d->B, d->N);
   if (!(d->De == 8 || d->De == 16 || d->De == 32 || d->De == 48 || d->De == 64))
     EGT_FAIL(EGT_E_SHAPE, "edge head covers De in {8,16,32,48,64} (got %d)", d->De);
-  if (!((d->M0 == 24 && d->M1 == 12) || (d->M0 == 32 && d->M1 == 16)))
-    EGT_FAIL(EGT_E_SHAPE, "edge head covers (M0, M1) in {(24,12), (32,16)}: model widths 48 / 64 (got %d, %d)", d->M0, d->M1);
-  if (d->C < 2 || d->C > 16) EGT_FAIL(EGT_E_SHAPE, "edge head covers 2 <= C <= 16 classes (got %d)", d->C);
-  if (d->activation != EGT_ACT_ELU && d->activation != EGT_ACT_RELU)
-    EGT_FAIL(EGT_E_SHAPE, "edge head activation is EGT_ACT_ELU or EGT_ACT_RELU (got %d)", d->activation);
-  return EGT_OK;
+  return eh_mlp_check("edge head", d->M0, d->M1, d->C, d->activation);
+}
+static EhShape head_shape(const egt_head_desc* d) {
+  return {"edge head", "EGT_EH_LAYERNORM", d->De, eh_det(d->De), d->M0, d->M1, d->C, d->activation,
+          (d->flags & EGT_EH_LAYERNORM) ? 1 : 0, d->ln_eps};
 }
 extern "C" int egt_edge_head_supported(const egt_head_desc* d) { return head_check(d) == EGT_OK ? 1 : 0; }
 
@@ -918,42 +832,22 @@ extern "C" size_t egt_edge_head_workspace_bytes(const egt_head_desc* d) {
   return sizeof(float) * ((size_t)eh_img(det) + nwg + nwg * eh_pg(det) + eh_pg(det));
 }
 
-static int head_params_check(const egt_head_desc* d, const egt_head_params* p, const char* what) {
-  if (!p) EGT_FAIL(EGT_E_NULL, "edge head: %s is NULL", what);
-  if ((d->flags & EGT_EH_LAYERNORM) && (!p->edge_norm_final_gamma || !p->edge_norm_final_beta))
-    EGT_FAIL(EGT_E_NULL, "edge head: EGT_EH_LAYERNORM set but %s gamma/beta is NULL", what);
-  if (!p->mlp_out_dist_targ_0_kernel || !p->mlp_out_dist_targ_0_bias || !p->mlp_out_dist_targ_1_kernel ||
-      !p->mlp_out_dist_targ_1_bias || !p->distance_target_kernel || !p->distance_target_bias)
-    EGT_FAIL(EGT_E_NULL, "edge head: a kernel / bias pointer of %s is NULL", what);
-  return EGT_OK;
-}
-
-static void head_prep(const egt_head_desc* d, const egt_head_params* p, float* img, hipStream_t st) {
-  EGT_LAUNCH("k_edge_head_prep", k_edge_head_prep, dim3(1), dim3(64), 0, st, (const float*)p->edge_norm_final_gamma,
-             (const float*)p->edge_norm_final_beta, (const float*)p->mlp_out_dist_targ_0_kernel,
-             (const float*)p->mlp_out_dist_targ_0_bias, (const float*)p->mlp_out_dist_targ_1_kernel,
-             (const float*)p->mlp_out_dist_targ_1_bias, (const float*)p->distance_target_kernel,
-             (const float*)p->distance_target_bias, img, d->De, 16 * eh_det(d->De), d->M0, d->M1, d->C,
-             (d->flags & EGT_EH_LAYERNORM) ? 1 : 0);
-}
-
 template <int DET, typename T, bool BWD>
-static void head_launch(const egt_head_desc* d, const void* e, const uint8_t* target, const float* img, const float* s, void* de,
-                        float* loss_part, float* part, hipStream_t st) {
+static void head_launch(const egt_head_desc* d, const EhShape& s, const void* e, const uint8_t* target, const float* img,
+                        const float* sg, void* de, float* loss_part, float* part, hipStream_t st) {
   const int G = head_chunks(d), tpg = (d->N * d->N + 15) / 16, chunk = (tpg + G - 1) / G;
   EGT_LAUNCH(BWD ? "k_edge_head_bwd" : "k_edge_head_fwd", (k_edge_head<DET, T, BWD>), dim3((unsigned)(d->B * G)), dim3(EH_NW * 64),
-             0, st, (const T*)e, target, img, s, (T*)de, loss_part, part, d->N, G, chunk, d->De, d->C, d->activation,
-             (d->flags & EGT_EH_LAYERNORM) ? 1 : 0, d->ln_eps);
+             0, st, (const T*)e, target, img, sg, (T*)de, loss_part, part, d->N, G, chunk, s.width, s.C, s.act, s.ln, s.eps);
 }
 template <bool BWD>
-static void head_dispatch(const egt_head_desc* d, const void* e, const uint8_t* target, const float* img, const float* s, void* de,
-                          float* loss_part, float* part, hipStream_t st) {
+static void head_dispatch(const egt_head_desc* d, const EhShape& s, const void* e, const uint8_t* target, const float* img,
+                          const float* sg, void* de, float* loss_part, float* part, hipStream_t st) {
   const bool bf = d->dtype == EGT_BF16;
-  switch (eh_det(d->De)) {
-#define EH_CASE(DET_)                                                                              \
-  case DET_:                                                                                       \
-    if (bf) head_launch<DET_, uint16_t, BWD>(d, e, target, img, s, de, loss_part, part, st);        \
-    else head_launch<DET_, float, BWD>(d, e, target, img, s, de, loss_part, part, st);              \
+  switch (s.det) {
+#define EH_CASE(DET_)                                                                                 \
+  case DET_:                                                                                          \
+    if (bf) head_launch<DET_, uint16_t, BWD>(d, s, e, target, img, sg, de, loss_part, part, st);       \
+    else head_launch<DET_, float, BWD>(d, s, e, target, img, sg, de, loss_part, part, st);             \
     break;
     EH_CASE(1) EH_CASE(2) EH_CASE(3) EH_CASE(4)
 #undef EH_CASE
@@ -964,14 +858,16 @@ extern "C" int egt_edge_head_fwd(const egt_head_desc* d, const egt_head_params* 
                                  float* per_graph_loss, void* workspace, void* stream) {
   int rc = head_check(d);
   if (rc) return rc;
-  if ((rc = head_params_check(d, params, "params"))) return rc;
+  const EhShape s = head_shape(d);
+  EhParams P;
+  if ((rc = eh_params(s, params, "params", &P))) return rc;
   if (!e || !target || !per_graph_loss || !workspace) EGT_FAIL(EGT_E_NULL, "edge head: e/target/per_graph_loss/workspace is NULL");
   hipStream_t st = (hipStream_t)stream;
-  const int det = eh_det(d->De), G = head_chunks(d);
+  const int G = head_chunks(d);
   float* img = (float*)workspace;
-  float* loss_part = img + eh_img(det);
-  head_prep(d, params, img, st);
-  head_dispatch<false>(d, e, target, img, nullptr, nullptr, loss_part, nullptr, st);
+  float* loss_part = img + eh_img(s.det);
+  eh_prep("k_edge_head_prep", s, P, img, st);
+  head_dispatch<false>(d, s, e, target, img, nullptr, nullptr, loss_part, nullptr, st);
   EGT_LAUNCH("k_edge_head_finish", k_edge_head_loss, dim3((unsigned)((d->B + 63) / 64)), dim3(64), 0, st, (const float*)loss_part,
              per_graph_loss, d->B, G);
   EGT_HIP_LAUNCH_CHECK("egt_edge_head_fwd");
@@ -983,26 +879,19 @@ extern "C" int egt_edge_head_bwd(const egt_head_desc* d, const egt_head_params* 
                                  void* stream) {
   int rc = head_check(d);
   if (rc) return rc;
-  if ((rc = head_params_check(d, params, "params"))) return rc;
-  if ((rc = head_params_check(d, grads, "grads"))) return rc;
+  const EhShape s = head_shape(d);
+  EhParams P, Gr;
+  if ((rc = eh_params(s, params, "params", &P))) return rc;
+  if ((rc = eh_params(s, grads, "grads", &Gr))) return rc;
   if (!e || !target || !d_per_graph || !d_e || !workspace) EGT_FAIL(EGT_E_NULL, "edge head: e/target/d_per_graph/d_e/workspace is NULL");
   hipStream_t st = (hipStream_t)stream;
-  const int det = eh_det(d->De), G = head_chunks(d), nwg = d->B * G, PG = eh_pg(det);
-  const int ln = (d->flags & EGT_EH_LAYERNORM) ? 1 : 0;
+  const int nwg = d->B * head_chunks(d);
   float* img = (float*)workspace;
-  float* part = img + eh_img(det) + nwg;
-  float* red = part + (size_t)nwg * PG;
-  head_prep(d, params, img, st);
-  head_dispatch<true>(d, e, target, img, d_per_graph, d_e, nullptr, part, st);
-  EGT_LAUNCH("k_edge_head_finish", k_edge_head_reduce, dim3((unsigned)((PG + 63) / 64)), dim3(256), 0, st, (const float*)part, red,
-             nwg, PG);
-  EGT_LAUNCH("k_edge_head_finish", k_edge_head_finish, dim3(1), dim3(256), 0, st, (const float*)red,
-             (const float*)params->edge_norm_final_gamma, (const float*)params->edge_norm_final_beta,
-             (const float*)params->mlp_out_dist_targ_0_kernel,
-             (float*)grads->edge_norm_final_gamma, (float*)grads->edge_norm_final_beta, (float*)grads->mlp_out_dist_targ_0_kernel,
-             (float*)grads->mlp_out_dist_targ_0_bias, (float*)grads->mlp_out_dist_targ_1_kernel,
-             (float*)grads->mlp_out_dist_targ_1_bias, (float*)grads->distance_target_kernel, (float*)grads->distance_target_bias,
-             d->De, 16 * det, d->M0, d->M1, d->C, ln);
+  float* part = img + eh_img(s.det) + nwg;
+  float* red = part + (size_t)nwg * eh_pg(s.det);
+  eh_prep("k_edge_head_prep", s, P, img, st);
+  head_dispatch<true>(d, s, e, target, img, d_per_graph, d_e, nullptr, part, st);
+  eh_reduce_finish("k_edge_head_finish", s, P, Gr, part, red, nwg, st);
   EGT_HIP_LAUNCH_CHECK("egt_edge_head_bwd");
   return EGT_OK;
 }
@@ -1016,12 +905,11 @@ static int node_head_check(const egt_node_head_desc* d) {
     EGT_FAIL(EGT_E_SHAPE, "node head: B, N >= 1 and B*N inside 32-bit indexing (B=%d N=%d)", d->B, d->N);
   if (!(d->W == 16 || d->W == 32 || d->W == 48 || d->W == 64))
     EGT_FAIL(EGT_E_SHAPE, "node head covers W in {16,32,48,64} (got %d)", d->W);
-  if (!((d->M0 == 24 && d->M1 == 12) || (d->M0 == 32 && d->M1 == 16)))
-    EGT_FAIL(EGT_E_SHAPE, "node head covers (M0, M1) in {(24,12), (32,16)}: model widths 48 / 64 (got %d, %d)", d->M0, d->M1);
-  if (d->C < 2 || d->C > 16) EGT_FAIL(EGT_E_SHAPE, "node head covers 2 <= C <= 16 classes (got %d)", d->C);
-  if (d->activation != EGT_ACT_ELU && d->activation != EGT_ACT_RELU)
-    EGT_FAIL(EGT_E_SHAPE, "node head activation is EGT_ACT_ELU or EGT_ACT_RELU (got %d)", d->activation);
-  return EGT_OK;
+  return eh_mlp_check("node head", d->M0, d->M1, d->C, d->activation);
+}
+static EhShape node_head_shape(const egt_node_head_desc* d) {
+  return {"node head", "EGT_NH_LAYERNORM", d->W, d->W / 16, d->M0, d->M1, d->C, d->activation,
+          (d->flags & EGT_NH_LAYERNORM) ? 1 : 0, d->ln_eps};
 }
 extern "C" int egt_node_head_supported(const egt_node_head_desc* d) { return node_head_check(d) == EGT_OK ? 1 : 0; }
 
@@ -1041,34 +929,17 @@ extern "C" size_t egt_node_head_workspace_bytes(const egt_node_head_desc* d) {
   return sizeof(float) * ((size_t)eh_img(det) + 3 * G + G * eh_pg(det) + eh_pg(det));
 }
 
-static int node_head_params_check(const egt_node_head_desc* d, const egt_node_head_params* p, const char* what) {
-  if (!p) EGT_FAIL(EGT_E_NULL, "node head: %s is NULL", what);
-  if ((d->flags & EGT_NH_LAYERNORM) && (!p->node_norm_final_gamma || !p->node_norm_final_beta))
-    EGT_FAIL(EGT_E_NULL, "node head: EGT_NH_LAYERNORM set but %s gamma/beta is NULL", what);
-  if (!p->mlp_out_0_kernel || !p->mlp_out_0_bias || !p->mlp_out_1_kernel || !p->mlp_out_1_bias || !p->target_kernel ||
-      !p->target_bias)
-    EGT_FAIL(EGT_E_NULL, "node head: a kernel / bias pointer of %s is NULL", what);
-  return EGT_OK;
-}
-
-static void node_head_prep(const egt_node_head_desc* d, const egt_node_head_params* p, float* img, hipStream_t st) {
-  EGT_LAUNCH("k_node_head_prep", k_edge_head_prep, dim3(1), dim3(64), 0, st, (const float*)p->node_norm_final_gamma,
-             (const float*)p->node_norm_final_beta, (const float*)p->mlp_out_0_kernel, (const float*)p->mlp_out_0_bias,
-             (const float*)p->mlp_out_1_kernel, (const float*)p->mlp_out_1_bias, (const float*)p->target_kernel,
-             (const float*)p->target_bias, img, d->W, d->W, d->M0, d->M1, d->C, (d->flags & EGT_NH_LAYERNORM) ? 1 : 0);
-}
-
 template <bool BWD>
-static void node_head_dispatch(const egt_node_head_desc* d, const float* h, const int32_t* target, const uint8_t* mask,
-                               const float* cw, const float* img, const float* s, float* dh, float* stat_part, float* part,
-                               hipStream_t st) {
+static void node_head_dispatch(const egt_node_head_desc* d, const EhShape& s, const float* h, const int32_t* target,
+                               const uint8_t* mask, const float* cw, const float* img, const float* sg, float* dh, float* stat_part,
+                               float* part, hipStream_t st) {
   const int G = node_head_groups(d), tiles = node_head_tiles(d), chunk = (tiles + G - 1) / G;
-  const int R = d->B * d->N, ln = (d->flags & EGT_NH_LAYERNORM) ? 1 : 0;
-  switch (d->W / 16) {
+  const int R = d->B * d->N;
+  switch (s.det) {
 #define NH_CASE(DET_)                                                                                                          \
   case DET_:                                                                                                                   \
     EGT_LAUNCH(BWD ? "k_node_head_bwd" : "k_node_head_fwd", (k_node_head<DET_, BWD>), dim3((unsigned)G), dim3(EH_NW * 64), 0, st, \
-               h, target, mask, cw, img, s, dh, stat_part, part, R, chunk, d->W, d->C, d->activation, ln, d->ln_eps);           \
+               h, target, mask, cw, img, sg, dh, stat_part, part, R, chunk, s.width, s.C, s.act, s.ln, s.eps);                  \
     break;
     NH_CASE(1) NH_CASE(2) NH_CASE(3) NH_CASE(4)
 #undef NH_CASE
@@ -1080,16 +951,17 @@ extern "C" int egt_node_head_fwd(const egt_node_head_desc* d, const egt_node_hea
                                  void* workspace, void* stream) {
   int rc = node_head_check(d);
   if (rc) return rc;
-  if ((rc = node_head_params_check(d, params, "params"))) return rc;
+  const EhShape s = node_head_shape(d);
+  EhParams P;
+  if ((rc = eh_params(s, params, "params", &P))) return rc;
   if (!h || !target || !mask || !class_weights || !stats || !workspace)
     EGT_FAIL(EGT_E_NULL, "node head: h/target/mask/class_weights/stats/workspace is NULL");
   hipStream_t st = (hipStream_t)stream;
-  const int det = d->W / 16, G = node_head_groups(d);
   float* img = (float*)workspace;
-  float* stat_part = img + eh_img(det);
-  node_head_prep(d, params, img, st);
-  node_head_dispatch<false>(d, h, target, mask, class_weights, img, nullptr, nullptr, stat_part, nullptr, st);
-  EGT_LAUNCH("k_node_head_finish", k_node_head_stats, dim3(1), dim3(64), 0, st, (const float*)stat_part, stats, G);
+  float* stat_part = img + eh_img(s.det);
+  eh_prep("k_node_head_prep", s, P, img, st);
+  node_head_dispatch<false>(d, s, h, target, mask, class_weights, img, nullptr, nullptr, stat_part, nullptr, st);
+  EGT_LAUNCH("k_node_head_finish", k_node_head_stats, dim3(1), dim3(64), 0, st, (const float*)stat_part, stats, node_head_groups(d));
   EGT_HIP_LAUNCH_CHECK("egt_node_head_fwd");
   return EGT_OK;
 }
@@ -1099,26 +971,20 @@ extern "C" int egt_node_head_bwd(const egt_node_head_desc* d, const egt_node_hea
                                  float* d_h, const egt_node_head_params* grads, void* workspace, void* stream) {
   int rc = node_head_check(d);
   if (rc) return rc;
-  if ((rc = node_head_params_check(d, params, "params"))) return rc;
-  if ((rc = node_head_params_check(d, grads, "grads"))) return rc;
+  const EhShape s = node_head_shape(d);
+  EhParams P, Gr;
+  if ((rc = eh_params(s, params, "params", &P))) return rc;
+  if ((rc = eh_params(s, grads, "grads", &Gr))) return rc;
   if (!h || !target || !mask || !class_weights || !d_loss || !d_h || !workspace)
     EGT_FAIL(EGT_E_NULL, "node head: h/target/mask/class_weights/d_loss/d_h/workspace is NULL");
   hipStream_t st = (hipStream_t)stream;
-  const int det = d->W / 16, G = node_head_groups(d), PG = eh_pg(det);
-  const int ln = (d->flags & EGT_NH_LAYERNORM) ? 1 : 0;
+  const int G = node_head_groups(d);
   float* img = (float*)workspace;
-  float* part = img + eh_img(det) + 3 * (size_t)G;
-  float* red = part + (size_t)G * PG;
-  node_head_prep(d, params, img, st);
-  node_head_dispatch<true>(d, h, target, mask, class_weights, img, d_loss, d_h, nullptr, part, st);
-  EGT_LAUNCH("k_node_head_finish", k_edge_head_reduce, dim3((unsigned)((PG + 63) / 64)), dim3(256), 0, st, (const float*)part, red,
-             G, PG);
-  EGT_LAUNCH("k_node_head_finish", k_edge_head_finish, dim3(1), dim3(256), 0, st, (const float*)red,
-             (const float*)params->node_norm_final_gamma, (const float*)params->node_norm_final_beta,
-             (const float*)params->mlp_out_0_kernel, (float*)grads->node_norm_final_gamma, (float*)grads->node_norm_final_beta,
-             (float*)grads->mlp_out_0_kernel, (float*)grads->mlp_out_0_bias, (float*)grads->mlp_out_1_kernel,
-             (float*)grads->mlp_out_1_bias, (float*)grads->target_kernel, (float*)grads->target_bias, d->W, d->W, d->M0, d->M1,
-             d->C, ln);
+  float* part = img + eh_img(s.det) + 3 * (size_t)G;
+  float* red = part + (size_t)G * eh_pg(s.det);
+  eh_prep("k_node_head_prep", s, P, img, st);
+  node_head_dispatch<true>(d, s, h, target, mask, class_weights, img, d_loss, d_h, nullptr, part, st);
+  eh_reduce_finish("k_node_head_finish", s, P, Gr, part, red, G, st);
   EGT_HIP_LAUNCH_CHECK("egt_node_head_bwd");
   return EGT_OK;
 }

@@ -69,13 +69,6 @@ def distance_head_composed(e, target, params, activation="elu", eps=LN_EPS):
     return (ce * (t > 0).to(ce.dtype)).sum(dim=(1, 2))
 
 
-def _pstruct(tensors) -> L.HeadParams:
-    st = L.HeadParams()
-    for name, t in zip(L.HEAD_PARAM_FIELDS, tensors):
-        setattr(st, name, None if t is None else t.data_ptr())
-    return st
-
-
 class _FusedHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, e, target, desc, *params):
@@ -89,7 +82,7 @@ class _FusedHead(torch.autograd.Function):
         params = tuple(None if p is None else _f32c(p) for p in params)
         per_graph = torch.empty(desc.B, dtype=torch.float32, device=e.device)
         ws = torch.empty(lib.egt_edge_head_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=e.device)
-        pst = _pstruct(params)
+        pst = L.params_struct(L.HeadParams, L.HEAD_PARAM_FIELDS, params)
         L.check(lib.egt_edge_head_fwd(C.byref(desc), C.byref(pst), L.ptr(e), L.ptr(target), L.ptr(per_graph), L.ptr(ws),
                                       L.current_stream()))
         ctx.desc = desc
@@ -109,7 +102,7 @@ class _FusedHead(torch.autograd.Function):
         from .fused import grad_sinks
         grads, rets = grad_sinks(ctx.param_objs)
         ws = torch.empty(lib.egt_edge_head_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=e.device)
-        pst, gst = _pstruct(params), _pstruct(grads)
+        pst, gst = (L.params_struct(L.HeadParams, L.HEAD_PARAM_FIELDS, t) for t in (params, grads))
         L.check(lib.egt_edge_head_bwd(C.byref(desc), C.byref(pst), L.ptr(e), L.ptr(target), L.ptr(s), L.ptr(de),
                                       C.byref(gst), L.ptr(ws), L.current_stream()))
         return (de, None, None, *rets)

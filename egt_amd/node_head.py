@@ -66,13 +66,6 @@ def node_head_composed(h, target, mask, class_weights, params, activation="elu",
     return torch.stack([loss, hit, m.sum()])
 
 
-def _pstruct(tensors) -> L.NodeHeadParams:
-    st = L.NodeHeadParams()
-    for name, t in zip(L.NODE_HEAD_PARAM_FIELDS, tensors):
-        setattr(st, name, None if t is None else t.data_ptr())
-    return st
-
-
 class _FusedNodeHead(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, target, mask, class_weights, desc, *params):
@@ -83,7 +76,7 @@ class _FusedNodeHead(torch.autograd.Function):
         params = tuple(None if p is None else _f32c(p) for p in params)
         stats = torch.empty(3, dtype=torch.float32, device=h.device)
         ws = torch.empty(lib.egt_node_head_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=h.device)
-        pst = _pstruct(params)
+        pst = L.params_struct(L.NodeHeadParams, L.NODE_HEAD_PARAM_FIELDS, params)
         L.check(lib.egt_node_head_fwd(C.byref(desc), C.byref(pst), L.ptr(h), L.ptr(target), L.ptr(mask), L.ptr(class_weights),
                                       L.ptr(stats), L.ptr(ws), L.current_stream()))
         ctx.desc = desc
@@ -103,7 +96,7 @@ class _FusedNodeHead(torch.autograd.Function):
         from .fused import grad_sinks
         grads, rets = grad_sinks(ctx.param_objs)
         ws = torch.empty(lib.egt_node_head_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=h.device)
-        pst, gst = _pstruct(params), _pstruct(grads)
+        pst, gst = (L.params_struct(L.NodeHeadParams, L.NODE_HEAD_PARAM_FIELDS, t) for t in (params, grads))
         L.check(lib.egt_node_head_bwd(C.byref(desc), C.byref(pst), L.ptr(h), L.ptr(target), L.ptr(mask), L.ptr(class_weights),
                                       L.ptr(s), L.ptr(dh), C.byref(gst), L.ptr(ws), L.current_stream()))
         return (dh, None, None, None, None, *rets)

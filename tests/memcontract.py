@@ -332,11 +332,7 @@ def _ptr(v, name):
 
 
 def _struct(cls, fields, v, prefix):
-    st = cls()
-    for f in fields:
-        t = v.get(prefix + f)
-        setattr(st, f, None if t is None else t.data_ptr())
-    return st
+    return _L().params_struct(cls, fields, [v.get(prefix + f) for f in fields])
 
 
 def _gen(name):

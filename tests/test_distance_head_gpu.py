@@ -93,7 +93,8 @@ def _check(got, ref, comp, dtype=torch.float32, names=DR.HEAD_NAMES):
     assert float(got["d_e"][t > 0].abs().max()) > 0.0
 
 
-CASES = [(48, 48, 3, "elu", True), (64, 64, 8, "elu", True), (8, 64, 3, "relu", True), (16, 64, 3, "elu", False)]
+CASES = [(48, 48, 3, "elu", True), (64, 64, 8, "elu", True), (8, 64, 3, "relu", True), (16, 64, 3, "elu", False),
+         (32, 64, 3, "elu", True)]           # De = 32: the two-tile instance of the shared tile body
 
 
 @pytest.mark.parametrize("De,width,T,act,ln", CASES)

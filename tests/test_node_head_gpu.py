@@ -14,7 +14,8 @@ S_UP = 0.7                                  # a non-unit upstream gradient of st
 CASES = [(64, 64, 6, "elu", True, 3, 19), (64, 64, 2, "elu", True, 3, 19), (48, 48, 6, "relu", True, 3, 19),
          (16, 64, 3, "elu", False, 3, 19),
          (64, 64, 6, "elu", True, 2, 16),    # nothing masked, every tile full
-         (64, 64, 6, "elu", True, 4, 70)]    # 280 rows = 18 tiles -> 18 // 4 = 4 workgroups of 5, 5, 5, 3 tiles (NR.workgroups)
+         (64, 64, 6, "elu", True, 4, 70),    # 280 rows = 18 tiles -> 18 // 4 = 4 workgroups of 5, 5, 5, 3 tiles (NR.workgroups)
+         (32, 64, 6, "elu", True, 3, 19)]    # W = 32: the two-tile instance of the shared tile body
 _REF = {}
 
 
