@@ -2,8 +2,8 @@
 
 A torch-CPU restatement (any dtype; tests evaluate it in fp64) of what `DCSVDTransformer`
 builds for scheme `zinc.svd` with the shipped ZINC configs (`use_svd: false`), composed from
-oracle/egt_oracle.py for the layer stack.  Parity is UNPINNED by the reference (TensorFlow cannot
-run here; the reference ships no vectors): correctness is by construction from the cited lines.
+oracle/egt_oracle.py for the layer stack.  Pinned by execution: tests/test_reference_exec_cpu.py compares it with the
+reference's own zinc / cifar10 model code run on the eager stand-in (oracle/ref_exec.py, tests/golden/reference/).
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline may import this module.
 
 Model (all citations relative to /root/reference/):
@@ -274,9 +274,10 @@ def zinc_embeddings(node_features, feature_matrix, graph_matrix, p, cfg, pe=None
     return h, e, mask
 
 
-def zinc_forward(node_features, feature_matrix, graph_matrix, p, cfg, rand_masks=None, return_hidden=False, pe=None):
+def zinc_forward(node_features, feature_matrix, graph_matrix, p, cfg, rand_masks=None, return_hidden=False, pe=None, attn_mask=None):
     """DCSVDTransformer.call -> prediction [B, num_targets] (graph_xformer_model_base.py:447-466).
-    rand_masks: per-layer injected random attention masks (training with random_mask_prob > 0)."""
+    rand_masks: per-layer injected random attention masks (training with random_mask_prob > 0).
+    attn_mask: the [B,N,N,H] mask of 'constrained' edge channels (graph_model_base.py:131-142), handed to every layer."""
     H, Ly = cfg.get("num_heads", 8), cfg["model_height"]
     act = cfg.get("activation", "elu")
     h, e, mask = zinc_embeddings(node_features, feature_matrix, graph_matrix, p, cfg, pe)
@@ -284,7 +285,7 @@ def zinc_forward(node_features, feature_matrix, graph_matrix, p, cfg, rand_masks
         bp = {k[len(f"layer{ii}."):]: v for k, v in p.items()
               if k.startswith(f"layer{ii}.") and ".ffn_" not in k}
         rm = None if rand_masks is None else rand_masks[ii]
-        h, e = O.block_forward(h, e, mask, bp, num_heads=H, rand_mask=rm)                   # layer/ii/attention, :338-339
+        h, e = O.block_forward(h, e, mask, bp, num_heads=H, rand_mask=rm, attn_mask=attn_mask)   # layer/ii/attention, :338-339
         fn = {k.split(".", 2)[2]: v for k, v in p.items() if k.startswith(f"layer{ii}.ffn_node.")}
         fe = {k.split(".", 2)[2]: v for k, v in p.items() if k.startswith(f"layer{ii}.ffn_edge.")}
         e = O.ffn_forward(e, fe, activation=act)                                            # layer/ii/ffn, :309-324

@@ -4,14 +4,16 @@ TEST INFRASTRUCTURE ONLY.  Nothing under ``egt_amd/`` may import this module;
 only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline``
 leg use it, and there only as the checker / the timed CPU baseline.
 
-PARITY UNPINNED: the reference (shamim-hussain/egt) ships no tests, golden
-vectors or saved weights, and its arithmetic lives in TensorFlow
-(tensorflow-gpu 2.1.0, environment.yml:187-189), which is not installed in this
-image.  This file therefore restates the reference's op sequence from its
+PINNED BY EXECUTION: the reference (shamim-hussain/egt) ships no tests, golden
+vectors or saved weights, and its arithmetic lives in TensorFlow, which is not
+installed here.  This file restates the reference's op sequence from its
 source, op by op, in torch-CPU (dtype-parametric: fp64 for checking, fp32 for
-the timed baseline).  It is pinned only by self-consistency (hand-derived
-backward vs autograd, algebraic identities, SDPA cross-check) — see
-tests/test_oracle.py — and by the committed fixtures generated from it.
+the timed baseline).  tests/test_reference_exec_cpu.py compares it with what
+the reference's own model code computes when it runs, unmodified, on the eager
+stand-in of oracle/tf_eager (oracle/ref_exec.py; fixtures in
+tests/golden/reference/): every tensor within 1e-12 of its magnitude.  It is
+also held by self-consistency (hand-derived backward vs autograd, algebraic
+identities, SDPA cross-check; tests/test_oracle.py) and by its own fixtures.
 
 Reference lines followed (relative to /root/reference):
   * inner op   lib/models/egt_layers.py:57-143 (gated), :145-213 (ungated)

@@ -67,8 +67,8 @@ def _key_mask(B, N, nodes):
     return m
 
 
-def make_attn_case(name, seed=1234):
-    c = dict(ATTN_CASES[name])
+def make_attn_case(name, seed=1234, case=None):
+    c = dict(ATTN_CASES[name] if case is None else case)
     g = torch.Generator().manual_seed(seed + sum(map(ord, name)))
     B, N, H, d = c["B"], c["N"], c["H"], c["d"]
     r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float32)

@@ -1,6 +1,7 @@
-"""CPU tests that pin the oracle (it is 'parity unpinned' by the reference, which
-ships no vectors): hand-derived backward vs autograd, the algebraic identities
-and probed facts of SURVEY §8(a)/(c), and the committed golden fixtures."""
+"""CPU tests of the oracle's self-consistency: hand-derived backward vs autograd, the
+algebraic identities and probed facts of SURVEY §8(a)/(c), and the committed golden
+fixtures.  (Its parity with the reference is pinned by execution in
+tests/test_reference_exec_cpu.py.)"""
 import glob
 import os
 
