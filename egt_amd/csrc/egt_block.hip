@@ -93,26 +93,24 @@ int egt_device_cus() {
 }
 
 static int block_check(const egt_block_desc* d, bool report) {
-#define BAD(code, ...) do { if (report) egt_set_error(__VA_ARGS__); return (code); } while (0)
-  if (!d) BAD(EGT_E_NULL, "desc is NULL");
-  if (d->dtype != EGT_F32 && d->dtype != EGT_BF16) BAD(EGT_E_DTYPE, "dtype must be EGT_F32 or EGT_BF16 (got %d)", d->dtype);
-  if (d->B <= 0 || d->N <= 0) BAD(EGT_E_SHAPE, "B and N must be positive");
-  if (d->H != BH) BAD(EGT_E_SHAPE, "fused block is built for num_heads=8 (got %d)", d->H);
-  if (d->d < 1 || d->d > 8) BAD(EGT_E_SHAPE, "fused block covers per-head dim <= 8 (got %d)", d->d);
+  if (!d) EGT_BAD(EGT_E_NULL, "desc is NULL");
+  if (d->dtype != EGT_F32 && d->dtype != EGT_BF16) EGT_BAD(EGT_E_DTYPE, "dtype must be EGT_F32 or EGT_BF16 (got %d)", d->dtype);
+  if (d->B <= 0 || d->N <= 0) EGT_BAD(EGT_E_SHAPE, "B and N must be positive");
+  if (d->H != BH) EGT_BAD(EGT_E_SHAPE, "fused block is built for num_heads=8 (got %d)", d->H);
+  if (d->d < 1 || d->d > 8) EGT_BAD(EGT_E_SHAPE, "fused block covers per-head dim <= 8 (got %d)", d->d);
   switch (d->De) {
     case 8: case 16: case 32: case 48: case 64: break;
-    default: BAD(EGT_E_SHAPE, "fused block covers edge_width in {8,16,32,48,64} (got %d)", d->De);
+    default: EGT_BAD(EGT_E_SHAPE, "fused block covers edge_width in {8,16,32,48,64} (got %d)", d->De);
   }
-  if ((size_t)d->B * d->N * d->N * d->H > 0xFFFFFFFFull) BAD(EGT_E_SHAPE, "B*N*N*H exceeds the 32-bit RNG counter");
-  if ((d->flags & EGT_BF_SEED_DEVICE) && !d->seed_device) BAD(EGT_E_NULL, "EGT_BF_SEED_DEVICE set but seed_device is NULL");
+  if ((size_t)d->B * d->N * d->N * d->H > 0xFFFFFFFFull) EGT_BAD(EGT_E_SHAPE, "B*N*N*H exceeds the 32-bit RNG counter");
+  if ((d->flags & EGT_BF_SEED_DEVICE) && !d->seed_device) EGT_BAD(EGT_E_NULL, "EGT_BF_SEED_DEVICE set but seed_device is NULL");
   if (d->flags & EGT_BF_STATIC_EDGE) {   // the static-edge mode lives in the De = 8 pair kernels (egt_narrow.hip) and nowhere else
-    if (!(d->flags & EGT_BF_NO_EDGE_LN)) BAD(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE is only valid together with EGT_BF_NO_EDGE_LN");
-    if (d->flags & EGT_BF_ATTN_MASK) BAD(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE does not take EGT_BF_ATTN_MASK");
-    if (d->De != 8) BAD(EGT_E_SHAPE, "EGT_BF_STATIC_EDGE covers edge_width 8 (got %d)", d->De);
-    if (block_env().no_narrow_fwd || block_env().no_narrow_bwd) BAD(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE needs the De = 8 pair kernels (EGT_NO_NARROW* is set)");
+    if (!(d->flags & EGT_BF_NO_EDGE_LN)) EGT_BAD(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE is only valid together with EGT_BF_NO_EDGE_LN");
+    if (d->flags & EGT_BF_ATTN_MASK) EGT_BAD(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE does not take EGT_BF_ATTN_MASK");
+    if (d->De != 8) EGT_BAD(EGT_E_SHAPE, "EGT_BF_STATIC_EDGE covers edge_width 8 (got %d)", d->De);
+    if (block_env().no_narrow_fwd || block_env().no_narrow_bwd) EGT_BAD(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE needs the De = 8 pair kernels (EGT_NO_NARROW* is set)");
   }
   return EGT_OK;
-#undef BAD
 }
 
 extern "C" int egt_block_supported(const egt_block_desc* d) { return block_check(d, false) == EGT_OK; }

@@ -16,8 +16,15 @@ void egt_set_error(const char* fmt, ...);
     egt_set_error(__VA_ARGS__);  \
     return (code);               \
   } while (0)
+// in a predicate with a `bool report` parameter (one text behind an entry point and its *_supported query): the reason is
+// left with egt_set_error only where the caller reports
+#define EGT_BAD(code, ...)                      \
+  do {                                          \
+    if (report) egt_set_error(__VA_ARGS__);     \
+    return (code);                              \
+  } while (0)
 
-#define EGT_HIP_LAUNCH_CHECK(name)                                              \
+#define EGT_HIP_LAUNCH_CHECK(name)                                             \
   do {                                                                          \
     hipError_t e__ = hipGetLastError();                                         \
     if (e__ != hipSuccess)                                                      \

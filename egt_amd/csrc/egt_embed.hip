@@ -18,7 +18,7 @@ typedef float v4f_e __attribute__((ext_vector_type(4)));
 // MFMA tiles per wave: every A / B fragment feeds two products, half the L2 -> L1 operand traffic of one tile per wave
 // (N = 150: 57 us per hop with 16 x 16 tiles and scalar loads -> 42 us with 16-byte A loads -> this form).
 __global__ void __launch_bounds__(64) k_hop_step(const float* __restrict__ adj, float* __restrict__ hops, int B, int N,
-                                                 int K, int k, int clip) {
+                                                 int k, int clip) {
   const int T2 = (N + 31) / 32;
   const int tile = blockIdx.x % (T2 * T2), b = blockIdx.x / (T2 * T2);
   const int l0 = (tile / T2) * 32, m0 = (tile % T2) * 32;
@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(HOP_NW * 64) k_hop_chain(const float* __restri
   }
 }
 
-__global__ void __launch_bounds__(256) k_hop_first(const float* __restrict__ adj, float* __restrict__ hops, long pairs, int K) {
+__global__ void __launch_bounds__(256) k_hop_first(const float* __restrict__ adj, float* __restrict__ hops, long pairs) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i < pairs) hops[i] = adj[i];   // plane 0
 }
@@ -170,54 +170,62 @@ __device__ __forceinline__ void embed_store4(float* p, float4 v) { *reinterpret_
 __device__ __forceinline__ void embed_store4(uint16_t* p, float4 v) { *reinterpret_cast<uint2*>(p) = f4_to_bf4(v); }
 __device__ __forceinline__ float4 embed_load4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 embed_load4(const uint16_t* p) { return bf4_to_f4(*reinterpret_cast<const uint2*>(p)); }
-template <int KMAX, typename T>
+
+// the forward kernels' LDS image: Ws [K][De], behind it Ts [V][De] (+ bias folded in); returns the first float behind both
+__device__ __forceinline__ float* embed_stage(float* sm, const float* __restrict__ W, const float* __restrict__ table,
+                                              const float* __restrict__ bias, int De, int K, int V) {
+  float* Ts = sm + K * De;
+  for (int i = threadIdx.x; i < K * De; i += 256) sm[i] = W[i];
+  for (int i = threadIdx.x; i < V * De; i += 256) Ts[i] = table[i] + bias[i % De];
+  return Ts + V * De;
+}
+// channels 4 c4 .. 4 c4 + 3 of e0[pair] from that image: the table row, then one FMA per plane in plane order
+__device__ __forceinline__ float4 embed_interior4(const int32_t* __restrict__ fmat, const float* __restrict__ hops, const float* sm,
+                                                  long pair, long pairs, int c4, int De, int K, int V) {
+  int f = fmat[pair] + 1;
+  f = min(max(f, 0), V - 1);
+  float4 acc = *reinterpret_cast<const float4*>(sm + (K + f) * De + 4 * c4);
+  const float* hp = hops + pair;
+#pragma unroll 4
+  for (int k = 0; k < K; ++k) {
+    const float hv = hp[(size_t)k * pairs];
+    const float4 w = *reinterpret_cast<const float4*>(sm + k * De + 4 * c4);
+    acc.x = fmaf(hv, w.x, acc.x); acc.y = fmaf(hv, w.y, acc.y);
+    acc.z = fmaf(hv, w.z, acc.z); acc.w = fmaf(hv, w.w, acc.w);
+  }
+  return acc;
+}
+
+template <typename T>
 __global__ void __launch_bounds__(256) k_edge_embed_fwd(const int32_t* __restrict__ fmat, const float* __restrict__ hops,
                                                         const float* __restrict__ table, const float* __restrict__ W,
                                                         const float* __restrict__ bias, T* __restrict__ e, long pairs,
                                                         int De, int K, int V) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* Ws = sm;                 // [K][De]
-  float* Ts = Ws + K * De;        // [V][De] (+ bias folded in)
-  for (int i = threadIdx.x; i < K * De; i += 256) Ws[i] = W[i];
-  for (int i = threadIdx.x; i < V * De; i += 256) Ts[i] = table[i] + bias[i % De];
+  embed_stage(sm, W, table, bias, De, K, V);
   __syncthreads();
   const int C4 = De / 4;
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   const long pair = gid / C4;
   const int c4 = (int)(gid % C4);
   if (pair >= pairs) return;
-  int f = fmat[pair] + 1;
-  f = min(max(f, 0), V - 1);
-  float4 acc = *reinterpret_cast<const float4*>(Ts + f * De + 4 * c4);
-  const float* hp = hops + pair;
-#pragma unroll 4
-  for (int k = 0; k < K; ++k) {
-    const float hv = hp[(size_t)k * pairs];
-    const float4 w = *reinterpret_cast<const float4*>(Ws + k * De + 4 * c4);
-    acc.x = fmaf(hv, w.x, acc.x); acc.y = fmaf(hv, w.y, acc.y);
-    acc.z = fmaf(hv, w.z, acc.z); acc.w = fmaf(hv, w.w, acc.w);
-  }
-  embed_store4(e + pair * De + 4 * c4, acc);
+  embed_store4(e + pair * De + 4 * c4, embed_interior4(fmat, hops, sm, pair, pairs, c4, De, K, V));
 }
 
 // the same embedding with the border of nv virtual nodes (lib/base/graph_layers/virtual_nodes.py:86-99) in ONE write of the
 // [B,N',N',De] tensor, N' = nv + N:   interior (nv + l, nv + m) = e0[l,m];   virtual row (i, nv + m) = vn[i] (padded columns
 // too: the reference tiles over the whole axis);   virtual column (nv + l, j) = vn[j];   box (i, j) = 0.5 (vn[i] + vn[j]).
 // thread = (pair', 4 channels), pair' = (row, column) of the bordered matrix of graph blockIdx.x / bpg (32-bit index math:
-// N' N' De / 4 < 2^31).  Interior threads run k_edge_embed_fwd's table + FMA chain in its order (bit-identical values); border
+// N' N' De / 4 < 2^31).  Interior threads run embed_interior4 as k_edge_embed_fwd does (bit-identical values); border
 // threads read the virtual table staged beside W and the table.  The hop planes keep the interior pitch N.
-template <int KMAX, typename T>
+template <typename T>
 __global__ void __launch_bounds__(256) k_edge_embed_vn_fwd(const int32_t* __restrict__ fmat, const float* __restrict__ hops,
                                                            const float* __restrict__ table, const float* __restrict__ W,
                                                            const float* __restrict__ bias, const float* __restrict__ vn,
                                                            T* __restrict__ e, long pairs, int N, int nv, int De, int K, int V,
                                                            unsigned bpg) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* Ws = sm;                 // [K][De]
-  float* Ts = Ws + K * De;        // [V][De] (+ bias folded in)
-  float* Vs = Ts + V * De;        // [nv][De]
-  for (int i = threadIdx.x; i < K * De; i += 256) Ws[i] = W[i];
-  for (int i = threadIdx.x; i < V * De; i += 256) Ts[i] = table[i] + bias[i % De];
+  float* Vs = embed_stage(sm, W, table, bias, De, K, V);   // [nv][De]
   for (int i = threadIdx.x; i < nv * De; i += 256) Vs[i] = vn[i];
   __syncthreads();
   const unsigned C4 = De / 4, NV = nv + N;
@@ -228,18 +236,7 @@ __global__ void __launch_bounds__(256) k_edge_embed_vn_fwd(const int32_t* __rest
   const unsigned r = pv / NV, c = pv % NV;
   float4 acc;
   if (r >= (unsigned)nv && c >= (unsigned)nv) {
-    const long pair = ((long)b * N + (r - nv)) * N + (c - nv);
-    int f = fmat[pair] + 1;
-    f = min(max(f, 0), V - 1);
-    acc = *reinterpret_cast<const float4*>(Ts + f * De + 4 * c4);
-    const float* hp = hops + pair;
-#pragma unroll 4
-    for (int k = 0; k < K; ++k) {
-      const float hv = hp[(size_t)k * pairs];
-      const float4 w = *reinterpret_cast<const float4*>(Ws + k * De + 4 * c4);
-      acc.x = fmaf(hv, w.x, acc.x); acc.y = fmaf(hv, w.y, acc.y);
-      acc.z = fmaf(hv, w.z, acc.z); acc.w = fmaf(hv, w.w, acc.w);
-    }
+    acc = embed_interior4(fmat, hops, sm, ((long)b * N + (r - nv)) * N + (c - nv), pairs, (int)c4, De, K, V);
   } else {
     const float4 vr = *reinterpret_cast<const float4*>(Vs + min(r, (unsigned)nv - 1) * De + 4 * c4);
     const float4 vc = *reinterpret_cast<const float4*>(Vs + min(c, (unsigned)nv - 1) * De + 4 * c4);
@@ -254,66 +251,17 @@ __global__ void __launch_bounds__(256) k_edge_embed_vn_fwd(const int32_t* __rest
 // backward: dW[k,c] = sum_pairs hops[pair,k] de[pair,c];  dtable[v,c] = sum_{fmat+1 == v} de[pair,c];  dbias = sum de
 // block = PL pair lanes x C4P channel quads (C4P = De/4 rounded up to a power of two, PL = 256 / C4P: narrow edge
 // channels get more pair lanes instead of idle threads); each thread owns 4 channels and walks its pairs; the
-// (K + V) x 4 accumulators per thread are reduced over the pair lanes in LDS; one partial per workgroup
-// (k_edge_embed_vn_bwd below is this kernel with another row walk over de: a fix here belongs there too)
+// (K + V) x 4 accumulators per thread are reduced over the pair lanes in LDS; one partial per workgroup.
+// VN (launched as "k_edge_embed_vn_bwd"): de is the bordered gradient [B,N',N',De] (N' = nv + N) and the contraction runs over its
+// INTERIOR: pair (b, l, m) sits at row q = (b N' + nv + l) N' + nv + m of de; q follows the pair walk (one division per thread,
+// before the loop).  !VN: the row of de is the pair index; N and nv are not read.  One kernel template, not two kernels around a
+// shared inlined body: so every instance keeps the instruction sequence it had as a kernel of its own
+// (profiles/embed_refactor_kres.txt).
 #define EMB_PPB 2048   // pairs per workgroup
-template <int K_, int V_, typename T>   // T: storage of de (float or bfloat16 bits); the sums stay fp32
+template <int K_, int V_, typename T, bool VN>   // T: storage of de (float or bfloat16 bits); the sums stay fp32
 __global__ void __launch_bounds__(256) k_edge_embed_bwd(const int32_t* __restrict__ fmat, const float* __restrict__ hops,
                                                         const T* __restrict__ de, float* __restrict__ part, long pairs,
-                                                        int De, int C4P) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];   // [PL pair lanes][(K+V)][De]
-  const int C4 = De / 4;
-  const int PL = 256 / C4P;
-  const int c4 = threadIdx.x % C4P, pl = threadIdx.x / C4P;
-  float4 aw[K_], at[V_];
-#pragma unroll
-  for (int k = 0; k < K_; ++k) aw[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int v = 0; v < V_; ++v) at[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-  const long p0 = (long)blockIdx.x * EMB_PPB;
-  const long p1 = min(pairs, p0 + EMB_PPB);
-  if (c4 < C4) {
-    for (long pair = p0 + pl; pair < p1; pair += PL) {
-      const float4 d = embed_load4(de + pair * De + 4 * c4);
-      const float* hp = hops + pair;
-      int f = fmat[pair] + 1;
-      f = min(max(f, 0), V_ - 1);
-#pragma unroll
-      for (int k = 0; k < K_; ++k) {
-        const float hv = hp[(size_t)k * pairs];
-        aw[k].x = fmaf(hv, d.x, aw[k].x); aw[k].y = fmaf(hv, d.y, aw[k].y);
-        aw[k].z = fmaf(hv, d.z, aw[k].z); aw[k].w = fmaf(hv, d.w, aw[k].w);
-      }
-#pragma unroll
-      for (int v = 0; v < V_; ++v) {   // branch-free one-hot accumulate (static register indexing)
-        const float s = (f == v) ? 1.0f : 0.0f;
-        at[v].x = fmaf(s, d.x, at[v].x); at[v].y = fmaf(s, d.y, at[v].y);
-        at[v].z = fmaf(s, d.z, at[v].z); at[v].w = fmaf(s, d.w, at[v].w);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < K_; ++k) *reinterpret_cast<float4*>(sm + ((size_t)pl * (K_ + V_) + k) * De + 4 * c4) = aw[k];
-#pragma unroll
-    for (int v = 0; v < V_; ++v) *reinterpret_cast<float4*>(sm + ((size_t)pl * (K_ + V_) + K_ + v) * De + 4 * c4) = at[v];
-  }
-  __syncthreads();
-  const int R = (K_ + V_) * De;
-  float* out = part + (size_t)blockIdx.x * R;
-  for (int i = threadIdx.x; i < R; i += 256) {
-    float s = 0.f;
-    for (int j = 0; j < PL; ++j) s += sm[(size_t)j * R + i];   // fixed order: bit-reproducible
-    out[i] = s;
-  }
-}
-
-// the same contraction over the INTERIOR of the bordered gradient de [B,N',N',De] (N' = nv + N): pair (b, l, m) sits at row
-// q = (b N' + nv + l) N' + nv + m of de; q follows the pair walk (one division per thread, before the loop).  A kernel of its
-// own, not a switch in k_edge_embed_bwd: that kernel's instances stay instruction for instruction what they were.
-// (Its twin: everything but the walk of q is k_edge_embed_bwd's text, and a fix to either belongs in both.)
-template <int K_, int V_, typename T>
-__global__ void __launch_bounds__(256) k_edge_embed_vn_bwd(const int32_t* __restrict__ fmat, const float* __restrict__ hops,
-                                                           const T* __restrict__ de, float* __restrict__ part, long pairs,
-                                                           int De, int C4P, int N, int nv) {
+                                                        int De, int C4P, int N, int nv) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // [PL pair lanes][(K+V)][De]
   const int C4 = De / 4;
   const int PL = 256 / C4P;
@@ -328,17 +276,21 @@ __global__ void __launch_bounds__(256) k_edge_embed_vn_bwd(const int32_t* __rest
   if (c4 < C4) {
     long q = 0;
     int l = 0, m = 0;
-    if (p0 + pl < p1) {
-      const long row = (p0 + pl) / N, NV = nv + N;
-      m = (int)((p0 + pl) % N); l = (int)(row % N);
-      q = ((row / N) * NV + nv + l) * NV + nv + m;
+    if constexpr (VN) {
+      if (p0 + pl < p1) {
+        const long row = (p0 + pl) / N, NV = nv + N;
+        m = (int)((p0 + pl) % N); l = (int)(row % N);
+        q = ((row / N) * NV + nv + l) * NV + nv + m;
+      }
     }
     for (long pair = p0 + pl; pair < p1; pair += PL) {
-      const float4 d = embed_load4(de + q * De + 4 * c4);
-      m += PL; q += PL;
-      while (m >= N) {   // next interior row: past the nv virtual columns; next graph: past its nv virtual rows too
-        m -= N; q += nv;
-        if (++l == N) { l = 0; q += (long)nv * (nv + N); }
+      const float4 d = embed_load4(de + (VN ? q : pair) * De + 4 * c4);
+      if constexpr (VN) {
+        m += PL; q += PL;
+        while (m >= N) {   // next interior row: past the nv virtual columns; next graph: past its nv virtual rows too
+          m -= N; q += nv;
+          if (++l == N) { l = 0; q += (long)nv * (nv + N); }
+        }
       }
       const float* hp = hops + pair;
       int f = fmat[pair] + 1;
@@ -436,22 +388,18 @@ __global__ void __launch_bounds__(64) k_edge_embed_bias_grad(const float* __rest
   dbias[c] = b;
 }
 
-static int embed_check(const egt_embed_desc* d) {
-  if (!d) EGT_FAIL(EGT_E_NULL, "desc is NULL");
-  if (d->B <= 0 || d->N <= 0) EGT_FAIL(EGT_E_SHAPE, "B and N must be positive");
-  if (d->De < 4 || d->De > 64 || d->De % 4) EGT_FAIL(EGT_E_SHAPE, "edge embedding covers edge_width in 4..64, multiple of 4 (got %d)", d->De);
-  if (d->upto_hop < 1 || d->upto_hop > 16) EGT_FAIL(EGT_E_SHAPE, "upto_hop must be in 1..16 (got %d)", d->upto_hop);
-  if (d->num_float_features < 0 || d->num_float_features > 4) EGT_FAIL(EGT_E_SHAPE, "num_float_features must be in 0..4 (got %d)", d->num_float_features);
-  if (d->num_edge_features < 0 || d->num_edge_features > 7) EGT_FAIL(EGT_E_SHAPE, "num_edge_features must be in 0..7 (got %d)", d->num_edge_features);
-  if (d->dtype != EGT_F32 && d->dtype != EGT_BF16) EGT_FAIL(EGT_E_DTYPE, "edge embedding stores e0 / reads de as EGT_F32 or EGT_BF16 (got %d)", d->dtype);
+// what the embedding covers: `report` leaves the reason with egt_last_error (the entry points), or not (the *_supported queries)
+static int embed_check(const egt_embed_desc* d, bool report) {
+  if (!d) EGT_BAD(EGT_E_NULL, "desc is NULL");
+  if (d->B <= 0 || d->N <= 0) EGT_BAD(EGT_E_SHAPE, "B and N must be positive");
+  if (d->De < 4 || d->De > 64 || d->De % 4) EGT_BAD(EGT_E_SHAPE, "edge embedding covers edge_width in 4..64, multiple of 4 (got %d)", d->De);
+  if (d->upto_hop < 1 || d->upto_hop > 16) EGT_BAD(EGT_E_SHAPE, "upto_hop must be in 1..16 (got %d)", d->upto_hop);
+  if (d->num_float_features < 0 || d->num_float_features > 4) EGT_BAD(EGT_E_SHAPE, "num_float_features must be in 0..4 (got %d)", d->num_float_features);
+  if (d->num_edge_features < 0 || d->num_edge_features > 7) EGT_BAD(EGT_E_SHAPE, "num_edge_features must be in 0..7 (got %d)", d->num_edge_features);
+  if (d->dtype != EGT_F32 && d->dtype != EGT_BF16) EGT_BAD(EGT_E_DTYPE, "edge embedding stores e0 / reads de as EGT_F32 or EGT_BF16 (got %d)", d->dtype);
   return EGT_OK;
 }
-extern "C" int egt_edge_embed_supported(const egt_embed_desc* d) {
-  if (!d) return 0;
-  return d->B > 0 && d->N > 0 && d->De >= 4 && d->De <= 64 && d->De % 4 == 0 && d->upto_hop >= 1 && d->upto_hop <= 16 &&
-         d->num_float_features >= 0 && d->num_float_features <= 4 &&
-         d->num_edge_features >= 0 && d->num_edge_features <= 7 && (d->dtype == EGT_F32 || d->dtype == EGT_BF16);
-}
+extern "C" int egt_edge_embed_supported(const egt_embed_desc* d) { return embed_check(d, false) == EGT_OK; }
 extern "C" size_t egt_edge_embed_hops_bytes(const egt_embed_desc* d) {
   if (!egt_edge_embed_supported(d)) return 0;
   return (size_t)d->B * d->N * d->N * (d->upto_hop + d->num_float_features) * sizeof(float);
@@ -469,7 +417,7 @@ extern "C" size_t egt_edge_embed_workspace_bytes(const egt_embed_desc* d) {
 static void embed_planes(const egt_embed_desc* d, const void* graph_matrix, const void* float_features, void* hops,
                          hipStream_t st) {
   const long pairs = (long)d->B * d->N * d->N;
-  const int KH = d->upto_hop, K = KH + d->num_float_features, T2 = (d->N + 31) / 32;
+  const int KH = d->upto_hop, T2 = (d->N + 31) / 32;
   // one launch for all planes when the adjacency and one column block fit in LDS (N <= ~180), else a launch per hop
   int CT = 0;
   {
@@ -490,65 +438,78 @@ static void embed_planes(const egt_embed_desc* d, const void* graph_matrix, cons
   }
   if (!CT) {
     EGT_LAUNCH("k_hop_first", k_hop_first, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, (const float*)graph_matrix,
-               (float*)hops, pairs, K);
+               (float*)hops, pairs);
     for (int k = 1; k < KH; ++k)
       EGT_LAUNCH("k_hop_step", k_hop_step, dim3((unsigned)(d->B * T2 * T2)), dim3(64), 0, st, (const float*)graph_matrix,
-                 (float*)hops, d->B, d->N, K, k, d->clip_hops ? 1 : 0);
+                 (float*)hops, d->B, d->N, k, d->clip_hops ? 1 : 0);
   }
   if (d->num_float_features > 0)
     EGT_LAUNCH("k_feature_planes", k_feature_planes, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st,
                (const float*)float_features, (float*)hops + (size_t)KH * pairs, pairs, d->num_float_features, d->mask_value);
 }
 
+// f(T{}), T the storage type of the descriptor's edge tensors (e0, d_e): float, or uint16_t = bfloat16 bits
+template <typename F>
+static void embed_typed(const egt_embed_desc* d, F&& f) {
+  if (d->dtype == EGT_BF16) f(uint16_t{}); else f(float{});
+}
+// the channel-quad lanes of a backward workgroup: the power of two at or above De / 4
+static int embed_c4p(int De) {
+  int c4p = 1;
+  while (c4p < De / 4) c4p *= 2;
+  return c4p;
+}
+
+// the pointer checks of both forwards (`vn`: the bordered one, whose list names vn_table)
+static int embed_fwd_pointers(const egt_embed_desc* d, bool vn, bool one_is_null, const void* float_features) {
+  if (one_is_null)
+    EGT_FAIL(EGT_E_NULL, "feature_matrix/graph_matrix/fm_table/adj_kernel/adj_bias/%shops/e_out is NULL", vn ? "vn_table/" : "");
+  if (d->num_float_features > 0 && !float_features) EGT_FAIL(EGT_E_NULL, "num_float_features set but float_features is NULL");
+  return EGT_OK;
+}
+
 extern "C" int egt_edge_embed_fwd(const egt_embed_desc* d, const int32_t* feature_matrix, const void* graph_matrix,
                                   const void* float_features, const void* fm_table, const void* adj_kernel,
                                   const void* adj_bias, void* hops, void* e_out, void* stream) {
-  int rc = embed_check(d);
+  int rc = embed_check(d, true);
+  if (!rc) rc = embed_fwd_pointers(d, false, !feature_matrix || !graph_matrix || !fm_table || !adj_kernel || !adj_bias || !hops || !e_out,
+                                   float_features);
   if (rc) return rc;
-  if (!feature_matrix || !graph_matrix || !fm_table || !adj_kernel || !adj_bias || !hops || !e_out)
-    EGT_FAIL(EGT_E_NULL, "feature_matrix/graph_matrix/fm_table/adj_kernel/adj_bias/hops/e_out is NULL");
   hipStream_t st = (hipStream_t)stream;
   const long pairs = (long)d->B * d->N * d->N;
-  if (d->num_float_features > 0 && !float_features) EGT_FAIL(EGT_E_NULL, "num_float_features set but float_features is NULL");
   const int K = d->upto_hop + d->num_float_features, V = d->num_edge_features + 1;
   embed_planes(d, graph_matrix, float_features, hops, st);
   const long threads = pairs * (d->De / 4);
   const size_t lds = (size_t)(K + V) * d->De * sizeof(float);
-  if (d->dtype == EGT_BF16)
-    EGT_LAUNCH("k_edge_embed_fwd", (k_edge_embed_fwd<16, uint16_t>), dim3((unsigned)((threads + 255) / 256)), dim3(256), lds, st,
-               feature_matrix, (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias,
-               (uint16_t*)e_out, pairs, d->De, K, V);
-  else
-    EGT_LAUNCH("k_edge_embed_fwd", (k_edge_embed_fwd<16, float>), dim3((unsigned)((threads + 255) / 256)), dim3(256), lds, st,
-               feature_matrix, (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias,
-               (float*)e_out, pairs, d->De, K, V);
+  embed_typed(d, [&](auto t) {
+    using T = decltype(t);
+    EGT_LAUNCH("k_edge_embed_fwd", k_edge_embed_fwd<T>, dim3((unsigned)((threads + 255) / 256)), dim3(256), lds, st, feature_matrix,
+               (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias, (T*)e_out, pairs, d->De,
+               K, V);
+  });
   EGT_HIP_LAUNCH_CHECK("egt_edge_embed_fwd");
   return EGT_OK;
 }
 
+template <int K_, int V_, typename T, bool VN>
+static void launch_embed_bwd_instance(const egt_embed_desc* d, const int32_t* fmat, const float* hops, const T* de, float* part,
+                                      hipStream_t st, int nv) {
+  int c4p = embed_c4p(d->De);
+  while ((size_t)(256 / c4p) * (K_ + 8) * d->De * sizeof(float) > 150 * 1024) c4p *= 2;   // LDS reduction image must fit
+  const size_t lds = (size_t)(256 / c4p) * (K_ + V_) * d->De * sizeof(float);
+  EGT_MAX_LDS_ONCE((k_edge_embed_bwd<K_, V_, T, VN>));
+  EGT_LAUNCH(VN ? "k_edge_embed_vn_bwd" : "k_edge_embed_bwd", (k_edge_embed_bwd<K_, V_, T, VN>), dim3(embed_nparts(d)), dim3(256), lds,
+             st, fmat, hops, de, part, (long)d->B * d->N * d->N, d->De, c4p, d->N, nv);
+}
 template <int K_, typename T>
 static void launch_embed_bwd(const egt_embed_desc* d, const int32_t* fmat, const float* hops, const T* de, float* part,
-                             hipStream_t st, int nv = 0) {   // nv > 0: de is the bordered [B,nv+N,nv+N,De] gradient
-  const long pairs = (long)d->B * d->N * d->N;
-  const int nparts = embed_nparts(d);
-  int c4p = 1;
-  while (c4p < d->De / 4) c4p *= 2;
-  while ((size_t)(256 / c4p) * (K_ + 8) * d->De * sizeof(float) > 150 * 1024) c4p *= 2;   // LDS reduction image must fit
-#define EB(V_)                                                                                                      \
-  do {                                                                                                              \
-    const size_t lds = (size_t)(256 / c4p) * (K_ + V_) * d->De * sizeof(float);                                     \
-    if (nv > 0) {                                                                                                   \
-      EGT_MAX_LDS_ONCE((k_edge_embed_vn_bwd<K_, V_, T>));                                                           \
-      EGT_LAUNCH("k_edge_embed_vn_bwd", (k_edge_embed_vn_bwd<K_, V_, T>), dim3(nparts), dim3(256), lds, st, fmat, hops, de, part, \
-                 pairs, d->De, c4p, d->N, nv);                                                                      \
-    } else {                                                                                                        \
-      EGT_MAX_LDS_ONCE((k_edge_embed_bwd<K_, V_, T>));                                                              \
-      EGT_LAUNCH("k_edge_embed_bwd", (k_edge_embed_bwd<K_, V_, T>), dim3(nparts), dim3(256), lds, st, fmat, hops, de, part, pairs, d->De, c4p); \
-    }                                                                                                               \
-  } while (0)
+                             hipStream_t st, int nv) {   // nv > 0: de is the bordered [B,nv+N,nv+N,De] gradient
+#define EB(V_)                                                                                   \
+  if (nv > 0) launch_embed_bwd_instance<K_, V_, T, true>(d, fmat, hops, de, part, st, nv);       \
+  else launch_embed_bwd_instance<K_, V_, T, false>(d, fmat, hops, de, part, st, nv);             \
+  break
   switch (d->num_edge_features + 1) {
-    case 1: EB(1); break; case 2: EB(2); break; case 3: EB(3); break; case 4: EB(4); break;
-    case 5: EB(5); break; case 6: EB(6); break; case 7: EB(7); break; default: EB(8); break;
+    case 1: EB(1); case 2: EB(2); case 3: EB(3); case 4: EB(4); case 5: EB(5); case 6: EB(6); case 7: EB(7); default: EB(8);
   }
 #undef EB
 }
@@ -560,12 +521,10 @@ static void embed_bwd_interior(const egt_embed_desc* d, int nv, const int32_t* f
   const float* h = (const float*)hops;
   float* part = (float*)workspace;
   const int KT = d->upto_hop + d->num_float_features;   // hop planes + real-valued feature planes
-  const bool bf = d->dtype == EGT_BF16;
   switch (KT) {
-#define C(K_)                                                                                   \
-  case K_:                                                                                      \
-    if (bf) launch_embed_bwd<K_, uint16_t>(d, feature_matrix, h, (const uint16_t*)d_e, part, st, nv); \
-    else launch_embed_bwd<K_, float>(d, feature_matrix, h, (const float*)d_e, part, st, nv);         \
+#define C(K_)                                                                                                          \
+  case K_:                                                                                                             \
+    embed_typed(d, [&](auto t) { launch_embed_bwd<K_, decltype(t)>(d, feature_matrix, h, (const decltype(t)*)d_e, part, st, nv); }); \
     break;
     C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13) C(14) C(15) C(16) C(17) C(18) C(19) C(20)
 #undef C
@@ -581,7 +540,7 @@ static void embed_bwd_interior(const egt_embed_desc* d, int nv, const int32_t* f
 extern "C" int egt_edge_embed_bwd(const egt_embed_desc* d, const int32_t* feature_matrix, const void* hops,
                                   const void* d_e, void* d_fm_table, void* d_adj_kernel, void* d_adj_bias,
                                   void* workspace, void* stream) {
-  int rc = embed_check(d);
+  int rc = embed_check(d, true);
   if (rc) return rc;
   if (!feature_matrix || !hops || !d_e || !d_fm_table || !d_adj_kernel || !d_adj_bias || !workspace)
     EGT_FAIL(EGT_E_NULL, "feature_matrix/hops/d_e/d_fm_table/d_adj_kernel/d_adj_bias/workspace is NULL");
@@ -592,46 +551,40 @@ extern "C" int egt_edge_embed_bwd(const egt_embed_desc* d, const int32_t* featur
 
 // ---- the embedding bordered with nv virtual nodes (VNModel, lib/models/graph_model_base.py:212-246) ----
 #define EMB_MAX_VN 16
-extern "C" int egt_edge_embed_vn_supported(const egt_embed_desc* d, int32_t nv) {
-  if (nv < 1 || nv > EMB_MAX_VN || !egt_edge_embed_supported(d)) return 0;
-  const long NV = (long)nv + d->N;
-  return NV * NV * (d->De / 4) < (1l << 31) && ((NV * NV * (d->De / 4) + 255) / 256) * d->B < (1l << 31) &&
-         (long)d->B * nv < (1l << 31);
+static int embed_vn_check(const egt_embed_desc* d, int32_t nv, bool report) {
+  int rc = embed_check(d, report);
+  if (rc) return rc;
+  if (nv < 1 || nv > EMB_MAX_VN) EGT_BAD(EGT_E_SHAPE, "num_virtual_nodes must be in 1..%d (got %d)", EMB_MAX_VN, nv);
+  const long NV = (long)nv + d->N;   // 32-bit index math inside a graph, 32-bit grids
+  if (NV * NV * (d->De / 4) >= (1l << 31) || ((NV * NV * (d->De / 4) + 255) / 256) * d->B >= (1l << 31) || (long)d->B * nv >= (1l << 31))
+    EGT_BAD(EGT_E_SHAPE, "bordered edge embedding: (nv + N)^2 De / 4 must stay below 2^31 per graph");
+  return EGT_OK;
 }
+extern "C" int egt_edge_embed_vn_supported(const egt_embed_desc* d, int32_t nv) { return embed_vn_check(d, nv, false) == EGT_OK; }
 extern "C" size_t egt_edge_embed_vn_workspace_bytes(const egt_embed_desc* d, int32_t nv) {
   if (!egt_edge_embed_vn_supported(d, nv)) return 0;
   return egt_edge_embed_workspace_bytes(d) + (size_t)d->B * nv * d->De * sizeof(float);
-}
-static int embed_vn_check(const egt_embed_desc* d, int32_t nv) {
-  int rc = embed_check(d);
-  if (rc) return rc;
-  if (nv < 1 || nv > EMB_MAX_VN) EGT_FAIL(EGT_E_SHAPE, "num_virtual_nodes must be in 1..%d (got %d)", EMB_MAX_VN, nv);
-  if (!egt_edge_embed_vn_supported(d, nv)) EGT_FAIL(EGT_E_SHAPE, "bordered edge embedding: (nv + N)^2 De / 4 must stay below 2^31 per graph");
-  return EGT_OK;
 }
 
 extern "C" int egt_edge_embed_vn_fwd(const egt_embed_desc* d, int32_t nv, const int32_t* feature_matrix, const void* graph_matrix,
                                      const void* float_features, const void* fm_table, const void* adj_kernel,
                                      const void* adj_bias, const void* vn_table, void* hops, void* e_out, void* stream) {
-  int rc = embed_vn_check(d, nv);
+  int rc = embed_vn_check(d, nv, true);
+  if (!rc) rc = embed_fwd_pointers(d, true, !feature_matrix || !graph_matrix || !fm_table || !adj_kernel || !adj_bias || !vn_table ||
+                                   !hops || !e_out, float_features);
   if (rc) return rc;
-  if (!feature_matrix || !graph_matrix || !fm_table || !adj_kernel || !adj_bias || !vn_table || !hops || !e_out)
-    EGT_FAIL(EGT_E_NULL, "feature_matrix/graph_matrix/fm_table/adj_kernel/adj_bias/vn_table/hops/e_out is NULL");
-  if (d->num_float_features > 0 && !float_features) EGT_FAIL(EGT_E_NULL, "num_float_features set but float_features is NULL");
   hipStream_t st = (hipStream_t)stream;
   const long pairs = (long)d->B * d->N * d->N, NV = (long)nv + d->N;
   const int K = d->upto_hop + d->num_float_features, V = d->num_edge_features + 1;
   embed_planes(d, graph_matrix, float_features, hops, st);
   const unsigned bpg = (unsigned)((NV * NV * (d->De / 4) + 255) / 256);   // workgroups per graph
   const size_t lds = (size_t)(K + V + nv) * d->De * sizeof(float);
-  if (d->dtype == EGT_BF16)
-    EGT_LAUNCH("k_edge_embed_vn_fwd", (k_edge_embed_vn_fwd<16, uint16_t>), dim3(bpg * (unsigned)d->B), dim3(256), lds, st,
-               feature_matrix, (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias,
-               (const float*)vn_table, (uint16_t*)e_out, pairs, d->N, nv, d->De, K, V, bpg);
-  else
-    EGT_LAUNCH("k_edge_embed_vn_fwd", (k_edge_embed_vn_fwd<16, float>), dim3(bpg * (unsigned)d->B), dim3(256), lds, st,
-               feature_matrix, (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias,
-               (const float*)vn_table, (float*)e_out, pairs, d->N, nv, d->De, K, V, bpg);
+  embed_typed(d, [&](auto t) {
+    using T = decltype(t);
+    EGT_LAUNCH("k_edge_embed_vn_fwd", k_edge_embed_vn_fwd<T>, dim3(bpg * (unsigned)d->B), dim3(256), lds, st, feature_matrix,
+               (const float*)hops, (const float*)fm_table, (const float*)adj_kernel, (const float*)adj_bias, (const float*)vn_table,
+               (T*)e_out, pairs, d->N, nv, d->De, K, V, bpg);
+  });
   EGT_HIP_LAUNCH_CHECK("egt_edge_embed_vn_fwd");
   return EGT_OK;
 }
@@ -639,7 +592,7 @@ extern "C" int egt_edge_embed_vn_fwd(const egt_embed_desc* d, int32_t nv, const 
 extern "C" int egt_edge_embed_vn_bwd(const egt_embed_desc* d, int32_t nv, const int32_t* feature_matrix, const void* hops,
                                      const void* d_e, void* d_fm_table, void* d_adj_kernel, void* d_adj_bias, void* d_vn_table,
                                      void* workspace, void* stream) {
-  int rc = embed_vn_check(d, nv);
+  int rc = embed_vn_check(d, nv, true);
   if (rc) return rc;
   if (!feature_matrix || !hops || !d_e || !d_fm_table || !d_adj_kernel || !d_adj_bias || !d_vn_table || !workspace)
     EGT_FAIL(EGT_E_NULL, "feature_matrix/hops/d_e/d_fm_table/d_adj_kernel/d_adj_bias/d_vn_table/workspace is NULL");
@@ -647,14 +600,11 @@ extern "C" int egt_edge_embed_vn_bwd(const egt_embed_desc* d, int32_t nv, const 
   embed_bwd_interior(d, nv, feature_matrix, hops, d_e, d_fm_table, d_adj_kernel, d_adj_bias, workspace, st);
   // the border: one partial per (graph, virtual node) behind the interior partials, summed over the graphs in a fixed order
   float* vpart = (float*)((char*)workspace + egt_edge_embed_workspace_bytes(d));
-  int c4p = 1;
-  while (c4p < d->De / 4) c4p *= 2;
-  if (d->dtype == EGT_BF16)
-    EGT_LAUNCH("k_edge_embed_vn_border_bwd", k_edge_embed_vn_border_bwd<uint16_t>, dim3((unsigned)(d->B * nv)), dim3(256), 0, st,
-               (const uint16_t*)d_e, vpart, d->N, nv, d->De, c4p);
-  else
-    EGT_LAUNCH("k_edge_embed_vn_border_bwd", k_edge_embed_vn_border_bwd<float>, dim3((unsigned)(d->B * nv)), dim3(256), 0, st,
-               (const float*)d_e, vpart, d->N, nv, d->De, c4p);
+  embed_typed(d, [&](auto t) {
+    using T = decltype(t);
+    EGT_LAUNCH("k_edge_embed_vn_border_bwd", k_edge_embed_vn_border_bwd<T>, dim3((unsigned)(d->B * nv)), dim3(256), 0, st,
+               (const T*)d_e, vpart, d->N, nv, d->De, embed_c4p(d->De));
+  });
   const int R = nv * d->De;
   EGT_LAUNCH("k_edge_embed_bwd_reduce", k_edge_embed_bwd_reduce, dim3((R + 63) / 64), dim3(256), 0, st, (const float*)vpart, d->B,
              nv, 0, d->De, (float*)d_vn_table, (float*)nullptr, (float*)nullptr);   // V = 0: no table / bias part

@@ -96,6 +96,34 @@ def test_bordered_embedding_backward(De, edge_dtype, gpu, egt_lib):
     assert_close(dvn, want, name="d vn (box only)", **BWD)
 
 
+@pytest.mark.parametrize("edge_dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("F", [0, 1])
+@pytest.mark.parametrize("De", [8, 48])
+@pytest.mark.parametrize("nv", [1, 3])
+def test_bordered_backward_is_the_plain_backward_of_the_interior(nv, De, F, edge_dtype, gpu, egt_lib):
+    """the gradients of table, W and b (and of the feature Dense) from the bordered d_e are, bit for bit, those of the plain
+    embedding from d_e[:, nv:, nv:]: both kernels walk the pairs in one order.  B N N = 2250 pairs: the second 2048-pair workgroup
+    starts mid-row (graph 81, row 4, column 3).  N = 5 is below the pair lanes at either width (128 at De = 8, 16 at De = 48):
+    one step of the row walk crosses several rows, at De = 8 several graphs.  De = 48: 12 quads on 16 quad lanes, so idle lanes
+    meet the bordered walk.  F = 0: a table of 5 rows; F = 1: one row and one real-valued feature plane."""
+    B, N, K = 90, 5, 4
+    adj, fm, ff, p = _embed_inputs(B, N, De, K, nv, F, seed=1000 + nv * 100 + De + F)
+    g = torch.Generator().manual_seed(7 + De + nv)
+    de = torch.randn(B, nv + N, nv + N, De, generator=g).to(DT[edge_dtype])
+    names = [k for k in p if k != "vn"]
+    e, q = _run_embed(adj, fm, ff, p, gpu, edge_dtype)
+    e.backward(de.to(gpu))
+    e0, q0 = _run_embed(adj, fm, ff, p, gpu, edge_dtype, vn=False)
+    e0.backward(de[:, nv:, nv:].contiguous().to(gpu))
+    for k in names:
+        assert torch.equal(q[k].grad, q0[k].grad), f"d {k}: bordered and plain differ"
+    p64 = {k: v.double().requires_grad_() for k, v in p.items()}
+    ref = VR.embed_ref(fm, adj, p64["table"], p64["W"], p64["b"], p64["vn"], K, ff, p64.get("We"), p64.get("be"))
+    gr = torch.autograd.grad(ref, [p64[k] for k in names], de.double())
+    for k, r in zip(names, gr):
+        assert_close(q[k].grad, r, name=f"d {k}", **BWD)
+
+
 # ------------------------------------------------------------------------------------------------- models -----
 MODEL_CASES = {   # kind, model_width, edge_width, model_height, nv, edge_channel_type, edge_dtype, N, node counts
     "zinc_w48_nv2": ("zinc", 48, 48, 2, 2, "residual", "f32", 12, (9, 5, 12)),

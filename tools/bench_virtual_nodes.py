@@ -4,16 +4,21 @@ one virtual node costs a model step -- on the same GPU in the same run, every me
 
 (a) op scope: forward + backward of the embedding with nv = 1, fused (egt_edge_embed_vn_fwd / _bwd: one write of the
     [B,N',N',De] tensor, its gradient read once) against composed (edge_embed + two torch.cat passes, autograd's slice / pad
-    backward), at [128,64,64,64] fp32 and [128,150,150,8] bf16 (upto_hop 16).
+    backward), at [128,64,64,64] fp32 and [128,150,150,8] bf16 (upto_hop 16, a table of 5 rows), and at [128,150,150,8] bf16 with
+    one real-valued feature plane and a table of one row: the CIFAR10 embedding (backward instance <17, 1, bf16>); and at
+    [16,200,200,8] bf16, where the adjacency does not fit in LDS and the hop planes come from one k_hop_step launch per hop.
 (b) step scope: one training step (forward + loss + backward into a flat gradient buffer, eager) of the ZINC-500k model
     (B = 128, N = 64, widths 64 / 64, 10 layers) and the CIFAR10 model (B = 128, N = 150, widths 64 / 8, 4 layers) at nv = 0
-    and nv = 1.  --parent-tree DIR (a built checkout of the parent commit) adds the nv = 0 step of that tree, so that both values
-    come from one visit of one GPU.
-Every figure is the median of `--steps` individually timed iterations after `--warmup` untimed ones.
+    and nv = 1.
+--parent-tree DIR (a built checkout of the parent commit): every measurement is taken in that tree too, so that both values come
+from one visit of one GPU; --rounds R repeats the parent / this pair of every measurement R times, alternating.
+Every figure is the median of `--steps` individually timed iterations after `--warmup` untimed ones; a comparison takes the median
+of the R per-round medians.  Against the parent the margin is the parent's own spread: the largest minus the smallest of its
+per-round medians.
 
-    python tools/bench_virtual_nodes.py [--out profiles/virtual_nodes.jsonl] [--steps 20] [--warmup 5] [--parent-tree DIR]
+    python tools/bench_virtual_nodes.py [--out profiles/virtual_nodes.jsonl] [--steps 20] [--warmup 5] [--parent-tree DIR] [--rounds 3]
 
-Output: one JSON line per measurement, then one comparison line per row."""
+Output: one JSON line per measurement (with its tree and round), then one comparison line per row."""
 import argparse
 import json
 import os
@@ -22,7 +27,8 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OP_SHAPES = {"op_f32_n64_de64": (128, 64, 64, "f32"), "op_bf16_n150_de8": (128, 150, 8, "bf16")}
+OP_SHAPES = {"op_f32_n64_de64": (128, 64, 64, "f32", 0), "op_bf16_n150_de8": (128, 150, 8, "bf16", 0),   # B, N, De, edge dtype, F
+             "op_bf16_n150_de8_v1": (128, 150, 8, "bf16", 1), "op_bf16_n200_de8": (16, 200, 8, "bf16", 0)}
 MODELS = {"zinc_500k": ("zinc", 64, 64, 10, 64, (38, 64)), "cifar10": ("cifar10", 64, 8, 4, 150, (85, 150))}
 NV = 1
 
@@ -53,22 +59,27 @@ def child_op(args):
     import torch
     sys.path.insert(0, args.tree)
     from egt_amd import edge_embed
-    B, N, De, edt = OP_SHAPES[args.child]
+    B, N, De, edt, F = OP_SHAPES[args.child]
     dev = torch.device("cuda", 0)
     g = torch.Generator().manual_seed(0)
     _, adj = _graphs(B, N, int(0.6 * N), g)
-    fm = torch.where(adj > 0, torch.randint(0, 4, (B, N, N), generator=g), torch.tensor(-1)).to(dev)
-    adj = adj.to(dev)
-    prm = [torch.randn(s, generator=g).to(dev).requires_grad_() for s in ((5, De), (16, De), (De,), (NV, De))]
-    table, W, b, vn = prm
+    fm = torch.where(adj > 0, torch.randint(0, 4, (B, N, N), generator=g), torch.tensor(-1))
+    shapes = [(5, De), (16, De), (De,), (NV, De)]
+    if F:                                                 # real-valued features: no table index, F planes behind the hop planes
+        fm, shapes = torch.full((B, N, N), -1), [(1, De)] + shapes[1:] + [(F, De), (De,)]
+        ff = torch.rand(B, N, N, F, generator=g); ff[adj == 0] = -1.0
+    fm, adj = fm.to(dev), adj.to(dev)
+    prm = [torch.randn(s, generator=g).to(dev).requires_grad_() for s in shapes]
+    table, W, b, vn = prm[:4]
+    kw = dict(float_features=ff.to(dev), float_kernel=prm[4], float_bias=prm[5]) if F else {}
     dt = torch.bfloat16 if edt == "bf16" else torch.float32
     de = torch.randn(B, NV + N, NV + N, De, generator=g).to(dev).to(dt)
 
     def fused():
-        return edge_embed(fm, adj, table, W, b, edge_dtype=edt, virtual_edge_table=vn)
+        return edge_embed(fm, adj, table, W, b, edge_dtype=edt, virtual_edge_table=vn, **kw)
 
     def composed():                                       # virtual_nodes.py:86-99 with torch ops around the existing op
-        e = edge_embed(fm, adj, table, W, b, edge_dtype=edt)
+        e = edge_embed(fm, adj, table, W, b, edge_dtype=edt, **kw)
         v = vn.to(dt)
         rows = v[None, :, None, :].expand(B, NV, N, De)
         cols = v[None, None, :, :].expand(B, N, NV, De)
@@ -82,8 +93,8 @@ def child_op(args):
             fn().backward(de)
         med, ts = _timed(step, args.warmup, args.steps)
         out[route] = fn().detach().float()
-        print("RESULT " + json.dumps(dict(scope="op", case=args.child, shape=[B, N, N, De], nv=NV, edge_dtype=edt, route=route,
-                                          steps=args.steps, ms=med, min_ms=min(ts), max_ms=max(ts))), flush=True)
+        print("RESULT " + json.dumps(dict(scope="op", case=args.child, tree=args.tree_name, shape=[B, N, N, De], nv=NV, edge_dtype=edt,
+                                          float_features=F, route=route, steps=args.steps, ms=med, min_ms=min(ts), max_ms=max(ts))), flush=True)
     assert torch.equal(out["fused"], out["composed"]), "the two routes must time the same result"
 
 
@@ -126,7 +137,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--B", type=int, default=128)
     ap.add_argument("--only", default="op,step")
-    ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit: its nv = 0 model steps are timed too")
+    ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit: every measurement is taken there too")
+    ap.add_argument("--rounds", type=int, default=3, help="repetitions of every measurement (parent / this alternating)")
     ap.add_argument("--child", default=None)
     ap.add_argument("--tree", default=REPO)
     ap.add_argument("--tree-name", default="this")
@@ -137,9 +149,9 @@ def main():
         return child_op(args)
     if args.child:
         return child_step(args)
-    recs = []
+    recs, rounds = [], {}       # rounds[("op", case, route) | ("step", model, nv)][tree name]: the per-round medians
 
-    def run(child, nv=0, tree=REPO, name="this"):
+    def run(child, nv, tree, name, rnd):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", child, "--steps", str(args.steps), "--warmup", str(args.warmup),
                "--B", str(args.B), "--nv", str(nv), "--tree", os.path.abspath(tree), "--tree-name", name]
         r = subprocess.run(cmd, cwd=tree, capture_output=True, text=True, timeout=args.child_timeout)
@@ -148,34 +160,35 @@ def main():
             raise SystemExit(f"child {child} (nv={nv}, tree={name}) failed with exit status {r.returncode}")
         for line in r.stdout.splitlines():
             if line.startswith("RESULT "):
-                recs.append(json.loads(line[7:]))
-                print(line[7:], flush=True)
+                rec = dict(json.loads(line[7:]), round=rnd)
+                recs.append(rec)
+                key = ("op", rec["case"], rec["route"]) if rec["scope"] == "op" else ("step", rec["model"], rec["nv"])
+                rounds.setdefault(key, {}).setdefault(name, []).append(rec["ms"])
+                print(json.dumps(rec), flush=True)
 
-    if "op" in args.only.split(","):
-        for c in OP_SHAPES:
-            run(c)
-    if "step" in args.only.split(","):
-        for m in MODELS:
-            if args.parent_tree:
-                run(m, 0, args.parent_tree, "parent")
-            run(m, 0)
-            run(m, NV)
+    only = args.only.split(",")
+    trees = ([(args.parent_tree, "parent")] if args.parent_tree else []) + [(REPO, "this")]
+    for child, nv in [(c, 0) for c in OP_SHAPES if "op" in only] + [(m, nv) for m in MODELS for nv in (0, NV) if "step" in only]:
+        for rnd in range(args.rounds):
+            for tree, name in trees:
+                run(child, nv, tree, name, rnd)
+    med = lambda key, tree="this": statistics.median(rounds[key][tree])
     cmp_ = []
-    ops = {(r["case"], r["route"]): r for r in recs if r["scope"] == "op"}
     for c in OP_SHAPES:
-        if (c, "fused") in ops and (c, "composed") in ops:
-            f, b = ops[(c, "fused")]["ms"], ops[(c, "composed")]["ms"]
+        if ("op", c, "fused") in rounds:
+            f, b = med(("op", c, "fused")), med(("op", c, "composed"))
             cmp_.append(dict(compare=True, scope="op", case=c, fused_ms=f, composed_ms=b, gain_pct=round(100.0 * (b - f) / b, 2),
                              fused_is_faster=f < b))
-    st = {(r["model"], r["tree"], r["nv"]): r["ms"] for r in recs if r["scope"] == "step"}
     for m in MODELS:
-        if (m, "this", 0) in st and (m, "this", NV) in st:
-            row = dict(compare=True, scope="step", model=m, nv0_ms=st[(m, "this", 0)], nv1_ms=st[(m, "this", NV)],
-                       nv1_cost_pct=round(100.0 * (st[(m, "this", NV)] / st[(m, "this", 0)] - 1.0), 2))
-            if (m, "parent", 0) in st:
-                row.update(parent_nv0_ms=st[(m, "parent", 0)],
-                           nv0_vs_parent_pct=round(100.0 * (st[(m, "this", 0)] / st[(m, "parent", 0)] - 1.0), 2))
-            cmp_.append(row)
+        if ("step", m, 0) in rounds:
+            n0, n1 = med(("step", m, 0)), med(("step", m, NV))
+            cmp_.append(dict(compare=True, scope="step", model=m, nv0_ms=n0, nv1_ms=n1, nv1_cost_pct=round(100.0 * (n1 / n0 - 1.0), 2)))
+    if args.parent_tree:        # this tree may be slower than the parent by no more than the parent's own spread over the rounds
+        for key, by_tree in rounds.items():
+            t, p, spread = med(key), med(key, "parent"), max(by_tree["parent"]) - min(by_tree["parent"])
+            cmp_.append(dict(compare=True, against="parent", scope=key[0], case=key[1], **{"route" if key[0] == "op" else "nv": key[2]},
+                             this_ms=t, parent_ms=p, parent_round_ms=by_tree["parent"], this_round_ms=by_tree["this"],
+                             parent_spread_ms=spread, vs_parent_pct=round(100.0 * (t / p - 1.0), 2), no_slower=t - p <= spread))
     for c in cmp_:
         print(json.dumps(c), flush=True)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

@@ -8,6 +8,8 @@ symbol names normalised).  Kernels are matched by their demangled names.  Prints
 at a time) into SCRATCH_DIR/old and /new, one count line per translation unit; exit status 1 if any unit has differ, new-only or old unmatched above 0.
 --mnemonics (either mode): the opcode sequences only -- operands and .amdhsa metadata dropped (for a change that moves kernel-argument
 offsets; tools/kres.py compares registers, spills, scratch and LDS).
+--rename 'REGEX=>REPL' (either mode, repeatable, applied in order to OLD's demangled names before matching): for a change that renames
+kernels or alters their template or argument lists.
 """
 import concurrent.futures, difflib, importlib.util, os, re, subprocess, sys
 
@@ -41,6 +43,7 @@ def dem(names):
 def compare(old_s, new_s, label=''):   # prints the differing kernels and the count line; returns differ + new-only + old unmatched
     a, b = funcs(old_s), funcs(new_s)
     da, db = dem(list(a)), dem(list(b))
+    for pat, repl in RENAME: da = {k: re.sub(pat, repl, v) for k, v in da.items()}
     ia = {v: k for k, v in da.items()}
     same, diff, newonly = 0, 0, []
     for nb, d in db.items():
@@ -67,7 +70,8 @@ def compile_unit(build, tree, out, src):   # as build.build() compiles it, plus 
 
 argv = sys.argv[1:]
 MNEMONICS, SHOW = '--mnemonics' in argv, argv[argv.index('--show') + 1] if '--show' in argv else None
-pos = [x for i, x in enumerate(argv) if not x.startswith('-') and (i == 0 or argv[i - 1] != '--show')]
+RENAME = [argv[i + 1].split('=>') for i, x in enumerate(argv) if x == '--rename']
+pos = [x for i, x in enumerate(argv) if not x.startswith('-') and (i == 0 or argv[i - 1] not in ('--show', '--rename'))]
 if '--trees' not in argv: compare(pos[0], pos[1])
 else:
     spec = importlib.util.spec_from_file_location('egt_build', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'egt_amd', 'build.py'))

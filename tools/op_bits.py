@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""A sha256 per output tensor of single ops, over the cases of their GPU tests, for comparing two builds of the library bit by bit.
+One process loads one library: run it once per build (each run under its own time limit, chained with &&) and diff the listings.
+
+    python tools/op_bits.py [--ops head,embed] [--lib path/to/libegt_amd.so] > listing.txt      (--lib: the EGT_AMD_LIB of this process)
+
+head:  the fused edge head and node head over the cases of tests/test_distance_head_gpu.py and tests/test_node_head_gpu.py (their
+       CASES, the bf16 and the full-tile case).  Edge head: per_graph, d_e and the parameter gradients; node head: stats, d_h and the
+       parameter gradients (two without LayerNorm).
+embed: the edge embedding in both edge dtypes: e, hops and every parameter gradient.  Plain: the shapes of test_edge_embed_vs_oracle
+       and test_edge_embed_float_features_vs_oracle (tests/test_model.py), inputs of the tool's own seeds.  Bordered: the shapes,
+       graphs and parameters (_embed_inputs with the tests' seeds) of the three bordered embedding tests of
+       tests/test_virtual_nodes_gpu.py.  d_e is drawn by the tool in every case."""
+import argparse
+import hashlib
+import itertools
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def emit(tag, tensors):
+    import torch
+    for name, t in tensors:
+        raw = t.detach().contiguous().cpu().view(torch.uint8).numpy().tobytes()
+        print(f"{hashlib.sha256(raw).hexdigest()}  {tag} {name} {str(t.dtype)[6:]}{list(t.shape)}", flush=True)
+
+
+def params_of(test, names):
+    """the values of one pytest.mark.parametrize of `test`, by its argument names"""
+    return next(m.args[1] for m in test.pytestmark if m.name == "parametrize" and m.args[0] == names)
+
+
+def head(gpu):
+    import torch
+    import test_distance_head_gpu as TD
+    import test_node_head_gpu as TN
+    from egt_amd.node_head import node_head_loss
+
+    def out_of(out, first, grad_in, names):
+        return [(first, out[first]), (grad_in, out[grad_in])] + [("d " + n, g) for n, g in zip(names, out["grads"])]
+
+    edge = [(c, {}) for c in TD.CASES] + [((8, 64, 3, "relu", True), dict(dtype=torch.bfloat16)), ((64, 64, 3, "elu", True), dict(N=16))]
+    for case, kw in edge:
+        got = TD._run_case(gpu, *case, **kw)[0]
+        tag = "edge " + "-".join(map(str, case)) + "".join(f" {k}={str(v).replace('torch.', '')}" for k, v in kw.items())
+        emit(tag, out_of(got, "per_graph", "d_e", TD.DR.HEAD_NAMES if case[4] else TD.DR.HEAD_NAMES[2:]))
+    for case in TN.CASES:
+        x, params, _ = TN._reference(case)
+        got, _ = TN._run(node_head_loss, x, params, case[3], gpu)
+        emit("node " + "-".join(map(str, case)), out_of(got, "stats", "d_h", TN.NR.NAMES if case[4] else TN.NR.NAMES[2:]))
+
+
+def embed(gpu):
+    import torch
+    import test_model as TM
+    import test_virtual_nodes_gpu as TV
+    from egt_amd import edge_embed
+
+    def plain_inputs(B, N, De, K, V, F):
+        g = torch.Generator().manual_seed(B * 100 + N + F)
+        adj = (torch.rand(B, N, N, generator=g) > 0.8).float()
+        adj = ((adj + adj.transpose(1, 2)) > 0).float()
+        fm = torch.where(adj > 0, torch.randint(0, V - 1, (B, N, N), generator=g), torch.tensor(-1)) if V > 1 else torch.full((B, N, N), -1)
+        p = dict(table=torch.randn(V, De, generator=g) if V > 1 else torch.zeros(1, De), W=torch.randn(K, De, generator=g) * 0.3,
+                 b=torch.randn(De, generator=g) * 0.2)
+        ff = None
+        if F:
+            ff = torch.rand(B, N, N, F, generator=g); ff[adj == 0] = -1.0
+            p.update(We=torch.randn(F, De, generator=g), be=torch.randn(De, generator=g) * 0.2)
+        return adj, fm, ff, p
+
+    def run(tag, adj, fm, ff, p):
+        for edt in ("f32", "bf16"):
+            q = {k: v.to(gpu).requires_grad_() for k, v in p.items()}
+            kw = {} if ff is None else dict(float_features=ff.to(gpu), float_kernel=q["We"], float_bias=q["be"])
+            e, hops = edge_embed(fm.to(gpu), adj.to(gpu), q["table"], q["W"], q["b"], edge_dtype=edt, return_hops=True,
+                                 virtual_edge_table=q.get("vn"), **kw)
+            de = torch.randn(e.shape, generator=torch.Generator().manual_seed(e.shape[1])).to(e.dtype)
+            e.backward(de.to(gpu))
+            emit(f"{tag} {edt}", [("e", e), ("hops", hops)] + [("d " + k, v.grad) for k, v in q.items()])
+
+    for B, N, De, K, V in params_of(TM.test_edge_embed_vs_oracle, "B,N,De,K,V"):
+        run(f"embed B{B}-N{N}-De{De}-K{K}-V{V}", *plain_inputs(B, N, De, K, V, 0))
+    for B, N, De, K, F in params_of(TM.test_edge_embed_float_features_vs_oracle, "B,N,De,K,F"):
+        run(f"embed B{B}-N{N}-De{De}-K{K}-F{F}", *plain_inputs(B, N, De, K, 1, F))
+    # the bordered tests fix B, N, K (and nv) and the seed of _embed_inputs in their bodies
+    fwd = [(2, 19, 4, nv, De, F, nv * 100 + De + F)
+           for nv, De, F in params_of(TV.test_bordered_embedding_forward_is_the_plain_one_plus_the_border, "nv,De,F")]
+    bwd = [(3, 37, 4, 2, De, 0, De) for De in params_of(TV.test_bordered_embedding_backward, "De")]
+    t = TV.test_bordered_backward_is_the_plain_backward_of_the_interior
+    walk = [(90, 5, 4, nv, De, F, 1000 + nv * 100 + De + F)
+            for nv, De, F in itertools.product(params_of(t, "nv"), params_of(t, "De"), params_of(t, "F"))]
+    for B, N, K, nv, De, F, seed in fwd + bwd + walk:
+        run(f"embed_vn B{B}-N{N}-De{De}-K{K}-nv{nv}-F{F}", *TV._embed_inputs(B, N, De, K, nv, F, seed=seed))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--ops", default="head,embed")
+    args = ap.parse_args()
+    ops = args.ops.split(",")
+    if not ops or set(ops) - {"head", "embed"}:
+        ap.error("--ops takes head, embed or both")
+    if args.lib:
+        os.environ["EGT_AMD_LIB"] = os.path.abspath(args.lib)      # read when egt_amd._lib is imported
+    sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
+    import torch
+    gpu = torch.device("cuda", 0)
+    for op, fn in (("head", head), ("embed", embed)):
+        if op in ops:
+            fn(gpu)
+
+
+if __name__ == "__main__":
+    main()
