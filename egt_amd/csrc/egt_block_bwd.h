@@ -1,8 +1,9 @@
 // Backward pair kernels of the fused attention block (included by egt_block.hip, which holds the dispatch):
 // k_block_bwd_v4 (mask tensors / ragged N / bf16), k_block_bwd_v5 (LDS-DMA staged e tiles: the headline),
-// k_block_bwd_v4r (narrow edge channels, R rows per iteration).  Each kernel carries its OWN copy of the P3 softmax / gate backward,
-// the dK / dV / dQ block and the weight-gradient (edge-partial) epilogue.  The copies are deliberate: the kernels sit at the register
-// edge, and moving a phase into a shared helper changes their instruction streams and register counts.
+// k_block_bwd_v4r (narrow edge channels, R rows per iteration).  The phases of the per-tile body (K / V fragments, weight slabs, P1 .. P5,
+// the hand-off, dK / dV / dQ, the partial stores) are the bwd_* functions below; a kernel is its LDS carve-up, its staging
+// and its loop around them.  The kernels sit at the register edge: a change to a phase moves the register counts of all of them
+// (tools/kres.py; profiles/bwd_phases_kres.txt has the counts of this split against the three pasted copies it replaced).
 #pragma once
 // Cache-policy hints of the streamed tiles (egt_tile.h) in k_block_bwd_v5: e_l is read once (LDS-DMA, non-temporal), de' was written by
 // the launch before and de is the next launch's de' (both cached: 134 MB of the 256 MB memory-side cache at the headline batch).
@@ -16,6 +17,291 @@
 #ifndef EGT_NT_BWD_ST
 #define EGT_NT_BWD_ST false
 #endif
+
+// ================================================ tile phases of the backward =====
+// Every phase of the per-tile body, once.  Lane = (p, q) = (lane & 15, lane >> 4): key p of the tile, head pair q.  The kernels keep
+// what really differs: the LDS carve-up, staging and prefetch, the loop shape, the a.guard branches, the scheduling fences and the
+// LDS syncs between the phases (they shape hipcc's scheduling regions), v5's bf16 branches and the wave-pair hand-off.
+// Two kernels keep copies of their own where the shared function measured slower than the parent's pasted text (DESIGN 4.2 has the
+// figures): k_block_bwd_v5 its fp32 P1, P2 and P5 (interleaved with the MM != 0 branches), dQ / dK / dV and P4; k_block_bwd_v4 its P4.
+// A change to one of those phases is made here and in these copies.
+
+// K / V fragments of key row `rowm` ([B * N] row index, clamped by the caller): the 16 channels of the lane's head pair
+__device__ __forceinline__ void bwd_kv_frags(const BlockArgs& a, size_t rowm, int q, float (&Kf)[16], float (&Vf)[16]) {
+  const float4* kp = reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 64 + q * 16);
+  const float4* vp = reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 128 + q * 16);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float4 kv = kp[i], vv = vp[i];
+    Kf[4*i] = kv.x; Kf[4*i+1] = kv.y; Kf[4*i+2] = kv.z; Kf[4*i+3] = kv.w;
+    Vf[4*i] = vv.x; Vf[4*i+1] = vv.y; Vf[4*i+2] = vv.z; Vf[4*i+3] = vv.w;
+  }
+}
+__device__ __forceinline__ void bwd_dkv_zero(float (&dKa)[16], float (&dVa)[16]) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { dKa[i] = 0.f; dVa[i] = 0.f; }
+}
+
+// fp32 weight slabs [TILES][64 lanes] float4: element i = (t, lane, u) of wsA (projection weights wA[4t+u]), wsB (dH_ext weights
+// wrB[4t+u]) and wsD (d(ehat) weights wD[t][s])
+template <int DE>
+__device__ __forceinline__ void bwd_slab_elem(const BlockArgs& a, int i, float& wA, float& wB, float& wD) {
+  const int t = i >> 8, ln = (i >> 2) & 63, u = i & 3, pp = ln & 15, qq = ln >> 4;
+  const int c = 16 * t + 4 * qq + u;
+  const int hd = 2 * (pp >> 2) + (pp & 1);
+  wA = a.pw[c * 16 + pp];
+  wB = ((pp & 2) == 0 && c < DE) ? a.Wr[hd * DE + c] : 0.f;
+  wD = a.pw[(16 * t + pp) * 16 + 4 * qq + u];
+}
+template <int DE>
+__device__ __forceinline__ void bwd_fill_slabs(const BlockArgs& a, float* wsA, float* wsB, float* wsD) {
+  for (int i = threadIdx.x; i < Geo<DE>::TILES * 256; i += 256) bwd_slab_elem<DE>(a, i, wsA[i], wsB[i], wsD[i]);
+}
+
+// projection biases of the lane's head pair; zeroed weight-gradient accumulators and dGE column sums
+template <int DE>
+__device__ __forceinline__ void bwd_acc_init(const BlockArgs& a, int q, float (&c2r)[4], v4f (&accT)[Geo<DE>::TILES],
+                                             v4f (&accR)[Geo<DE>::TILES], float (&ssum)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) c2r[r] = a.pw[Geo<DE>::DEP * 16 + 4 * q + r];
+#pragma unroll
+  for (int t = 0; t < Geo<DE>::TILES; ++t) { accT[t] = (v4f){0.f, 0.f, 0.f, 0.f}; accR[t] = (v4f){0.f, 0.f, 0.f, 0.f}; }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) ssum[r] = 0.f;
+}
+
+// P1 (fp32): norm_edge of the e tile, xhat written back over it (it stays there for the later phases), projections recomputed:
+// returns (G, E) of the lane's two heads on top of the biases c2r
+template <int DE>
+__device__ __forceinline__ v4f bwd_p1_project(const BlockArgs& a, float* et, const float* wsA, int lane, int p, int q,
+                                              const float (&c2r)[4], float& rstd) {
+  using G = Geo<DE>;
+  v4f acc = {c2r[0], c2r[1], c2r[2], c2r[3]};
+  float4 x[G::TILES];
+#pragma unroll
+  for (int t = 0; t < G::TILES; ++t) x[t] = frag_read<DE>(et, p, q, t);
+  rstd = ln_frags<DE>(x, q, a.ln_eps, (a.flags & EGT_BF_NO_EDGE_LN) == 0);
+#pragma unroll
+  for (int t = 0; t < G::TILES; ++t) {
+    frag_write<DE>(et, p, q, t, x[t]);
+    const float4 w = *reinterpret_cast<const float4*>(wsA + (t * 64 + lane) * 4);
+    acc = MFMA(w.x, x[t].x, acc);
+    acc = MFMA(w.y, x[t].y, acc);
+    acc = MFMA(w.z, x[t].z, acc);
+    acc = MFMA(w.w, x[t].w, acc);
+  }
+  return acc;
+}
+
+// P2 (fp32): dH_ext = de'.Wr^T
+template <int DE>
+__device__ __forceinline__ v4f bwd_p2_dhext(const float* dt, const float* wsB, int lane, int p, int q) {
+  v4f dhx = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < Geo<DE>::TILES; ++t) {
+    const float4 dyv = frag_read<DE>(dt, p, q, t);
+    const float4 w = *reinterpret_cast<const float4*>(wsB + (t * 64 + lane) * 4);
+    dhx = MFMA(w.x, dyv.x, dhx);
+    dhx = MFMA(w.y, dyv.y, dhx);
+    dhx = MFMA(w.z, dyv.z, dhx);
+    dhx = MFMA(w.w, dyv.w, dhx);
+  }
+  return dhx;
+}
+
+// P3: logits of the lane's two heads against query row qr (Q | dV_att | stats of the row in LDS), clip, masks, softmax / gate
+// backward.  dge = (dG, dH) per head, hh = the clipped logits + E (H_hat), dA = d(Q.K) scaled, at = S * gate.
+// The Q / dV_att fragments are fetched from LDS here and again in bwd_dqkv_accum instead of being held across the exp / sigmoid chain.
+// RAG: a key past N (!kvalid) gets probability and gate exactly 0.  GP: its gate goes through the sigmoid also without EGT_BF_GATE.
+template <bool ML, bool RAG, bool GP>
+__device__ __forceinline__ void bwd_pair_grad(const BlockArgs& a, const float* qr, const float (&Kf)[16], const float (&Vf)[16],
+                                              const v4f& acc, const v4f& dhx, float kadd, const MaskRegs& mr, size_t idx8, int q,
+                                              bool kvalid, bool gated, bool clip, float (&dge)[4], float (&hh)[2], float (&dA)[2],
+                                              float (&at)[2]) {
+  float dots[2], dAd[2];
+  {
+    const float4* qp = reinterpret_cast<const float4*>(qr + q * 16);
+    const float4* dp = reinterpret_cast<const float4*>(qr + 64 + q * 16);
+    float d0 = 0.f, d1 = 0.f, e0 = 0.f, e1 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float4 u = qp[i], v = dp[i];
+      d0 = fmaf(u.x, Kf[4*i], d0);   d1 = fmaf(u.y, Kf[4*i+1], d1);
+      d0 = fmaf(u.z, Kf[4*i+2], d0); d1 = fmaf(u.w, Kf[4*i+3], d1);
+      e0 = fmaf(v.x, Vf[4*i], e0);   e1 = fmaf(v.y, Vf[4*i+1], e1);
+      e0 = fmaf(v.z, Vf[4*i+2], e0); e1 = fmaf(v.w, Vf[4*i+3], e1);
+    }
+    dots[0] = d0; dots[1] = d1; dAd[0] = e0; dAd[1] = e1;
+  }
+  const float4* sp = reinterpret_cast<const float4*>(qr + 128 + q * 8);
+  const float4 s0 = sp[0], s1 = sp[1];
+  const float st[8] = {s0.x, s0.y, s0.z, 0.f, s1.x, s1.y, s1.z, 0.f};
+  float xl[2], gl[2], inr[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const float araw = dots[j] * a.scale;
+    float ah = araw;
+    inr[j] = 1.0f;
+    if (clip) {
+      inr[j] = (araw >= a.clip_lo && araw <= a.clip_hi) ? 1.0f : 0.0f;
+      ah = fminf(fmaxf(araw, a.clip_lo), a.clip_hi);
+    }
+    hh[j] = ah + acc[2 * j + 1];
+    xl[j] = hh[j];
+    gl[j] = acc[2 * j];
+  }
+  apply_masks<ML>(a, kadd, mr, idx8, q, xl, gl);
+  if (RAG && !kvalid) { xl[0] = xl[1] = -3.0e38f; gl[0] = gl[1] = -3.0e38f; }   // a key past N: S = 0, gate = 0 (exactly)
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const float S = __expf(xl[j] - st[4 * j]) * st[4 * j + 1];
+    const float g = (gated || (GP && RAG && !kvalid)) ? egt_sigmoid(gl[j]) : 1.0f;
+    const float dS = dAd[j] * g;
+    const float dGl = gated ? dAd[j] * S * g * (1.0f - g) : 0.f;
+    const float dH = S * (dS - st[4 * j + 2]) + dhx[j];
+    dA[j] = dH * inr[j] * a.scale;
+    at[j] = S * g;
+    dge[2 * j] = dGl;
+    dge[2 * j + 1] = dH;
+  }
+}
+
+// dGE / H_hat of the lane's pair to the hand-off tiles sc1 [16][16] / sc2 [16][12] (column 8 of sc2 = 1: the bias row of dense_edge_r);
+// the dGE column sums take their share.  The caller syncs the LDS before P4 reads the tiles.
+__device__ __forceinline__ void bwd_handoff(float* sc1, float* sc2, int p, int q, const float (&dge)[4], const float (&hh)[2],
+                                            float (&ssum)[4]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) ssum[r] += dge[r];
+  *reinterpret_cast<float4*>(sc1 + p * 16 + 4 * q) = make_float4(dge[0], dge[1], dge[2], dge[3]);
+  *reinterpret_cast<float2*>(sc2 + p * 12 + 2 * q) = make_float2(hh[0], hh[1]);
+  if (q == 0) sc2[p * 12 + 8] = 1.0f;
+}
+
+// dK / dV accumulation of the lane's key over query row qr; the row's dQ partial over this tile's 16 keys goes to *dqo (HBM: summed
+// over the key tiles by the next prologue or k_node_bwd)
+__device__ __forceinline__ void bwd_dqkv_accum(const float* qr, int p, int q, const float (&Kf)[16], const float (&dA)[2],
+                                               const float (&at)[2], float (&dKa)[16], float (&dVa)[16], float* dqo) {
+  const float4* qp = reinterpret_cast<const float4*>(qr + q * 16);
+  const float4* dp = reinterpret_cast<const float4*>(qr + 64 + q * 16);
+  float dq[16];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float4 u = qp[i], v = dp[i];
+    dKa[4*i]   = fmaf(dA[0], u.x, dKa[4*i]);   dKa[4*i+1] = fmaf(dA[1], u.y, dKa[4*i+1]);
+    dKa[4*i+2] = fmaf(dA[0], u.z, dKa[4*i+2]); dKa[4*i+3] = fmaf(dA[1], u.w, dKa[4*i+3]);
+    dVa[4*i]   = fmaf(at[0], v.x, dVa[4*i]);   dVa[4*i+1] = fmaf(at[1], v.y, dVa[4*i+1]);
+    dVa[4*i+2] = fmaf(at[0], v.z, dVa[4*i+2]); dVa[4*i+3] = fmaf(at[1], v.w, dVa[4*i+3]);
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { dq[2 * k] = dA[0] * Kf[2 * k]; dq[2 * k + 1] = dA[1] * Kf[2 * k + 1]; }
+  *dqo = reduce16_keep_own(dq, p);
+}
+
+// P4: weight-gradient contractions over the 16 pairs of the tile: accT += xhat^T.dGE, accR += de'^T.[H_hat | 1].
+// rd(tile, s, t) reads element (pair q + 4s, channel 16t + p) of the e / de' tile.
+template <int DE, class RD>
+__device__ __forceinline__ void bwd_wgrad_accum(const float* et, const float* dt, const float* sc1, const float* sc2, int p, int q,
+                                                v4f (&accT)[Geo<DE>::TILES], v4f (&accR)[Geo<DE>::TILES], RD rd) {
+  float bT[4], bR[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    bT[s] = sc1[(q + 4 * s) * 16 + p];
+    bR[s] = (p < 9) ? sc2[(q + 4 * s) * 12 + p] : 0.f;
+  }
+#pragma unroll
+  for (int t = 0; t < Geo<DE>::TILES; ++t)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      accT[t] = MFMA(rd(et, s, t), bT[s], accT[t]);
+      accR[t] = MFMA(rd(dt, s, t), bR[s], accR[t]);
+    }
+}
+
+// P5a: d(ehat) = Wp . dGE per fragment (wd(t): the product of tile t, bwd_dehat_f32 for the fp32 kernels) and the two LayerNorm-backward
+// means m1 = mean(d ehat), m2 = mean(d ehat * xhat) of the lane's pair (0 without norm_edge: d e = de' + d(proj input))
+__device__ __forceinline__ v4f bwd_dehat_f32(const float* wsD, int lane, int t, const float (&dge)[4]) {
+  const float4 w = *reinterpret_cast<const float4*>(wsD + (t * 64 + lane) * 4);
+  v4f d = {0.f, 0.f, 0.f, 0.f};
+  d = MFMA(w.x, dge[0], d);
+  d = MFMA(w.y, dge[1], d);
+  d = MFMA(w.z, dge[2], d);
+  d = MFMA(w.w, dge[3], d);
+  return d;
+}
+template <int DE, class WD>
+__device__ __forceinline__ void bwd_dehat(const BlockArgs& a, const float* et, int p, int q, float4 (&dxh)[Geo<DE>::TILES], float& m1,
+                                          float& m2, WD wd) {
+  m1 = 0.f; m2 = 0.f;
+#pragma unroll
+  for (int t = 0; t < Geo<DE>::TILES; ++t) {
+    const float4 xh = frag_read<DE>(et, p, q, t);
+    const v4f d = wd(t);
+    dxh[t] = make_float4(d[0], d[1], d[2], d[3]);
+    m1 += (d[0] + d[1]) + (d[2] + d[3]);
+    m2 = fmaf(d[0], xh.x, m2); m2 = fmaf(d[1], xh.y, m2);
+    m2 = fmaf(d[2], xh.z, m2); m2 = fmaf(d[3], xh.w, m2);
+  }
+  m1 = sum_over_q(m1) * (1.0f / DE);
+  m2 = sum_over_q(m2) * (1.0f / DE);
+  if (a.flags & EGT_BF_NO_EDGE_LN) { m1 = 0.f; m2 = 0.f; }
+}
+
+// P5b: de = de' + rstd (d ehat - m1 - xhat m2) of one fragment
+__device__ __forceinline__ float4 bwd_ln_bwd_frag(const float4& dyv, const float4& xh, const float4& dxh, float rstd, float m1, float m2) {
+  float4 o;
+  o.x = dyv.x + rstd * (dxh.x - m1 - xh.x * m2);
+  o.y = dyv.y + rstd * (dxh.y - m1 - xh.y * m2);
+  o.z = dyv.z + rstd * (dxh.z - m1 - xh.z * m2);
+  o.w = dyv.w + rstd * (dxh.w - m1 - xh.w * m2);
+  return o;
+}
+
+// dK / dV of key m, head pair q, in the partial slot of row group lr: dkvp [B][NLR][N][2][4][16]
+__device__ __forceinline__ float4* bwd_dkv_slot(const BlockArgs& a, int b, int lr, int N, int m, int kv01, int q) {
+  return reinterpret_cast<float4*>(a.dkvp + (((((size_t)b * a.NLR + lr) * N + m) * 2 + kv01) * 4 + q) * 16);
+}
+__device__ __forceinline__ void bwd_store_dkv(float4* ko, float4* vo, const float (&dKa)[16], const float (&dVa)[16]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ko[i] = make_float4(dKa[4*i], dKa[4*i+1], dKa[4*i+2], dKa[4*i+3]);
+    vo[i] = make_float4(dVa[4*i], dVa[4*i+1], dVa[4*i+2], dVa[4*i+3]);
+  }
+}
+__device__ __forceinline__ void bwd_add_dkv(const float4* ko, const float4* vo, float (&dKa)[16], float (&dVa)[16]) {   // a parked partial
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float4 kk = ko[i], vv = vo[i];
+    dKa[4*i] += kk.x; dKa[4*i+1] += kk.y; dKa[4*i+2] += kk.z; dKa[4*i+3] += kk.w;
+    dVa[4*i] += vv.x; dVa[4*i+1] += vv.y; dVa[4*i+2] += vv.z; dVa[4*i+3] += vv.w;
+  }
+}
+
+// Edge-parameter partials of the workgroup: the four waves' accT / accR / column sums meet in LDS (sm: the tile area, dead by now) and
+// their sum goes to epart [workgroup][Geo::EP]
+template <int DE>
+__device__ __forceinline__ void bwd_store_epart(const BlockArgs& a, float* sm, int wg, int wave, int p, int q,
+                                                const v4f (&accT)[Geo<DE>::TILES], const v4f (&accR)[Geo<DE>::TILES], float (&ssum)[4]) {
+  using G = Geo<DE>;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) ssum[r] = row_sum16(ssum[r]);
+  __syncthreads();
+  float* ep = sm + wave * G::EP;
+#pragma unroll
+  for (int t = 0; t < G::TILES; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      ep[(16 * t + 4 * q + r) * 16 + p] = accT[t][r];
+      ep[G::DEP * 16 + 16 + (16 * t + 4 * q + r) * 16 + p] = accR[t][r];
+    }
+  if (p == 0) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ep[G::DEP * 16 + 4 * q + r] = ssum[r];
+  }
+  __syncthreads();
+  float* out = a.epart + (size_t)wg * G::EP;
+  for (int i = threadIdx.x; i < G::EP; i += 256)
+    out[i] = (sm[i] + sm[G::EP + i]) + (sm[2 * G::EP + i] + sm[3 * G::EP + i]);
+}
 
 // ================================================================ backward =====
 // Workgroup = (graph b, TL query rows); wave w owns key tiles w, w+4, ...; for each it walks the TL rows.  Q / dV_att /
@@ -73,23 +359,10 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
     __syncthreads();
     bwd_node_prologue<DE>(a, sm, qd, b, l_begin, wg);
   }
-  // weight slabs: element (t, lane, u)
-  for (int i = threadIdx.x; i < G::TILES * 256; i += 256) {
-    const int t = i >> 8, ln = (i >> 2) & 63, u = i & 3, pp = ln & 15, qq = ln >> 4;
-    const int c = 16 * t + 4 * qq + u;
-    wsA[i] = a.pw[c * 16 + pp];
-    const int hd = 2 * (pp >> 2) + (pp & 1);
-    wsB[i] = ((pp & 2) == 0 && c < DE) ? a.Wr[hd * DE + c] : 0.f;
-    wsD[i] = a.pw[(16 * t + pp) * 16 + 4 * qq + u];
-  }
-  float c2r[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) c2r[r] = a.pw[G::DEP * 16 + 4 * q + r];
-
+  bwd_fill_slabs<DE>(a, wsA, wsB, wsD);
+  float c2r[4], ssum[4];
   v4f accT[G::TILES], accR[G::TILES];
-#pragma unroll
-  for (int t = 0; t < G::TILES; ++t) { accT[t] = (v4f){0.f, 0.f, 0.f, 0.f}; accR[t] = (v4f){0.f, 0.f, 0.f, 0.f}; }
-  float ssum[4] = {0.f, 0.f, 0.f, 0.f};
+  bwd_acc_init<DE>(a, q, c2r, accT, accR, ssum);
   __syncthreads();
 
   const int ntile = RAG ? (N + 15) / 16 : N / 16;
@@ -99,18 +372,8 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
     const bool kvalid = RAG ? (m < N) : true;
     float Kf[16], Vf[16], dKa[16], dVa[16];
     const size_t rowm = (size_t)b * N + (kvalid ? m : N - 1);
-    {
-      const float4* kp = reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 64 + q * 16);
-      const float4* vp = reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 128 + q * 16);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float4 kv = kp[i], vv = vp[i];
-        Kf[4*i] = kv.x; Kf[4*i+1] = kv.y; Kf[4*i+2] = kv.z; Kf[4*i+3] = kv.w;
-        Vf[4*i] = vv.x; Vf[4*i+1] = vv.y; Vf[4*i+2] = vv.z; Vf[4*i+3] = vv.w;
-      }
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { dKa[i] = 0.f; dVa[i] = 0.f; }
-    }
+    bwd_kv_frags(a, rowm, q, Kf, Vf);
+    bwd_dkv_zero(dKa, dVa);
     const float kadd = (a.km && a.km[rowm] == 0) ? -EGT_NEG : 0.0f;
 
     TileRegs<DE> te, td;
@@ -133,115 +396,22 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
       lds_sync();
       SCHED_FENCE();
       // ---- P1: norm_edge, projections (recompute) ----
+      const float* qr = qd + li * QD_LD;
       float rstd;
-      v4f acc = {c2r[0], c2r[1], c2r[2], c2r[3]};
-      {
-        float4 x[G::TILES];
-#pragma unroll
-        for (int t = 0; t < G::TILES; ++t) x[t] = frag_read<DE>(et, p, q, t);
-        rstd = ln_frags<DE>(x, q, a.ln_eps, (a.flags & EGT_BF_NO_EDGE_LN) == 0);
-#pragma unroll
-        for (int t = 0; t < G::TILES; ++t) {
-          frag_write<DE>(et, p, q, t, x[t]);     // xhat stays in the tile for the later phases
-          const float4 w = *reinterpret_cast<const float4*>(wsA + (t * 64 + lane) * 4);
-          acc = MFMA(w.x, x[t].x, acc);
-          acc = MFMA(w.y, x[t].y, acc);
-          acc = MFMA(w.z, x[t].z, acc);
-          acc = MFMA(w.w, x[t].w, acc);
-        }
-      }
+      const v4f acc = bwd_p1_project<DE>(a, et, wsA, lane, p, q, c2r, rstd);
       SCHED_FENCE();
       // ---- P2: dH_ext = de'.Wr^T ----
       v4f dhx = {0.f, 0.f, 0.f, 0.f};
-      if (!(a.guard & 8))
-#pragma unroll
-      for (int t = 0; t < G::TILES; ++t) {
-        const float4 dyv = frag_read<DE>(dt, p, q, t);
-        const float4 w = *reinterpret_cast<const float4*>(wsB + (t * 64 + lane) * 4);
-        dhx = MFMA(w.x, dyv.x, dhx);
-        dhx = MFMA(w.y, dyv.y, dhx);
-        dhx = MFMA(w.z, dyv.z, dhx);
-        dhx = MFMA(w.w, dyv.w, dhx);
-      }
+      if (!(a.guard & 8)) dhx = bwd_p2_dhext<DE>(dt, wsB, lane, p, q);
       SCHED_FENCE();
-      // ---- P3: logits, softmax/gate backward, dQ/dK/dV ----
-      // Q / dV_att fragments are fetched from LDS twice (once for the dot products, once for the
-      // dK/dV accumulation) instead of being held across the exp / sigmoid chain.
+      // ---- P3: logits, softmax/gate backward ----
       float dge[4], hh[2], dA[2], at[2];
-      {
-        const float* qr = qd + li * QD_LD;
-        float dots[2], dAd[2];
-        {
-          const float4* qp = reinterpret_cast<const float4*>(qr + q * 16);
-          const float4* dp = reinterpret_cast<const float4*>(qr + 64 + q * 16);
-          float d0 = 0.f, d1 = 0.f, e0 = 0.f, e1 = 0.f;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float4 u = qp[i], v = dp[i];
-            d0 = fmaf(u.x, Kf[4*i], d0);   d1 = fmaf(u.y, Kf[4*i+1], d1);
-            d0 = fmaf(u.z, Kf[4*i+2], d0); d1 = fmaf(u.w, Kf[4*i+3], d1);
-            e0 = fmaf(v.x, Vf[4*i], e0);   e1 = fmaf(v.y, Vf[4*i+1], e1);
-            e0 = fmaf(v.z, Vf[4*i+2], e0); e1 = fmaf(v.w, Vf[4*i+3], e1);
-          }
-          dots[0] = d0; dots[1] = d1; dAd[0] = e0; dAd[1] = e1;
-        }
-        const float4* sp = reinterpret_cast<const float4*>(qr + 128 + q * 8);
-        const float4 s0 = sp[0], s1 = sp[1];
-        const float st[8] = {s0.x, s0.y, s0.z, 0.f, s1.x, s1.y, s1.z, 0.f};
-        float xl[2], gl[2], inr[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const float araw = dots[j] * a.scale;
-          float ah = araw;
-          inr[j] = 1.0f;
-          if (clip) {
-            inr[j] = (araw >= a.clip_lo && araw <= a.clip_hi) ? 1.0f : 0.0f;
-            ah = fminf(fmaxf(araw, a.clip_lo), a.clip_hi);
-          }
-          hh[j] = ah + acc[2 * j + 1];
-          xl[j] = hh[j];
-          gl[j] = acc[2 * j];
-        }
-        apply_masks<ML>(a, kadd, mr, (pair0 + p) * BH, q, xl, gl);
-        if (RAG && !kvalid) { xl[0] = xl[1] = -3.0e38f; gl[0] = gl[1] = -3.0e38f; }   // a key past N: S = 0, gate = 0
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const float S = __expf(xl[j] - st[4 * j]) * st[4 * j + 1];
-          const float g = gated ? egt_sigmoid(gl[j]) : 1.0f;
-          const float dS = dAd[j] * g;
-          const float dGl = gated ? dAd[j] * S * g * (1.0f - g) : 0.f;
-          const float dH = S * (dS - st[4 * j + 2]) + dhx[j];
-          dA[j] = dH * inr[j] * a.scale;
-          at[j] = S * g;
-          dge[2 * j] = dGl;
-          dge[2 * j + 1] = dH;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ssum[r] += dge[r];
-      *reinterpret_cast<float4*>(sc1 + p * 16 + 4 * q) = make_float4(dge[0], dge[1], dge[2], dge[3]);
-      *reinterpret_cast<float2*>(sc2 + p * 12 + 2 * q) = make_float2(hh[0], hh[1]);
-      if (q == 0) sc2[p * 12 + 8] = 1.0f;
+      bwd_pair_grad<ML, RAG, false>(a, qr, Kf, Vf, acc, dhx, kadd, mr, (pair0 + p) * BH, q, kvalid, gated, clip, dge, hh, dA, at);
+      bwd_handoff(sc1, sc2, p, q, dge, hh, ssum);
       lds_sync();
       SCHED_FENCE();
-      if (!(a.guard & 4)) {
-        const float* qr = qd + li * QD_LD;
-        const float4* qp = reinterpret_cast<const float4*>(qr + q * 16);
-        const float4* dp = reinterpret_cast<const float4*>(qr + 64 + q * 16);
-        float dq[16];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float4 u = qp[i], v = dp[i];
-          dKa[4*i]   = fmaf(dA[0], u.x, dKa[4*i]);   dKa[4*i+1] = fmaf(dA[1], u.y, dKa[4*i+1]);
-          dKa[4*i+2] = fmaf(dA[0], u.z, dKa[4*i+2]); dKa[4*i+3] = fmaf(dA[1], u.w, dKa[4*i+3]);
-          dVa[4*i]   = fmaf(at[0], v.x, dVa[4*i]);   dVa[4*i+1] = fmaf(at[1], v.y, dVa[4*i+1]);
-          dVa[4*i+2] = fmaf(at[0], v.z, dVa[4*i+2]); dVa[4*i+3] = fmaf(at[1], v.w, dVa[4*i+3]);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { dq[2 * k] = dA[0] * Kf[2 * k]; dq[2 * k + 1] = dA[1] * Kf[2 * k + 1]; }
-        // dQ[l] partial over this tile's 16 keys -> HBM, summed over key tiles by the next prologue (or k_node_bwd)
-        a.dqp[(((size_t)b * ntile + mt) * N + l) * 64 + lane] = reduce16_keep_own(dq, p);
-      }
+      if (!(a.guard & 4))
+        bwd_dqkv_accum(qr, p, q, Kf, dA, at, dKa, dVa, a.dqp + (((size_t)b * ntile + mt) * N + l) * 64 + lane);
       SCHED_FENCE();
       // ---- P4: weight-gradient contractions over the 16 pairs of the tile ----
       if (!(a.guard & 1)) {
@@ -264,36 +434,12 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
       // ---- P5: d(ehat) = Wp . dGE, LayerNorm backward, de = de' + ... in place over the de' tile ----
       if (!(a.guard & 2)) {
         float4 dxh[G::TILES];
-        float m1 = 0.f, m2 = 0.f;
-#pragma unroll
-        for (int t = 0; t < G::TILES; ++t) {
-          const float4 w = *reinterpret_cast<const float4*>(wsD + (t * 64 + lane) * 4);
-          const float4 xh = frag_read<DE>(et, p, q, t);
-          v4f d = {0.f, 0.f, 0.f, 0.f};
-          d = MFMA(w.x, dge[0], d);
-          d = MFMA(w.y, dge[1], d);
-          d = MFMA(w.z, dge[2], d);
-          d = MFMA(w.w, dge[3], d);
-          dxh[t] = make_float4(d[0], d[1], d[2], d[3]);
-          m1 += (d[0] + d[1]) + (d[2] + d[3]);
-          m2 = fmaf(d[0], xh.x, m2); m2 = fmaf(d[1], xh.y, m2);
-          m2 = fmaf(d[2], xh.z, m2); m2 = fmaf(d[3], xh.w, m2);
-        }
-        m1 = sum_over_q(m1) * (1.0f / DE);
-        m2 = sum_over_q(m2) * (1.0f / DE);
-        if (a.flags & EGT_BF_NO_EDGE_LN) { m1 = 0.f; m2 = 0.f; }   // no norm_edge: d e = de' + d(proj input)
+        float m1, m2;
+        bwd_dehat<DE>(a, et, p, q, dxh, m1, m2, [&](int t) { return bwd_dehat_f32(wsD, lane, t, dge); });
         lds_sync();
 #pragma unroll
-        for (int t = 0; t < G::TILES; ++t) {
-          const float4 dyv = frag_read<DE>(dt, p, q, t);
-          const float4 xh = frag_read<DE>(et, p, q, t);
-          float4 o;
-          o.x = dyv.x + rstd * (dxh[t].x - m1 - xh.x * m2);
-          o.y = dyv.y + rstd * (dxh[t].y - m1 - xh.y * m2);
-          o.z = dyv.z + rstd * (dxh[t].z - m1 - xh.z * m2);
-          o.w = dyv.w + rstd * (dxh[t].w - m1 - xh.w * m2);
-          frag_write<DE>(dt, p, q, t, o);
-        }
+        for (int t = 0; t < G::TILES; ++t)
+          frag_write<DE>(dt, p, q, t, bwd_ln_bwd_frag(frag_read<DE>(dt, p, q, t), frag_read<DE>(et, p, q, t), dxh[t], rstd, m1, m2));
       }
       SCHED_FENCE();
     }
@@ -302,35 +448,9 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
       tile_from_lds<DE>(dt0 + ((nl - 1) & 1) * G::TILE_FLOATS,
                         dex_o + (((size_t)b * N + l_end - 1) * N + m0) * DE, lane, kv);
     }
-    float4* ko = reinterpret_cast<float4*>(a.dkvp + (((((size_t)b * a.NLR + lr) * N + m) * 2 + 0) * 4 + q) * 16);
-    float4* vo = reinterpret_cast<float4*>(a.dkvp + (((((size_t)b * a.NLR + lr) * N + m) * 2 + 1) * 4 + q) * 16);
-    if (kvalid) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        ko[i] = make_float4(dKa[4*i], dKa[4*i+1], dKa[4*i+2], dKa[4*i+3]);
-        vo[i] = make_float4(dVa[4*i], dVa[4*i+1], dVa[4*i+2], dVa[4*i+3]);
-      }
-    }
+    if (kvalid) bwd_store_dkv(bwd_dkv_slot(a, b, lr, N, m, 0, q), bwd_dkv_slot(a, b, lr, N, m, 1, q), dKa, dVa);
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) ssum[r] = row_sum16(ssum[r]);
-  __syncthreads();
-  float* ep = sm + wave * G::EP;
-#pragma unroll
-  for (int t = 0; t < G::TILES; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      ep[(16 * t + 4 * q + r) * 16 + p] = accT[t][r];
-      ep[G::DEP * 16 + 16 + (16 * t + 4 * q + r) * 16 + p] = accR[t][r];
-    }
-  if (p == 0) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ep[G::DEP * 16 + 4 * q + r] = ssum[r];
-  }
-  __syncthreads();
-  float* out = a.epart + (size_t)wg * G::EP;
-  for (int i = threadIdx.x; i < G::EP; i += 256)
-    out[i] = (sm[i] + sm[G::EP + i]) + (sm[2 * G::EP + i] + sm[3 * G::EP + i]);
+  bwd_store_epart<DE>(a, sm, wg, wave, p, q, accT, accR, ssum);
 }
 
 // ================================================ backward, LDS-DMA staged ("v5") ====
@@ -428,13 +548,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
     if (RAG && kv_ < 16) tile_dma_ragged<DE>(et_lds, e_in + (((size_t)b * N + l_begin + (ROW_)) * N + m0_) * DE, lane, kv_); \
     else tile_dma<DE, EGT_NT_BWD_E>(et_lds, e_in + (((size_t)b * N + l_begin + (ROW_)) * N + m0_) * DE, off0);      \
     const size_t rowm_ = (size_t)b * N + (RAG ? min(m0_ + p, N - 1) : m0_ + p);                                     \
-    const float4* kp_ = reinterpret_cast<const float4*>(a.qkvp + rowm_ * QKVP + 64 + q * 16);                       \
-    const float4* vp_ = reinterpret_cast<const float4*>(a.qkvp + rowm_ * QKVP + 128 + q * 16);                      \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                 \
-      const float4 kv4 = kp_[i], vv4 = vp_[i];                                                                      \
-      Kf[4*i] = kv4.x; Kf[4*i+1] = kv4.y; Kf[4*i+2] = kv4.z; Kf[4*i+3] = kv4.w;                                     \
-      Vf[4*i] = vv4.x; Vf[4*i+1] = vv4.y; Vf[4*i+2] = vv4.z; Vf[4*i+3] = vv4.w;                                     \
-    }                                                                                                               \
+    bwd_kv_frags(a, rowm_, q, Kf, Vf);                                                                              \
     kmv = a.km ? (int)a.km[rowm_] : 1;                                                                              \
   } while (0)
   if (have) V5_TILE_START(mt_first, r0_first);
@@ -457,14 +571,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
     float sA[G::TILES], sB[G::TILES], sD[G::TILES];
     if constexpr (MM == 0) {
 #pragma unroll
-      for (int t = 0; t < G::TILES; ++t) {
-        const int i = threadIdx.x + 256 * t, ln = (i >> 2) & 63, u = i & 3, pp = ln & 15, qq = ln >> 4;
-        const int c = 16 * t + 4 * qq + u;
-        const int hd = 2 * (pp >> 2) + (pp & 1);
-        sA[t] = a.pw[c * 16 + pp];
-        sB[t] = ((pp & 2) == 0 && c < DE) ? a.Wr[hd * DE + c] : 0.f;
-        sD[t] = a.pw[(16 * t + pp) * 16 + 4 * qq + u];
-      }
+      for (int t = 0; t < G::TILES; ++t) bwd_slab_elem<DE>(a, threadIdx.x + 256 * t, sA[t], sB[t], sD[t]);
     }
     if (a.pro) bwd_node_prologue_load<DE>(a, proR, b, l_begin);   // the prologue's own loads: issued before the first wait of the kernel
 #pragma unroll
@@ -518,14 +625,9 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
       D16[(t * 64 + ln) * 8 + u] = hi; D16[(t * 64 + ln) * 8 + 4 + u] = lo;
     }
   }
-  float c2r[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) c2r[r] = a.pw[G::DEP * 16 + 4 * q + r];
-
+  float c2r[4], ssum[4];
   v4f accT[G::TILES], accR[G::TILES];
-#pragma unroll
-  for (int t = 0; t < G::TILES; ++t) { accT[t] = (v4f){0.f, 0.f, 0.f, 0.f}; accR[t] = (v4f){0.f, 0.f, 0.f, 0.f}; }
-  float ssum[4] = {0.f, 0.f, 0.f, 0.f};
+  bwd_acc_init<DE>(a, q, c2r, accT, accR, ssum);
   __syncthreads();   // the prologue's scratch (the tile area behind the parity-0 e buffers) is dead from here
 
   for (int mt = mt_first; have && mt <= mt_last; mt += mt_step) {
@@ -537,8 +639,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
     // a later key tile of this wave (N > 64): its first e tile is in flight while K / V are fetched
     if (mt != mt_first) V5_TILE_START(mt, r0);
     float dKa[16], dVa[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { dKa[i] = 0.f; dVa[i] = 0.f; }
+    bwd_dkv_zero(dKa, dVa);
     asm volatile("" : "+v"(kmv));   // (the byte was requested long ago; its first use stays here)
     const float kadd = kmv == 0 ? -EGT_NEG : 0.0f;
     const int l_first = l_begin + r0, l_stop = l_begin + r1;
@@ -557,23 +658,28 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
       if (lj == 0) vm_wait<(G::NF4 + 63) / 64>(); else vm_wait<2 * ((G::NF4 + 63) / 64) + 1>();
       SCHED_FENCE();
       // ---- P1: norm_edge, projections (recompute) ----
+      const float* qr = qd + li * QD_LD;
       float rstd;
-      v4f acc = {c2r[0], c2r[1], c2r[2], c2r[3]};
-      {
+      v4f acc;
+      if constexpr (MM != 0) {
         float4 x[G::TILES];
 #pragma unroll
         for (int t = 0; t < G::TILES; ++t) x[t] = frag_read<DE>(et, p, q, t);
         rstd = ln_frags<DE>(x, q, a.ln_eps, (a.flags & EGT_BF_NO_EDGE_LN) == 0);
-        if constexpr (MM != 0) {
 #pragma unroll
-          for (int t = 0; t < G::TILES; ++t) frag_write<DE>(et, p, q, t, x[t]);     // xhat stays in the tile for the later phases
-          v4f xv[G::TILES];
-          Bf8 xh[NS], xl[NS];
+        for (int t = 0; t < G::TILES; ++t) frag_write<DE>(et, p, q, t, x[t]);     // xhat stays in the tile for the later phases
+        v4f xv[G::TILES];
+        Bf8 xh[NS], xl[NS];
 #pragma unroll
-          for (int t = 0; t < G::TILES; ++t) xv[t] = (v4f){x[t].x, x[t].y, x[t].z, x[t].w};
-          split_tiles<G::TILES, SPLIT>(xv, xh, xl);
-          acc = bf_gemm<NS, SPLIT>(wsA, 0, lane, xh, xl, acc);
-        } else {
+        for (int t = 0; t < G::TILES; ++t) xv[t] = (v4f){x[t].x, x[t].y, x[t].z, x[t].w};
+        split_tiles<G::TILES, SPLIT>(xv, xh, xl);
+        acc = bf_gemm<NS, SPLIT>(wsA, 0, lane, xh, xl, (v4f){c2r[0], c2r[1], c2r[2], c2r[3]});
+      } else {
+        acc = (v4f){c2r[0], c2r[1], c2r[2], c2r[3]};
+        float4 x[G::TILES];
+#pragma unroll
+        for (int t = 0; t < G::TILES; ++t) x[t] = frag_read<DE>(et, p, q, t);
+        rstd = ln_frags<DE>(x, q, a.ln_eps, (a.flags & EGT_BF_NO_EDGE_LN) == 0);
 #pragma unroll
         for (int t = 0; t < G::TILES; ++t) {
           frag_write<DE>(et, p, q, t, x[t]);     // xhat stays in the tile for the later phases
@@ -582,7 +688,6 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
           acc = MFMA(w.y, x[t].y, acc);
           acc = MFMA(w.z, x[t].z, acc);
           acc = MFMA(w.w, x[t].w, acc);
-        }
         }
       }
       SCHED_FENCE();
@@ -617,67 +722,14 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
       }
       }
       SCHED_FENCE();
-      // ---- P3: logits, softmax/gate backward, dQ/dK/dV ----
+      // ---- P3: logits, softmax/gate backward ----
       float dge[4], hh[2], dA[2], at[2];
-      {
-        const float* qr = qd + li * QD_LD;
-        float dots[2], dAd[2];
-        {
-          const float4* qp = reinterpret_cast<const float4*>(qr + q * 16);
-          const float4* dp = reinterpret_cast<const float4*>(qr + 64 + q * 16);
-          float d0 = 0.f, d1 = 0.f, e0 = 0.f, e1 = 0.f;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float4 u = qp[i], v = dp[i];
-            d0 = fmaf(u.x, Kf[4*i], d0);   d1 = fmaf(u.y, Kf[4*i+1], d1);
-            d0 = fmaf(u.z, Kf[4*i+2], d0); d1 = fmaf(u.w, Kf[4*i+3], d1);
-            e0 = fmaf(v.x, Vf[4*i], e0);   e1 = fmaf(v.y, Vf[4*i+1], e1);
-            e0 = fmaf(v.z, Vf[4*i+2], e0); e1 = fmaf(v.w, Vf[4*i+3], e1);
-          }
-          dots[0] = d0; dots[1] = d1; dAd[0] = e0; dAd[1] = e1;
-        }
-        const float4* sp = reinterpret_cast<const float4*>(qr + 128 + q * 8);
-        const float4 s0 = sp[0], s1 = sp[1];
-        const float st[8] = {s0.x, s0.y, s0.z, 0.f, s1.x, s1.y, s1.z, 0.f};
-        float xl[2], gl[2], inr[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const float araw = dots[j] * a.scale;
-          float ah = araw;
-          inr[j] = 1.0f;
-          if (clip) {
-            inr[j] = (araw >= a.clip_lo && araw <= a.clip_hi) ? 1.0f : 0.0f;
-            ah = fminf(fmaxf(araw, a.clip_lo), a.clip_hi);
-          }
-          hh[j] = ah + acc[2 * j + 1];
-          xl[j] = hh[j];
-          gl[j] = acc[2 * j];
-        }
-        apply_masks<false>(a, kadd, mr, (pair0 + p) * BH, q, xl, gl);
-        if (RAG && !kvalid) { xl[0] = xl[1] = -3.0e38f; gl[0] = gl[1] = -3.0e38f; }   // a key past N: S = 0, gate = 0 (exactly)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const float S = __expf(xl[j] - st[4 * j]) * st[4 * j + 1];
-          const float g = (gated || (RAG && !kvalid)) ? egt_sigmoid(gl[j]) : 1.0f;
-          const float dS = dAd[j] * g;
-          const float dGl = gated ? dAd[j] * S * g * (1.0f - g) : 0.f;
-          const float dH = S * (dS - st[4 * j + 2]) + dhx[j];
-          dA[j] = dH * inr[j] * a.scale;
-          at[j] = S * g;
-          dge[2 * j] = dGl;
-          dge[2 * j + 1] = dH;
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) ssum[r] += dge[r];
-      *reinterpret_cast<float4*>(sc1 + p * 16 + 4 * q) = make_float4(dge[0], dge[1], dge[2], dge[3]);
-      *reinterpret_cast<float2*>(sc2 + p * 12 + 2 * q) = make_float2(hh[0], hh[1]);
-      if (q == 0) sc2[p * 12 + 8] = 1.0f;
+      bwd_pair_grad<false, RAG, true>(a, qr, Kf, Vf, acc, dhx, kadd, mr, (pair0 + p) * BH, q, kvalid, gated, clip, dge, hh, dA, at);
+      bwd_handoff(sc1, sc2, p, q, dge, hh, ssum);
       lds_sync();
       SCHED_FENCE();
       if (!(a.guard & 4))
       {
-        const float* qr = qd + li * QD_LD;
         const float4* qp = reinterpret_cast<const float4*>(qr + q * 16);
         const float4* dp = reinterpret_cast<const float4*>(qr + 64 + q * 16);
         float dq[16];
@@ -696,8 +748,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
       }
       SCHED_FENCE();
       // ---- P4: weight-gradient contractions over the 16 pairs of the tile ----
-      if (!(a.guard & 1))
-      {
+      if (!(a.guard & 1)) {
         float bT[4], bR[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -722,7 +773,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
       // ---- P5: d(ehat) = Wp . dGE, LayerNorm backward, de = de' + ... straight to HBM ----
       if (!(a.guard & 2)) {
         float4 dxh[G::TILES];
-        float m1 = 0.f, m2 = 0.f;
+        float m1, m2;
         Bf8 gB1, gB2;   // B operands of the stacked K = 16 product: [dGE_hi | dGE_hi] and [dGE_lo | 0]
         if constexpr (MM != 0) {
           const uint32_t h0 = pk_bf16(dge[0], dge[1]), h1 = pk_bf16(dge[2], dge[3]);
@@ -731,6 +782,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
           gB2.u[1] = pk_bf16(dge[2] - __uint_as_float(h1 << 16), dge[3] - __uint_as_float(h1 & 0xFFFF0000u));
           gB2.u[2] = 0u; gB2.u[3] = 0u;
         }
+        m1 = 0.f; m2 = 0.f;
 #pragma unroll
         for (int t = 0; t < G::TILES; ++t) {
           const float4 xh = frag_read<DE>(et, p, q, t);
@@ -776,27 +828,14 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
       }
       SCHED_FENCE();
     }
-    float4* ko = reinterpret_cast<float4*>(a.dkvp + (((((size_t)b * a.NLR + lr) * N + m) * 2 + 0) * 4 + q) * 16);
-    float4* vo = reinterpret_cast<float4*>(a.dkvp + (((((size_t)b * a.NLR + lr) * N + m) * 2 + 1) * 4 + q) * 16);
+    float4* ko = bwd_dkv_slot(a, b, lr, N, m, 0, q);
+    float4* vo = bwd_dkv_slot(a, b, lr, N, m, 1, q);
     if (balance && r1 < nl && r0 == 0) {   // the tile's last rows were done by the next wave, at the START of its range: its partial sits in the slot
       while (pflag[wave + 1] == 0) __builtin_amdgcn_s_sleep(1);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      if (kvalid) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float4 kk = ko[i], vv = vo[i];
-          dKa[4*i] += kk.x; dKa[4*i+1] += kk.y; dKa[4*i+2] += kk.z; dKa[4*i+3] += kk.w;
-          dVa[4*i] += vv.x; dVa[4*i+1] += vv.y; dVa[4*i+2] += vv.z; dVa[4*i+3] += vv.w;
-        }
-      }
+      if (kvalid) bwd_add_dkv(ko, vo, dKa, dVa);
     }
-    if (kvalid) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        ko[i] = make_float4(dKa[4*i], dKa[4*i+1], dKa[4*i+2], dKa[4*i+3]);
-        vo[i] = make_float4(dVa[4*i], dVa[4*i+1], dVa[4*i+2], dVa[4*i+3]);
-      }
-    }
+    if (kvalid) bwd_store_dkv(ko, vo, dKa, dVa);
     if (balance && r0 > 0) {   // the tile's first rows belong to the previous wave: what was just stored is this wave's partial, parked in the
                                // slot (same CU: the stores are acknowledged by the L2 before the flag goes up, the slot was never in this L1)
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -804,30 +843,12 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
       if (lane == 0) pflag[wave] = 1;
     }
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) ssum[r] = row_sum16(ssum[r]);
-  __syncthreads();
-  float* ep = sm + wave * G::EP;
-#pragma unroll
-  for (int t = 0; t < G::TILES; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      ep[(16 * t + 4 * q + r) * 16 + p] = accT[t][r];
-      ep[G::DEP * 16 + 16 + (16 * t + 4 * q + r) * 16 + p] = accR[t][r];
-    }
-  if (p == 0) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ep[G::DEP * 16 + 4 * q + r] = ssum[r];
-  }
-  __syncthreads();
-  float* out = a.epart + (size_t)wg * G::EP;
-  for (int i = threadIdx.x; i < G::EP; i += 256)
-    out[i] = (sm[i] + sm[G::EP + i]) + (sm[2 * G::EP + i] + sm[3 * G::EP + i]);
+  bwd_store_epart<DE>(a, sm, wg, wave, p, q, accT, accR, ssum);
 }
 
 // ---------------------------------------------------------------- backward, narrow edge channels ---
-// k_block_bwd_v4 with the row loop unrolled by R (De <= 16, N % 16 == 0, no mask tensors): one
-// iteration = the wave's key tile x R query rows.  The rows' P1..P5 chains are independent, the LDS
+// k_block_bwd_v4 with the row loop unrolled by R (De <= 16, any N -- the last key tile and the last row group may be short --, no
+// mask tensors): one iteration = the wave's key tile x R query rows (R = V4R_RR).  The rows' P1..P5 chains are independent, the LDS
 // hand-offs are shared (5 per R rows instead of 5 per row), the e / de' tiles of the next R rows are
 // in flight during the arithmetic.  Same arguments, partial layouts and prologue as v4.
 template <int DE, bool BF, int R>
@@ -869,21 +890,10 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
     __syncthreads();
     bwd_node_prologue<DE>(a, sm, qd, b, l_begin, wg);
   }
-  for (int i = threadIdx.x; i < G::TILES * 256; i += 256) {
-    const int t = i >> 8, ln = (i >> 2) & 63, u = i & 3, pp = ln & 15, qq = ln >> 4;
-    const int c = 16 * t + 4 * qq + u;
-    wsA[i] = a.pw[c * 16 + pp];
-    const int hd = 2 * (pp >> 2) + (pp & 1);
-    wsB[i] = ((pp & 2) == 0 && c < DE) ? a.Wr[hd * DE + c] : 0.f;
-    wsD[i] = a.pw[(16 * t + pp) * 16 + 4 * qq + u];
-  }
-  float c2r[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) c2r[r] = a.pw[G::DEP * 16 + 4 * q + r];
+  bwd_fill_slabs<DE>(a, wsA, wsB, wsD);
+  float c2r[4], ssum[4];
   v4f accT[G::TILES], accR[G::TILES];
-#pragma unroll
-  for (int t = 0; t < G::TILES; ++t) { accT[t] = (v4f){0.f, 0.f, 0.f, 0.f}; accR[t] = (v4f){0.f, 0.f, 0.f, 0.f}; }
-  float ssum[4] = {0.f, 0.f, 0.f, 0.f};
+  bwd_acc_init<DE>(a, q, c2r, accT, accR, ssum);
   __syncthreads();
 
   // Ragged N: the last key tile has kv < 16 valid keys (loads clamped / zero-filled, the lanes of the
@@ -905,18 +915,8 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
     const bool kvalid = m < N;
     float Kf[16], Vf[16], dKa[16], dVa[16];
     const size_t rowm = (size_t)b * N + (kvalid ? m : N - 1);
-    {
-      const float4* kp = reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 64 + q * 16);
-      const float4* vp = reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 128 + q * 16);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float4 kv = kp[i], vv = vp[i];
-        Kf[4*i] = kv.x; Kf[4*i+1] = kv.y; Kf[4*i+2] = kv.z; Kf[4*i+3] = kv.w;
-        Vf[4*i] = vv.x; Vf[4*i+1] = vv.y; Vf[4*i+2] = vv.z; Vf[4*i+3] = vv.w;
-      }
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { dKa[i] = 0.f; dVa[i] = 0.f; }
-    }
+    bwd_kv_frags(a, rowm, q, Kf, Vf);
+    bwd_dkv_zero(dKa, dVa);
     const float kadd = (a.km && a.km[rowm] == 0) ? -EGT_NEG : 0.0f;
     const MaskRegs mr{make_float2(1.f, 1.f), 0};
     TileRegs<DE> te[R], td[R];
@@ -935,7 +935,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
       size_t pair0[R];
 #pragma unroll
       for (int i = 0; i < R; ++i) pair0[i] = ((size_t)b * N + min(lb + i, l_end - 1)) * N + m0;
-      lds_sync();   // the de tiles of the previous four rows have left the LDS tiles
+      lds_sync();   // the de tiles of the previous R rows have left the LDS tiles
 #pragma unroll
       for (int i = 0; i < R; ++i) {
         tile_lds_put<DE>(et0 + i * TF, te[i], lane, kv);
@@ -949,89 +949,18 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
 #pragma unroll
       for (int i = 0; i < R; ++i) {
         if (i >= nr) continue;
-        float* et = et0 + i * TF;
-        const float* dt = dt0 + i * TF;
-        acc[i] = (v4f){c2r[0], c2r[1], c2r[2], c2r[3]};
-        dhx[i] = (v4f){0.f, 0.f, 0.f, 0.f};
-        float4 x[G::TILES];
-#pragma unroll
-        for (int t = 0; t < G::TILES; ++t) x[t] = frag_read<DE>(et, p, q, t);
-        rstd[i] = ln_frags<DE>(x, q, a.ln_eps, (a.flags & EGT_BF_NO_EDGE_LN) == 0);
-#pragma unroll
-        for (int t = 0; t < G::TILES; ++t) {
-          frag_write<DE>(et, p, q, t, x[t]);     // xhat stays in the tile for the later phases
-          const float4 w = *reinterpret_cast<const float4*>(wsA + (t * 64 + lane) * 4);
-          acc[i] = MFMA(w.x, x[t].x, acc[i]);
-          acc[i] = MFMA(w.y, x[t].y, acc[i]);
-          acc[i] = MFMA(w.z, x[t].z, acc[i]);
-          acc[i] = MFMA(w.w, x[t].w, acc[i]);
-          const float4 dyv = frag_read<DE>(dt, p, q, t);
-          const float4 wb = *reinterpret_cast<const float4*>(wsB + (t * 64 + lane) * 4);
-          dhx[i] = MFMA(wb.x, dyv.x, dhx[i]);
-          dhx[i] = MFMA(wb.y, dyv.y, dhx[i]);
-          dhx[i] = MFMA(wb.z, dyv.z, dhx[i]);
-          dhx[i] = MFMA(wb.w, dyv.w, dhx[i]);
-        }
+        acc[i] = bwd_p1_project<DE>(a, et0 + i * TF, wsA, lane, p, q, c2r, rstd[i]);
+        dhx[i] = bwd_p2_dhext<DE>(dt0 + i * TF, wsB, lane, p, q);
       }
       // ---- P3: logits, softmax/gate backward ----
       float dge[R][4], dA[R][2], at[R][2];
 #pragma unroll
       for (int i = 0; i < R; ++i) {
         if (i >= nr) continue;
-        const float* qr = qd + (R * lq + i) * QD_LD;
-        float dots[2], dAd[2], hh[2];
-        {
-          const float4* qp = reinterpret_cast<const float4*>(qr + q * 16);
-          const float4* dp = reinterpret_cast<const float4*>(qr + 64 + q * 16);
-          float d0 = 0.f, d1 = 0.f, e0 = 0.f, e1 = 0.f;
-#pragma unroll
-          for (int u4 = 0; u4 < 4; ++u4) {
-            const float4 u = qp[u4], v = dp[u4];
-            d0 = fmaf(u.x, Kf[4*u4], d0);   d1 = fmaf(u.y, Kf[4*u4+1], d1);
-            d0 = fmaf(u.z, Kf[4*u4+2], d0); d1 = fmaf(u.w, Kf[4*u4+3], d1);
-            e0 = fmaf(v.x, Vf[4*u4], e0);   e1 = fmaf(v.y, Vf[4*u4+1], e1);
-            e0 = fmaf(v.z, Vf[4*u4+2], e0); e1 = fmaf(v.w, Vf[4*u4+3], e1);
-          }
-          dots[0] = d0; dots[1] = d1; dAd[0] = e0; dAd[1] = e1;
-        }
-        const float4* sp = reinterpret_cast<const float4*>(qr + 128 + q * 8);
-        const float4 s0 = sp[0], s1 = sp[1];
-        const float st[8] = {s0.x, s0.y, s0.z, 0.f, s1.x, s1.y, s1.z, 0.f};
-        float xl[2], gl[2], inr[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const float araw = dots[j] * a.scale;
-          float ah = araw;
-          inr[j] = 1.0f;
-          if (clip) {
-            inr[j] = (araw >= a.clip_lo && araw <= a.clip_hi) ? 1.0f : 0.0f;
-            ah = fminf(fmaxf(araw, a.clip_lo), a.clip_hi);
-          }
-          hh[j] = ah + acc[i][2 * j + 1];
-          xl[j] = hh[j];
-          gl[j] = acc[i][2 * j];
-        }
-        apply_masks<false>(a, kadd, mr, (pair0[i] + p) * BH, q, xl, gl);
-        if (!kvalid) { xl[0] = xl[1] = -3.0e38f; gl[0] = gl[1] = -3.0e38f; }   // a key past N: S = 0, gate = 0
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const float S = __expf(xl[j] - st[4 * j]) * st[4 * j + 1];
-          const float g = gated ? egt_sigmoid(gl[j]) : 1.0f;
-          const float dS = dAd[j] * g;
-          const float dGl = gated ? dAd[j] * S * g * (1.0f - g) : 0.f;
-          const float dH = S * (dS - st[4 * j + 2]) + dhx[i][j];
-          dA[i][j] = dH * inr[j] * a.scale;
-          at[i][j] = S * g;
-          dge[i][2 * j] = dGl;
-          dge[i][2 * j + 1] = dH;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ssum[r] += dge[i][r];
-        float* sc1 = sc10 + i * 256;
-        float* sc2 = sc20 + i * 192;
-        *reinterpret_cast<float4*>(sc1 + p * 16 + 4 * q) = make_float4(dge[i][0], dge[i][1], dge[i][2], dge[i][3]);
-        *reinterpret_cast<float2*>(sc2 + p * 12 + 2 * q) = make_float2(hh[0], hh[1]);
-        if (q == 0) sc2[p * 12 + 8] = 1.0f;
+        float hh[2];
+        bwd_pair_grad<false, true, false>(a, qd + (R * lq + i) * QD_LD, Kf, Vf, acc[i], dhx[i], kadd, mr, (pair0[i] + p) * BH, q, kvalid,
+                                          gated, clip, dge[i], hh, dA[i], at[i]);
+        bwd_handoff(sc10 + i * 256, sc20 + i * 192, p, q, dge[i], hh, ssum);
         SCHED_FENCE();   // one row's Q / dV_att fragments (32 registers) at a time
       }
       lds_sync();
@@ -1039,38 +968,10 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
 #pragma unroll
       for (int i = 0; i < R; ++i) {
         if (i >= nr) continue;
-        const float* qr = qd + (R * lq + i) * QD_LD;
-        const float4* qp = reinterpret_cast<const float4*>(qr + q * 16);
-        const float4* dp = reinterpret_cast<const float4*>(qr + 64 + q * 16);
-        float dq[16];
-#pragma unroll
-        for (int u4 = 0; u4 < 4; ++u4) {
-          const float4 u = qp[u4], v = dp[u4];
-          dKa[4*u4]   = fmaf(dA[i][0], u.x, dKa[4*u4]);   dKa[4*u4+1] = fmaf(dA[i][1], u.y, dKa[4*u4+1]);
-          dKa[4*u4+2] = fmaf(dA[i][0], u.z, dKa[4*u4+2]); dKa[4*u4+3] = fmaf(dA[i][1], u.w, dKa[4*u4+3]);
-          dVa[4*u4]   = fmaf(at[i][0], v.x, dVa[4*u4]);   dVa[4*u4+1] = fmaf(at[i][1], v.y, dVa[4*u4+1]);
-          dVa[4*u4+2] = fmaf(at[i][0], v.z, dVa[4*u4+2]); dVa[4*u4+3] = fmaf(at[i][1], v.w, dVa[4*u4+3]);
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { dq[2 * k] = dA[i][0] * Kf[2 * k]; dq[2 * k + 1] = dA[i][1] * Kf[2 * k + 1]; }
-        a.dqp[(((size_t)b * ntile + mt) * N + lb + i) * 64 + lane] = reduce16_keep_own(dq, p);
-        const float* et = et0 + i * TF;
-        const float* dt = dt0 + i * TF;
-        const float* sc1 = sc10 + i * 256;
-        const float* sc2 = sc20 + i * 192;
-        float bT[4], bR[4];
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-          bT[s4] = sc1[(q + 4 * s4) * 16 + p];
-          bR[s4] = (p < 9) ? sc2[(q + 4 * s4) * 12 + p] : 0.f;
-        }
-#pragma unroll
-        for (int t = 0; t < G::TILES; ++t)
-#pragma unroll
-          for (int s4 = 0; s4 < 4; ++s4) {
-            accT[t] = MFMA(elem_read<DE>(et, q + 4 * s4, 16 * t + p), bT[s4], accT[t]);
-            accR[t] = MFMA(elem_read<DE>(dt, q + 4 * s4, 16 * t + p), bR[s4], accR[t]);
-          }
+        bwd_dqkv_accum(qd + (R * lq + i) * QD_LD, p, q, Kf, dA[i], at[i], dKa, dVa,
+                       a.dqp + (((size_t)b * ntile + mt) * N + lb + i) * 64 + lane);
+        bwd_wgrad_accum<DE>(et0 + i * TF, dt0 + i * TF, sc10 + i * 256, sc20 + i * 192, p, q, accT, accR,
+                            [&](const float* tile, int s, int t) { return elem_read<DE>(tile, q + 4 * s, 16 * t + p); });
         SCHED_FENCE();
       }
       lds_sync();
@@ -1080,25 +981,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
 #pragma unroll
       for (int i = 0; i < R; ++i) {
         if (i >= nr) continue;
-        const float* et = et0 + i * TF;
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int t = 0; t < G::TILES; ++t) {
-          const float4 w = *reinterpret_cast<const float4*>(wsD + (t * 64 + lane) * 4);
-          const float4 xh = frag_read<DE>(et, p, q, t);
-          v4f d = {0.f, 0.f, 0.f, 0.f};
-          d = MFMA(w.x, dge[i][0], d);
-          d = MFMA(w.y, dge[i][1], d);
-          d = MFMA(w.z, dge[i][2], d);
-          d = MFMA(w.w, dge[i][3], d);
-          dxh[i][t] = make_float4(d[0], d[1], d[2], d[3]);
-          s1 += (d[0] + d[1]) + (d[2] + d[3]);
-          s2 = fmaf(d[0], xh.x, s2); s2 = fmaf(d[1], xh.y, s2);
-          s2 = fmaf(d[2], xh.z, s2); s2 = fmaf(d[3], xh.w, s2);
-        }
-        m1[i] = sum_over_q(s1) * (1.0f / DE);
-        m2[i] = sum_over_q(s2) * (1.0f / DE);
-        if (a.flags & EGT_BF_NO_EDGE_LN) { m1[i] = 0.f; m2[i] = 0.f; }   // no norm_edge: d e = de' + d(proj input)
+        bwd_dehat<DE>(a, et0 + i * TF, p, q, dxh[i], m1[i], m2[i], [&](int t) { return bwd_dehat_f32(wsD, lane, t, dge[i]); });
       }
       lds_sync();
 #pragma unroll
@@ -1107,18 +990,10 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
         const float* et = et0 + i * TF;
         float* dt = dt0 + i * TF;
 #pragma unroll
-        for (int t = 0; t < G::TILES; ++t) {
-          const float4 dyv = frag_read<DE>(dt, p, q, t);
-          const float4 xh = frag_read<DE>(et, p, q, t);
-          float4 o;
-          o.x = dyv.x + rstd[i] * (dxh[i][t].x - m1[i] - xh.x * m2[i]);
-          o.y = dyv.y + rstd[i] * (dxh[i][t].y - m1[i] - xh.y * m2[i]);
-          o.z = dyv.z + rstd[i] * (dxh[i][t].z - m1[i] - xh.z * m2[i]);
-          o.w = dyv.w + rstd[i] * (dxh[i][t].w - m1[i] - xh.w * m2[i]);
-          frag_write<DE>(dt, p, q, t, o);
-        }
+        for (int t = 0; t < G::TILES; ++t)
+          frag_write<DE>(dt, p, q, t, bwd_ln_bwd_frag(frag_read<DE>(dt, p, q, t), frag_read<DE>(et, p, q, t), dxh[i][t], rstd[i], m1[i], m2[i]));
       }
-      lds_sync();   // stream out the four de tiles
+      lds_sync();   // stream out the R de tiles
 #pragma unroll
       for (int i = 0; i < R; ++i)
         if (i < nr) tile_from_lds<DE>(dt0 + i * TF, dex_o + pair0[i] * DE, lane, kv);
@@ -1137,35 +1012,9 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
 #pragma unroll
         for (int i = 0; i < 16; ++i) { dKa[i] += pk[i * 64]; dVa[i] += pk[(16 + i) * 64]; }
       }
-      float4* ko = reinterpret_cast<float4*>(a.dkvp + (((((size_t)b * a.NLR + lr) * N + m) * 2 + 0) * 4 + q) * 16);
-      float4* vo = reinterpret_cast<float4*>(a.dkvp + (((((size_t)b * a.NLR + lr) * N + m) * 2 + 1) * 4 + q) * 16);
-      if (kvalid) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          ko[i] = make_float4(dKa[4*i], dKa[4*i+1], dKa[4*i+2], dKa[4*i+3]);
-          vo[i] = make_float4(dVa[4*i], dVa[4*i+1], dVa[4*i+2], dVa[4*i+3]);
-        }
-      }
+      if (kvalid) bwd_store_dkv(bwd_dkv_slot(a, b, lr, N, m, 0, q), bwd_dkv_slot(a, b, lr, N, m, 1, q), dKa, dVa);
     }
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) ssum[r] = row_sum16(ssum[r]);
-  __syncthreads();
-  float* ep = sm + wave * G::EP;
-#pragma unroll
-  for (int t = 0; t < G::TILES; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      ep[(16 * t + 4 * q + r) * 16 + p] = accT[t][r];
-      ep[G::DEP * 16 + 16 + (16 * t + 4 * q + r) * 16 + p] = accR[t][r];
-    }
-  if (p == 0) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ep[G::DEP * 16 + 4 * q + r] = ssum[r];
-  }
-  __syncthreads();
-  float* out = a.epart + (size_t)wg * G::EP;
-  for (int i = threadIdx.x; i < G::EP; i += 256)
-    out[i] = (sm[i] + sm[G::EP + i]) + (sm[2 * G::EP + i] + sm[3 * G::EP + i]);
+  bwd_store_epart<DE>(a, sm, wg, wave, p, q, accT, accR, ssum);
 }
 

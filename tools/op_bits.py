@@ -10,7 +10,11 @@ head:  the fused edge head and node head over the cases of tests/test_distance_h
 embed: the edge embedding in both edge dtypes: e, hops and every parameter gradient.  Plain: the shapes of test_edge_embed_vs_oracle
        and test_edge_embed_float_features_vs_oracle (tests/test_model.py), inputs of the tool's own seeds.  Bordered: the shapes,
        graphs and parameters (_embed_inputs with the tests' seeds) of the three bordered embedding tests of
-       tests/test_virtual_nodes_gpu.py.  d_e is drawn by the tool in every case."""
+       tests/test_virtual_nodes_gpu.py.  d_e is drawn by the tool in every case.
+block: one forward and backward of the fused block / stack through the C ABI: h', e', d_h, d_e and the fourteen parameter gradients
+       (per layer) over the block and stack rows of tests/memcontract.py plus BLOCK_EXTRA below; the answer of egt_block_launch_form
+       stands next to each row.  The plan's switches are read once per process: run it again under EGT_BWD_MATMUL=bf16x3 (the v5 MM = 1
+       instances) and under EGT_NO_NARROW=1 (De = 8 on k_block_bwd_v4r<8>; the static-edge rows are left out there)."""
 import argparse
 import hashlib
 import itertools
@@ -96,20 +100,43 @@ def embed(gpu):
         run(f"embed_vn B{B}-N{N}-De{De}-K{K}-nv{nv}-F{F}", *TV._embed_inputs(B, N, De, K, nv, F, seed=seed))
 
 
+# block: rows beside the tables of tests/memcontract.py, in their format (no forms claimed: the listing prints what the library answers)
+BLOCK_EXTRA = [("n32_de64", 2, 32, 8, 64, False, "", None, None),                  # N a multiple of 16: the non-ragged instances
+               ("n32_de32_mask", 2, 32, 8, 32, False, "attn_mask", None, None),
+               ("n32_de16", 2, 32, 8, 16, False, "", None, None),
+               ("n21_de8", 2, 21, 8, 8, False, "", None, None)]                    # k_block_bwd_v4r<8> under EGT_NO_NARROW=1
+
+
+def block(gpu):
+    import ctypes as C
+    import torch
+    import memcontract as M
+    from egt_amd import _lib as L
+    lib = L.load()
+    no_narrow = os.environ.get("EGT_NO_NARROW", "") not in ("", "0")       # (the static-edge rows are refused there)
+    rows = [(M.block_case, r) for r in M.BLOCK_TABLE + BLOCK_EXTRA if not (no_narrow and "static" in r[6])]
+    rows += [(M.stack_case, r) for r in M.STACK_TABLE]
+    for make, row in rows:
+        case = make(lib, row)
+        form = lib.egt_block_launch_form(C.byref(case.claims["desc"])).decode()
+        out = M.run(case, M.ZERO, gpu, sync=torch.cuda.synchronize, check_rc=L.check)
+        emit(f"block {case.name} [{form}]", sorted(out.items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=None)
     ap.add_argument("--ops", default="head,embed")
     args = ap.parse_args()
     ops = args.ops.split(",")
-    if not ops or set(ops) - {"head", "embed"}:
-        ap.error("--ops takes head, embed or both")
+    if not ops or set(ops) - {"head", "embed", "block"}:
+        ap.error("--ops takes head, embed, block or several of them")
     if args.lib:
         os.environ["EGT_AMD_LIB"] = os.path.abspath(args.lib)      # read when egt_amd._lib is imported
     sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
     import torch
     gpu = torch.device("cuda", 0)
-    for op, fn in (("head", head), ("embed", embed)):
+    for op, fn in (("head", head), ("embed", embed), ("block", block)):
         if op in ops:
             fn(gpu)
 
