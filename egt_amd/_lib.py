@@ -123,6 +123,16 @@ class NodeHeadParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in NODE_HEAD_PARAM_FIELDS]
 
 
+GH_LAYERNORM = 0x1            # egt_graph_head_desc.flags
+GH_MAE, GH_XENT = 0, 1        # egt_graph_head_desc.loss
+
+
+class GraphHeadDesc(C.Structure):   # (its parameter / gradient structs are NodeHeadParams)
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("W", C.c_int32), ("M0", C.c_int32), ("M1", C.c_int32),
+                ("C", C.c_int32), ("nv", C.c_int32), ("loss", C.c_int32), ("activation", C.c_int32), ("flags", C.c_int32),
+                ("ln_eps", C.c_float), ("reserved", C.c_int32)]
+
+
 def params_struct(cls, fields, tensors):
     """A parameter struct of the C-ABI (`cls`, its `fields` in order) filled with the tensors' device pointers (None -> NULL)."""
     st = cls()
@@ -182,6 +192,11 @@ _PROTOS = {
     "egt_node_head_fwd": (C.c_int, [C.POINTER(NodeHeadDesc), C.POINTER(NodeHeadParams)] + [_VP] * 7),
     "egt_node_head_bwd": (C.c_int, [C.POINTER(NodeHeadDesc), C.POINTER(NodeHeadParams)] + [_VP] * 6
                           + [C.POINTER(NodeHeadParams)] + [_VP] * 2),
+    "egt_graph_head_supported": (C.c_int, [C.POINTER(GraphHeadDesc)]),
+    "egt_graph_head_workspace_bytes": (C.c_size_t, [C.POINTER(GraphHeadDesc)]),
+    "egt_graph_head_fwd": (C.c_int, [C.POINTER(GraphHeadDesc), C.POINTER(NodeHeadParams)] + [_VP] * 7),
+    "egt_graph_head_bwd": (C.c_int, [C.POINTER(GraphHeadDesc), C.POINTER(NodeHeadParams)] + [_VP] * 5
+                           + [C.POINTER(NodeHeadParams)] + [_VP] * 2),
     "egt_dp_unique_id": (C.c_int, [_VP]),
     "egt_dp_init": (C.c_int, [_VP, C.c_int32, C.c_int32]),
     "egt_dp_allreduce": (C.c_int, [_VP, C.c_size_t, C.c_int32, _VP]),

@@ -377,12 +377,63 @@ class ZincDCTransformer(nn.Module):
             x = F.elu(x) if self.cfg["activation"] == 'elu' else torch.relu(x)
         return self._aux(self.target(x), e, graph_matrix, return_aux)                   # zinc/dc.py:116-117
 
+    GRAPH_LOSS = "mae"            # the loss of graph_loss: MeanAbsoluteError here, the sparse cross-entropy in the CIFAR10 / MNIST models
+
+    def graph_head_params(self):
+        """(gamma, beta, mlp_out kernels / biases ..., target kernel, target bias): the readout's parameters in the order
+        egt_amd.graph_head takes them (gamma / beta None without node_norm_final)"""
+        n = self.node_norm_final
+        mid = [t for m in self.mlp_out for t in (m.kernel, m.bias)]
+        return (None if n is None else n.gamma, None if n is None else n.beta, *mid, self.target.kernel, self.target.bias)
+
+    def graph_head_fused(self, h) -> bool:
+        """whether the readout + loss of a step run in the fused kernels: h [B,nv+N,Dh] is fp32 on the GPU, the library
+        covers the geometry (egt_graph_head_supported) and EGT_NO_GRAPH_HEAD is not set"""
+        from .graph_head import graph_head_disabled, graph_head_supported
+        if not h.is_cuda or h.dtype != torch.float32 or len(self.mlp_out) != 2 or graph_head_disabled():
+            return False
+        nv = self.num_virtual_nodes
+        return graph_head_supported(h.shape[0], h.shape[1] - nv, h.shape[2], self.mlp_out[0].kernel.shape[1],
+                                    self.mlp_out[1].kernel.shape[1], self.target.kernel.shape[1], nv, self.GRAPH_LOSS,
+                                    self.cfg["activation"], self.node_norm_final is not None)
+
+    def graph_loss(self, node_features, feature_matrix, graph_matrix, target, attn_mask=None, singular_vectors=None,
+                   eigen_vectors=None, pe_signs=None, return_aux=False):
+        """The step's end of the model: embeddings, positional encodings, virtual nodes and layers as in `forward`, then
+        node_norm_final, the pooling, the readout MLP, the loss and the metric sums as ONE op (egt_amd.graph_head: the fused
+        kernels where they cover the geometry, the composed head otherwise).  Returns (loss, stats, pred, aux): stats =
+        [sum |y - t|, 0, B C] (GRAPH_LOSS 'mae') or [sum CE, sum [argmax == t], B] ('xent'), loss = stats[0] / stats[2] (the
+        Keras batch mean), pred [B,C] what `forward` returns (no gradient), aux as `forward(return_aux=True)` returns it."""
+        from .graph_head import graph_head_composed, graph_head_loss
+        h, e, mask = self.embeddings(node_features, feature_matrix, graph_matrix)
+        h = self.with_virtual_nodes(self.positional(h, singular_vectors, eigen_vectors, pe_signs))
+        h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask), skip_last_edge_ffn=self.dist_head is None)
+        head = graph_head_loss if self.graph_head_fused(h) else graph_head_composed
+        stats, pred = head(h, target, mask, self.graph_head_params(), self.GRAPH_LOSS, self.num_virtual_nodes,
+                           self.cfg["activation"])
+        loss = stats[0] / stats[2].detach()
+        aux = self.distance_aux(e, graph_matrix) if (return_aux and self.dist_head is not None) else {}
+        return loss, stats, pred.detach(), aux
+
+
+class _NotInherited:
+    """a method of the graph-level models that a per-node model does not have (hasattr is False)"""
+
+    def __set_name__(self, owner, name):
+        self.name = name
+
+    def __get__(self, obj, owner=None):
+        raise AttributeError(f"{getattr(owner, '__name__', 'model')} has no {self.name}: its readout is per node (classification_loss)")
+
 
 class PatternDCTransformer(ZincDCTransformer):
     """lib.models.sbm_pattern.dc.DCSVDTransformer for scheme pattern.svd (use_svd false): integer node features
     (3 values), the adjacency hop embedding as the ONLY edge-channel input (no feature matrix), per-node readout
     `mlp_out -> Dense(num_target_labels)` (sbm_pattern/dc.py:51-58).  edge_width 8 in the shipped configs."""
     HAS_VIRTUAL_NODES = False
+    graph_head_params = _NotInherited()
+    graph_head_fused = _NotInherited()
+    graph_loss = _NotInherited()
 
     def __init__(self, num_node_features=3, num_target_labels=2, edge_width=8, model_height=16, **kw):
         kw.pop("num_edge_features", None); kw.pop("num_targets", None)
@@ -461,6 +512,8 @@ class Cifar10DCTransformer(ZincDCTransformer):
     structure): real-valued node features [B,N,5] and edge features [B,N,N,1], each through keras Masking(mask_value)
     + Dense (cifar10/dc.py:66-73); the adjacency hop embedding is added to the edge embedding; graph-level readout
     (masked mean pool -> mlp_out -> Dense(num_target_labels)).  edge_width 8 / model_height 4 in the shipped config."""
+
+    GRAPH_LOSS = "xent"
 
     def __init__(self, num_node_features=5, num_edge_features=1, num_target_labels=10, mask_value=-1., edge_width=8,
                  model_height=4, **kw):

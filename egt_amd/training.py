@@ -581,6 +581,8 @@ class ZincSVDScheme:
     def batch_loss(self, batch):
         """(loss, metric sums) of one batch: scheme-specific"""
         nf, fm, adj, tgt = self._batch(batch)
+        if hasattr(self.model, "graph_loss"):
+            return self._graph_batch_loss(nf, fm, adj, tgt, batch)
         y = self.model(nf, fm, adj, **self._pe(batch), **self._aux_kwargs())
         if self._distance_on():
             y, aux = y
@@ -591,6 +593,23 @@ class ZincSVDScheme:
         loss, dm = self._add_distance(loss, aux)
         n = y.shape[0]
         return loss, dict(mae=(sabs, tgt.numel()), distance_loss=dm, loss=(loss.detach() * n, n))
+
+    def _graph_batch_loss(self, nf, fm, adj, tgt, batch):
+        """batch_loss through the model's graph_loss: layers, then readout + loss + metric sums as one op (the fused graph head
+        where the library covers the geometry, egt_amd.graph_head); stats = [sum |y - t|, 0, B C] or [sum CE, hits, B].  The
+        metric sums stay on the device."""
+        loss, stats, _, aux = self.model.graph_loss(nf, fm, adj, tgt, **self._pe(batch), **self._aux_kwargs())
+        st = stats.detach()
+        mae = self.model.GRAPH_LOSS == "mae"
+        ms = dict(mae=(st[0], st[2])) if mae else dict(xent=(st[0], st[2]), acc=(st[1], st[2]))
+        if self._distance_on():
+            loss, ms["distance_loss"] = self._add_distance(loss, aux)
+        if mae and not self._distance_on():
+            ms["loss"] = (st[0], st[2])                         # (the MAE loss IS the mae metric)
+        else:
+            graphs = torch.full((), float(nf.shape[0]), device=st.device, dtype=st.dtype)   # (a fill kernel: capturable, unlike a host -> device copy)
+            ms["loss"] = (loss.detach() * graphs, graphs)
+        return loss, ms
 
     def _graphed_loss(self, batch):
         """config.use_hipgraph: forward + loss + backward of a training batch as ONE hipGraph launch.  A graph is captured
@@ -967,6 +986,8 @@ class Cifar10SVDScheme(ZincSVDScheme):
 
     def batch_loss(self, batch):
         nf, fm, adj, tgt = self._batch(batch)
+        if hasattr(self.model, "graph_loss"):
+            return self._graph_batch_loss(nf, fm, adj, tgt, batch)
         logits = self.model(nf, fm, adj, **self._pe(batch), **self._aux_kwargs())
         if self._distance_on():
             logits, aux = logits

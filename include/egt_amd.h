@@ -577,6 +577,47 @@ int egt_node_head_bwd(const egt_node_head_desc* desc, const egt_node_head_params
                       const float* d_loss /* device, [1] */, float* d_h, const egt_node_head_params* grads, void* workspace,
                       void* stream);
 
+/* ---- graph-level readout head (the ZINC / ZINC-full / CIFAR10 / MNIST readout and its loss) ----
+ *   x      = node_norm_final(h)                                          h [B,N',W] fp32, N' = nv + N
+ *   pooled = nv == 0 ? sum_n mask[b,n] x[b,n,:] / sum_n mask[b,n]        MaskedGlobalAvgPooling, lib/models/zinc/dc.py:109
+ *                    : concat_{i<nv} x[b,i,:]                            GetVirtualNodes -> Flatten, zinc/dc.py:105-108   [B, max(nv,1) W]
+ *   y      = Dense_t(act(Dense_1(act(Dense_0(pooled)))))                 max(nv,1) W -> M0 -> M1 -> C
+ *   MAE :  stats = { sum_b sum_c |y - t|,         0,                     B*C }   target [B,C] fp32    schemes/zinc/svd.py:37-42
+ *   XENT:  stats = { sum_b CE(y_b, t_b),  sum_b [argmax_c y_b == t_b],   B   }   target [B] int32     schemes/cifar10/svd.py:37-48
+ * mask [B,N'] uint8 (the node mask, virtual rows included).  The parameter and gradient structs are egt_node_head_params with
+ * mlp_out_0_kernel [max(nv,1) W, M0].  pred [B,C] (the predictions / logits) is written by the forward; on an arg-max tie the
+ * lowest class wins.  With nv == 0 a masked row never enters the pooled sum (a predicate, not a product: its content is never
+ * used); with nv > 0 only the first nv rows of a graph are read and the mask is not consulted (virtual rows are real by
+ * construction).  Where |y - t| is exactly 0 the MAE gradient is 0.  The backward recomputes the forward from h; d_loss is a
+ * DEVICE pointer to the upstream gradient of stats[0] (no host read, allocation or synchronisation: the step stays
+ * capturable); d_h gets exact zeros on masked rows (nv == 0) / on every row >= nv (nv > 0).  A graph without a real node is
+ * 0/0 as in the reference (outside the contract; the kernels stay inside their buffers).
+ * Covered: W in {48,64}, (M0, M1) in {(24,12), (32,16)}, 1 <= C <= 16, 0 <= nv <= 4, EGT_ACT_ELU / EGT_ACT_RELU, any N >= 1,
+ * B*N' < 2^31.  Kernels in Keras layout [in, out].  No atomics: the sums over rows and over graphs run in a fixed order, two
+ * calls on the same inputs give the same bits.  `workspace` (egt_graph_head_workspace_bytes) is scratch: nothing is carried
+ * from the forward to the backward. */
+#define EGT_GH_LAYERNORM 0x1 /* node_norm_final (eps = ln_eps) before the pooling; off: gamma / beta may be NULL */
+#define EGT_GH_MAE 0
+#define EGT_GH_XENT 1
+typedef struct egt_graph_head_desc {
+  int32_t B, N, W, M0, M1, C;
+  int32_t nv;         /* virtual nodes in front of every graph's N nodes (0: masked mean pooling) */
+  int32_t loss;       /* EGT_GH_MAE or EGT_GH_XENT */
+  int32_t activation; /* EGT_ACT_ELU or EGT_ACT_RELU (config.activation) */
+  int32_t flags;      /* EGT_GH_LAYERNORM */
+  float ln_eps;
+  int32_t reserved;   /* 0 */
+} egt_graph_head_desc;
+
+int egt_graph_head_supported(const egt_graph_head_desc* desc);
+size_t egt_graph_head_workspace_bytes(const egt_graph_head_desc* desc);
+int egt_graph_head_fwd(const egt_graph_head_desc* desc, const egt_node_head_params* params, const float* h,
+                       const void* target, const uint8_t* mask, float* stats /* [3] */, float* pred /* [B,C] */,
+                       void* workspace, void* stream);
+int egt_graph_head_bwd(const egt_graph_head_desc* desc, const egt_node_head_params* params, const float* h,
+                       const void* target, const uint8_t* mask, const float* d_loss /* device, [1] */, float* d_h,
+                       const egt_node_head_params* grads, void* workspace, void* stream);
+
 /* ---- batch data parallelism: the gradient all-reduce on RCCL -------------------
  * Replaces what tf.distribute.MirroredStrategy does for the reference
  * (lib/training/training_base.py:230-247): one synchronous all-reduce of every
