@@ -133,6 +133,20 @@ class GraphHeadDesc(C.Structure):   # (its parameter / gradient structs are Node
                 ("ln_eps", C.c_float), ("reserved", C.c_int32)]
 
 
+OPT_ADAM, OPT_RMSPROP, OPT_SGD = 0, 1, 2     # egt_optim_desc.algo
+OPT_CLIP, OPT_ZERO_GRAD = 0x1, 0x2            # egt_optim_desc.flags
+OPTIM_STATE_BYTES = 64                        # EGT_OPTIM_STATE_BYTES
+
+
+class OptimDesc(C.Structure):
+    _fields_ = [("algo", C.c_int32), ("flags", C.c_uint32), ("num_segments", C.c_int32), ("reserved", C.c_int32),
+                ("total", C.c_int64), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float), ("clip_value", C.c_float)]
+
+
+class OptimSegment(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("count", C.c_int64)]
+
+
 def params_struct(cls, fields, tensors):
     """A parameter struct of the C-ABI (`cls`, its `fields` in order) filled with the tensors' device pointers (None -> NULL)."""
     st = cls()
@@ -233,6 +247,9 @@ _PROTOS = {
     "egt_ffn_fwd": (C.c_int, [C.POINTER(FfnDesc), C.POINTER(FfnParams)] + [_VP] * 4),
     "egt_ffn_bwd": (C.c_int, [C.POINTER(FfnDesc), C.POINTER(FfnParams)] + [_VP] * 3
                     + [C.POINTER(FfnParams)] + [_VP] * 2),
+    "egt_optim_supported": (C.c_int, [C.POINTER(OptimDesc)]),
+    "egt_optim_prepare": (C.c_int, [C.POINTER(OptimDesc), _VP, _VP]),
+    "egt_optim_step": (C.c_int, [C.POINTER(OptimDesc)] + [_VP] * 6),
 }
 
 

@@ -61,9 +61,10 @@ class FlatGradAllReduce:
 
     def rebind(self):
         """Re-alias .grad after something replaced it (e.g. zero_grad(set_to_none))."""
-        off = 0
-        for p in self.params:
-            if p.grad is None or p.grad.data_ptr() != self.flat[off:].data_ptr():
+        off, base, es = 0, self.flat.data_ptr(), self.flat.element_size()
+        for p in self.params:                       # (addresses compared as integers: a slice per parameter costs microseconds each)
+            g = p.grad
+            if g is None or g.data_ptr() != base + off * es:
                 p.grad = self.flat[off:off + p.numel()].view_as(p)
             off += p.numel()
 

@@ -95,6 +95,8 @@ def default_config(scheme: str = "zinc.svd") -> Config:
                                  # captured per batch geometry: egt_amd.graph; for launch-bound per-GPU batches
         edge_dtype="f32",        # (not a reference key) storage of the [B,N,N,De] edge tensor: "f32" or "bf16" (fp32 math,
                                  # bf16 in HBM: BASELINE config 3); handed to the model by get_model, not part of model_config
+        fused_optimizer=False,   # (not a reference key) the parameter update as two launches over the flat gradient buffer:
+                                 # egt_amd.optim.FlatOptimizer (same arithmetic and checkpoints as torch.optim); needs a GPU
     )
     c.update(  # BaseDCModelScheme
         model_name="dc", dataset_name="dataset",
@@ -394,6 +396,11 @@ class ZincSVDScheme:
         opt = dict(adam=lambda p: torch.optim.Adam(p, lr=c.initial_lr, betas=(0.9, 0.999), eps=1e-7),     # Keras Adam epsilon
                    rmsprop=lambda p: torch.optim.RMSprop(p, lr=c.initial_lr, alpha=0.9, eps=1e-7),        # Keras rho=0.9
                    sgd=lambda p: torch.optim.SGD(p, lr=c.initial_lr))[c.optimizer]
+        if getattr(self, "_fused_opt", False):        # config.fused_optimizer: the same three, clipvalue folded into the update
+            from .optim import FlatOptimizer
+            # eager steps let the update zero the gradients it has read; a captured step graph keeps its own zeroing
+            return FlatOptimizer(params, self.flat, algo=c.optimizer, lr=c.initial_lr, clip_value=c.gradient_clipval,
+                                 zero_grad=not self._use_graph)
         return opt(params)
 
     def get_loss(self):                              # zinc/svd.py:37-39
@@ -426,16 +433,23 @@ class ZincSVDScheme:
             self.model = self.model.to(self.device)
         params = self.model.trainable_parameters() if hasattr(self.model, "trainable_parameters") else list(self.model.parameters())
         self.params = params
-        self.optimizer = self.get_optimizer(params)
+        self._use_graph = bool(self.config.use_hipgraph)
+        self._fused_opt = bool(self.config.fused_optimizer)
+        on_gpu = self.device is not None and torch.device(self.device).type == "cuda"
+        if not self._fused_opt:
+            self.optimizer = self.get_optimizer(params)
         self.loss_fn = self.get_loss()
         self.flat = None
         self._graphs, self._seeds = {}, None
-        self._use_graph = bool(self.config.use_hipgraph)
-        if self._use_graph and not (self.device is not None and torch.device(self.device).type == "cuda"):
+        if self._use_graph and not on_gpu:
             raise ValueError("config.use_hipgraph needs the model on a GPU (device='cuda')")
-        if self._use_graph or (self.config.distributed and torch.distributed.is_available() and torch.distributed.is_initialized()):
+        if self._fused_opt and not on_gpu:
+            raise ValueError("config.fused_optimizer needs the model on a GPU (device='cuda')")
+        if self._use_graph or self._fused_opt or (self.config.distributed and torch.distributed.is_available() and torch.distributed.is_initialized()):
             from .dp import FlatGradAllReduce
             self.flat = FlatGradAllReduce(params, direct=True)     # one flat-buffer all-reduce per step (MirroredStrategy, :230-247)
+        if self._fused_opt:                           # the update reads that buffer: built after it
+            self.optimizer = self.get_optimizer(params)
         if self._use_graph:                           # every captured geometry writes its gradients into this one flat buffer
             from .graph import DeviceSeeds
             from .layers import EGT
@@ -654,7 +668,9 @@ class ZincSVDScheme:
             loss, ms = self._graphed_loss(batch)
         else:
             if self.flat is not None:
-                self.flat.zero(); self.flat.rebind()
+                if not self._fused_opt:              # (the fused update zeroed what it read: FlatOptimizer(zero_grad=True))
+                    self.flat.zero()
+                self.flat.rebind()
             else:
                 self.optimizer.zero_grad(set_to_none=True)
             loss, ms = self.batch_loss(batch)
@@ -665,7 +681,7 @@ class ZincSVDScheme:
             # every graph of the GLOBAL batch counts once (the Keras loss is a mean over the global batch)
             lc, gc = batch.get("_local_count"), batch.get("_global_count")
             self.flat.all_reduce(average=True, local_count=lc, global_count=gc)
-        if c.gradient_clipval is not None:           # Keras clipvalue: elementwise clip of every gradient
+        if c.gradient_clipval is not None and not self._fused_opt:   # Keras clipvalue: elementwise clip of every gradient (the fused update clips)
             torch.nn.utils.clip_grad_value_(self.params, c.gradient_clipval)
         self.optimizer.step()
         self.state.global_step += 1                  # on_batch_end (:136)

@@ -654,6 +654,53 @@ int egt_prof_collect_graph(int reset_counts);
 int egt_prof_forget_graphs(void);             /* drop the event pairs of captured graphs from the profile (the graphs may go on replaying) */
 int egt_prof_names(char* buf, size_t cap);
 
+/* ---- fused flat optimizer: the parameter update of a step as two launches -----
+ * Adam / RMSprop / SGD with torch.optim's arithmetic (what the training driver runs: lib/training/training_base.py:59-72)
+ * over flat buffers in the layout of FlatGradAllReduce: element k of `grad`, `m`, `v` belongs to the parameter whose running
+ * sum of element counts covers k; no padding.  The parameters stay separate tensors, reached through `table`: device-resident
+ * work items {param, offset, count} -- `count` floats at `param` pair with the flat elements [offset, offset + count).  The host
+ * cuts the table so that no item straddles a parameter (egt_amd.optim.plan_items: at most 2048 elements per item; the kernel
+ * takes any count >= 1) and one workgroup runs one item.  `param` needs 4-byte alignment and `offset` is any float offset;
+ * grad / m / v are 16-byte-aligned buffers of exactly `total` floats; nothing outside an item's floats is read or written.
+ * An element's result does not depend on the item it falls into.
+ *   EGT_OPT_ADAM     m = lerp(m, g, 1-beta1); v = beta2 v + (1-beta2) g^2; p -= step_size m / (sqrt(v) / bc2_sqrt + eps)
+ *   EGT_OPT_RMSPROP  v = beta2 v + (1-beta2) g^2 (beta2 is RMSprop's alpha);  p -= lr g / (sqrt(v) + eps);  m ignored (NULL accepted)
+ *   EGT_OPT_SGD      p -= lr g;  m and v ignored (NULL accepted)
+ * with g = grad * grad_scale, clamped to +-clip_value under EGT_OPT_CLIP (Keras clipvalue).  Under EGT_OPT_ZERO_GRAD every
+ * gradient element is set to 0 after it was read: `grad` is written, which is why it is not const.
+ * State block: EGT_OPTIM_STATE_BYTES on the device, 8-byte aligned.  Kernel arguments are frozen when a hipGraph is captured,
+ * so what changes from step to step lives here.  The host owns the first 24 bytes:
+ *   int64 t (steps taken so far; 0 for a fresh run), double lr, float grad_scale, 4 bytes padding
+ * and updates lr / grad_scale with a plain copy (bytes 8..23); the rest belongs to the library.  egt_optim_prepare (ONE thread)
+ * increments t and forms step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) in fp64; egt_optim_step reads them and
+ * writes no state.  A step is egt_optim_prepare, then egt_optim_step, on one stream; both are capturable. */
+#define EGT_OPT_ADAM 0
+#define EGT_OPT_RMSPROP 1
+#define EGT_OPT_SGD 2
+#define EGT_OPT_CLIP 0x1u      /* clamp g to [-clip_value, clip_value] before use */
+#define EGT_OPT_ZERO_GRAD 0x2u /* store 0 to each gradient element after reading it */
+#define EGT_OPTIM_STATE_BYTES 64
+typedef struct {
+  int32_t algo;         /* EGT_OPT_ADAM / _RMSPROP / _SGD */
+  uint32_t flags;       /* EGT_OPT_* */
+  int32_t num_segments; /* entries of `table` = workgroups */
+  int32_t reserved;     /* 0 */
+  int64_t total;        /* floats in grad / m / v = sum of the counts */
+  double beta1;         /* Adam */
+  double beta2;         /* Adam's beta2, RMSprop's alpha */
+  float eps;
+  float clip_value;     /* EGT_OPT_CLIP */
+} egt_optim_desc;
+typedef struct {
+  float* param;   /* first float of the item in its parameter */
+  int64_t offset; /* of the item in the flat buffers, in floats */
+  int64_t count;  /* >= 1 */
+} egt_optim_segment; /* 24 bytes */
+int egt_optim_supported(const egt_optim_desc* desc);
+int egt_optim_prepare(const egt_optim_desc* desc, void* state, void* stream);
+int egt_optim_step(const egt_optim_desc* desc, const egt_optim_segment* table /* device */, float* grad, float* m, float* v,
+                   void* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
