@@ -12,6 +12,9 @@
 // the 128 hidden activations of a row never leave the registers of its four lanes.  The
 // LN-folded weights live in LDS as [tile][k-tile][lane] float4 slabs (conflict-free
 // ds_read_b128, four contraction steps per read), built once per call by k_ffn_prep.
+// One kernel per role for the three product modes of egt_ffn_desc.matmul: k_ffn_prep<W, MM>, k_ffn_fwd<W, ACT, MM, T>,
+// k_ffn_bwd<W, ACT, MM, T>.  MM sizes the staged slabs (FFN_SLABS) and picks the products behind `if constexpr`: f32_gemm on the fp32
+// slabs, or split_tiles / bf_gemm (egt_tile.h) on the bf16 hi | lo slabs; everything around the products is written once.
 //   forward : 256 MFMA / tile, 2 waves per SIMD, tiles streamed through ping-pong LDS buffers.
 //   backward: recompute + dHid + dXhat (384 MFMA) and the two weight-gradient contractions over
 //             the row axis (256 MFMA) in ONE kernel: 1 wave per SIMD so that a wave owns 512
@@ -44,7 +47,6 @@ struct FfnArgs {
   float *slab1, *slab2, *slab3, *slab4, *b1p;
   uint16_t *sA1, *sA2;   // EGT_MM_BF16X3 / EGT_MM_BF16: bf16 (hi | lo) A-operand slabs of the two forward GEMMs
   uint16_t *sA3, *sA4;   // ... and of the backward's dhid = W2 . dy and dxhat = W1p . dpre
-  int mm;                // egt_ffn_desc.matmul
   float *x16;            // workspace: the prepared operands of the width-8 kernels (F8_* offsets, k_ffn8_prep)
   float *part, *red;   // backward: per-workgroup partials, reduced sums
   float *g_gamma, *g_beta, *g_W1, *g_b1, *g_W2, *g_b2;
@@ -55,28 +57,65 @@ struct FfnArgs {
   int guard;   // always 0: opaque phase guards of the backward (see k_ffn_bwd)
 };
 
-// slab1[j][t][lane].u = gamma[c] W1[c][16j+pl],            c = 16t+4q+u     (A operand of  pre  = W1p^T . xhat)
-// slab2[i][j][lane].u = W2[16j+4q+u][16i+pl]                                (A operand of  y    = W2^T . hid)
-// slab3[j][t][lane].u = W2[16j+pl][16t+4q+u]                                (A operand of  dhid = W2 . dy)
-// slab4[i][j][lane].u = gamma[16i+pl] W1[16i+pl][16j+4q+u]                  (A operand of  dxhat= W1p . dpre)
-// b1p[h] = b1[h] + sum_c beta[c] W1[c][h]
-template <int W>
+// slab sizes of product mode MM in floats: S1F of the W -> 2W operands (slab1 / slab3, sA1 / sA3), S2F of the 2W -> W ones (slab2 /
+// slab4, sA2 / sA4).  A bf16 slab holds ceil(TW / 2) (resp. TW) 32-deep steps per output tile as [part][lane] blocks of 1 KiB.
+#define FFN_SLABS(MM)                                                                        \
+  constexpr int NS1 = (TW + 1) / 2, S1F = (MM) ? TH * NS1 * 2 * 256 : SLABF, S2F = (MM) ? TW * TW * 2 * 256 : SLABF; \
+  (void)NS1
+
+// v as its hi | lo bfloat16 terms (hi = bf16(v), lo = bf16(v - hi)) into slot i of the lane, in both parts of slab block blk
+__device__ __forceinline__ void bf_slab_put(uint16_t* slab, int blk, int lane, int i, float v) {
+  const uint32_t h = pk_bf16(v, 0.f) & 0xFFFFu;
+  slab[((size_t)(blk * 2 + 0) * 64 + lane) * 8 + i] = (uint16_t)h;
+  slab[((size_t)(blk * 2 + 1) * 64 + lane) * 8 + i] = (uint16_t)(pk_bf16(v - __uint_as_float(h << 16), 0.f) & 0xFFFFu);
+}
+
+// The prepared operands, once per call.  EGT_MM_F32 writes the fp32 slabs:
+//   slab1[j][t][lane].u = gamma[c] W1[c][16j+pl],            c = 16t+4q+u     (A operand of  pre  = W1p^T . xhat)
+//   slab2[i][j][lane].u = W2[16j+4q+u][16i+pl]                                (A operand of  y    = W2^T . hid)
+//   slab3[j][t][lane].u = W2[16j+pl][16t+4q+u]                                (A operand of  dhid = W2 . dy)
+//   slab4[i][j][lane].u = gamma[16i+pl] W1[16i+pl][16j+4q+u]                  (A operand of  dxhat= W1p . dpre)
+// EGT_MM_BF16X3 / EGT_MM_BF16 write the bf16 slabs ONLY (the same four operands; one 16x16x32 step contracts the 8 values a lane
+// holds of channel tiles 2s and 2s+1: slot i <-> tile 2s + (i >> 2), offset i & 3; part 0 = hi, 1 = lo):
+//   sA1[j][s][part][lane][i] = bf16_part( gamma[c] W1[c][16j + pl] ),  c = 16 (2s + (i >> 2)) + 4q + (i & 3)   (0 past W)
+//   sA3[j][s][part][lane][i] = bf16_part( W2[16j + pl][c] )                                                     (0 past W)
+//   sA2[o][s][part][lane][i] = bf16_part( W2[hc][16o + pl] ),         hc = 16 (2s + (i >> 2)) + 4q + (i & 3)
+//   sA4[o][s][part][lane][i] = bf16_part( gamma[16o + pl] W1[16o + pl][hc] )
+// Every mode writes b1p[h] = b1[h] + sum_c beta[c] W1[c][h].
+template <int W, int MM>
 __global__ void __launch_bounds__(256) k_ffn_prep(FfnArgs a) {
   FFN_GEO(W);
+  FFN_SLABS(MM);
   const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx < SLABF) {
-    const int u = idx & 3, lane = (idx >> 2) & 63, pl = lane & 15, q = lane >> 4, blk = idx >> 8;
-    {
-      const int t = blk % TW, j = blk / TW;
-      const int c = 16 * t + 4 * q + u;
-      a.slab1[idx] = a.gamma[c] * a.W1[c * FH + 16 * j + pl];
-      a.slab3[idx] = a.W2[(16 * j + pl) * FW + c];
+  if constexpr (MM == EGT_MM_F32) {
+    if (idx < SLABF) {
+      const int u = idx & 3, lane = (idx >> 2) & 63, pl = lane & 15, q = lane >> 4, blk = idx >> 8;
+      {
+        const int t = blk % TW, j = blk / TW;
+        const int c = 16 * t + 4 * q + u;
+        a.slab1[idx] = a.gamma[c] * a.W1[c * FH + 16 * j + pl];
+        a.slab3[idx] = a.W2[(16 * j + pl) * FW + c];
+      }
+      {
+        const int j = blk % TH, i = blk / TH;
+        const int hc = 16 * j + 4 * q + u;
+        a.slab2[idx] = a.W2[hc * FW + 16 * i + pl];
+        a.slab4[idx] = a.gamma[16 * i + pl] * a.W1[(16 * i + pl) * FH + hc];
+      }
     }
-    {
-      const int j = blk % TH, i = blk / TH;
-      const int hc = 16 * j + 4 * q + u;
-      a.slab2[idx] = a.W2[hc * FW + 16 * i + pl];
-      a.slab4[idx] = a.gamma[16 * i + pl] * a.W1[(16 * i + pl) * FH + hc];
+  } else {   // one thread per (block, lane, i)
+    const int i = idx & 7, lane = (idx >> 3) & 63, pl = lane & 15, q = lane >> 4, blk = idx >> 9;
+    if (idx < S1F) {   // (a block is 512 slots = 512 floats of both parts)
+      const int s = blk % NS1, j = blk / NS1, t = 2 * s + (i >> 2);
+      const int c = 16 * t + 4 * q + (i & 3);
+      bf_slab_put(a.sA1, blk, lane, i, t < TW ? a.gamma[c] * a.W1[c * FH + 16 * j + pl] : 0.f);
+      bf_slab_put(a.sA3, blk, lane, i, t < TW ? a.W2[(16 * j + pl) * FW + c] : 0.f);
+    }
+    if (idx < S2F) {
+      const int s = blk % TW, o = blk / TW;
+      const int hc = 16 * (2 * s + (i >> 2)) + 4 * q + (i & 3);
+      bf_slab_put(a.sA2, blk, lane, i, a.W2[hc * FW + 16 * o + pl]);
+      bf_slab_put(a.sA4, blk, lane, i, a.gamma[16 * o + pl] * a.W1[(16 * o + pl) * FH + hc]);
     }
   }
   if (idx < FH) {
@@ -142,113 +181,40 @@ __device__ __forceinline__ void slab_read(v4f (&w)[N], const float* slab_lane) {
   }
 }
 
-// pre-activation tile j of the lane's row: W1p^T . xhat + b1p   (16 MFMA)
-// TWO: two alternating accumulators (k_ffn_bwd: one wave per SIMD, nothing else fills the 8 idle cycles between dependent MFMAs;
-// the forward's two waves per SIMD cover each other and keep the single chain -- and its bit pattern)
-template <int W, bool TWO = false>
-__device__ __forceinline__ v4f ffn_gemm1(const float* s1, const float* b1s, const float4 (&x)[W / 16], int j, int lane, int q) {
-  constexpr int TW = W / 16;
-  const float4 bj = *reinterpret_cast<const float4*>(b1s + 16 * j + 4 * q);
-  v4f acc = {bj.x, bj.y, bj.z, bj.w};
-  v4f w[TW];
-  slab_read<TW>(w, s1 + (j * TW * 64 + lane) * 4);
+// fp32 products, the twin of bf_gemm: acc += sum_n A[n] . B[n] over the N [lane] float4 slab blocks at slab_lane (one slab_read), 4 N MFMAs.
+// TWO: two alternating accumulators, summed at the end.  A chain of MFMAs on ONE accumulator issues every 40 cycles (dependent
+// latency) instead of every 32; k_ffn_bwd runs one wave per SIMD and nothing else fills the gap.  The forward's two waves per SIMD
+// cover each other: it keeps the single chain -- and its bit pattern.
+template <int N, bool TWO>
+__device__ __forceinline__ v4f f32_gemm(const float* slab_lane, const v4f (&b)[N], v4f acc) {
+  v4f w[N];
+  slab_read<N>(w, slab_lane);
   if constexpr (TWO) {
     v4f acc2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int t = 0; t < TW; ++t) {
-      acc = MFMA(w[t][0], x[t].x, acc);
-      acc2 = MFMA(w[t][1], x[t].y, acc2);
-      acc = MFMA(w[t][2], x[t].z, acc);
-      acc2 = MFMA(w[t][3], x[t].w, acc2);
+    for (int n = 0; n < N; ++n) {
+      acc = MFMA(w[n][0], b[n][0], acc);
+      acc2 = MFMA(w[n][1], b[n][1], acc2);
+      acc = MFMA(w[n][2], b[n][2], acc);
+      acc2 = MFMA(w[n][3], b[n][3], acc2);
     }
     return acc + acc2;
   } else {
 #pragma unroll
-  for (int t = 0; t < TW; ++t) {
-    acc = MFMA(w[t][0], x[t].x, acc);
-    acc = MFMA(w[t][1], x[t].y, acc);
-    acc = MFMA(w[t][2], x[t].z, acc);
-    acc = MFMA(w[t][3], x[t].w, acc);
-  }
-  return acc;
+    for (int n = 0; n < N; ++n) {
+      acc = MFMA(w[n][0], b[n][0], acc);
+      acc = MFMA(w[n][1], b[n][1], acc);
+      acc = MFMA(w[n][2], b[n][2], acc);
+      acc = MFMA(w[n][3], b[n][3], acc);
+    }
+    return acc;
   }
 }
 
 // ================================================================== forward =====
 // T: storage type of x / y (float, or uint16_t = bfloat16 bits for EGT_BF16; the LDS tiles and the arithmetic stay fp32)
-template <int W, int ACT, typename T>
-__global__ void __launch_bounds__(512, 2) k_ffn_fwd(FfnArgs a) {
-  FFN_GEO(W);
-  const T* xg = reinterpret_cast<const T*>(a.x);
-  T* yg = reinterpret_cast<T*>(a.y);
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* s1 = sm;
-  float* s2 = s1 + SLABF;
-  float* b1s = s2 + SLABF;          // [128]
-  float* b2s = b1s + FH;            // [64]
-  float* tiles = b2s + FW;          // [8 waves][2][16 W]
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int p = lane & 15, q = lane >> 4;
-  slab_to_lds(s1, a.slab1, SLABF, 512);
-  slab_to_lds(s2, a.slab2, SLABF, 512);
-  if (threadIdx.x < FH) b1s[threadIdx.x] = a.b1p[threadIdx.x];
-  if (threadIdx.x < FW) b2s[threadIdx.x] = a.b2[threadIdx.x];
-  __syncthreads();
-  float* tl0 = tiles + wave * 2 * TILEF;
-  const long ntiles = (a.rows + 15) / 16;
-  const long stride = (long)gridDim.x * 8;
-  long tile = (long)blockIdx.x * 8 + wave;
-  typename TileIn<FW, T>::type tr;
-  if (tile < ntiles) tile_gload<FW, EGT_NT_FFN>(tr, xg + tile * TILEF, lane, (int)min(16L, a.rows - tile * 16));
-  long prev = -1;
-  for (int it = 0; tile < ntiles; tile += stride, ++it) {
-    const int rows_valid = (int)min(16L, a.rows - tile * 16);
-    float* tl = tl0 + (it & 1) * TILEF;
-    lds_sync();
-    if (prev >= 0)   // stream out the previous tile's y from the other buffer
-      tile_from_lds<FW>(tl0 + ((it - 1) & 1) * TILEF, yg + prev * TILEF, lane, (int)min(16L, a.rows - prev * 16));
-    tile_lds_put<FW>(tl, tr, lane, rows_valid);
-    const long nxt = tile + stride;
-    if (nxt < ntiles) tile_gload<FW, EGT_NT_FFN>(tr, xg + nxt * TILEF, lane, (int)min(16L, a.rows - nxt * 16));
-    lds_sync();
-    float4 x[TW];
-#pragma unroll
-    for (int t = 0; t < TW; ++t) x[t] = frag_read<FW>(tl, p, q, t);
-    ln_frags<W>(x, q, a.ln_eps);                            // norm_fnn (gamma/beta folded into the weights)
-    v4f h[TH];
-#pragma unroll
-    for (int j = 0; j < TH; ++j) {                                    // fnn_lr1 + activation
-      const v4f pre = ffn_gemm1<W>(s1, b1s, x, j, lane, q);
-      h[j] = (v4f){ffn_act<ACT>(pre[0]), ffn_act<ACT>(pre[1]), ffn_act<ACT>(pre[2]), ffn_act<ACT>(pre[3])};
-    }
-#pragma unroll
-    for (int i = 0; i < TW; ++i) {                                    // fnn_lr2 + res_fnn
-      const float4 xr = frag_read<FW>(tl, p, q, i);
-      const float4 b = *reinterpret_cast<const float4*>(b2s + 16 * i + 4 * q);
-      // the residual joins AFTER the chain: with x in the accumulator each of the 2W accumulations rounds at ulp(x), which at
-      // |x| ~ 100 is 1.2 - 1.5 of the forward tolerance on the update y - x (tests/test_conditioning_gpu.py, big / outliers)
-      v4f acc = {b.x, b.y, b.z, b.w};
-      v4f w[TH];
-      slab_read<TH>(w, s2 + (i * TH * 64 + lane) * 4);
-#pragma unroll
-      for (int j = 0; j < TH; ++j) {
-        acc = MFMA(w[j][0], h[j][0], acc);
-        acc = MFMA(w[j][1], h[j][1], acc);
-        acc = MFMA(w[j][2], h[j][2], acc);
-        acc = MFMA(w[j][3], h[j][3], acc);
-      }
-      frag_write<FW>(tl, p, q, i, make_float4(acc[0] + xr.x, acc[1] + xr.y, acc[2] + xr.z, acc[3] + xr.w));
-    }
-    prev = tile;
-    if (nxt >= ntiles) {   // last tile of this wave: flush
-      lds_sync();
-      tile_from_lds<FW>(tl, yg + tile * TILEF, lane, rows_valid);
-    }
-  }
-}
-
-// ================================================= forward on the bf16 matrix pipe =====
-// egt_ffn_desc.matmul = EGT_MM_BF16X3: every fp32 operand v is split into two bfloat16 terms,
+// MM: egt_ffn_desc.matmul, how the two GEMMs are evaluated.  EGT_MM_F32: exact fp32 MFMAs.
+// EGT_MM_BF16X3: every fp32 operand v is split into two bfloat16 terms,
 // v = hi + lo (hi = bf16(v), lo = bf16(v - hi): 16 mantissa bits survive), and a product a.b is
 // evaluated as a_hi.b_hi + a_lo.b_hi + a_hi.b_lo on v_mfma_f32_16x16x32_bf16 with fp32 accumulation
 // (the dropped a_lo.b_lo term is 2^-18 relative; every bf16 x bf16 product is exact in fp32).  Per-product
@@ -257,79 +223,26 @@ __global__ void __launch_bounds__(512, 2) k_ffn_fwd(FfnArgs a) {
 // cost: 96 bf16 MFMAs of 16 cycles per 16-row tile instead of 256 fp32 MFMAs of 32 cycles, which turns
 // the FFN from MFMA-bound (0.46 of the fp32 matrix peak) into an HBM-bound streaming kernel.
 // EGT_MM_BF16 keeps only the hi terms (plain bf16 products, fp32 accumulate; tolerance rtol 2e-2).
-// Same tile flow and fragment layout as k_ffn_fwd: lane (p, q) holds row p's channels 16t + 4q + {0..3};
-// one 16x16x32 step contracts the 8 values a lane holds of channel tiles 2s and 2s+1 (slot i <-> tile
-// 2s + (i >> 2), offset i & 3) -- both operands use that order, so the accumulators of GEMM 1 are again
-// the B operand of GEMM 2 without leaving the lane.
-// sA1[j][s][part][lane][i] = bf16_part( gamma[c] W1[c][16j + pl] ),  c = 16 (2s + (i >> 2)) + 4q + (i & 3)   (0 past W)
-// sA2[o][s][part][lane][i] = bf16_part( W2[hc][16o + pl] ),         hc = 16 (2s + (i >> 2)) + 4q + (i & 3)
-// part 0 = hi, 1 = lo; NS1 = ceil(TW / 2) steps for GEMM 1, TW steps for GEMM 2 (hidden = 2W = TW x 32)
-template <int W>
-__global__ void __launch_bounds__(256) k_ffn_prep_bf(FfnArgs a) {
+// Same tile flow and fragment layout in every mode: lane (p, q) holds row p's channels 16t + 4q + {0..3};
+// one 16x16x32 step contracts the 8 values a lane holds of channel tiles 2s and 2s+1 -- both operands use
+// that order (k_ffn_prep), so the accumulators of GEMM 1 are again the B operand of GEMM 2 without leaving the lane.
+template <int W, int ACT, int MM, typename T>
+__global__ void __launch_bounds__(512, 2) k_ffn_fwd(FfnArgs a) {
   FFN_GEO(W);
-  constexpr int NS1 = (TW + 1) / 2;
-  const int idx = blockIdx.x * 256 + threadIdx.x;   // one thread per (block, lane, i)
-  auto parts = [](float v, uint16_t& hi, uint16_t& lo) {
-    const uint32_t h = pk_bf16(v, 0.f) & 0xFFFFu;
-    hi = (uint16_t)h;
-    lo = (uint16_t)(pk_bf16(v - __uint_as_float(h << 16), 0.f) & 0xFFFFu);
-  };
-  if (idx < TH * NS1 * 512) {
-    const int i = idx & 7, lane = (idx >> 3) & 63, blk = idx >> 9, s = blk % NS1, j = blk / NS1;
-    const int pl = lane & 15, q = lane >> 4, t = 2 * s + (i >> 2);
-    const int c = 16 * t + 4 * q + (i & 3);
-    const float v = t < TW ? a.gamma[c] * a.W1[c * FH + 16 * j + pl] : 0.f;
-    uint16_t hi, lo;
-    parts(v, hi, lo);
-    a.sA1[((size_t)(blk * 2 + 0) * 64 + lane) * 8 + i] = hi;
-    a.sA1[((size_t)(blk * 2 + 1) * 64 + lane) * 8 + i] = lo;
-  }
-  if (idx < TW * TW * 512) {
-    const int i = idx & 7, lane = (idx >> 3) & 63, blk = idx >> 9, s = blk % TW, o = blk / TW;
-    const int pl = lane & 15, q = lane >> 4;
-    const int hc = 16 * (2 * s + (i >> 2)) + 4 * q + (i & 3);
-    uint16_t hi, lo;
-    parts(a.W2[hc * FW + 16 * o + pl], hi, lo);
-    a.sA2[((size_t)(blk * 2 + 0) * 64 + lane) * 8 + i] = hi;
-    a.sA2[((size_t)(blk * 2 + 1) * 64 + lane) * 8 + i] = lo;
-    // sA4[o][s][part][lane][i] = gamma[16o + pl] W1[16o + pl][hc]      (A operand of dxhat = W1p . dpre)
-    parts(a.gamma[16 * o + pl] * a.W1[(16 * o + pl) * FH + hc], hi, lo);
-    a.sA4[((size_t)(blk * 2 + 0) * 64 + lane) * 8 + i] = hi;
-    a.sA4[((size_t)(blk * 2 + 1) * 64 + lane) * 8 + i] = lo;
-  }
-  if (idx < TH * NS1 * 512) {   // sA3[j][s][part][lane][i] = W2[16j + pl][c]   (A operand of dhid = W2 . dy)
-    const int i = idx & 7, lane = (idx >> 3) & 63, blk = idx >> 9, s = blk % NS1, j = blk / NS1;
-    const int pl = lane & 15, q = lane >> 4, t = 2 * s + (i >> 2);
-    const int c = 16 * t + 4 * q + (i & 3);
-    uint16_t hi, lo;
-    parts(t < TW ? a.W2[(16 * j + pl) * FW + c] : 0.f, hi, lo);
-    a.sA3[((size_t)(blk * 2 + 0) * 64 + lane) * 8 + i] = hi;
-    a.sA3[((size_t)(blk * 2 + 1) * 64 + lane) * 8 + i] = lo;
-  }
-  if (idx < FH) {
-    float s = a.b1[idx];
-    for (int c = 0; c < FW; ++c) s = fmaf(a.beta[c], a.W1[c * FH + idx], s);
-    a.b1p[idx] = s;
-  }
-}
-
-template <int W, int ACT, bool SPLIT, typename T>
-__global__ void __launch_bounds__(512, 2) k_ffn_fwd_bf(FfnArgs a) {
-  FFN_GEO(W);
+  FFN_SLABS(MM);
+  constexpr bool SPLIT = MM == EGT_MM_BF16X3;
   const T* xg = reinterpret_cast<const T*>(a.x);
   T* yg = reinterpret_cast<T*>(a.y);
-  constexpr int NS1 = (TW + 1) / 2;
-  constexpr int A1F = TH * NS1 * 2 * 256, A2F = TW * TW * 2 * 256;   // slab sizes in floats (1 KiB = 256 floats per [part][lane] block)
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* s1 = sm;
-  float* s2 = s1 + A1F;
-  float* b1s = s2 + A2F;            // [2W]
+  float* s2 = s1 + S1F;
+  float* b1s = s2 + S2F;            // [2W]
   float* b2s = b1s + FH;            // [W]
   float* tiles = b2s + FW;          // [8 waves][2][16 W]
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int p = lane & 15, q = lane >> 4;
-  slab_to_lds(s1, reinterpret_cast<const float*>(a.sA1), A1F, 512);
-  slab_to_lds(s2, reinterpret_cast<const float*>(a.sA2), A2F, 512);
+  slab_to_lds(s1, MM ? reinterpret_cast<const float*>(a.sA1) : a.slab1, S1F, 512);
+  slab_to_lds(s2, MM ? reinterpret_cast<const float*>(a.sA2) : a.slab2, S2F, 512);
   if (threadIdx.x < FH) b1s[threadIdx.x] = a.b1p[threadIdx.x];
   if (threadIdx.x < FW) b2s[threadIdx.x] = a.b2[threadIdx.x];
   __syncthreads();
@@ -354,54 +267,31 @@ __global__ void __launch_bounds__(512, 2) k_ffn_fwd_bf(FfnArgs a) {
 #pragma unroll
     for (int t = 0; t < TW; ++t) x[t] = frag_read<FW>(tl, p, q, t);
     ln_frags<W>(x, q, a.ln_eps);                            // norm_fnn (gamma/beta folded into the weights)
+    v4f xv[TW], h[TH];
     Bf8 xh[NS1], xl[NS1];
 #pragma unroll
-    for (int s = 0; s < NS1; ++s) {
-      const float4 x0 = x[2 * s];
-      const float4 x1 = (2 * s + 1 < TW) ? x[(2 * s + 1 < TW) ? 2 * s + 1 : 0] : make_float4(0.f, 0.f, 0.f, 0.f);
-      const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-      split8<SPLIT>(v, xh[s], xl[s]);
-    }
-    v4f h[TH];
+    for (int t = 0; t < TW; ++t) xv[t] = (v4f){x[t].x, x[t].y, x[t].z, x[t].w};
+    if constexpr (MM != 0) split_tiles<TW, SPLIT>(xv, xh, xl);
 #pragma unroll
     for (int j = 0; j < TH; ++j) {                                    // fnn_lr1 + activation
       const float4 bj = *reinterpret_cast<const float4*>(b1s + 16 * j + 4 * q);
-      v4f acc = {bj.x, bj.y, bj.z, bj.w};
-#pragma unroll
-      for (int s = 0; s < NS1; ++s) {
-        Bf8 ah, al;
-        ah.q = *reinterpret_cast<const uint4*>(s1 + ((size_t)((j * NS1 + s) * 2 + 0) * 64 + lane) * 4);
-        acc = MFMA_BF(ah.v, xh[s].v, acc);
-        if (SPLIT) {
-          al.q = *reinterpret_cast<const uint4*>(s1 + ((size_t)((j * NS1 + s) * 2 + 1) * 64 + lane) * 4);
-          acc = MFMA_BF(al.v, xh[s].v, acc);
-          acc = MFMA_BF(ah.v, xl[s].v, acc);
-        }
-      }
-      h[j] = (v4f){ffn_act<ACT>(acc[0]), ffn_act<ACT>(acc[1]), ffn_act<ACT>(acc[2]), ffn_act<ACT>(acc[3])};
+      v4f pre = {bj.x, bj.y, bj.z, bj.w};
+      if constexpr (MM != 0) pre = bf_gemm<NS1, SPLIT>(s1, j * NS1, lane, xh, xl, pre);
+      else pre = f32_gemm<TW, false>(s1 + (j * TW * 64 + lane) * 4, xv, pre);
+      h[j] = (v4f){ffn_act<ACT>(pre[0]), ffn_act<ACT>(pre[1]), ffn_act<ACT>(pre[2]), ffn_act<ACT>(pre[3])};
     }
     Bf8 hh[TW], hl[TW];
-#pragma unroll
-    for (int s = 0; s < TW; ++s) {
-      const float v[8] = {h[2 * s][0], h[2 * s][1], h[2 * s][2], h[2 * s][3], h[2 * s + 1][0], h[2 * s + 1][1], h[2 * s + 1][2], h[2 * s + 1][3]};
-      split8<SPLIT>(v, hh[s], hl[s]);
-    }
+    if constexpr (MM != 0) split_tiles<TH, SPLIT>(h, hh, hl);
 #pragma unroll
     for (int i = 0; i < TW; ++i) {                                    // fnn_lr2 + res_fnn
       const float4 xr = frag_read<FW>(tl, p, q, i);
       const float4 b = *reinterpret_cast<const float4*>(b2s + 16 * i + 4 * q);
-      v4f acc = {b.x, b.y, b.z, b.w};   // the residual joins after the chain, as in k_ffn_fwd (0.93 of the tolerance with x inside)
-#pragma unroll
-      for (int s = 0; s < TW; ++s) {
-        Bf8 ah, al;
-        ah.q = *reinterpret_cast<const uint4*>(s2 + ((size_t)((i * TW + s) * 2 + 0) * 64 + lane) * 4);
-        acc = MFMA_BF(ah.v, hh[s].v, acc);
-        if (SPLIT) {
-          al.q = *reinterpret_cast<const uint4*>(s2 + ((size_t)((i * TW + s) * 2 + 1) * 64 + lane) * 4);
-          acc = MFMA_BF(al.v, hh[s].v, acc);
-          acc = MFMA_BF(ah.v, hl[s].v, acc);
-        }
-      }
+      // the residual joins AFTER the chain: with x in the accumulator each of the 2W accumulations rounds at ulp(x), which at
+      // |x| ~ 100 is 1.2 - 1.5 of the forward tolerance on the update y - x (tests/test_conditioning_gpu.py, big / outliers;
+      // 0.93 of it on the bf16 pipe)
+      v4f acc = {b.x, b.y, b.z, b.w};
+      if constexpr (MM != 0) acc = bf_gemm<TW, SPLIT>(s2, i * TW, lane, hh, hl, acc);
+      else acc = f32_gemm<TH, false>(s2 + (i * TH * 64 + lane) * 4, h, acc);
       frag_write<FW>(tl, p, q, i, make_float4(acc[0] + xr.x, acc[1] + xr.y, acc[2] + xr.z, acc[3] + xr.w));
     }
     prev = tile;
@@ -417,32 +307,28 @@ __global__ void __launch_bounds__(512, 2) k_ffn_fwd_bf(FfnArgs a) {
 // dhid = W2 . dy, dxhat = W1p . dpre: 384 of the 640 fp32 MFMAs of a tile) to the bf16 matrix pipe (144 / 48
 // MFMAs of 16 cycles); the weight-gradient contractions over the ROW axis stay exact fp32 (their operands are
 // read transposed out of the fp32 LDS tiles).
+// Every tile phase opens with its own copy of the lane's (p, q), opaque to the compiler: the phase's LDS address math stays inside
+// the phase (no hoisting out of the tile loop).
+#define FFN_PHASE_PQ int p = p0, q = q0; asm volatile("" : "+v"(p), "+v"(q))
 template <int W, int ACT, int MM, typename T>
 __global__ void __launch_bounds__(256, 1) k_ffn_bwd(FfnArgs a) {
   FFN_GEO(W);
   const T* xg = reinterpret_cast<const T*>(a.x);
   const T* dyg = reinterpret_cast<const T*>(a.dy);
   T* dxg = reinterpret_cast<T*>(a.dx);
-  constexpr int NS1 = (TW + 1) / 2;
+  FFN_SLABS(MM);
   constexpr bool SPLIT = MM == EGT_MM_BF16X3;
-  constexpr int S1F = MM ? TH * NS1 * 2 * 256 : SLABF, S4F = MM ? TW * TW * 2 * 256 : SLABF;   // slab sizes in floats
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* s1 = sm;
   float* s3 = s1 + S1F;
   float* s4 = s3 + S1F;
-  float* b1s = s4 + S4F;            // [128]
+  float* b1s = s4 + S2F;            // [2W]
   float* tiles = b1s + FH;          // [4 waves][x | dy | hid/dpre half][TILEF]
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int p0 = lane & 15, q0 = lane >> 4;
-  if constexpr (MM != 0) {
-    slab_to_lds(s1, reinterpret_cast<const float*>(a.sA1), S1F, 256);
-    slab_to_lds(s3, reinterpret_cast<const float*>(a.sA3), S1F, 256);
-    slab_to_lds(s4, reinterpret_cast<const float*>(a.sA4), S4F, 256);
-  } else {
-    slab_to_lds(s1, a.slab1, SLABF, 256);
-    slab_to_lds(s3, a.slab3, SLABF, 256);
-    slab_to_lds(s4, a.slab4, SLABF, 256);
-  }
+  slab_to_lds(s1, MM ? reinterpret_cast<const float*>(a.sA1) : a.slab1, S1F, 256);
+  slab_to_lds(s3, MM ? reinterpret_cast<const float*>(a.sA3) : a.slab3, S1F, 256);
+  slab_to_lds(s4, MM ? reinterpret_cast<const float*>(a.sA4) : a.slab4, S2F, 256);
   if (threadIdx.x < FH) b1s[threadIdx.x] = a.b1p[threadIdx.x];
   __syncthreads();
   float* et = tiles + wave * 3 * TILEF;
@@ -492,70 +378,44 @@ __global__ void __launch_bounds__(256, 1) k_ffn_bwd(FfnArgs a) {
     float rstd;
     v4f h[TH], dp[TH];
     {
-      int p = p0, q = q0;
-      asm volatile("" : "+v"(p), "+v"(q));   // keep this phase's LDS address math inside the phase (no hoisting out of the tile loop)
+      FFN_PHASE_PQ;
       float4 x[TW];
 #pragma unroll
       for (int t = 0; t < TW; ++t) x[t] = frag_read<FW>(et, p, q, t);
       rstd = ln_frags<W>(x, q, a.ln_eps);
 #pragma unroll
       for (int t = 0; t < TW; ++t) frag_write<FW>(et, p, q, t, x[t]);   // xhat: A operand of T1 (other rows) + LN backward
-      if constexpr (MM != 0) {
-        v4f xv[TW];
-        Bf8 xh[NS1], xl[NS1];
+      v4f xv[TW];
+      Bf8 xh[NS1], xl[NS1];
 #pragma unroll
-        for (int t = 0; t < TW; ++t) xv[t] = (v4f){x[t].x, x[t].y, x[t].z, x[t].w};
-        split_tiles<TW, SPLIT>(xv, xh, xl);
+      for (int t = 0; t < TW; ++t) xv[t] = (v4f){x[t].x, x[t].y, x[t].z, x[t].w};
+      if constexpr (MM != 0) split_tiles<TW, SPLIT>(xv, xh, xl);
 #pragma unroll
-        for (int j = 0; j < TH; ++j) {
-          const float4 bj = *reinterpret_cast<const float4*>(b1s + 16 * j + 4 * q);
-          const v4f pre = bf_gemm<NS1, SPLIT>(s1, j * NS1, lane, xh, xl, (v4f){bj.x, bj.y, bj.z, bj.w});
-          h[j] = (v4f){ffn_act<ACT>(pre[0]), ffn_act<ACT>(pre[1]), ffn_act<ACT>(pre[2]), ffn_act<ACT>(pre[3])};
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < TH; ++j) {
-          const v4f pre = ffn_gemm1<W, (W < 64)>(s1, b1s, x, j, lane, q);   // (W = 64: the extra accumulator would spill)
-          h[j] = (v4f){ffn_act<ACT>(pre[0]), ffn_act<ACT>(pre[1]), ffn_act<ACT>(pre[2]), ffn_act<ACT>(pre[3])};
-        }
+      for (int j = 0; j < TH; ++j) {
+        const float4 bj = *reinterpret_cast<const float4*>(b1s + 16 * j + 4 * q);
+        v4f pre = {bj.x, bj.y, bj.z, bj.w};
+        if constexpr (MM != 0) pre = bf_gemm<NS1, SPLIT>(s1, j * NS1, lane, xh, xl, pre);
+        else pre = f32_gemm<TW, (W < 64)>(s1 + (j * TW * 64 + lane) * 4, xv, pre);   // (W = 64: the extra accumulator would spill)
+        h[j] = (v4f){ffn_act<ACT>(pre[0]), ffn_act<ACT>(pre[1]), ffn_act<ACT>(pre[2]), ffn_act<ACT>(pre[3])};
       }
     }
     lds_sync();
     // ---- dhid = W2 . dy ; dpre = dhid * act'(pre) ----
     if (a.guard == 0) {
-      int p = p0, q = q0;
-      asm volatile("" : "+v"(p), "+v"(q));   // keep this phase's LDS address math inside the phase (no hoisting out of the tile loop)
-      float4 dyf[TW];
+      FFN_PHASE_PQ;
+      v4f dv[TW];
 #pragma unroll
       for (int t = 0; t < TW; ++t) {
-        dyf[t] = frag_read<FW>(dt, p, q, t);
+        const float4 dyf = frag_read<FW>(dt, p, q, t);
+        dv[t] = (v4f){dyf.x, dyf.y, dyf.z, dyf.w};
       }
       Bf8 dyh[NS1], dyl[NS1];
-      if constexpr (MM != 0) {
-        v4f dv[TW];
-#pragma unroll
-        for (int t = 0; t < TW; ++t) dv[t] = (v4f){dyf[t].x, dyf[t].y, dyf[t].z, dyf[t].w};
-        split_tiles<TW, SPLIT>(dv, dyh, dyl);
-      }
+      if constexpr (MM != 0) split_tiles<TW, SPLIT>(dv, dyh, dyl);
 #pragma unroll
       for (int j = 0; j < TH; ++j) {
         v4f acc = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (MM != 0) {
-          acc = bf_gemm<NS1, SPLIT>(s3, j * NS1, lane, dyh, dyl, acc);
-        } else {
-          // two alternating accumulators: a chain of MFMAs on ONE accumulator issues every 40 cycles (dependent latency) instead of
-          // every 32, and with one wave per SIMD nothing else fills the gap
-          v4f w[TW], acc2 = {0.f, 0.f, 0.f, 0.f};
-          slab_read<TW>(w, s3 + (j * TW * 64 + lane) * 4);
-#pragma unroll
-          for (int t = 0; t < TW; ++t) {
-            acc = MFMA(w[t][0], dyf[t].x, acc);
-            acc2 = MFMA(w[t][1], dyf[t].y, acc2);
-            acc = MFMA(w[t][2], dyf[t].z, acc);
-            acc2 = MFMA(w[t][3], dyf[t].w, acc2);
-          }
-          acc += acc2;
-        }
+        if constexpr (MM != 0) acc = bf_gemm<NS1, SPLIT>(s3, j * NS1, lane, dyh, dyl, acc);
+        else acc = f32_gemm<TW, true>(s3 + (j * TW * 64 + lane) * 4, dv, acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[r] *= ffn_dact<ACT>(h[j][r]);
         dp[j] = acc;
@@ -563,8 +423,7 @@ __global__ void __launch_bounds__(256, 1) k_ffn_bwd(FfnArgs a) {
     }
     // ---- weight gradients: contractions over the 16 rows of the tile (row index rho = q + 4s) ----
     if (a.guard == 0) {                             // T2 += hid^T . dy
-      int p = p0, q = q0;
-      asm volatile("" : "+v"(p), "+v"(q));   // keep this phase's LDS address math inside the phase (no hoisting out of the tile loop)
+      FFN_PHASE_PQ;
       float bdy[TW][4];   // dy[rho][16i+pl]
 #pragma unroll
       for (int i = 0; i < TW; ++i)
@@ -590,8 +449,7 @@ __global__ void __launch_bounds__(256, 1) k_ffn_bwd(FfnArgs a) {
       }
     }
     if (a.guard == 0) {                             // T1 += xhat^T . dpre
-      int p = p0, q = q0;
-      asm volatile("" : "+v"(p), "+v"(q));   // keep this phase's LDS address math inside the phase (no hoisting out of the tile loop)
+      FFN_PHASE_PQ;
       float axh[TW][4];   // xhat[rho][16t+pl]
 #pragma unroll
       for (int t = 0; t < TW; ++t)
@@ -617,8 +475,7 @@ __global__ void __launch_bounds__(256, 1) k_ffn_bwd(FfnArgs a) {
     }
     // ---- dxhat = W1p . dpre ; LayerNorm backward ; dx = dy + ... (in place over the dy tile) ----
     if (a.guard == 0) {
-      int p = p0, q = q0;
-      asm volatile("" : "+v"(p), "+v"(q));   // keep this phase's LDS address math inside the phase (no hoisting out of the tile loop)
+      FFN_PHASE_PQ;
       float4 dxh[TW], x[TW];
       float m1 = 0.f, m2 = 0.f;
       Bf8 dph[TW], dpl[TW];
@@ -627,20 +484,8 @@ __global__ void __launch_bounds__(256, 1) k_ffn_bwd(FfnArgs a) {
       for (int i = 0; i < TW; ++i) {
         x[i] = frag_read<FW>(et, p, q, i);          // xhat
         v4f acc = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (MM != 0) {
-          acc = bf_gemm<TW, SPLIT>(s4, i * TW, lane, dph, dpl, acc);
-        } else {
-          v4f w[TH], acc2 = {0.f, 0.f, 0.f, 0.f};   // (two alternating accumulators, as in the dhid product)
-          slab_read<TH>(w, s4 + (i * TH * 64 + lane) * 4);
-#pragma unroll
-          for (int j = 0; j < TH; ++j) {
-            acc = MFMA(w[j][0], dp[j][0], acc);
-            acc2 = MFMA(w[j][1], dp[j][1], acc2);
-            acc = MFMA(w[j][2], dp[j][2], acc);
-            acc2 = MFMA(w[j][3], dp[j][3], acc2);
-          }
-          acc += acc2;
-        }
+        if constexpr (MM != 0) acc = bf_gemm<TW, SPLIT>(s4, i * TW, lane, dph, dpl, acc);
+        else acc = f32_gemm<TH, true>(s4 + (i * TH * 64 + lane) * 4, dp, acc);
         dxh[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
         m1 += (acc[0] + acc[1]) + (acc[2] + acc[3]);
         m2 = fmaf(acc[0], x[i].x, m2); m2 = fmaf(acc[1], x[i].y, m2);
@@ -1045,11 +890,12 @@ extern "C" int egt_ffn_supported(const egt_ffn_desc* d) {
 //   [slab1 slab2 slab3 slab4 | b1p | red | part x ffn_nwg_cap | sA1 sA2 sA3 sA4 (bf16 modes) | x16 (width 8: F8_* operands)]
 // The storage dtype changes only the kernel instances (x / y / dy / dx as T): the workspace holds fp32 operands and partials in
 // both, so an EGT_BF16 descriptor has the same plan sizes as its fp32 twin.
-enum FfnFamily { FFN_ROW8, FFN_F32, FFN_BF16 };   // k_ffn8_* (one row per lane) | k_ffn_* fp32 tiles | bf16 tiles (EGT_MM_BF16X3 / _BF16)
+enum FfnFamily { FFN_ROW8, FFN_TILE };   // k_ffn8_* (one row per lane) | k_ffn_* (16-row tiles, every product mode)
 struct FfnPlan {
   FfnFamily fam;
   bool bf16;   // desc.dtype == EGT_BF16: the uint16_t (bfloat16) storage instances
   int W;   // layout width
+  int mm;  // desc.matmul: the product mode of the tile kernels' instances
   size_t slab, b1p, red, part, sA1, sA2, sA3, sA4, x16, total;
   int part_len;                 // floats per backward workgroup partial
   EgtLaunch prep, fwd, bwd;     // bwd.grid: backward workgroups (= partials)
@@ -1057,8 +903,9 @@ struct FfnPlan {
 
 static FfnPlan plan_ffn(const egt_ffn_desc* d) {
   FfnPlan P{};
-  P.fam = d->width == 8 ? FFN_ROW8 : (d->matmul == EGT_MM_F32 ? FFN_F32 : FFN_BF16);
+  P.fam = d->width == 8 ? FFN_ROW8 : FFN_TILE;
   P.bf16 = d->dtype == EGT_BF16;
+  P.mm = d->matmul;
   const size_t W = P.W = d->width == 8 ? 16 : d->width, TW = W / 16, NS1 = (TW + 1) / 2;
   const size_t slab = 2 * W * W, part = 2 * slab + 3 * W;                     // slab = W*2W floats; partial = T1 | T2 | s1 | s2
   const size_t a1 = 2 * TW * NS1 * 2 * 256, a2 = TW * TW * 2 * 256;           // sA1, sA3: [TH][NS1][2][256]; sA2, sA4: [TW][TW][2][256]
@@ -1076,16 +923,15 @@ static FfnPlan plan_ffn(const egt_ffn_desc* d) {
     return P;
   }
   P.part_len = (int)part;
-  if (P.fam == FFN_F32) {
-    P.prep = {(int)((slab + 255) / 256), 256, 0};
-    P.fwd = {clamp((tiles + 7) / 8, 256), 512, (2 * slab + 3 * W + 8 * 2 * 16 * W) * 4};
-  } else {
-    P.prep = {(int)(((a1 > a2 ? a1 : a2) + 255) / 256), 256, 0};
-    P.fwd = {clamp((tiles + 7) / 8, 512), 512, (a1 + a2 + 3 * W + 8 * 2 * 16 * W) * 4};
-  }
+  // the slabs the kernels stage (FFN_SLABS): s1f floats each of the W -> 2W operands, s2f of the 2W -> W ones.  The bf16 modes' forward
+  // is HBM-bound and takes twice the workgroups.
+  const bool bf = P.mm != EGT_MM_F32;
+  const size_t s1f = bf ? a1 : slab, s2f = bf ? a2 : slab;
+  P.prep = {(int)(((s1f > s2f ? s1f : s2f) + 255) / 256), 256, 0};
+  P.fwd = {clamp((tiles + 7) / 8, bf ? 512 : 256), 512, (s1f + s2f + 3 * W + 8 * 2 * 16 * W) * 4};
   // backward workgroups: one per CU for large inputs; small inputs (node channels) one tile per wave (a tile is ~16 us of dependent
   // work: spreading beats amortising the slab staging).  LDS: the operand slabs, with the partial staged over them at the end
-  const size_t slabs = P.fam == FFN_BF16 ? 2 * a1 + a2 : 3 * slab;
+  const size_t slabs = 2 * s1f + s2f;
   P.bwd = {clamp((tiles + 3) / 4, (long)ffn_nwg_cap(W)), 256, ((slabs > part ? slabs : part) + 2 * W + 4 * 3 * 16 * W) * 4};
   return P;
 }
@@ -1112,7 +958,6 @@ static int ffn_fill(const egt_ffn_desc* d, const egt_ffn_params* p, void* ws, Ff
   float* w = (float*)ws;
   a.slab1 = w; a.slab2 = w + P.slab; a.slab3 = w + 2 * P.slab; a.slab4 = w + 3 * P.slab;
   a.b1p = w + P.b1p; a.red = w + P.red; a.part = w + P.part;
-  a.mm = d->matmul;
   a.sA1 = reinterpret_cast<uint16_t*>(w + P.sA1); a.sA2 = reinterpret_cast<uint16_t*>(w + P.sA2);
   a.sA3 = reinterpret_cast<uint16_t*>(w + P.sA3); a.sA4 = reinterpret_cast<uint16_t*>(w + P.sA4);
   a.x16 = w + P.x16;
@@ -1120,46 +965,37 @@ static int ffn_fill(const egt_ffn_desc* d, const egt_ffn_params* p, void* ws, Ff
   return EGT_OK;
 }
 
-// one instance of the tile kernels: width W, activation ACT, products MM (the forward of the bf16 modes: k_ffn_fwd_bf, SPLIT for bf16x3),
-// storage T of x / y / dy / dx
+// one instance of the tile kernels: width W, activation ACT, products MM, storage T of x / y / dy / dx
 template <int W, int ACT, int MM, typename T>
 static void ffn_launch_tiles(const FfnPlan& P, const FfnArgs& a, bool bwd, bool prep, hipStream_t st) {
-  if (prep) {
-    if constexpr (MM == EGT_MM_F32) EGT_LAUNCH("k_ffn_prep", k_ffn_prep<W>, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
-    else EGT_LAUNCH("k_ffn_prep", k_ffn_prep_bf<W>, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
-  }
+  if (prep) EGT_LAUNCH("k_ffn_prep", (k_ffn_prep<W, MM>), dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
   if (bwd) egt_launch_planned<k_ffn_bwd<W, ACT, MM, T>>("k_ffn_bwd", P.bwd, st, a);
-  else if constexpr (MM == EGT_MM_F32) egt_launch_planned<k_ffn_fwd<W, ACT, T>>("k_ffn_fwd", P.fwd, st, a);
-  else egt_launch_planned<k_ffn_fwd_bf<W, ACT, MM == EGT_MM_BF16X3, T>>("k_ffn_fwd", P.fwd, st, a);
+  else egt_launch_planned<k_ffn_fwd<W, ACT, MM, T>>("k_ffn_fwd", P.fwd, st, a);
 }
-template <int W, typename T>
-static void ffn_launch_w(const FfnPlan& P, const FfnArgs& a, int act, bool bwd, bool prep, hipStream_t st) {
-  switch (2 * a.mm + (act == EGT_ACT_RELU)) {   // products, activation
-    case 2 * EGT_MM_F32 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_F32, T>(P, a, bwd, prep, st); break;
-    case 2 * EGT_MM_F32: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_F32, T>(P, a, bwd, prep, st); break;
-    case 2 * EGT_MM_BF16X3 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_BF16X3, T>(P, a, bwd, prep, st); break;
-    case 2 * EGT_MM_BF16X3: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_BF16X3, T>(P, a, bwd, prep, st); break;
-    case 2 * EGT_MM_BF16 + 1: ffn_launch_tiles<W, EGT_ACT_RELU, EGT_MM_BF16, T>(P, a, bwd, prep, st); break;
-    default: ffn_launch_tiles<W, EGT_ACT_ELU, EGT_MM_BF16, T>(P, a, bwd, prep, st); break;
-  }
-}
+// the planned family's instance for storage T: the row-per-lane kernels by activation, the tile kernels by (W, MM, ACT)
 template <typename T>
 static void ffn_launch_t(const FfnPlan& P, const FfnArgs& a, int act, bool bwd, bool prep, hipStream_t st) {
+  const bool relu = act == EGT_ACT_RELU;
   if (P.fam == FFN_ROW8) {
     if (prep) EGT_LAUNCH("k_ffn_prep", k_ffn8_prep, dim3(P.prep.grid), dim3(P.prep.block), P.prep.lds, st, a);
     const EgtLaunch& s = bwd ? P.bwd : P.fwd;
-    if (bwd && act == EGT_ACT_RELU) EGT_LAUNCH("k_ffn_bwd", (k_ffn8_bwd<EGT_ACT_RELU, T>), dim3(s.grid), dim3(s.block), s.lds, st, a);
+    if (bwd && relu) EGT_LAUNCH("k_ffn_bwd", (k_ffn8_bwd<EGT_ACT_RELU, T>), dim3(s.grid), dim3(s.block), s.lds, st, a);
     else if (bwd) EGT_LAUNCH("k_ffn_bwd", (k_ffn8_bwd<EGT_ACT_ELU, T>), dim3(s.grid), dim3(s.block), s.lds, st, a);
-    else if (act == EGT_ACT_RELU) EGT_LAUNCH("k_ffn_fwd", (k_ffn8_fwd<EGT_ACT_RELU, T>), dim3(s.grid), dim3(s.block), s.lds, st, a);
+    else if (relu) EGT_LAUNCH("k_ffn_fwd", (k_ffn8_fwd<EGT_ACT_RELU, T>), dim3(s.grid), dim3(s.block), s.lds, st, a);
     else EGT_LAUNCH("k_ffn_fwd", (k_ffn8_fwd<EGT_ACT_ELU, T>), dim3(s.grid), dim3(s.block), s.lds, st, a);
     return;
   }
-  switch (P.W) {
-    case 16: ffn_launch_w<16, T>(P, a, act, bwd, prep, st); break;
-    case 32: ffn_launch_w<32, T>(P, a, act, bwd, prep, st); break;
-    case 48: ffn_launch_w<48, T>(P, a, act, bwd, prep, st); break;
-    default: ffn_launch_w<64, T>(P, a, act, bwd, prep, st); break;
+#define FFN_TILE_CASE(W, MM)                                                                              \
+  case (W) * 4 + (MM):                                                                                    \
+    if (relu) ffn_launch_tiles<W, EGT_ACT_RELU, MM, T>(P, a, bwd, prep, st);                              \
+    else ffn_launch_tiles<W, EGT_ACT_ELU, MM, T>(P, a, bwd, prep, st);                                    \
+    break;
+#define FFN_TILE_CASES(W) FFN_TILE_CASE(W, EGT_MM_F32) FFN_TILE_CASE(W, EGT_MM_BF16X3) FFN_TILE_CASE(W, EGT_MM_BF16)
+  switch (P.W * 4 + P.mm) {   // (egt_ffn_supported has passed: the widths and modes below are all there are)
+    FFN_TILE_CASES(16) FFN_TILE_CASES(32) FFN_TILE_CASES(48) FFN_TILE_CASES(64)
   }
+#undef FFN_TILE_CASES
+#undef FFN_TILE_CASE
 }
 // prep (unless a backward finds its workspace prepared), then the planned family's forward / backward instance
 static void ffn_launch(const FfnPlan& P, const FfnArgs& a, int act, bool bwd, bool prep, hipStream_t st) {
@@ -1193,7 +1029,7 @@ extern "C" int egt_ffn_bwd(const egt_ffn_desc* desc, const egt_ffn_params* param
   a.g_W2 = (float*)grads->lr2_kernel; a.g_b2 = (float*)grads->lr2_bias;
   hipStream_t st = (hipStream_t)stream;
   // EGT_FFN_WS_PREPARED: the forward's workspace, its prepared operands are still there (the bf16 modes read their own slabs and b1p
-  // only: k_ffn_prep_bf writes all of that)
+  // only: k_ffn_prep<W, MM> writes all of that)
   ffn_launch(P, a, desc->activation, true, !(desc->flags & EGT_FFN_WS_PREPARED), st);
   EGT_LAUNCH("k_ffn_sum", k_ffn_sum, dim3((P.part_len + 63) / 64), dim3(1024), 0, st, a);
   EGT_LAUNCH("k_ffn_param_grads", k_ffn_param_grads, dim3(1), dim3(1024), 0, st, a);

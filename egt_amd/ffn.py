@@ -106,12 +106,12 @@ class FFN(nn.Module):
             raise ValueError("fused FFN is built for ffn_multiplier = 2")
         if activation not in _ACT:
             raise ValueError(f"fused FFN activation must be one of {sorted(_ACT)} (got {activation!r})")
-        # fail at construction for a width the kernels do not cover (there is no composed fallback);
-        # the C library decides (egt_ffn_supported), so the Python side never drifts from it
-        if not L.load().egt_ffn_supported(C.byref(_desc(16, width, activation, 1e-3, matmul if matmul in _MM else "f32"))):
-            raise ValueError(f"fused FFN does not cover width {width} with matmul={matmul!r} (fp32; width 8: exact products only)")
         if matmul not in _MM:
             raise ValueError(f"matmul must be one of {sorted(_MM)} (got {matmul!r})")
+        # fail at construction for a width the kernels do not cover (there is no composed fallback);
+        # the C library decides (egt_ffn_supported), so the Python side never drifts from it
+        if not L.load().egt_ffn_supported(C.byref(_desc(16, width, activation, 1e-3, matmul))):
+            raise ValueError(f"fused FFN does not cover width {width} with matmul={matmul!r} (fp32; width 8: exact products only)")
         self.width, self.activation, self.matmul = width, activation, matmul
         self.norm_gamma = nn.Parameter(torch.ones(width))
         self.norm_beta = nn.Parameter(torch.zeros(width))

@@ -9,28 +9,63 @@ pytestmark = pytest.mark.gpu
 NAMES = ("norm_gamma", "norm_beta", "lr1_kernel", "lr1_bias", "lr2_kernel", "lr2_bias")
 
 
-def _run(shape, act, gpu, seed=0, W=64, matmul="f32", fwd_tol=FWD, bwd_tol=BWD):
+def _ffn_case(shape, act, gpu, seed=0, W=64, matmul="f32", dtype=torch.float32):
+    """the module, the inputs (x, dy as stored: fp32 or bf16) and one forward + backward of them: m, x, dy, y, dx"""
     from egt_amd import FFN
-    from oracle import egt_oracle as O
     torch.manual_seed(seed)
     m = FFN(W, activation=act, matmul=matmul).to(gpu)
     with torch.no_grad():
         for n in ("norm_gamma", "norm_beta", "lr1_bias", "lr2_bias"):
             getattr(m, n).add_(0.3 * torch.randn_like(getattr(m, n)))
     g = torch.Generator().manual_seed(seed + 1)
-    x = torch.randn(*shape, W, generator=g) * 1.5 + 0.2
-    dy = torch.randn(*shape, W, generator=g)
+    x = (torch.randn(*shape, W, generator=g) * 1.5 + 0.2).to(dtype)
+    dy = torch.randn(*shape, W, generator=g).to(dtype)
     xg = x.to(gpu).requires_grad_()
     y = m(xg)
     y.backward(dy.to(gpu))
+    return m, x, dy, y.detach(), xg.grad
+
+
+def _run(shape, act, gpu, seed=0, W=64, matmul="f32", fwd_tol=FWD, bwd_tol=BWD, dtype=torch.float32):
+    """dtype: storage of x / y / dy / dx.  In bf16 the oracle reads the same bf16 inputs, and y / dx are held to the stored-value
+    rule of tests/test_bf16_edges_gpu.py (check_stored); the parameter gradients are fp32 in both."""
+    from oracle import egt_oracle as O
+    m, x, dy, y, dx = _ffn_case(shape, act, gpu, seed, W, matmul, dtype)
     p64 = {n: getattr(m, n).detach().double().cpu().requires_grad_() for n in NAMES}
     x64 = x.double().requires_grad_()
     yo = O.ffn_forward(x64, p64, activation=act)
     gr = torch.autograd.grad(yo, [x64] + [p64[n] for n in NAMES], dy.double())
-    assert_close(y, yo, name="y", **fwd_tol)
-    assert_close(xg.grad, gr[0], name="dx", **bwd_tol)
+    if dtype == torch.float32:
+        assert_close(y, yo, name="y", **fwd_tol)
+        assert_close(dx, gr[0], name="dx", **bwd_tol)
+    else:
+        from test_bf16_edges_gpu import check_stored
+        check_stored(y, yo, name="y", **fwd_tol)
+        check_stored(dx, gr[0], name="dx", **bwd_tol)
     for n, gref in zip(NAMES, gr[1:]):
         assert_close(getattr(m, n).grad, gref, name="d" + n, **bwd_tol)
+
+
+BF16_TOL = dict(rtol=2e-2, arel=1e-2, l2=2e-2)   # plain bf16 products: SURVEY 8(c)'s bf16 tolerance
+SEVERAL_TILES_ROWS = 131159
+# (W = 48, bf16x3, fp32 storage, relu is not here: at this row count 17 rows have a pre-activation within 6.2e-6 of relu's step, which
+#  the 2^-16 products of that mode put on the other side of it -- 756 dx elements of those rows miss BWD, every other row stays
+#  below 0.03 of it, y below 0.07 of FWD -- the same in the library before the kernels were merged; tools/op_bits.py keeps the case)
+SEVERAL_TILES = [(64, "f32", torch.float32, "elu"), (64, "bf16x3", torch.bfloat16, "elu"),
+                 (32, "bf16", torch.float32, "elu"), (16, "f32", torch.bfloat16, "relu")]
+
+
+@pytest.mark.parametrize("W,matmul,dtype,act", SEVERAL_TILES)
+def test_ffn_several_tiles_per_wave(W, matmul, dtype, act, gpu, egt_lib):
+    """Every wave of the tile kernels takes more than one tile: 131159 rows = 8198 tiles of 16 rows, 7 rows in the last one.
+    The launch plan caps the forward at 256 workgroups (fp32 products) or 512 (bf16 modes) of 8 waves, and the backward at 1024
+    (W = 16), 512 (W = 32) or 256 (W >= 48) workgroups of 4 waves: the widest launches, the bf-mode forward (512 x 8) and the
+    W = 16 backward (1024 x 4), take 4096 tiles per trip.  More than 2 x 4096 tiles gives the first waves of every instance three
+    trips: both ping-pong LDS buffers are used and one of them reused, the prefetch of the next tile is carried across iterations,
+    the store of the previous tile's result is deferred into the next trip, and the last tile flushed is a ragged one.
+    The tolerances are the file's own for each product mode."""
+    tol = dict(fwd_tol=BF16_TOL, bwd_tol=BF16_TOL) if matmul == "bf16" else {}
+    _run((SEVERAL_TILES_ROWS,), act, gpu, seed=W + 3, W=W, matmul=matmul, dtype=dtype, **tol)
 
 
 @pytest.mark.parametrize("W,shape,act", [(64, (2, 24, 24), "elu"), (64, (3, 17, 17), "relu"), (64, (4, 64, 64), "elu"), (64, (1, 5), "elu"),

@@ -2,7 +2,7 @@
 """A sha256 per output tensor of single ops, over the cases of their GPU tests, for comparing two builds of the library bit by bit.
 One process loads one library: run it once per build (each run under its own time limit, chained with &&) and diff the listings.
 
-    python tools/op_bits.py [--ops head,embed] [--lib path/to/libegt_amd.so] > listing.txt      (--lib: the EGT_AMD_LIB of this process)
+    python tools/op_bits.py [--ops head,embed,block,ffn] [--lib path/to/libegt_amd.so] > listing.txt      (--lib: the EGT_AMD_LIB of this process)
 
 head:  the fused edge head and node head over the cases of tests/test_distance_head_gpu.py and tests/test_node_head_gpu.py (their
        CASES, the bf16 and the full-tile case).  Edge head: per_graph, d_e and the parameter gradients; node head: stats, d_h and the
@@ -14,7 +14,11 @@ embed: the edge embedding in both edge dtypes: e, hops and every parameter gradi
 block: one forward and backward of the fused block / stack through the C ABI: h', e', d_h, d_e and the fourteen parameter gradients
        (per layer) over the block and stack rows of tests/memcontract.py plus BLOCK_EXTRA below; the answer of egt_block_launch_form
        stands next to each row.  The plan's switches are read once per process: run it again under EGT_BWD_MATMUL=bf16x3 (the v5 MM = 1
-       instances) and under EGT_NO_NARROW=1 (De = 8 on k_block_bwd_v4r<8>; the static-edge rows are left out there)."""
+       instances) and under EGT_NO_NARROW=1 (De = 8 on k_block_bwd_v4r<8>; the static-edge rows are left out there).
+ffn:   the channel FFN: y, dx and the six parameter gradients over every (W, matmul, shape, act) of the parametrisations of
+       tests/test_ffn_gpu.py (fp32 storage, the tests' seeds), CASES of tests/test_bf16_edges_gpu.py with bf16 storage, and the
+       several-tiles-per-wave cases; then, on the cases of test_ffn_bwd_on_a_fresh_workspace_equals_the_prepared_one, egt_ffn_bwd
+       on a fresh workspace (flags = 0: it prepares its own operands) next to the autograd path's prepared one."""
 import argparse
 import hashlib
 import itertools
@@ -123,20 +127,64 @@ def block(gpu):
         emit(f"block {case.name} [{form}]", sorted(out.items()))
 
 
+def ffn(gpu):
+    import ctypes as C
+    import torch
+    import test_ffn_gpu as TF
+    import test_bf16_edges_gpu as TB
+    from egt_amd import _lib as L
+    from egt_amd.ffn import _desc, _pstruct
+    f32, bf16 = torch.float32, torch.bfloat16
+
+    def run(tag, W, mm, shape, act, seed, dtype=f32):
+        m, x, dy, y, dx = TF._ffn_case(shape, act, gpu, seed=seed, W=W, matmul=mm, dtype=dtype)
+        tag = f"{tag} W{W}-{mm}-{'x'.join(map(str, shape))}-{act}-{str(dtype)[6:]}"
+        emit(tag, [("y", y), ("dx", dx)] + [("d " + n, getattr(m, n).grad) for n in TF.NAMES])
+        return m, x, dy, tag
+
+    for W, shape, act in params_of(TF.test_ffn_bf16x3_matmul_holds_the_fp32_tolerances, "W,shape,act"):
+        run("ffn", W, "bf16x3", shape, act, W + 1)
+    for W, shape in params_of(TF.test_ffn_plain_bf16_matmul, "W,shape"):
+        run("ffn", W, "bf16", shape, "elu", W + 2)
+    for shape, act in params_of(TF.test_ffn_vs_oracle, "shape,act"):
+        run("ffn", 64, "f32", shape, act, 0)
+    for W, shape, act in params_of(TF.test_ffn_other_widths_vs_oracle, "W,shape,act"):
+        run("ffn", W, "f32", shape, act, W)
+    for shape, act in params_of(TF.test_ffn_width8_vs_oracle, "shape,act"):
+        run("ffn", 8, "f32", shape, act, 8)
+    for W, mm, shape, act in TB.CASES:
+        run("ffn_bf16_edges", W, mm, shape, act, W + len(shape), bf16)
+    for W, mm, dtype, act in TF.SEVERAL_TILES + [(48, "bf16x3", f32, "relu")]:    # (the last one: relu-step flips keep it out of the test)
+        run("ffn_several_tiles", W, mm, (TF.SEVERAL_TILES_ROWS,), act, W + 3, dtype)
+    lib = L.load()
+    for W, mm in params_of(TF.test_ffn_bwd_on_a_fresh_workspace_equals_the_prepared_one, "W,matmul"):
+        m, x, dy, tag = run("ffn_prepared", W, mm, (3, 33, 33), "elu", 11)
+        x, dy = x.to(gpu), dy.to(gpu)
+        params = [getattr(m, n).detach().contiguous() for n in TF.NAMES]
+        desc = _desc(x.numel() // W, W, "elu", 1e-3, mm)
+        ws = torch.empty(lib.egt_ffn_workspace_bytes(C.byref(desc)), dtype=torch.uint8, device=gpu)
+        dx = torch.empty_like(x)
+        grads = [torch.empty_like(p) for p in params]
+        pst, gst = _pstruct(params), _pstruct(grads)
+        L.check(lib.egt_ffn_bwd(C.byref(desc), C.byref(pst), L.ptr(x), L.ptr(dy), L.ptr(dx), C.byref(gst), L.ptr(ws), L.current_stream()))
+        torch.cuda.synchronize()
+        emit(tag.replace("ffn_prepared", "ffn_fresh"), [("dx", dx)] + [("d " + n, g) for n, g in zip(TF.NAMES, grads)])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=None)
     ap.add_argument("--ops", default="head,embed")
     args = ap.parse_args()
     ops = args.ops.split(",")
-    if not ops or set(ops) - {"head", "embed", "block"}:
-        ap.error("--ops takes head, embed, block or several of them")
+    if not ops or set(ops) - {"head", "embed", "block", "ffn"}:
+        ap.error("--ops takes head, embed, block, ffn or several of them")
     if args.lib:
         os.environ["EGT_AMD_LIB"] = os.path.abspath(args.lib)      # read when egt_amd._lib is imported
     sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
     import torch
     gpu = torch.device("cuda", 0)
-    for op, fn in (("head", head), ("embed", embed), ("block", block)):
+    for op, fn in (("head", head), ("embed", embed), ("block", block), ("ffn", ffn)):
         if op in ops:
             fn(gpu)
 
