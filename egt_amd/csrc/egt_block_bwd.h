@@ -1,7 +1,8 @@
 // Backward pair kernels of the fused attention block (included by egt_block.hip, which holds the dispatch):
 // k_block_bwd_v4 (mask tensors / ragged N / bf16), k_block_bwd_v5 (LDS-DMA staged e tiles: the headline),
-// k_block_bwd_v4r (narrow edge channels, R rows per iteration).  The phases of the per-tile body (K / V fragments, weight slabs, P1 .. P5,
-// the hand-off, dK / dV / dQ, the partial stores) are the bwd_* functions below; a kernel is its LDS carve-up, its staging
+// k_block_bwd_v4r (narrow edge channels, R rows per iteration).  The phases of the per-tile body (weight slabs, P1 .. P5,
+// the hand-off, dK / dV / dQ, the partial stores) are the bwd_* functions below (the K / V fragment reader kv_frags_row and the
+// key-padding term key_mask_add are the forward's too: egt_block_dev.h); a kernel is its LDS carve-up, its staging
 // and its loop around them.  The kernels sit at the register edge: a change to a phase moves the register counts of all of them
 // (tools/kres.py; profiles/bwd_phases_kres.txt has the counts of this split against the three pasted copies it replaced).
 #pragma once
@@ -26,17 +27,6 @@
 // figures): k_block_bwd_v5 its fp32 P1, P2 and P5 (interleaved with the MM != 0 branches), dQ / dK / dV and P4; k_block_bwd_v4 its P4.
 // A change to one of those phases is made here and in these copies.
 
-// K / V fragments of key row `rowm` ([B * N] row index, clamped by the caller): the 16 channels of the lane's head pair
-__device__ __forceinline__ void bwd_kv_frags(const BlockArgs& a, size_t rowm, int q, float (&Kf)[16], float (&Vf)[16]) {
-  const float4* kp = reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 64 + q * 16);
-  const float4* vp = reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 128 + q * 16);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float4 kv = kp[i], vv = vp[i];
-    Kf[4*i] = kv.x; Kf[4*i+1] = kv.y; Kf[4*i+2] = kv.z; Kf[4*i+3] = kv.w;
-    Vf[4*i] = vv.x; Vf[4*i+1] = vv.y; Vf[4*i+2] = vv.z; Vf[4*i+3] = vv.w;
-  }
-}
 __device__ __forceinline__ void bwd_dkv_zero(float (&dKa)[16], float (&dVa)[16]) {
 #pragma unroll
   for (int i = 0; i < 16; ++i) { dKa[i] = 0.f; dVa[i] = 0.f; }
@@ -372,9 +362,9 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
     const bool kvalid = RAG ? (m < N) : true;
     float Kf[16], Vf[16], dKa[16], dVa[16];
     const size_t rowm = (size_t)b * N + (kvalid ? m : N - 1);
-    bwd_kv_frags(a, rowm, q, Kf, Vf);
+    kv_frags_row(a, rowm, q, Kf, Vf);
     bwd_dkv_zero(dKa, dVa);
-    const float kadd = (a.km && a.km[rowm] == 0) ? -EGT_NEG : 0.0f;
+    const float kadd = key_mask_add(a, rowm);
 
     TileRegs<DE> te, td;
     for (int l = l_begin; l < l_end; ++l) {
@@ -548,7 +538,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
     if (RAG && kv_ < 16) tile_dma_ragged<DE>(et_lds, e_in + (((size_t)b * N + l_begin + (ROW_)) * N + m0_) * DE, lane, kv_); \
     else tile_dma<DE, EGT_NT_BWD_E>(et_lds, e_in + (((size_t)b * N + l_begin + (ROW_)) * N + m0_) * DE, off0);      \
     const size_t rowm_ = (size_t)b * N + (RAG ? min(m0_ + p, N - 1) : m0_ + p);                                     \
-    bwd_kv_frags(a, rowm_, q, Kf, Vf);                                                                              \
+    kv_frags_row(a, rowm_, q, Kf, Vf);                                                                              \
     kmv = a.km ? (int)a.km[rowm_] : 1;                                                                              \
   } while (0)
   if (have) V5_TILE_START(mt_first, r0_first);
@@ -915,9 +905,9 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
     const bool kvalid = m < N;
     float Kf[16], Vf[16], dKa[16], dVa[16];
     const size_t rowm = (size_t)b * N + (kvalid ? m : N - 1);
-    bwd_kv_frags(a, rowm, q, Kf, Vf);
+    kv_frags_row(a, rowm, q, Kf, Vf);
     bwd_dkv_zero(dKa, dVa);
-    const float kadd = (a.km && a.km[rowm] == 0) ? -EGT_NEG : 0.0f;
+    const float kadd = key_mask_add(a, rowm);
     const MaskRegs mr{make_float2(1.f, 1.f), 0};
     TileRegs<DE> te[R], td[R];
     auto prefetch = [&](int lq) {

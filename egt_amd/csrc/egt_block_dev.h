@@ -38,6 +38,27 @@ __device__ __forceinline__ void mask_gload(const BlockArgs& a, MaskRegs& mr, siz
   if (a.rm) mr.rb = *reinterpret_cast<const unsigned short*>(a.rm + pairc * BH + 2 * q);
 }
 
+// key-padding term of key row `row` ([B * N] row index): what apply_masks adds as `kadd`
+__device__ __forceinline__ float key_mask_add(const BlockArgs& a, size_t row) {
+  return (a.km && a.km[row] == 0) ? -EGT_NEG : 0.0f;
+}
+
+// 16 channels of a head pair (four float4 of a packed qkv row, in LDS or in HBM) as a register fragment
+__device__ __forceinline__ void frag16(const float4* s, float (&f)[16]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { const float4 v = s[i]; f[4*i] = v.x; f[4*i+1] = v.y; f[4*i+2] = v.z; f[4*i+3] = v.w; }
+}
+// K / V fragments of one key: the 16 channels of the lane's head pair, from LDS rows or from qkvp rows
+__device__ __forceinline__ void kv_frags(const float4* kp, const float4* vp, float (&Kf)[16], float (&Vf)[16]) {
+  frag16(kp, Kf);
+  frag16(vp, Vf);
+}
+// ... of key row `rowm` of qkvp ([B * N] row index, clamped by the caller)
+__device__ __forceinline__ void kv_frags_row(const BlockArgs& a, size_t rowm, int q, float (&Kf)[16], float (&Vf)[16]) {
+  kv_frags(reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 64 + q * 16),
+           reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 128 + q * 16), Kf, Vf);
+}
+
 // logits x and gate-logits gl of the lane's pair, heads 2q+j; masks ADDED in the
 // reference's order (egt_layers.py:91-108): key padding, attention mask, random mask
 template <bool ML>

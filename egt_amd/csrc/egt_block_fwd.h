@@ -1,5 +1,11 @@
 // Forward pair kernels of the fused attention block (included by egt_block.hip, which holds the dispatch):
 // k_block_fwd<De,KVL,ML,FULL,BF> and the four-rows-per-iteration k_block_fwd_r4<De,FULL,NW,BF> for narrow edge channels.
+// The phases of the per-pair body (lane-constant operands, logits, online softmax and A.V, dense_edge_r, the row finish) are the
+// fwd_* functions below, with kv_frags / frag16 / key_mask_add of egt_block_dev.h; a kernel is its LDS carve-up, its staging and
+// prefetch, and its loop around them (profiles/fwd_phases_kres.txt has the register counts of this split against the pasted copies).
+// Two phases keep a pasted copy in one kernel each, because the shared function measured slower there than the parent's text (DESIGN 4.1
+// has the figures): k_block_fwd_r4 its online softmax x gate, A.V, the mask-tensor instances (ML) of k_block_fwd their row finish.  A change to fwd_softmax_av or
+// fwd_row_finish is made in that copy too.
 #pragma once
 // Cache-policy hints of the streamed tiles (egt_tile.h).  k_block_fwd reads e_l ONCE: non-temporal, so that it does not push e_{l+1} --
 // which this launch writes and the next one reads, 134 MB of the 256 MB memory-side cache at the headline batch -- out.  Measured
@@ -10,6 +16,112 @@
 #ifndef EGT_NT_FWD_ST
 #define EGT_NT_FWD_ST false
 #endif
+
+// ================================================ tile phases of the forward =====
+// Every phase of the per-pair body, once.  Lane = (p, q) = (lane & 15, lane >> 4): key p of the tile, head pair q (heads 2q + j).
+// Row state of a (wave, query row): running max `mx` and sum `sum` per head j, O[2k + j] = channel k of head 2q + j of A.V.
+
+// lane-constant MFMA operands: projection weights wA and bias c2r (a.pw), dense_edge_r weights wrA and bias brv
+template <int DE>
+__device__ __forceinline__ void fwd_lane_weights(const BlockArgs& a, int p, int q, float (&wA)[4 * Geo<DE>::TILES], float (&c2r)[4],
+                                                 float (&wrA)[Geo<DE>::TILES][2], float4 (&brv)[Geo<DE>::TILES]) {
+  using G = Geo<DE>;
+#pragma unroll
+  for (int t = 0; t < 4 * G::TILES; ++t) wA[t] = a.pw[(16 * (t >> 2) + 4 * q + (t & 3)) * 16 + p];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) c2r[r] = a.pw[G::DEP * 16 + 4 * q + r];
+#pragma unroll
+  for (int t = 0; t < G::TILES; ++t) {
+    const int c = 16 * t + p;
+    wrA[t][0] = c < DE ? a.Wr[(2 * q + 0) * DE + c] : 0.f;
+    wrA[t][1] = c < DE ? a.Wr[(2 * q + 1) * DE + c] : 0.f;
+    const int cb = 16 * t + 4 * q;   // scalar loads: parameter tensors need not be 16-byte aligned
+    brv[t] = (cb < DE) ? make_float4(a.br[cb], a.br[cb + 1], a.br[cb + 2], a.br[cb + 3])
+                       : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+__device__ __forceinline__ void fwd_row_init(float (&mx)[2], float (&sum)[2], float (&O)[16]) {
+  mx[0] = mx[1] = -3.0e38f; sum[0] = sum[1] = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) O[i] = 0.f;
+}
+
+// scaled QK^T, clip, + E (egt_layers.py:79-86): hh = H_hat of the pair (what dense_edge_r reads), xl = the logits the masks are
+// added to, gl = the gate logits.  acc = the projection of the pair: acc[2j] = G, acc[2j + 1] = E of head 2q + j.
+__device__ __forceinline__ void fwd_pair_logits(const BlockArgs& a, bool clip, const float (&Qf)[16], const float (&Kf)[16], const v4f& acc,
+                                                float (&hh)[2], float (&xl)[2], float (&gl)[2]) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    float dot = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dot = fmaf(Qf[2 * k + j], Kf[2 * k + j], dot);
+    float ah = dot * a.scale;
+    if (clip) ah = fminf(fmaxf(ah, a.clip_lo), a.clip_hi);
+    hh[j] = ah + acc[2 * j + 1];
+    xl[j] = hh[j];
+    gl[j] = acc[2 * j];
+  }
+}
+
+// online softmax x gate, A.V (per lane); a key past N (!valid) leaves max and sum alone and weighs 0
+__device__ __forceinline__ void fwd_softmax_av(bool valid, bool gated, const float (&xl)[2], const float (&gl)[2], const float (&Vf)[16],
+                                               float (&mx)[2], float (&sum)[2], float (&O)[16]) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const float xv = xl[j];
+    const float mn = valid ? fmaxf(mx[j], xv) : mx[j];
+    const float alpha = __expf(mx[j] - mn);
+    const float pe = valid ? __expf(xv - mn) : 0.f;
+    mx[j] = mn;
+    sum[j] = fmaf(sum[j], alpha, pe);
+    const float av = gated ? pe * egt_sigmoid(gl[j]) : pe;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) O[2 * k + j] = fmaf(O[2 * k + j], alpha, av * Vf[2 * k + j]);
+  }
+}
+
+// dense_edge_r + res_edge on the LDS tile: e' = e + H_hat.Wr + br (H_hat of a key past N reads as 0)
+template <int DE>
+__device__ __forceinline__ void fwd_edge_update(float* tl, int p, int q, bool valid, const float (&hh)[2],
+                                                const float (&wrA)[Geo<DE>::TILES][2], const float4 (&brv)[Geo<DE>::TILES]) {
+  const float h0 = valid ? hh[0] : 0.f, h1 = valid ? hh[1] : 0.f;
+#pragma unroll
+  for (int t = 0; t < Geo<DE>::TILES; ++t) {
+    v4f d = {brv[t].x, brv[t].y, brv[t].z, brv[t].w};
+    d = MFMA(wrA[t][0], h0, d);
+    d = MFMA(wrA[t][1], h1, d);
+    const float4 ev = frag_read<DE>(tl, p, q, t);
+    frag_write<DE>(tl, p, q, t, make_float4(ev.x + d[0], ev.y + d[1], ev.z + d[2], ev.w + d[3]));
+  }
+}
+
+// end of query row `rowl` ([B * N] row index): merge the 16 key lanes (same q), max first, then the sums; V_att and the row statistics
+// (max, sum per head) to HBM.  keep: V_att also into the row's Q slot `qrow` in LDS for the node epilogue (the row's Q is dead).
+__device__ __forceinline__ void fwd_row_finish(const BlockArgs& a, size_t rowl, int p, int q, float (&mx)[2], float (&sum)[2], float (&O)[16],
+                                               bool keep, float* qrow) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const float mr2 = row_max16(mx[j]);
+    const float f = __expf(mx[j] - mr2);
+    mx[j] = mr2;
+    sum[j] = row_sum16(sum[j] * f);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) O[2 * k + j] *= f;
+  }
+  const float o = reduce16_keep_own(O, p);
+  // element i = p: k = p>>1, j = p&1 -> head 2q + j
+  const int k = p >> 1, j = p & 1;
+  const float sj = j ? sum[1] : sum[0];
+  const float vo = o / sj;
+  if (k < a.DK) a.v_att[rowl * a.Dh + k * BH + 2 * q + j] = vo;
+  if (keep) qrow[k * BH + 2 * q + j] = vo;
+  if (p < 2) {
+    float* st = a.stats + (rowl * BH + 2 * q + p) * 4;
+    st[0] = p ? mx[1] : mx[0];
+    st[1] = sj;
+  }
+}
 
 // ================================================================= forward =====
 // Workgroup = (graph b, 16 query rows); wave w owns rows l = 16*lg + w + 4*i.
@@ -60,24 +172,12 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
       const int row = threadIdx.x >> 4, f = threadIdx.x & 15, l = min(l0 + row, N - 1);
       qb = *reinterpret_cast<const float4*>(kvsrc + (size_t)l * QKVP + f * 4);
     }
-    if ((int)threadIdx.x < N) kmb = (a.km && a.km[(size_t)b * N + threadIdx.x] == 0) ? -EGT_NEG : 0.0f;
+    if ((int)threadIdx.x < N) kmb = key_mask_add(a, (size_t)b * N + threadIdx.x);
   }
   // lane-constant MFMA operands
   float wA[4 * G::TILES], wrA[G::TILES][2], c2r[4];
   float4 brv[G::TILES];
-#pragma unroll
-  for (int t = 0; t < 4 * G::TILES; ++t) wA[t] = a.pw[(16 * (t >> 2) + 4 * q + (t & 3)) * 16 + p];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) c2r[r] = a.pw[G::DEP * 16 + 4 * q + r];
-#pragma unroll
-  for (int t = 0; t < G::TILES; ++t) {
-    const int c = 16 * t + p;
-    wrA[t][0] = c < DE ? a.Wr[(2 * q + 0) * DE + c] : 0.f;
-    wrA[t][1] = c < DE ? a.Wr[(2 * q + 1) * DE + c] : 0.f;
-    const int cb = 16 * t + 4 * q;   // scalar loads: parameter tensors need not be 16-byte aligned
-    brv[t] = (cb < DE) ? make_float4(a.br[cb], a.br[cb + 1], a.br[cb + 2], a.br[cb + 3])
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
+  fwd_lane_weights<DE>(a, p, q, wA, c2r, wrA, brv);
   if (KVL) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -90,7 +190,7 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
       const int row = i >> 5, f = i & 31;
       *reinterpret_cast<float4*>(kvs + row * KV_LD + f * 4) = *reinterpret_cast<const float4*>(kvsrc + (size_t)row * QKVP + 64 + f * 4);
     }
-    for (int i = 256 + threadIdx.x; i < N; i += 256) kms[i] = (a.km && a.km[(size_t)b * N + i] == 0) ? -EGT_NEG : 0.0f;
+    for (int i = 256 + threadIdx.x; i < N; i += 256) kms[i] = key_mask_add(a, (size_t)b * N + i);
     __syncthreads();
   }
 
@@ -127,13 +227,9 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
     const size_t rowl = (size_t)b * N + l;
     const size_t pair0 = rowl * N + m0;
     if (mt == 0) {
-      const float4* qp = KVL ? reinterpret_cast<const float4*>(qs + (wave + 4 * li) * QS_LD + q * 16)
-                             : reinterpret_cast<const float4*>(a.qkvp + rowl * QKVP + q * 16);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { const float4 v = qp[i]; Qf[4*i] = v.x; Qf[4*i+1] = v.y; Qf[4*i+2] = v.z; Qf[4*i+3] = v.w; }
-      mx[0] = mx[1] = -3.0e38f; sum[0] = sum[1] = 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) O[i] = 0.f;
+      frag16(KVL ? reinterpret_cast<const float4*>(qs + (wave + 4 * li) * QS_LD + q * 16)
+                 : reinterpret_cast<const float4*>(a.qkvp + rowl * QKVP + q * 16), Qf);
+      fwd_row_init(mx, sum, O);
     }
     // ---- stage this tile, start the next one's loads ----
     MaskRegs mr{make_float2(1.f, 1.f), 0};   // issued before the prefetch, consumed after the MFMAs
@@ -158,23 +254,14 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
     float Kf[16], Vf[16], kadd = 0.f;
     {
       const int mc = valid ? m : 0;
-      const float4* kp;
-      const float4* vp;
       if (KVL) {
-        kp = reinterpret_cast<const float4*>(kvs + mc * KV_LD + q * 16);
-        vp = reinterpret_cast<const float4*>(kvs + mc * KV_LD + 64 + q * 16);
+        kv_frags(reinterpret_cast<const float4*>(kvs + mc * KV_LD + q * 16),
+                 reinterpret_cast<const float4*>(kvs + mc * KV_LD + 64 + q * 16), Kf, Vf);
         kadd = kms[mc];
       } else {
         const size_t rowm = (size_t)b * N + mc;
-        kp = reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 64 + q * 16);
-        vp = reinterpret_cast<const float4*>(a.qkvp + rowm * QKVP + 128 + q * 16);
-        kadd = (a.km && a.km[rowm] == 0) ? -EGT_NEG : 0.0f;
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float4 kv = kp[i], vv = vp[i];
-        Kf[4*i] = kv.x; Kf[4*i+1] = kv.y; Kf[4*i+2] = kv.z; Kf[4*i+3] = kv.w;
-        Vf[4*i] = vv.x; Vf[4*i+1] = vv.y; Vf[4*i+2] = vv.z; Vf[4*i+3] = vv.w;
+        kv_frags_row(a, rowm, q, Kf, Vf);
+        kadd = key_mask_add(a, rowm);
       }
     }
     // ---- norm_edge + [attention_gates | dense_edge_b] ----
@@ -183,72 +270,45 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
       ln_frags<DE>(x, q, a.ln_eps, (a.flags & EGT_BF_NO_EDGE_LN) == 0);
       acc = project<DE>(x, wA, acc);
     }
-    // ---- scaled QK^T, clip, + E (egt_layers.py:79-86) ----
     float hh[2] = {0.f, 0.f}, xl[2] = {0.f, 0.f}, gl[2] = {0.f, 0.f};
-    {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      float dot = 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) dot = fmaf(Qf[2 * k + j], Kf[2 * k + j], dot);
-      float ah = dot * a.scale;
-      if (clip) ah = fminf(fmaxf(ah, a.clip_lo), a.clip_hi);
-      hh[j] = ah + acc[2 * j + 1];
-      xl[j] = hh[j];
-      gl[j] = acc[2 * j];
-    }
-    }
+    fwd_pair_logits(a, clip, Qf, Kf, acc, hh, xl, gl);
     apply_masks<ML>(a, kadd, mr, (pair0 + p) * BH, q, xl, gl);
-    // ---- online softmax x gate, A.V (per lane) ----
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const float xv = xl[j];
-      const float mn = valid ? fmaxf(mx[j], xv) : mx[j];
-      const float alpha = __expf(mx[j] - mn);
-      const float pe = valid ? __expf(xv - mn) : 0.f;
-      mx[j] = mn;
-      sum[j] = fmaf(sum[j], alpha, pe);
-      const float av = gated ? pe * egt_sigmoid(gl[j]) : pe;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) O[2 * k + j] = fmaf(O[2 * k + j], alpha, av * Vf[2 * k + j]);
-    }
-    // ---- dense_edge_r + res_edge: e' = e + H_hat.Wr + br ----
-    const float h0 = valid ? hh[0] : 0.f, h1 = valid ? hh[1] : 0.f;
-#pragma unroll
-    for (int t = 0; t < G::TILES; ++t) {
-      v4f d = {brv[t].x, brv[t].y, brv[t].z, brv[t].w};
-      d = MFMA(wrA[t][0], h0, d);
-      d = MFMA(wrA[t][1], h1, d);
-      const float4 ev = frag_read<DE>(tl, p, q, t);
-      frag_write<DE>(tl, p, q, t, make_float4(ev.x + d[0], ev.y + d[1], ev.z + d[2], ev.w + d[3]));
-    }
+    fwd_softmax_av(valid, gated, xl, gl, Vf, mx, sum, O);
+    fwd_edge_update<DE>(tl, p, q, valid, hh, wrA, brv);
     if (it_ + 1 == total) {   // last tile of the wave: flush
       lds_sync();
       tile_from_lds<DE, EGT_NT_FWD_ST>(tl, e_o + pair0 * DE, lane, rows_valid);
     }
     if (mt == ntile - 1 && live) {
-      // ---- merge the 16 key lanes (same q): max, then sums ----
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const float mr2 = row_max16(mx[j]);
-        const float f = __expf(mx[j] - mr2);
-        mx[j] = mr2;
-        sum[j] = row_sum16(sum[j] * f);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) O[2 * k + j] *= f;
-      }
-      const float o = reduce16_keep_own(O, p);
-      // element i = p: k = p>>1, j = p&1 -> head 2q + j
-      const int k = p >> 1, j = p & 1;
-      const float sj = j ? sum[1] : sum[0];
-      const float vo = o / sj;
-      if (k < a.DK) a.v_att[rowl * a.Dh + k * BH + 2 * q + j] = vo;
       // the row's Q is dead (read at mt == 0 by this wave only): its slot keeps V_att for the epilogue
-      if (KVL && a.epi) qs[(wave + 4 * li) * QS_LD + k * BH + 2 * q + j] = vo;
-      if (p < 2) {
-        float* st = a.stats + (rowl * BH + 2 * q + p) * 4;
-        st[0] = p ? mx[1] : mx[0];
-        st[1] = sj;
+      if (!ML) fwd_row_finish(a, rowl, p, q, mx, sum, O, KVL && a.epi, qs + (wave + 4 * li) * QS_LD);
+      else {
+        // Own copy of fwd_row_finish in the mask-tensor instances: with the shared one <64, true, true, false, false> (attention mask,
+        // h [128, 64, 64]) ran 69.8 us against the parent's 66.4 (its max - min over three runs: 0.5), with this copy 66.8.  In the
+        // instances without mask tensors it is the copy that costs: <64, false, false, false, false> (h [32, 90, 64]) 56.4 us against
+        // the parent's 54.0 (1.0) where the shared function ran 51.0 against 56.1 (1.8) in another visit.
+        // ---- merge the 16 key lanes (same q): max, then sums ----
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const float mr2 = row_max16(mx[j]);
+          const float f = __expf(mx[j] - mr2);
+          mx[j] = mr2;
+          sum[j] = row_sum16(sum[j] * f);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) O[2 * k + j] *= f;
+        }
+        const float o = reduce16_keep_own(O, p);
+        // element i = p: k = p>>1, j = p&1 -> head 2q + j
+        const int k = p >> 1, j = p & 1;
+        const float sj = j ? sum[1] : sum[0];
+        const float vo = o / sj;
+        if (k < a.DK) a.v_att[rowl * a.Dh + k * BH + 2 * q + j] = vo;
+        if (KVL && a.epi) qs[(wave + 4 * li) * QS_LD + k * BH + 2 * q + j] = vo;
+        if (p < 2) {
+          float* st = a.stats + (rowl * BH + 2 * q + p) * 4;
+          st[0] = p ? mx[1] : mx[0];
+          st[1] = sj;
+        }
       }
     }
   };
@@ -310,24 +370,11 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
       *reinterpret_cast<float4*>(qs + row * QS_LD + f * 4) =
           *reinterpret_cast<const float4*>(src + (size_t)l * QKVP + f * 4);
     }
-    for (int i = threadIdx.x; i < N; i += NT)
-      kms[i] = (a.km && a.km[(size_t)b * N + i] == 0) ? -EGT_NEG : 0.0f;
+    for (int i = threadIdx.x; i < N; i += NT) kms[i] = key_mask_add(a, (size_t)b * N + i);
   }
   float wA[4 * G::TILES], wrA[G::TILES][2], c2r[4];
   float4 brv[G::TILES];
-#pragma unroll
-  for (int t = 0; t < 4 * G::TILES; ++t) wA[t] = a.pw[(16 * (t >> 2) + 4 * q + (t & 3)) * 16 + p];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) c2r[r] = a.pw[G::DEP * 16 + 4 * q + r];
-#pragma unroll
-  for (int t = 0; t < G::TILES; ++t) {
-    const int c = 16 * t + p;
-    wrA[t][0] = c < DE ? a.Wr[(2 * q + 0) * DE + c] : 0.f;
-    wrA[t][1] = c < DE ? a.Wr[(2 * q + 1) * DE + c] : 0.f;
-    const int cb = 16 * t + 4 * q;
-    brv[t] = (cb < DE) ? make_float4(a.br[cb], a.br[cb + 1], a.br[cb + 2], a.br[cb + 3])
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
+  fwd_lane_weights<DE>(a, p, q, wA, c2r, wrA, brv);
   __syncthreads();
 
   const int ntile = (N + 15) / 16;
@@ -351,11 +398,7 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
     prefetch(0);
     float mx[4][2], sum[4][2], O[4][16];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      mx[i][0] = mx[i][1] = -3.0e38f; sum[i][0] = sum[i][1] = 0.f;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) O[i][k] = 0.f;
-    }
+    for (int i = 0; i < 4; ++i) fwd_row_init(mx[i], sum[i], O[i]);
     for (int mt = 0; mt < ntile; ++mt) {
       const int m0 = mt * 16, m = m0 + p;
       const bool valid = FULL ? true : (m < N);
@@ -368,16 +411,8 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
       // ---- K/V fragments of key m: shared by the four rows ----
       float Kf[16], Vf[16];
       const int mc = valid ? m : 0;
-      {
-        const float4* kp = reinterpret_cast<const float4*>(kvs + mc * KV_LD + q * 16);
-        const float4* vp = reinterpret_cast<const float4*>(kvs + mc * KV_LD + 64 + q * 16);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float4 kv = kp[i], vv = vp[i];
-          Kf[4*i] = kv.x; Kf[4*i+1] = kv.y; Kf[4*i+2] = kv.z; Kf[4*i+3] = kv.w;
-          Vf[4*i] = vv.x; Vf[4*i+1] = vv.y; Vf[4*i+2] = vv.z; Vf[4*i+3] = vv.w;
-        }
-      }
+      kv_frags(reinterpret_cast<const float4*>(kvs + mc * KV_LD + q * 16),
+               reinterpret_cast<const float4*>(kvs + mc * KV_LD + 64 + q * 16), Kf, Vf);
       const float kadd = kms[mc];
       const MaskRegs mr{make_float2(1.f, 1.f), 0};
 #pragma unroll
@@ -393,25 +428,13 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
           acc = project<DE>(x, wA, acc);
           // ---- scaled QK^T, clip, + E (egt_layers.py:79-86); Q of the row from LDS ----
           float Qf[16];
-          {
-            const float4* qp = reinterpret_cast<const float4*>(qs + (row0 + 4 * i) * QS_LD + q * 16);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { const float4 v = qp[u]; Qf[4*u] = v.x; Qf[4*u+1] = v.y; Qf[4*u+2] = v.z; Qf[4*u+3] = v.w; }
-          }
+          frag16(reinterpret_cast<const float4*>(qs + (row0 + 4 * i) * QS_LD + q * 16), Qf);
           float hh[2], xl[2], gl[2];
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            float dot = 0.f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) dot = fmaf(Qf[2 * k + j], Kf[2 * k + j], dot);
-            float ah = dot * a.scale;
-            if (clip) ah = fminf(fmaxf(ah, a.clip_lo), a.clip_hi);
-            hh[j] = ah + acc[2 * j + 1];
-            xl[j] = hh[j];
-            gl[j] = acc[2 * j];
-          }
+          fwd_pair_logits(a, clip, Qf, Kf, acc, hh, xl, gl);
           apply_masks<false>(a, kadd, mr, (rowl[i] * N + m0 + p) * BH, q, xl, gl);
-          // ---- online softmax x gate, A.V (per lane) ----
+          // ---- online softmax x gate, A.V (per lane).  Own copy of fwd_softmax_av: with the shared one r4<8, false, 8, false> ran
+          // 165.5 us against the parent's 161.4 (max - min 0.7) and r4<8, false, 4, false> 98.5 against 97.2 (0.3); with this copy
+          // 160.4 and 96.2 ----
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             const float xv = xl[j];
@@ -424,16 +447,7 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) O[i][2 * k + j] = fmaf(O[i][2 * k + j], alpha, av * Vf[2 * k + j]);
           }
-          // ---- dense_edge_r + res_edge: e' = e + H_hat.Wr + br ----
-          const float h0 = valid ? hh[0] : 0.f, h1 = valid ? hh[1] : 0.f;
-#pragma unroll
-          for (int t = 0; t < G::TILES; ++t) {
-            v4f d = {brv[t].x, brv[t].y, brv[t].z, brv[t].w};
-            d = MFMA(wrA[t][0], h0, d);
-            d = MFMA(wrA[t][1], h1, d);
-            const float4 ev = frag_read<DE>(tli, p, q, t);
-            frag_write<DE>(tli, p, q, t, make_float4(ev.x + d[0], ev.y + d[1], ev.z + d[2], ev.w + d[3]));
-          }
+          fwd_edge_update<DE>(tli, p, q, valid, hh, wrA, brv);
         }
       }
       lds_sync();   // stream out the four e' tiles
@@ -441,32 +455,10 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
       for (int i = 0; i < 4; ++i)
         if (i < nrows) tile_from_lds<DE>(tl + i * G::TILE_FLOATS, e_o + (rowl[i] * N + m0) * DE, lane, rows_valid);
     }
-    // ---- per row: merge the 16 key lanes (same q): max, then sums ----
+    // ---- per row: 16-lane merge, V_att (also into the row's Q slot: dead from here on), statistics ----
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (i < nrows) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const float mr2 = row_max16(mx[i][j]);
-          const float f = __expf(mx[i][j] - mr2);
-          mx[i][j] = mr2;
-          sum[i][j] = row_sum16(sum[i][j] * f);
-#pragma unroll
-          for (int k = 0; k < 8; ++k) O[i][2 * k + j] *= f;
-        }
-        const float o = reduce16_keep_own(O[i], p);
-        const int k = p >> 1, j = p & 1;   // element p: k = p>>1, j = p&1 -> head 2q + j
-        const float sj = j ? sum[i][1] : sum[i][0];
-        const float vo = o / sj;
-        if (k < a.DK) a.v_att[rowl[i] * a.Dh + k * BH + 2 * q + j] = vo;
-        if (a.epi) qs[(row0 + 4 * i) * QS_LD + k * BH + 2 * q + j] = vo;   // the row's Q is dead from here on
-        if (p < 2) {
-          float* st = a.stats + (rowl[i] * BH + 2 * q + p) * 4;
-          st[0] = p ? mx[i][1] : mx[i][0];
-          st[1] = sj;
-        }
-      }
-    }
+    for (int i = 0; i < 4; ++i)
+      if (i < nrows) fwd_row_finish(a, rowl[i], p, q, mx[i], sum[i], O[i], a.epi != 0, qs + (row0 + 4 * i) * QS_LD);
   }
   // each 16-row half runs the 4-wave epilogue on its own rows (staging area hs = its own tiles)
   if (a.epi) fwd_node_epilogue(a, sm + hf * 16 * QS_LD, qs + hf * 16 * QS_LD, b, lg * RW + hf * 16, min(16, N - (lg * RW + hf * 16)), N, wv, p, q);

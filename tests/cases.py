@@ -112,8 +112,8 @@ def attn_oracle(inp, attrs, dtype=torch.float64):
     return out
 
 
-def make_block_case(name, seed=4321):
-    c = dict(BLOCK_CASES[name])
+def make_block_case(name, seed=4321, case=None):
+    c = dict(BLOCK_CASES[name] if case is None else case)
     g = torch.Generator().manual_seed(seed + sum(map(ord, name)))
     B, N, Dh, De, H = c["B"], c["N"], c["Dh"], c["De"], 8
     r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float32)

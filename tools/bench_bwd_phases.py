@@ -1,21 +1,26 @@
 #!/usr/bin/env python3
-"""The backward pair kernels of the fused block (k_block_bwd_v4 / v5 / v4r), parent tree against this tree, on one GPU in one visit.
+"""The pair kernels of the fused block, parent tree against this tree, on one GPU in one visit: the backward kernels (k_block_bwd_v4 /
+v5 / v4r) or, with --kernel k_block_fwd, the forward ones (k_block_fwd / k_block_fwd_r4).
 
-    python tools/bench_bwd_phases.py --parent-tree PARENT [--rounds 3] [--out profiles/bwd_phases.jsonl]
+    python tools/bench_bwd_phases.py --parent-tree PARENT [--kernel k_block_bwd|k_block_fwd] [--rounds 3] [--out profiles/bwd_phases.jsonl]
 
 PARENT is a built checkout of the parent commit.  Every measurement is a fresh child process under its own time limit, run in the
 tree it measures; parent and this tree alternate over the rounds.  The first child that fails ends the run (nothing more is started on
 the GPU).  Cases:
-  bench.py --full --graph off workloads (the `kernels` figure of k_block_bwd and the step time; the step mode is fixed to the eager
+  bench.py --full --graph off workloads (the `kernels` figure of the kernel and the step time; the step mode is fixed to the eager
   stream because bench.py times the kernel by hipEvents on the stream there and by event nodes inside the captured graph otherwise, and
   the second way reads about 10 us more for the same code: a run that calibrates itself into the other mode is no comparison):
-    zinc500k_n64                       k_block_bwd_v5<64>, full tiles
-    zinc100k_n37                       k_block_bwd_v5<48>, ragged N, balanced ranges
-    zinc500k_n64 --edge-dtype bf16     k_block_bwd_v4<64, false, true, false>
-    cifar10_n150_fp32, EGT_NO_NARROW=1 k_block_bwd_v4r<8>
-  mask: one block forward and backward at h [128, 64, 64], De = 64 with an attention mask (k_block_bwd_v4<64, true, false, false>: no
-    bench.py workload reaches the mask-tensor instances), through the C ABI on the buffers of tests/memcontract.py, k_block_bwd timed by
-    the library's own launch profiler (egt_prof_*).
+    zinc500k_n64                       k_block_bwd_v5<64>, full tiles;  k_block_fwd<64, true, false, true, false>
+    zinc100k_n37                       k_block_bwd_v5<48>, ragged N, balanced ranges;  k_block_fwd<48, true, false, false, false>
+    zinc500k_n64 --edge-dtype bf16     k_block_bwd_v4<64, false, true, false>;  k_block_fwd<64, true, false, true, true>
+    cifar10_n150_fp32, EGT_NO_NARROW=1 k_block_bwd_v4r<8>                                                     (backward)
+    cifar10_n150_fp32, EGT_NO_NARROW_FWD=1      k_block_fwd_r4<8, false, 8, false>                            (forward)
+    pattern500k_n120_b128, EGT_NO_NARROW_FWD=1  k_block_fwd_r4<8, false, 4, false>                            (forward)
+  single blocks: one block forward and backward through the C ABI on the buffers of tests/memcontract.py, the kernel timed by the
+  library's own launch profiler (egt_prof_*); no bench.py workload reaches these instances:
+    h [128, 64, 64], De = 64 with an attention mask   k_block_bwd_v4<64, true, false, false>;  k_block_fwd<64, true, true, false, false>
+    h [32, 90, 64], De = 64 without one (forward)     k_block_fwd<64, false, false, false, false>: K / V do not fit in LDS
+  Before the first round, every case's answer of egt_block_launch_form (in each tree, under the case's environment) goes into the file.
 Verdict per case and figure: this tree may be slower than the parent by no more than the parent's own spread (max - min over its
 rounds)."""
 import argparse
@@ -26,21 +31,51 @@ import subprocess
 import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BENCH = [("zinc500k_n64", ["--workload", "zinc500k_n64"], {}),
-         ("zinc100k_n37", ["--workload", "zinc100k_n37"], {}),
-         ("zinc500k_n64_bf16", ["--workload", "zinc500k_n64", "--edge-dtype", "bf16"], {}),
-         ("cifar10_n150_fp32_no_narrow", ["--workload", "cifar10_n150_fp32"], {"EGT_NO_NARROW": "1"})]
+Z64, Z37, Z64B = (128, 64, 8, 64, False), (128, 37, 6, 48, False), (128, 64, 8, 64, True)      # (B, N, d, De, bf16) of the workload's block
 MASK_ROW = ("b128_n64_de64_mask", 128, 64, 8, 64, False, "attn_mask", None, None)
+# per kernel: bench.py cases (name, arguments, environment, block shape) and single-block cases (name, memcontract row)
+CASES = {
+    "k_block_bwd": dict(
+        bench=[("zinc500k_n64", ["--workload", "zinc500k_n64"], {}, Z64),
+               ("zinc100k_n37", ["--workload", "zinc100k_n37"], {}, Z37),
+               ("zinc500k_n64_bf16", ["--workload", "zinc500k_n64", "--edge-dtype", "bf16"], {}, Z64B),
+               ("cifar10_n150_fp32_no_narrow", ["--workload", "cifar10_n150_fp32"], {"EGT_NO_NARROW": "1"}, (128, 150, 8, 8, False))],
+        single=[("mask_b128_n64_de64", MASK_ROW)]),
+    "k_block_fwd": dict(
+        bench=[("zinc500k_n64", ["--workload", "zinc500k_n64"], {}, Z64),
+               ("zinc100k_n37", ["--workload", "zinc100k_n37"], {}, Z37),
+               ("zinc500k_n64_bf16", ["--workload", "zinc500k_n64", "--edge-dtype", "bf16"], {}, Z64B),
+               ("cifar10_n150_fp32_no_narrow_fwd", ["--workload", "cifar10_n150_fp32"], {"EGT_NO_NARROW_FWD": "1"}, (128, 150, 8, 8, False)),
+               ("pattern500k_n120_b128_no_narrow_fwd", ["--workload", "pattern500k_n120_b128"], {"EGT_NO_NARROW_FWD": "1"},
+                (128, 120, 8, 8, False))],
+        single=[("mask_b128_n64_de64", MASK_ROW), ("b32_n90_de64", ("b32_n90_de64", 32, 90, 8, 64, False, "", None, None))]),
+}
 
 
-def child_mask(steps):
+def _tree_imports():
     sys.path[:0] = [os.getcwd(), os.path.join(os.getcwd(), "tests")]      # the tree this child was started in
-    import torch
     import memcontract as M
     from egt_amd import _lib as L
-    lib = L.load()
+    return M, L, L.load()
+
+
+def child_forms(kernel, env):
+    """the launch form of every case of `kernel` whose environment is `env` (this process's: the plan reads its switches once), in this
+    process's tree; no GPU work"""
+    M, L, lib = _tree_imports()
+    cases = CASES[kernel]
+    rows = [(name, e, ("", *shape, "", None, None)) for name, _, e, shape in cases["bench"]] + [(n, {}, r) for n, r in cases["single"]]
+    for name, e, row in rows:
+        if e == env:
+            form = lib.egt_block_launch_form(C.byref(M.block_desc(row)))
+            print(json.dumps(dict(case=name, env=env, form=form.decode() if form else None)))
+
+
+def child_single(kernel, name, steps):
+    M, L, lib = _tree_imports()
+    import torch
     gpu = torch.device("cuda", 0)
-    case = M.block_case(lib, MASK_ROW)
+    case = M.block_case(lib, dict(CASES[kernel]["single"])[name])
     form = lib.egt_block_launch_form(C.byref(case.claims["desc"])).decode()
     M.run(case, M.ZERO, gpu, sync=torch.cuda.synchronize, check_rc=L.check)          # warm-up
     lib.egt_prof_filter(b""); lib.egt_prof_enable(2)
@@ -48,24 +83,30 @@ def child_mask(steps):
         M.run(case, M.ZERO, gpu, sync=torch.cuda.synchronize, check_rc=L.check)
     lib.egt_prof_enable(0)
     cnt, ms = C.c_int64(0), C.c_double(0.0)
-    lib.egt_prof_read(b"k_block_bwd", C.byref(cnt), C.byref(ms))
+    lib.egt_prof_read(kernel.encode(), C.byref(cnt), C.byref(ms))
     assert cnt.value == steps, cnt.value
-    print(json.dumps(dict(form=form, launches=cnt.value, k_block_bwd_us=ms.value / cnt.value * 1e3)))
+    print(json.dumps({"form": form, "launches": cnt.value, kernel + "_us": ms.value / cnt.value * 1e3}))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-tree", default=None)
+    ap.add_argument("--kernel", choices=sorted(CASES), default="k_block_bwd")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--mask-steps", type=int, default=8)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "bwd_phases.jsonl"))
+    ap.add_argument("--out", default=None, help="default: profiles/bwd_phases.jsonl, profiles/fwd_phases.jsonl for k_block_fwd")
     ap.add_argument("--child-timeout", type=int, default=240)
-    ap.add_argument("--child-mask", action="store_true")
+    ap.add_argument("--child-single", default=None, help="(internal) the single-block case this child runs")
+    ap.add_argument("--child-forms", default=None, help="(internal) print the launch form of every case of this environment (JSON)")
     args = ap.parse_args()
-    if args.child_mask:
-        return child_mask(args.mask_steps)
+    if args.child_forms:
+        return child_forms(args.kernel, json.loads(args.child_forms))
+    if args.child_single:
+        return child_single(args.kernel, args.child_single, args.mask_steps)
+    kfig, cases = args.kernel + "_us", CASES[args.kernel]
+    args.out = args.out or os.path.join(REPO, "profiles", ("fwd" if args.kernel == "k_block_fwd" else "bwd") + "_phases.jsonl")
     trees = ([(os.path.abspath(args.parent_tree), "parent")] if args.parent_tree else []) + [(REPO, "this")]
     recs = []
 
@@ -78,24 +119,40 @@ def main():
             raise SystemExit(f"{name} ({tag}, round {rnd}): child exit status {r.returncode}; nothing more is run")
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         if "roofline" in d:
-            rec = dict(k_block_bwd_us=d["roofline"]["kernels"]["k_block_bwd"]["avg_us"], ms_per_step=d["ms_per_step"],
-                       median_ms_per_step=d.get("median_ms_per_step"), step_mode=(d.get("config") or {}).get("step_mode"))
+            rec = {kfig: d["roofline"]["kernels"][args.kernel]["avg_us"], "ms_per_step": d["ms_per_step"],
+                   "median_ms_per_step": d.get("median_ms_per_step"), "step_mode": (d.get("config") or {}).get("step_mode")}
         else:
             rec = d
         rec = dict(case=name, tree=tag, round=rnd, env=env_extra, **rec)
         recs.append(rec)
         print(json.dumps(rec), flush=True)
 
+    me = os.path.abspath(__file__)
+    envs = [json.loads(x) for x in dict.fromkeys(json.dumps(e, sort_keys=True) for _, _, e, _ in cases["bench"])]
+    for tree, tag in trees:
+        for e in envs + ([] if {} in envs else [{}]):
+            env = dict(os.environ, **e)
+            env.pop("EGT_AMD_LIB", None)
+            r = subprocess.run([sys.executable, me, "--kernel", args.kernel, "--child-forms", json.dumps(e)], cwd=tree, env=env,
+                               capture_output=True, text=True, timeout=args.child_timeout)
+            if r.returncode != 0:
+                sys.stderr.write((r.stdout + r.stderr)[-4000:])
+                raise SystemExit(f"launch forms ({tag}): child exit status {r.returncode}; nothing more is run")
+            for l in r.stdout.splitlines():
+                if l.startswith("{"):
+                    recs.append(dict(tree=tag, **json.loads(l)))
+                    print(json.dumps(recs[-1]), flush=True)
     for rnd in range(args.rounds):
         for tree, tag in trees:
-            for name, extra, env in BENCH:
+            for name, extra, env, _ in cases["bench"]:
                 run(name, tree, tag, rnd, ["bench.py", "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup), "--full",
                                           "--no-cpu-baseline", "--no-graph-leg", "--graph", "off"] + extra, env)
-            run("mask_b128_n64_de64", tree, tag, rnd, [os.path.abspath(__file__), "--child-mask", "--mask-steps", str(args.mask_steps)], {})
-    ok, runs = True, list(recs)
+            for name, _ in cases["single"]:
+                run(name, tree, tag, rnd, [me, "--kernel", args.kernel, "--child-single", name, "--mask-steps", str(args.mask_steps)], {})
+    ok, runs = True, [r for r in recs if "round" in r]
     if args.parent_tree:
         for name in dict.fromkeys(r["case"] for r in runs):
-            for fig in ("k_block_bwd_us", "ms_per_step"):
+            for fig in (kfig, "ms_per_step"):
                 par = [r[fig] for r in runs if r["case"] == name and r["tree"] == "parent" and fig in r]
                 new = [r[fig] for r in runs if r["case"] == name and r["tree"] == "this" and fig in r]
                 if not par:

@@ -3,6 +3,7 @@
 One process loads one library: run it once per build (each run under its own time limit, chained with &&) and diff the listings.
 
     python tools/op_bits.py [--ops head,embed,block,ffn] [--lib path/to/libegt_amd.so] > listing.txt      (--lib: the EGT_AMD_LIB of this process)
+    python tools/op_bits.py --condense listing.txt      (the listing in one line per case: a sha256 over the case's lines; for keeping a comparison's result)
 
 head:  the fused edge head and node head over the cases of tests/test_distance_head_gpu.py and tests/test_node_head_gpu.py (their
        CASES, the bf16 and the full-tile case).  Edge head: per_graph, d_e and the parameter gradients; node head: stats, d_h and the
@@ -33,6 +34,18 @@ def emit(tag, tensors):
     for name, t in tensors:
         raw = t.detach().contiguous().cpu().view(torch.uint8).numpy().tobytes()
         print(f"{hashlib.sha256(raw).hexdigest()}  {tag} {name} {str(t.dtype)[6:]}{list(t.shape)}", flush=True)
+
+
+def condense(path):
+    """a listing in one line per case (sha256 over the case's lines, the number of its tensors, its tag) and one for the whole file"""
+    import re
+    cases, raw = {}, open(path, "rb").read()
+    for line in raw.decode().splitlines():
+        tag = re.match(r"\w{64}  (.*?) (?:d )?\S+ \w+\[[\d, ]*\]$", line).group(1)
+        cases.setdefault(tag, []).append(line)
+    for tag, lines in cases.items():
+        print(f"{hashlib.sha256(chr(10).join(lines).encode()).hexdigest()}  {len(lines):3d} tensors  {tag}")
+    print(f"{hashlib.sha256(raw).hexdigest()}  {len(raw.splitlines())} lines  whole listing")
 
 
 def params_of(test, names):
@@ -108,7 +121,10 @@ def embed(gpu):
 BLOCK_EXTRA = [("n32_de64", 2, 32, 8, 64, False, "", None, None),                  # N a multiple of 16: the non-ragged instances
                ("n32_de32_mask", 2, 32, 8, 32, False, "attn_mask", None, None),
                ("n32_de16", 2, 32, 8, 16, False, "", None, None),
-               ("n21_de8", 2, 21, 8, 8, False, "", None, None)]                    # k_block_bwd_v4r<8> under EGT_NO_NARROW=1
+               ("n21_de8", 2, 21, 8, 8, False, "", None, None),                    # k_block_bwd_v4r<8> under EGT_NO_NARROW=1
+               ("n90_de64_mask", 1, 90, 8, 64, False, "attn_mask", None, None),    # K/V do not fit in LDS, mask tensor: k_block_fwd<64, false, true, false>
+               ("n90_de64", 1, 90, 8, 64, False, "", None, None),                  # ... without one: k_block_fwd<64, false, false, false>
+               ("n160_de16", 1, 160, 8, 16, False, "", None, None)]                # k_block_fwd_r4, eight waves, full tiles
 
 
 def block(gpu):
@@ -175,7 +191,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=None)
     ap.add_argument("--ops", default="head,embed")
+    ap.add_argument("--condense", default=None, metavar="LISTING", help="print a saved listing in one line per case (no GPU work)")
     args = ap.parse_args()
+    if args.condense:
+        return condense(args.condense)
     ops = args.ops.split(",")
     if not ops or set(ops) - {"head", "embed", "block", "ffn"}:
         ap.error("--ops takes head, embed, block, ffn or several of them")
