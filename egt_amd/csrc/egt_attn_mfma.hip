@@ -33,67 +33,8 @@
 // general kernels of egt_attn.hip.
 #include <stdlib.h>
 
-#include "egt_common.h"
-#include "egt_stamps.h"
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-#define MFMA_(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
-#define AH 8
-#define L2E 1.4426950408889634f
-#define KEY_OFF (-3.0e38f)   // additive term of key slots past N (below every masked logit, above -inf)
-
-// packed operand arrays, each B*H*NP*d floats, in workspace order: Q rows (pre-scaled), K rows, V^T (what the forward
-// reads), V rows, K^T, dO rows (the backward's); then stats2 and dA (the layout: plan_attn).  A forward launched with
-// EGT_ATTN_WS_SHARED packs the five q/k/v arrays once and the backward, given the same workspace, adds only dO.
-enum { PK_QH = 0, PK_KH, PK_VT, PK_FWD_COUNT, PK_VH = PK_FWD_COUNT, PK_KT, PK_OH, PK_COUNT };
-enum { PACK_Q = 1, PACK_KH = 2, PACK_KT = 4, PACK_VT = 8, PACK_VH = 16, PACK_O = 32 };
-
-struct AttnMfmaArgs {
-  int B, N, NP, d;
-  uint32_t flags;
-  float clip_lo, clip_hi, scale;
-  uint32_t rm_thr, s0, s1;
-  int rng_rm;
-  const float *qkv, *E, *G, *M;
-  const uint8_t *km, *rm;
-  float *v_att, *h_hat, *rowstats;
-  float* pk;   // packed arrays
-  // backward
-  const float *v_att_in, *d_v_att, *d_h_ext;
-  float *d_qkv, *d_E, *d_G, *ws_dA, *stats2;
-  int pack_what;   // PACK_* bits
-};
-
-// Phase stamps (egt_stamps.h; measurement builds only).  Slots of this unit: a kernel's compute / attention waves and the pair kernels'
-// edge waves stamp different phases (the loader waves of k_attn_mfma_fwd / _bwd_kv do not stamp)
-enum { ST_ATTN_FWD, ST_ATTN_BWD_KV, ST_PAIR_FWD_ATT, ST_PAIR_FWD_EDGE, ST_PAIR_BWD_ATT, ST_PAIR_BWD_EDGE, ST_COUNT };
-EGT_STAMP_UNIT(ST_COUNT);
-// timing ablations (results are wrong): -DEGT_ATTN_ABL=<bits>: 1 no operand DMA, 2 no pair loads / scatter, 4 no output stores,
-// 8 no MFMAs, 16 no elementwise phase (probabilities = logits)
-#ifndef EGT_ATTN_ABL
-#define EGT_ATTN_ABL 0
-#endif
-#define ABL(bit) ((EGT_ATTN_ABL & (bit)) == 0)
-#if EGT_ATTN_ABL & 8
-__device__ __forceinline__ v4f MFMA(float a, float b, v4f c) { c[0] += a * b; return c; }
-#else
-#define MFMA(a, b, c) MFMA_(a, b, c)
-#endif
-
-// LDS hand-off between the waves of a workgroup WITHOUT draining vector memory: __syncthreads() is
-// s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier on gfx950; the operand prefetches and the output stores of
-// these kernels must stay in flight across the barrier, and nothing here communicates through global memory.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ float pair_max_q(float v) {   // max over lanes l, l+16, l+32, l+48
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float pair_sum_q(float v) { return sum_xor32(sum_xor16(v)); }
-__device__ __forceinline__ float exp2_fast(float x) { return __builtin_amdgcn_exp2f(x); }
+#include "egt_attn_dev.h"
+#include "egt_pair.h"   // the fused pair operator of the same geometry (k_pair_fwd / k_pair_bwd)
 
 // ------------------------------------------------------------------- pack --------
 // workgroup = (graph, 16 node rows), 512 threads: every section of the launch ([q | k | v | dO]) is de-interleaved
@@ -199,105 +140,6 @@ __global__ void __launch_bounds__(512) k_attn_pack(AttnMfmaArgs a) {
   }
 }
 
-// Feature set of a kernel instance.  V = 0 reads every switch at run time (any combination);
-// V = 1 / 2 are the straight-line instances of the main configuration (edge bias + gates + key
-// padding + clip, no attention-mask tensor, no injected mask bytes; 2 = in-kernel random mask).
-template <int V>
-struct Feat {
-  bool E, G, M, km, clip, rmb, rng, X;
-  __device__ __forceinline__ Feat(const AttnMfmaArgs& a) {
-    E = V ? true : a.E != nullptr;
-    G = V ? true : (a.flags & EGT_F_GATE_INPUT) != 0;
-    M = V ? false : a.M != nullptr;
-    km = V ? true : a.km != nullptr;
-    clip = V ? true : (a.flags & EGT_F_CLIP) != 0;
-    rmb = V ? false : a.rm != nullptr;
-    rng = V == 2 ? true : (V == 1 ? false : a.rng_rm != 0);
-    X = V ? true : a.d_h_ext != nullptr;
-  }
-};
-
-// additive mask of one element beyond its key term, in the reference's order (egt_layers.py:96-108)
-template <int V>
-__device__ __forceinline__ float mask_extra(const AttnMfmaArgs& a, const Feat<V>& f, float mval, uint32_t gi) {
-  float add = 0.f;
-  if (f.M) add += (mval - 1.0f) * EGT_NEG;
-  if (f.rmb || f.rng) {
-    const bool hit = f.rmb ? (a.rm[gi] != 0) : ((egt_hash32(gi, a.s0, a.s1) >> 8) < a.rm_thr);
-    add += hit ? -EGT_NEG : 0.0f;
-  }
-  return add;
-}
-
-// ---- pair-tile planes: a [16 rows][16 cols x 8 heads] tile of a [B,N,N,8] tensor is 16 contiguous 512-byte
-// runs; the workgroup's 512 threads move it with one 16-byte global access each (thread -> row tid>>5, column
-// (tid&31)>>1, heads 4*(tid&1)..+3).  In LDS the tile is HEAD-MAJOR: eight planes of stride PT_PL.
-//   forward planes  [query row][key]: the wave that owns head h reads the four consecutive keys of its lane with
-//     one ds_read_b128; rows 4..7 / 12..15 pair-swapped, 4-column chunks XORed with (row>>1)&3;
-//   backward planes [key][query row]: lane (key, q) moves query rows 4q..4q+3 with one b128; chunk XOR (0,2,3,1)[key>>2].
-// tools/lds_bank_check.py enumerates every pattern against the gfx950 lane-group tables: all conflict free except the
-// backward's 4 x b32 cooperative scatter / gather (4-way: 8 array cycles under a 4-cycle issue, 2 x).
-#define PT_PL 260
-#define PT_SZ (8 * PT_PL)
-
-__device__ __forceinline__ int pt_off(int row, int m) {
-  return ((row ^ ((row >> 2) & 1)) << 4) + ((((m >> 2) ^ (row >> 1)) & 3) << 2) + (m & 3);
-}
-__device__ __forceinline__ int ptT_off(int row, int col) {
-  const int c2 = col >> 2;
-  const int a = (0x78 >> (2 * c2)) & 3;   // (0, 2, 3, 1)[c2]
-  return (col << 4) + ((((row >> 2) ^ a) & 3) << 2) + (row & 3);
-}
-// address of a thread's 16 bytes inside a tile: workgroup-uniform base (tensor + graph + first row, scalar
-// registers) + a 32-bit lane offset: rowoff is fixed for the kernel, the column part is two VALU ops per tile
-__device__ __forceinline__ uint32_t ptile_rowoff(int N, int row0, int tid) {
-  return (uint32_t)(min(row0 + (tid >> 5), N - 1) - row0) * N * AH + (tid & 1) * 4;
-}
-__device__ __forceinline__ uint32_t ptile_off(uint32_t rowoff, int N, int col0, int tid) {
-  return rowoff + (uint32_t)min(col0 + ((tid & 31) >> 1), N - 1) * AH;
-}
-__device__ __forceinline__ const float* ptile_base(const float* src, int b, int N, int row0) {
-  return src + ((size_t)b * N + row0) * N * AH;
-}
-template <bool T>
-__device__ __forceinline__ void plane_scatter(float* tl, float4 v, int tid) {
-  const int row = tid >> 5, m = (tid & 31) >> 1;
-  float* p = tl + (tid & 1) * 4 * PT_PL + (T ? ptT_off(row, m) : pt_off(row, m));
-  p[0] = v.x; p[PT_PL] = v.y; p[2 * PT_PL] = v.z; p[3 * PT_PL] = v.w;
-}
-template <bool T>
-__device__ __forceinline__ float4 plane_gather(const float* tl, int tid) {
-  const int row = tid >> 5, m = (tid & 31) >> 1;
-  const float* p = tl + (tid & 1) * 4 * PT_PL + (T ? ptT_off(row, m) : pt_off(row, m));
-  return make_float4(p[0], p[PT_PL], p[2 * PT_PL], p[3 * PT_PL]);
-}
-
-// ---- producer / consumer split (tools/micro/mfma_stream.hip, profiles/r04_attn5_microbench.md) ----------------
-// One global_load in an fp32 MFMA stream costs the issuing wave ~80 cycles (= 2.5 MFMAs), a ds_read_b128 ~7; LDS-DMA
-// loader waves on the same SIMDs move 18 TB/s without slowing a compute wave's MFMA stream (33.7 vs 32 cycles per
-// MFMA).  So a workgroup is 4 COMPUTE waves (one per SIMD, one head each: ds_read + MFMA + VALU only) and 4 LOADER
-// waves: operand tiles by LDS-DMA (global_load_lds_dwordx4: no VGPR, no ds_write) one iteration ahead, pair tiles
-// HBM -> registers -> head-major planes two iterations ahead, output planes -> HBM one iteration behind.  One
-// s_barrier per iteration, which does not drain vector memory.
-//
-// Operand tile in LDS: the packed [T][16 rows][16 channels] block with the four 16-byte chunks of a row XORed by
-// (0,2,3,1)[row >> 2] (done by the DMA's lane -> source mapping: LDS slot s of a 1 KB piece receives row s >> 2,
-// chunk (s & 3) ^ a[s >> 4]): the row-form fragment reads (lane (row, q): ds_read_b128 of chunk q) are bank-conflict
-// free and the transposed reads (lane (channel, q): ds_read_b32 of rows 4q + r) 2-way (tools/lds_bank_check.py).
-__device__ __forceinline__ unsigned lds_addr(const void* p) { return (unsigned)(uintptr_t)p; }   // LDS byte address of a __shared__ pointer
-__device__ __forceinline__ int chunk_xor(int row) { return (0x78 >> (2 * (row >> 2))) & 3; }      // (0, 2, 3, 1)[row >> 2]
-// one 1 KB piece HBM -> LDS (any LDS address: tools/micro/dma_hi.hip): lane i lands at lds + 16 i and fetches src + off
-__device__ __forceinline__ void dma_piece(unsigned lds, const float* src, unsigned off) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %1\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "s"(src), "v"(off), "s"(lds) : "memory");
-}
-template <int N_>
-__device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "i"(N_) : "memory"); }
-__device__ __forceinline__ unsigned dma_lane_off(int lane) {   // source byte offset (inside a 1 KB block) of the chunk that lands in slot `lane`
-  return (unsigned)((lane >> 2) * 64 + (((lane & 3) ^ chunk_xor(lane >> 2)) << 4));
-}
-#define OPS_STAGE 32768   // bytes of one operand stage: 4 heads x (two 4 KB tiles)
 #define OPS_BYTES (2 * OPS_STAGE)
 
 // ================================================================== forward =====
@@ -335,13 +177,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
     // ------------------------------------------------------------------ loader waves ----
     const int lt = tid - 256;                   // 0..255
     const int crow = lt >> 4, ccol = lt & 15;   // pair-tile transfers: row crow, key ccol of every 16 x 16 sub-tile, 4 heads (16 bytes)
-    for (int m = lt; m < NP + 16; m += 256) {
-      float ka = 0.f;
-      if (m >= N) ka = KEY_OFF;
-      else if (f.km && a.km[(size_t)b * N + m] == 0) ka = -EGT_NEG;
-      kaddL[m] = ka;
-      kaddG[m] = m >= N ? 3.0e38f : -ka * L2E;
-    }
+    for (int m = lt; m < NP + 16; m += 256) key_terms(b, m, N, f.km, a.km, kaddL[m], kaddG[m]);
     const float* Kh = a.pk + PK_KH * arr + ((size_t)b * AH + h) * NP * D;   // [NP/16][D/16][16][16]   (this loader wave feeds head h)
     const float* VT = a.pk + PK_VT * arr + ((size_t)b * AH + h) * D * NP;   // [NP/16][D][16]
     const unsigned doff = dma_lane_off(lane);
@@ -467,9 +303,9 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
     const float* ops = opl + (it & 1) * (OPS_STAGE / 4);
     const float* Inb = In + (it & 1) * NIN * TS;
     float* Hb2 = Hout + (it & 1) * TS;
-    float4 kc[KT], vc[KT];
+    float4 kc[1][KT], vc[1][KT];   // one K / V^T fragment set for both query tiles
 #pragma unroll
-    for (int T = 0; T < KT; ++T) kc[T] = *reinterpret_cast<const float4*>(ops + T * 256);
+    for (int T = 0; T < KT; ++T) kc[0][T] = *reinterpret_cast<const float4*>(ops + T * 256);
     float4 e4[FQ], g4[FQ], m4[FQ], ka4, kg4 = make_float4(0.f, 0.f, 0.f, 0.f);
     ka4 = *reinterpret_cast<const float4*>(kaddL + m0 + 4 * q);
     if (V == 1) kg4 = *reinterpret_cast<const float4*>(kaddG + m0 + 4 * q);
@@ -485,100 +321,30 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
     EGT_STAMP(1);
     // ---- S^T[m][l] = sum_k K[m][k] (d^-1/2 Q)[l][k]: every K register feeds the two query tiles ----
     v4f s[FQ];
+    mfma_s<FQ, 1, KT>(kc, Qr, s);
 #pragma unroll
-    for (int qt = 0; qt < FQ; ++qt) s[qt] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int T = 0; T < KT; ++T)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float kk = u == 0 ? kc[T].x : u == 1 ? kc[T].y : u == 2 ? kc[T].z : kc[T].w;
-#pragma unroll
-        for (int qt = 0; qt < FQ; ++qt) s[qt] = MFMA(kk, Qr[qt][4 * T + u], s[qt]);
-      }
-#pragma unroll
-    for (int T = 0; T < KT; ++T) vc[T] = *reinterpret_cast<const float4*>(ops + KT * 256 + T * 256);   // V^T fragments: requested behind the S MFMAs, landed long before P.V
+    for (int T = 0; T < KT; ++T) vc[0][T] = *reinterpret_cast<const float4*>(ops + KT * 256 + T * 256);   // V^T fragments: requested behind the S MFMAs, landed long before P.V
     __builtin_amdgcn_sched_barrier(0);
     EGT_STAMP(2);
-    const float kav[4] = {ka4.x, ka4.y, ka4.z, ka4.w}, kgv[4] = {kg4.x, kg4.y, kg4.z, kg4.w};
     float pa[FQ][4];
 #pragma unroll
     for (int qt = 0; qt < FQ; ++qt) {
-      float x[4];
-      float tmax = KEY_OFF;
-      const int lq = min(l0 + 16 * qt + ll, N - 1);
-      const float ev[4] = {e4[qt].x, e4[qt].y, e4[qt].z, e4[qt].w}, gv[4] = {g4[qt].x, g4[qt].y, g4[qt].z, g4[qt].w};
-      const float mv[4] = {m4[qt].x, m4[qt].y, m4[qt].z, m4[qt].w};
       float hv4[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float ah = s[qt][r];
-        if (clip) ah = __builtin_amdgcn_fmed3f(ah, a.clip_lo, a.clip_hi);
-        const float hv = ah + ev[r];
-        hv4[r] = hv;                                            // H_hat: post-clip, pre-mask (egt_layers.py:85-86)
-        float add = kav[r];
-        if (V != 1) {
-          const int m = min(m0 + 4 * q + r, N - 1);
-          add += mask_extra(a, f, mv[r], (uint32_t)((((size_t)b * N + lq) * N + m) * AH + h));
-        }
-        x[r] = hv + add;
-        tmax = fmaxf(tmax, x[r]);
-        if (gated) {   // sigmoid(G + add); masked -> exp2(+1.4e9) = inf -> rcp = 0 exactly, as the reference's fp32 path
-          const float tg = V == 1 ? exp2_fast(fmaf(gv[r], -L2E, kgv[r])) : exp2_fast((gv[r] + add) * -L2E);
-          pa[qt][r] = __builtin_amdgcn_rcpf(1.0f + tg);
-        } else {
-          pa[qt][r] = 1.0f;
-        }
-      }
-      *reinterpret_cast<float4*>(Hb2 + qt * 4 * PT_PL + po4) = make_float4(hv4[0], hv4[1], hv4[2], hv4[3]);
-      // ---- online softmax over the 16 keys: in-lane over r, then across q ----
-      tmax = pair_max_q(tmax);
-      const float mnew = fmaxf(mrun[qt], tmax);
-      const float alpha = exp2_fast((mrun[qt] - mnew) * L2E);
-      float psum = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float pexp = exp2_fast((x[r] - mnew) * L2E);   // keys past N: exp2(-inf) = 0
-        psum += pexp;
-        pa[qt][r] *= pexp;
-      }
-      psum = pair_sum_q(psum);
-      lrun[qt] = fmaf(lrun[qt], alpha, psum);
-      mrun[qt] = mnew;
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) {
-        v4f o = oacc[qt][kt];
-        o[0] *= alpha; o[1] *= alpha; o[2] *= alpha; o[3] *= alpha;
-        oacc[qt][kt] = o;
-      }
+      attn_fwd_unit<V, KT>(a, f, clip, gated, s[qt], e4[qt], g4[qt], m4[qt], ka4, kg4, b, min(l0 + 16 * qt + ll, N - 1), m0 + 4 * q, N - 1, h,
+                           mrun[qt], lrun[qt], oacc[qt], pa[qt], hv4);
+      *reinterpret_cast<float4*>(Hb2 + qt * 4 * PT_PL + po4) = make_float4(hv4[0], hv4[1], hv4[2], hv4[3]);   // H_hat: post-clip, pre-mask
     }
     __builtin_amdgcn_sched_barrier(0);
     EGT_STAMP(3);
     // ---- O^T[k][l] += sum_m V^T[k][m] P^T[m][l]  (contraction order m = 4q + t): every V^T register feeds two MFMAs ----
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) {
-        const float va = r == 0 ? vc[kt].x : r == 1 ? vc[kt].y : r == 2 ? vc[kt].z : vc[kt].w;
-#pragma unroll
-        for (int qt = 0; qt < FQ; ++qt) oacc[qt][kt] = MFMA(va, pa[qt][r], oacc[qt][kt]);
-      }
+    mfma_pv<FQ, 1, KT>(vc, pa, oacc);
     EGT_STAMP(4);
     lds_barrier();
     EGT_STAMP(6);
   }
   // ---- finalize: O[l][k] / l_run into the (now idle) operand stages as [row][k][4 heads]; row statistics for the backward ----
 #pragma unroll
-  for (int qt = 0; qt < FQ; ++qt) {
-    const int l = l0 + 16 * qt + ll;
-    const float inv = 1.0f / lrun[qt];
-    float* vs = sm + ((16 * qt + ll) * D + 4 * q) * 4 + w;
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) vs[(16 * kt + r) * 4] = oacc[qt][kt][r] * inv;
-    if (l < N && q == 0)
-      *reinterpret_cast<float4*>(a.rowstats + (((size_t)b * N + l) * AH + h) * 4) = make_float4(mrun[qt], lrun[qt], 0.f, 0.f);
-  }
+  for (int qt = 0; qt < FQ; ++qt) attn_fwd_finalize<4, KT>(a, sm, 16 * qt + ll, q, w, b, l0 + 16 * qt + ll, h, oacc[qt], mrun[qt], lrun[qt]);
   EGT_STAMP(7);
   EGT_STAMP_OUT(ST_ATTN_FWD);
   }
@@ -636,7 +402,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
     const int crow = lt >> 4, ccol = lt & 15;   // query row, key of each 16 x 16 sub-tile; the group's 4 heads (16 bytes)
     const float* Qh = a.pk + PK_QH * arr + hb;  // this loader wave feeds head h
     const float* Oh = a.pk + PK_OH * arr + hb;
-    const unsigned doff = dma_lane_off(lane ^ (((lane >> 4) & 1) << 2));   // (operand-tile rows pair-swapped in LDS: LDS row sigma <- tile row sigma ^ ((sigma >> 2) & 1), see the compute waves)
+    const unsigned doff = dma_lane_off_swapped(lane);   // (operand-tile rows pair-swapped in LDS: bwd_operands)
     const unsigned ops0 = lds_addr(sm) + w * (KT * 2048);   // head w: Q tile, then dO tile
     auto dma_ops = [&](int ltile, int stage) __attribute__((always_inline)) {
       const float* qs = Qh + (size_t)ltile * 16 * D;
@@ -760,11 +526,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
         Kr[kb][T] = *reinterpret_cast<const float4*>(Kh + (size_t)mtc * 16 * D + 256 * T + ooff);
         Vr[kb][T] = *reinterpret_cast<const float4*>(Vh + (size_t)mtc * 16 * D + 256 * T + ooff);
       }
-      const int m = m0 + 16 * kb + mm;
-      kadd[kb] = 0.f;
-      if (m >= N) kadd[kb] = KEY_OFF;
-      else if (f.km && a.km[(size_t)b * N + m] == 0) kadd[kb] = -EGT_NEG;
-      kaddg[kb] = m < N ? -kadd[kb] * L2E : 3.0e38f;
+      key_terms(b, m0 + 16 * kb + mm, N, f.km, a.km, kadd[kb], kaddg[kb]);
     }
   }
   v4f dKacc[BK][KT], dVacc[BK][KT];
@@ -773,20 +535,13 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt) { dKacc[kb][kt] = (v4f){0.f, 0.f, 0.f, 0.f}; dVacc[kb][kt] = (v4f){0.f, 0.f, 0.f, 0.f}; }
   const int po4 = w * PT_PL + ptT_off(4 * q, mm);   // this lane's query rows 4q..4q+3 of key mm inside a sub-tile: one 16-byte access
-  // operand tiles of head w (Q, then dO): row form: lane (row mm, chunk q) b128; transposed form: lane (channel mm, q):
-  // rows 4q + r, dword mm & 3 of chunk mm >> 2
-  // (tile rows 4-7 / 12-15 pair-swapped in LDS, as in k_pair_bwd: the transposed b32 reads of a 32-lane group touch
-  //  tile rows r and 4 + r -- the same 16 banks with 16-float rows, 2-way on the 32 reads of a tile; swapped, the group covers 32 banks)
-  const float* oprow = sm + w * (KT * 512) + (mm ^ ((mm >> 2) & 1)) * 16 + ((q ^ chunk_xor(mm)) << 2);
-  const float* optr = sm + w * (KT * 512) + (4 * q) * 16 + (((mm >> 2) ^ chunk_xor(4 * q)) << 2) + (mm & 3);
-  const float* optr_e = optr + (q & 1) * 16;   // steps 0, 2: LDS row 4q + r + (q & 1)
-  const float* optr_o = optr - (q & 1) * 16;   // steps 1, 3: LDS row 4q + r - (q & 1)
+  const BwdOperands op = bwd_operands(sm + w * (KT * 512), mm, q);   // operand tiles of head w (Q, then dO)
   lds_barrier();
   EGT_STAMP(0);
   for (int l0 = 0, it = 0; it < mtiles; l0 += 16, ++it) {
-    const float* opr = oprow + (it & 1) * (OPS_STAGE / 4);
-    const float* opt_e = optr_e + (it & 1) * (OPS_STAGE / 4);
-    const float* opt_o = optr_o + (it & 1) * (OPS_STAGE / 4);
+    const float* opr = op.row + (it & 1) * (OPS_STAGE / 4);
+    const float* opt_e = op.t_e + (it & 1) * (OPS_STAGE / 4);
+    const float* opt_o = op.t_o + (it & 1) * (OPS_STAGE / 4);
     const float* Inb = In + (it & 1) * NIN * TS;
     float* Ob = Out + (it & 1) * 2 * TS;
     float4 qa[KT], oa[KT];   // row operands first: the S / dP MFMAs start as soon as they land, everything else lands behind them
@@ -809,57 +564,15 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
     EGT_STAMP(1);
     // ---- S[l][m] = sum_k (d^-1/2 Q)[l][k] K[m][k] ; dP[l][m] = sum_k dO[l][k] V[m][k]: every Q / dO register feeds two MFMAs ----
     v4f s[BK], dp[BK];
-#pragma unroll
-    for (int kb = 0; kb < BK; ++kb) { s[kb] = (v4f){0.f, 0.f, 0.f, 0.f}; dp[kb] = (v4f){0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-    for (int T = 0; T < KT; ++T) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float qq = u == 0 ? qa[T].x : u == 1 ? qa[T].y : u == 2 ? qa[T].z : qa[T].w;
-        const float oo = u == 0 ? oa[T].x : u == 1 ? oa[T].y : u == 2 ? oa[T].z : oa[T].w;
-#pragma unroll
-        for (int kb = 0; kb < BK; ++kb) {
-          const float kk = u == 0 ? Kr[kb][T].x : u == 1 ? Kr[kb][T].y : u == 2 ? Kr[kb][T].z : Kr[kb][T].w;
-          const float vv = u == 0 ? Vr[kb][T].x : u == 1 ? Vr[kb][T].y : u == 2 ? Vr[kb][T].z : Vr[kb][T].w;
-          s[kb] = MFMA(qq, kk, s[kb]);
-          dp[kb] = MFMA(oo, vv, dp[kb]);
-        }
-      }
-    }
+    mfma_s_dp<BK, KT>(qa, oa, Kr, Vr, s, dp);
     __builtin_amdgcn_sched_barrier(0);
     EGT_STAMP(2);
     float at[BK][4], da[BK][4];
 #pragma unroll
     for (int kb = 0; kb < BK; ++kb) {
-      const float ev[4] = {e4[kb].x, e4[kb].y, e4[kb].z, e4[kb].w}, gv[4] = {g4[kb].x, g4[kb].y, g4[kb].z, g4[kb].w};
-      const float xv4[4] = {x4[kb].x, x4[kb].y, x4[kb].z, x4[kb].w};
-      float dE4[4], dG4[4];
-      const int mc = min(m0 + 16 * kb + mm, N - 1);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float araw = s[kb][r];
-        float ah = araw;
-        if (clip) ah = __builtin_amdgcn_fmed3f(araw, a.clip_lo, a.clip_hi);
-        float add = kadd[kb];
-        if (V != 1) {
-          const int lq = min(l0 + 4 * q + r, N - 1);
-          add += mask_extra(a, f, 1.0f, (uint32_t)((((size_t)b * N + lq) * N + mc) * AH + h));   // (the mask tensor arrives inside E / G)
-        }
-        const float xx = ah + ev[r] + add;
-        const float S = exp2_fast((xx - stc[r].x) * L2E) * stc[r].y;   // rows past N: 1/l = 0; keys past N: exp2(-inf) = 0
-        float g = 1.0f;
-        if (gated) {
-          const float tg = V == 1 ? exp2_fast(fmaf(gv[r], -L2E, kaddg[kb])) : exp2_fast((gv[r] + add) * -L2E);
-          g = __builtin_amdgcn_rcpf(1.0f + tg);
-        }
-        const float dAt_ = dp[kb][r];
-        const float Sg = S * g;
-        const float dH = fmaf(S, fmaf(dAt_, g, -stc[r].z), xv4[r]);
-        at[kb][r] = Sg;
-        da[kb][r] = (clip && ah != araw) ? 0.f : dH;   // clip passes the gradient where lo <= x <= hi
-        dE4[r] = dH;
-        dG4[r] = gated ? dAt_ * Sg * (1.0f - g) : 0.f;
-      }
+      float dE4[4], dG4[4], hv4[4];   // (hv4: dropped, H_hat left in the forward)
+      attn_bwd_unit<V>(a, f, clip, gated, s[kb], dp[kb], e4[kb], g4[kb], x4[kb], stc, kadd[kb], kaddg[kb], b, l0 + 4 * q,
+                       min(m0 + 16 * kb + mm, N - 1), N - 1, h, at[kb], da[kb], dE4, dG4, hv4);   // (the mask tensor arrives inside E / G)
       if (f.E) *reinterpret_cast<float4*>(Ob + kb * 4 * PT_PL + po4) = make_float4(dE4[0], dE4[1], dE4[2], dE4[3]);
       if (f.G) *reinterpret_cast<float4*>(Ob + TS + kb * 4 * PT_PL + po4) = make_float4(dG4[0], dG4[1], dG4[2], dG4[3]);
       // dA tile [key][query] of (head, query tile, key tile): the lane's own four rows, one 16-byte store
@@ -869,19 +582,7 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
     __builtin_amdgcn_sched_barrier(0);
     EGT_STAMP(3);
     // ---- dV^T[k][m] += sum_l dO[l][k] A[l][m] ; dK^T[k][m] += sum_l (d^-1/2 Q)[l][k] dA[l][m]: transposed operands from the same tiles ----
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float* opt = (r & 1) ? opt_o : opt_e;
-        const float qq = opt[kt * 256 + r * 16];
-        const float oo = opt[KT * 256 + kt * 256 + r * 16];
-#pragma unroll
-        for (int kb = 0; kb < BK; ++kb) {
-          dVacc[kb][kt] = MFMA(oo, at[kb][r], dVacc[kb][kt]);
-          dKacc[kb][kt] = MFMA(qq, da[kb][r], dKacc[kb][kt]);
-        }
-      }
+    mfma_dv_dk<BK, KT>(opt_e, opt_o, at, da, dVacc, dKacc);
     EGT_STAMP(4);
     lds_barrier();
     EGT_STAMP(6);
@@ -1051,8 +752,6 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_q(AttnMfmaArgs a) {
     if (l < N && ABL(4)) a.d_qkv[((size_t)b * N + l) * 3 * DH + k * AH + h] = sm[p];
   }
 }
-
-#include "egt_pair.h"   // the fused pair operator of the same geometry (k_pair_fwd / k_pair_bwd)
 
 // ------------------------------------------------------------------ host glue --
 extern "C" int egt_attn_mfma_supported(const egt_attn_desc* d, int need_a_tild) {

@@ -109,6 +109,11 @@ __device__ __forceinline__ float row_max16(float v) {
   v = fmaxf(v, lane_xor<4>(v)); v = fmaxf(v, lane_xor<8>(v));
   return v;
 }
+// component r of a float4 (r a compile-time constant after unrolling: a register pick, no select)
+__device__ __forceinline__ float f4get(const float4& v, int r) { return r == 0 ? v.x : r == 1 ? v.y : r == 2 ? v.z : v.w; }
+// wait until at most N of the wave's vector-memory operations are outstanding (they retire in order)
+template <int N_>
+__device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "i"(N_) : "memory"); }
 
 // ---- egt_edge.hip, for the fused pair operator (egt_pair.h): edge-parameter gradients from per-workgroup partials ----
 void egt_edge_finish_param_grads(int De, const float* gamma, const float* beta, const float* Wg, const float* We,

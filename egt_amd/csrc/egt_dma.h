@@ -70,10 +70,6 @@ __device__ __forceinline__ void tile_dma_ragged(unsigned lds, const float* src, 
                  : "=&s"(keep) : "s"(src), "v"(off), "s"(lds + 1024u * i) : "memory");
   }
 }
-// wait until at most N of the wave's vector-memory operations are outstanding (they retire in order)
-template <int N_>
-__device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "i"(N_) : "memory"); }
-
 // transposed element (row q + 4s, channel 16t + p) of a swizzled De = 64 tile: the XOR swizzle splits into a
 // per-lane part and a part that depends only on (s, t), so ONE address register + compile-time offsets
 // replace 32 per-(s,t) address registers:  floats = [64 q + 4 ((p >> 2) ^ q) + (p & 3)] + 256 s + 16 (t ^ s)

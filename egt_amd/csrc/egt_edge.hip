@@ -73,7 +73,6 @@ __device__ __forceinline__ void frag_gload(float4 (&x)[EdgeGeo<DE>::T], const fl
     x[t] = make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
   }
 }
-__device__ __forceinline__ float f4c(const float4& v, int r) { return r == 0 ? v.x : r == 1 ? v.y : r == 2 ? v.z : v.w; }
 
 // column i of the concatenated projection [attention_gates | dense_edge_b] for channel c
 __device__ __forceinline__ float wcat(const EdgeArgs& a, bool gates, int c, int i) {

@@ -5,8 +5,8 @@
 // path (k_edge_proj_* -> k_attn_mfma_* -> k_edge_update_*) never reach HBM.  The node-side Dense layers around it
 // (norm_mha, dense_qkv, dense_mha: [B N, 512] x [512, 1536] GEMMs) stay library GEMMs.
 //
-// Included by egt_attn_mfma.hip (same translation unit: packed operand arrays, plane layouts, LDS-DMA helpers, k_attn_pack
-// and k_attn_mfma_bwd_q are shared with the inner-op kernels).
+// Part of egt_attn_mfma.hip's translation unit (the launches share k_attn_pack and k_attn_mfma_bwd_q with the inner op); the packed
+// operand arrays, the plane layouts, the LDS-DMA helpers and the attention phases of the attention waves are egt_attn_dev.h's.
 //
 // Workgroup = (graph, 16 query rows [forward] / 16 keys [backward], ALL 8 heads), 8 waves, one workgroup per CU:
 //   * 4 ATTENTION waves (one per SIMD), two heads each: QK^T / A.V (backward: S, dP, dV, dK) on v_mfma_f32_16x16x4_f32 with
@@ -21,6 +21,7 @@
 // VALU / LDS phase (the inner-op kernels pair a compute wave with a loader wave that issues none).
 // Two barriers per tile, neither drains vector memory.
 #pragma once
+#include "egt_attn_dev.h"
 
 struct PairArgs {
   int De;
@@ -103,7 +104,6 @@ __device__ __forceinline__ float pair_ln(float4 (&x)[T_], float eps) {
   for (int t = 0; t < T_; ++t) { x[t].x *= rstd; x[t].y *= rstd; x[t].z *= rstd; x[t].w *= rstd; }
   return rstd;
 }
-__device__ __forceinline__ float f4get(const float4& v, int r) { return r == 0 ? v.x : r == 1 ? v.y : r == 2 ? v.z : v.w; }
 
 // LN-folded projection weights of an edge wave (A operands, lane (i = lane&15, q)): wA[t][r] = gamma_c Wcat[c][i], c = 16 t + 4 q + r;
 // bias[r] = b_i' + sum_c beta_c Wcat[c][i'] for the lane's OUTPUT channels i' = 4 q + r.  Wcat = [attention_gates | dense_edge_b].
@@ -165,6 +165,7 @@ __global__ void __launch_bounds__(64) k_pair_prep(PairArgs pa) {
 // FULL: N is a multiple of 16 (no ragged tile: every row / key of every tile exists -- the clamps and the store-address selects fold away)
 template <int D, int DE, int V, bool FULL>
 __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, PairArgs pa) {
+  static_assert(D == 64 && DE == 32, "the instantiated geometry: an operand tile is four 1 KB pieces (dma_pieces4)");
   constexpr int KT = D / 16, DH = D * AH, T = PairGeo<DE>::T, HS = KT * 256;   // HS: floats of one head's operand tile
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -181,6 +182,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
   const int b = __builtin_amdgcn_readfirstlane(wg / mtiles), l0 = __builtin_amdgcn_readfirstlane((wg % mtiles) * 16);   // (the division runs on the VALU: back to scalar registers)
   const size_t arr = (size_t)a.B * AH * NP * D;
   const bool clip = (a.flags & EGT_F_CLIP) != 0;
+  const Feat<V> f(a);
   // Key tile of trip `it`: tile `it`.  (Measured and not kept: every workgroup starting on the key tile of its own row block, a test
   // for HBM channel camping -- no difference, 145.1-146.2 against 145.4-146.7 us.  What is left of it is this wrap past the last tile: dead,
   // but hipcc does not know mtiles > 0 and keeps it for trip 0's requests; taking it out changes k_pair_fwd's set-up code.)
@@ -191,13 +193,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
     // --------------------------------------------------------------------- edge waves ----
     const int j = wv - 4, p = lane & 15, q = lane >> 4;
     __builtin_amdgcn_s_setprio(PAIR_EDGE_PRIO);   // the edge waves are the longer role: the SIMD's issue arbitration (priority, then age) favours them
-    for (int m = tid - 256; m < NP + 16; m += 256) {
-      float ka = 0.f;
-      if (m >= N) ka = KEY_OFF;
-      else if (a.km && a.km[(size_t)b * N + m] == 0) ka = -EGT_NEG;
-      kaddL[m] = ka;
-      kaddG[m] = m >= N ? 3.0e38f : -ka * L2E;
-    }
+    for (int m = tid - 256; m < NP + 16; m += 256) key_terms(b, m, N, a.km != nullptr, a.km, kaddL[m], kaddG[m]);
     float wA[T][4];
     {   // LN-folded [gamma Wg | gamma We] and its bias, prepared once per launch (k_pair_prep)
 #pragma unroll
@@ -376,13 +372,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
     const unsigned doff1 = doff + 1024, doff2 = doff + 2048, doff3 = doff + 3072;
     auto dma_tile = [&](unsigned dst, const float* src) __attribute__((always_inline)) {   // src: [2 heads] x (KT pieces), head stride NP * D floats
 #pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        if constexpr (KT == 4) dma_pieces4(dst + hh * KT * 1024, src + (size_t)hh * NP * D, doff, doff1, doff2, doff3);
-        else {
-#pragma unroll
-          for (int Tt = 0; Tt < KT; ++Tt) dma_piece(dst + (hh * KT + Tt) * 1024, src + (size_t)hh * NP * D + Tt * 256, doff);
-        }
-      }
+      for (int hh = 0; hh < 2; ++hh) dma_pieces4(dst + hh * KT * 1024, src + (size_t)hh * NP * D, doff, doff1, doff2, doff3);
     };
     dma_tile(kdst, Kh + (size_t)mt_of(0) * 16 * D);
     dma_tile(vdst, VT + (size_t)mt_of(0) * 16 * D);
@@ -435,62 +425,19 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
       __builtin_amdgcn_sched_barrier(0);
       // ---- S^T[m][l] = sum_k K[m][k] (d^-1/2 Q)[l][k], two heads ----
       v4f s[2];
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) s[hh] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int Tt = 0; Tt < KT; ++Tt)
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int hh = 0; hh < 2; ++hh) s[hh] = MFMA(f4get(kc[hh][Tt], u), Qr[hh][4 * Tt + u], s[hh]);
+      mfma_s<2, 2, KT>(kc, Qr, s);
       __builtin_amdgcn_sched_barrier(0);
       EGT_STAMP(0);
       // the K tiles of the next key tile: this wave was their only reader and its reads have returned (the MFMAs above consumed them)
       if (more) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); dma_tile(kdst, Kh + (size_t)mt_of(it + 1) * 16 * D); }
-      const float kav[4] = {ka4.x, ka4.y, ka4.z, ka4.w}, kgv[4] = {kg4.x, kg4.y, kg4.z, kg4.w};
+      const float4 ones = make_float4(1.f, 1.f, 1.f, 1.f);   // (no attention-mask tensor here)
       float pa_[2][4];
 #pragma unroll
       for (int hh = 0; hh < 2; ++hh) {
-        const int h = 2 * w + hh;
-        float x[4], hv4[4];
-        float tmax = KEY_OFF;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float ah = s[hh][r];
-          if (clip) ah = __builtin_amdgcn_fmed3f(ah, a.clip_lo, a.clip_hi);
-          const float hv = ah + f4get(e4[hh], r);
-          hv4[r] = hv;                                          // H_hat: post-clip, pre-mask (egt_layers.py:85-86)
-          float add = kav[r];
-          if (V == 2) {
-            const int m = PR_CLAMP(m0 + 4 * q + r);
-            const uint32_t gi = (uint32_t)((((size_t)b * N + lq) * N + m) * AH + h);
-            add += ((egt_hash32(gi, a.s0, a.s1) >> 8) < a.rm_thr) ? -EGT_NEG : 0.0f;
-          }
-          x[r] = hv + add;
-          tmax = fmaxf(tmax, x[r]);
-          const float tg = V == 1 ? exp2_fast(fmaf(f4get(g4[hh], r), -L2E, kgv[r])) : exp2_fast((f4get(g4[hh], r) + add) * -L2E);
-          pa_[hh][r] = __builtin_amdgcn_rcpf(1.0f + tg);
-        }
-        *reinterpret_cast<float4*>(Hp + (it & 1) * (AH * PT_PL) + hh * PT_PL + po4) = make_float4(hv4[0], hv4[1], hv4[2], hv4[3]);
-        tmax = pair_max_q(tmax);
-        const float mnew = fmaxf(mrun[hh], tmax);
-        const float alpha = exp2_fast((mrun[hh] - mnew) * L2E);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pexp = exp2_fast((x[r] - mnew) * L2E);
-          psum += pexp;
-          pa_[hh][r] *= pexp;
-        }
-        psum = pair_sum_q(psum);
-        lrun[hh] = fmaf(lrun[hh], alpha, psum);
-        mrun[hh] = mnew;
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt) {
-          v4f o = oacc[hh][kt];
-          o[0] *= alpha; o[1] *= alpha; o[2] *= alpha; o[3] *= alpha;
-          oacc[hh][kt] = o;
-        }
+        float hv4[4];
+        attn_fwd_unit<V, KT>(a, f, clip, true, s[hh], e4[hh], g4[hh], ones, ka4, kg4, b, lq, m0 + 4 * q, FULL ? INT_MAX : N - 1, 2 * w + hh,
+                             mrun[hh], lrun[hh], oacc[hh], pa_[hh], hv4);
+        *reinterpret_cast<float4*>(Hp + (it & 1) * (AH * PT_PL) + hh * PT_PL + po4) = make_float4(hv4[0], hv4[1], hv4[2], hv4[3]);   // H_hat: post-clip, pre-mask
       }
       __builtin_amdgcn_sched_barrier(0);
       EGT_STAMP(1);
@@ -501,12 +448,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
 #pragma unroll
         for (int Tt = 0; Tt < KT; ++Tt) vc[hh][Tt] = *reinterpret_cast<const float4*>(opl + AH * HS + hh * HS + Tt * 256);
       // ---- O^T[k][l] += sum_m V^T[k][m] P^T[m][l] ----
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-          for (int hh = 0; hh < 2; ++hh) oacc[hh][kt] = MFMA(f4get(vc[hh][kt], r), pa_[hh][r], oacc[hh][kt]);
+      mfma_pv<2, 2, KT>(vc, pa_, oacc);
       __builtin_amdgcn_sched_barrier(0);
       EGT_STAMP(2);
       if (more) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); dma_tile(vdst, VT + (size_t)mt_of(it + 1) * 16 * D); }
@@ -515,17 +457,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
     }
     // ---- finalize: O[l][k] / l_run into the K stage as [row][k][8 heads]; row statistics for the backward ----
 #pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {
-      const int h = 2 * w + hh, l = l0 + ll;
-      const float inv = 1.0f / lrun[hh];
-      float* vs = sm + (ll * D + 4 * q) * AH + h;
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) vs[(16 * kt + r) * AH] = oacc[hh][kt][r] * inv;
-      if (l < N && q == 0)
-        *reinterpret_cast<float4*>(a.rowstats + (((size_t)b * N + l) * AH + h) * 4) = make_float4(mrun[hh], lrun[hh], 0.f, 0.f);
-    }
+    for (int hh = 0; hh < 2; ++hh) attn_fwd_finalize<AH, KT>(a, sm, ll, q, 2 * w + hh, b, l0 + ll, 2 * w + hh, oacc[hh], mrun[hh], lrun[hh]);
     EGT_STAMP_OUT(ST_PAIR_FWD_ATT);
   }
   // V_att[l][k * 8 + h]: 16 rows x 512 channels, consecutive threads consecutive 16-byte pieces
@@ -557,6 +489,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_fwd(AttnMfmaArgs a, P
 //   trip it:  attention: half A (head w), half B (head w + 4)       edge: POST(it-1) + e, de' requests of it+1; PRE(it+1); row constants of it+1
 template <int D, int DE, int V, bool FULL>
 __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, PairArgs pa) {
+  static_assert(D == 64 && DE == 32, "the instantiated geometry: an operand tile is four 1 KB pieces (dma_pieces4)");
   constexpr int KT = D / 16, DH = D * AH, T = PairGeo<DE>::T, HS = KT * 256, TSZ = AH * PT_PL;
   constexpr int PSZ1 = DE * 16 + 16, PSZ2 = AH * DE + DE;
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -572,6 +505,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
   const int b = __builtin_amdgcn_readfirstlane(wg / mtiles), mt0 = __builtin_amdgcn_readfirstlane(wg % mtiles), m0 = mt0 * 16;
   const size_t arr = (size_t)a.B * AH * NP * D;
   const bool clip = (a.flags & EGT_F_CLIP) != 0;
+  const Feat<V> f(a);
   EGT_STAMP_DECL;
 
   if (wv >= 4) {
@@ -873,13 +807,8 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
         Vr[hf][Tt] = *reinterpret_cast<const float4*>(Vh + (size_t)mt0 * 16 * D + 256 * Tt + ooff);
       }
     }
-    float kadd = 0.f;
-    {
-      const int m = m0 + mm;
-      if (m >= N) kadd = KEY_OFF;
-      else if (a.km && a.km[(size_t)b * N + m] == 0) kadd = -EGT_NEG;
-    }
-    const float kaddg = (m0 + mm) < N ? -kadd * L2E : 3.0e38f;
+    float kadd, kaddg;
+    key_terms(b, m0 + mm, N, a.km != nullptr, a.km, kadd, kaddg);
     const int mc = PR_CLAMP(m0 + mm);
     v4f dKacc[2][KT], dVacc[2][KT];
 #pragma unroll
@@ -887,17 +816,9 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
 #pragma unroll
       for (int kt = 0; kt < KT; ++kt) { dKacc[hf][kt] = (v4f){0.f, 0.f, 0.f, 0.f}; dVacc[hf][kt] = (v4f){0.f, 0.f, 0.f, 0.f}; }
     const int po4 = ptT_off(4 * q, mm);   // the lane's query rows 4q..4q+3 of key mm: one 16-byte access per plane
-    // operand tiles of head slot w (Q, then dO): row form: lane (row mm, chunk q) b128; transposed: lane (channel mm, q): rows 4q + r.
-    // Tile row rho lives in LDS row rho ^ ((rho >> 2) & 1) (rows 4-7 and 12-15 swapped in pairs -- the DMA's lane -> source mapping is
-    // free): the transposed b32 reads of a 32-lane group touch rows r and 4 + r, which 16-float rows put on the same 16 banks (2-way on
-    // the 32 reads of a half-trip); swapped, row 4 + r sits in an odd-even exchanged line and the group covers 32 banks.  Step r of a lane
-    // still reads tile row 4q + r: from LDS row 4q + (r ^ (q & 1)) = 4q + r +- (q & 1) (two base addresses, no arithmetic in the loop).
-    const float* oprow = Ops + w * (2 * HS) + (mm ^ ((mm >> 2) & 1)) * 16 + ((q ^ chunk_xor(mm)) << 2);
-    const float* optr = Ops + w * (2 * HS) + (4 * q) * 16 + (((mm >> 2) ^ chunk_xor(4 * q)) << 2) + (mm & 3);
-    const float* optr_e = optr + (q & 1) * 16;   // steps 0, 2: LDS row 4q + r + (q & 1)
-    const float* optr_o = optr - (q & 1) * 16;   // steps 1, 3: LDS row 4q + r - (q & 1)
+    const BwdOperands op = bwd_operands(Ops + w * (2 * HS), mm, q);   // operand tiles of head slot w (Q, then dO), tile rows pair-swapped
     // the wave's own operand stages: stage `half` = (Q, dO) tiles of head w + 4 half; four 1 KB pieces per tile
-    const unsigned doff = dma_lane_off(lane ^ (((lane >> 4) & 1) << 2));   // LDS slot of row sigma <- source row sigma ^ ((sigma >> 2) & 1) (same chunk XOR: it depends on sigma >> 2 only)
+    const unsigned doff = dma_lane_off_swapped(lane);
     const float* Qh = uni_ptr(a.pk + PK_QH * arr + ((size_t)b * AH + w) * NP * D);
     const float* Oh = uni_ptr(a.pk + PK_OH * arr + ((size_t)b * AH + w) * NP * D);
     const unsigned odst = lds_addr(Ops) + w * (2 * HS * 4);
@@ -905,16 +826,8 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
     auto dma_half = [&](int ltile, int half) __attribute__((always_inline)) {
       const size_t ho = (size_t)half * 4 * NP * D + (size_t)ltile * 16 * D;
       const unsigned dst = odst + half * (4 * 2 * HS * 4);
-      if constexpr (KT == 4) {
-        dma_pieces4(dst, Qh + ho, doff, doff1, doff2, doff3);
-        dma_pieces4(dst + KT * 1024, Oh + ho, doff, doff1, doff2, doff3);
-      } else {
-#pragma unroll
-        for (int Tt = 0; Tt < KT; ++Tt) {
-          dma_piece(dst + Tt * 1024, Qh + ho + Tt * 256, doff);
-          dma_piece(dst + (KT + Tt) * 1024, Oh + ho + Tt * 256, doff);
-        }
-      }
+      dma_pieces4(dst, Qh + ho, doff, doff1, doff2, doff3);
+      dma_pieces4(dst + KT * 1024, Oh + ho, doff, doff1, doff2, doff3);
     };
     dma_half(0, 0);
     dma_half(0, 1);
@@ -926,9 +839,9 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
 #pragma unroll
       for (int hf = 0; hf < 2; ++hf) {
         const int h = w + 4 * hf;
-        const float* opr = oprow + hf * (4 * 2 * HS);
-        const float* opt_e = optr_e + hf * (4 * 2 * HS);
-        const float* opt_o = optr_o + hf * (4 * 2 * HS);
+        const float* opr = op.row + hf * (4 * 2 * HS);
+        const float* opt_e = op.t_e + hf * (4 * 2 * HS);
+        const float* opt_o = op.t_o + hf * (4 * 2 * HS);
         // this stage landed: requested one half-trip ago; only the other stage's pieces (and the dA store) are younger -- except in the
         // second half of the last trip, where nothing was requested after it
         if (it + 1 < mtiles || hf == 0) { if (it > 0 || hf > 0) vm_wait<2 * KT>(); } else vm_wait<0>();
@@ -946,42 +859,12 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
         for (int r = 0; r < 4; ++r) stc[r] = *reinterpret_cast<const float4*>(statL + (((it & 1) * AH + h) * 16 + 4 * q + r) * 4);
         __builtin_amdgcn_sched_barrier(0);
         // ---- S[l][m] = sum_k (d^-1/2 Q)[l][k] K[m][k] ; dP[l][m] = sum_k dO[l][k] V[m][k] ----
-        v4f s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int Tt = 0; Tt < KT; ++Tt)
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            s = MFMA(f4get(qa[Tt], u), f4get(Kr[hf][Tt], u), s);
-            dp = MFMA(f4get(oa[Tt], u), f4get(Vr[hf][Tt], u), dp);
-          }
+        v4f s, dp;
+        mfma_s_dp<1, KT>(qa, oa, Kr + hf, Vr + hf, &s, &dp);
         __builtin_amdgcn_sched_barrier(0);
         EGT_STAMP(0);
         float at[4], da[4], dE4[4], dG4[4], hh4[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float araw = s[r];
-          float ah = araw;
-          if (clip) ah = __builtin_amdgcn_fmed3f(araw, a.clip_lo, a.clip_hi);
-          float add = kadd;
-          if (V == 2) {
-            const int lq = PR_CLAMP(l0 + 4 * q + r);
-            const uint32_t gi = (uint32_t)((((size_t)b * N + lq) * N + mc) * AH + h);
-            add += ((egt_hash32(gi, a.s0, a.s1) >> 8) < a.rm_thr) ? -EGT_NEG : 0.0f;
-          }
-          const float hv = ah + f4get(e4, r);
-          const float xx = hv + add;
-          const float S = exp2_fast((xx - stc[r].x) * L2E) * stc[r].y;   // rows past N: 1/l = 0; keys past N: exp2(-inf) = 0
-          const float tg = V == 1 ? exp2_fast(fmaf(f4get(g4, r), -L2E, kaddg)) : exp2_fast((f4get(g4, r) + add) * -L2E);
-          const float g = __builtin_amdgcn_rcpf(1.0f + tg);
-          const float dAt_ = dp[r];
-          const float Sg = S * g;
-          const float dH = fmaf(S, fmaf(dAt_, g, -stc[r].z), f4get(x4, r));
-          at[r] = Sg;
-          da[r] = (clip && ah != araw) ? 0.f : dH;
-          dE4[r] = dH;
-          dG4[r] = dAt_ * Sg * (1.0f - g);
-          hh4[r] = hv;
-        }
+        attn_bwd_unit<V>(a, f, clip, true, s, dp, e4, g4, x4, stc, kadd, kaddg, b, l0 + 4 * q, mc, FULL ? INT_MAX : N - 1, h, at, da, dE4, dG4, hh4);
         *reinterpret_cast<float4*>(ps + h * PT_PL + po4) = make_float4(dE4[0], dE4[1], dE4[2], dE4[3]);
         *reinterpret_cast<float4*>(ps + TSZ + h * PT_PL + po4) = make_float4(dG4[0], dG4[1], dG4[2], dG4[3]);
         *reinterpret_cast<float4*>(ps + 2 * TSZ + h * PT_PL + po4) = make_float4(hh4[0], hh4[1], hh4[2], hh4[3]);
@@ -989,16 +872,7 @@ __global__ void __launch_bounds__(64 * PR_WAVES, 2) k_pair_bwd(AttnMfmaArgs a, P
         __builtin_amdgcn_sched_barrier(0);
         EGT_STAMP(1);
         // ---- dV^T[k][m] += sum_l dO[l][k] A[l][m] ; dK^T[k][m] += sum_l (d^-1/2 Q)[l][k] dA[l][m] ----
-#pragma unroll
-        for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float* opt = (r & 1) ? opt_o : opt_e;
-            const float qq = opt[kt * 256 + r * 16];
-            const float oo = opt[HS + kt * 256 + r * 16];
-            dVacc[hf][kt] = MFMA(oo, at[r], dVacc[hf][kt]);
-            dKacc[hf][kt] = MFMA(qq, da[r], dKacc[hf][kt]);
-          }
+        mfma_dv_dk<1, KT>(opt_e, opt_o, &at, &da, dVacc + hf, dKacc + hf);
         EGT_STAMP(2);
         // the stage is free (this wave was its only reader): the same head's tiles of the next query tile
         if (it + 1 < mtiles) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); dma_half(it + 1, hf); }

@@ -138,6 +138,7 @@ def test_in_kernel_random_mask_matches_injected(gpu, egt_lib):
 @pytest.mark.parametrize("B,N,d,opts", [
     (1, 24, 64, {}), (2, 37, 16, {}), (1, 64, 32, dict(attn_mask=True)), (1, 40, 64, dict(gate=False)),
     (2, 16, 16, dict(rand_p=0.3)), (1, 33, 64, dict(clip=None, nomask=True)), (1, 128, 64, {}),
+    (2, 21, 32, {}),   # d = 32 on the straight-line instances (V = 1): two key tiles, the second ragged
 ])
 def test_attn_mfma_kernel_vs_oracle(B, N, d, opts, gpu, egt_lib):
     """MFMA-tiled inner op (d in {16,32,64}) forward + general backward vs the fp64 oracle, and
@@ -182,7 +183,7 @@ def test_attn_mfma_kernel_vs_oracle(B, N, d, opts, gpu, egt_lib):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("N,d", [(48, 64), (37, 16)])
+@pytest.mark.parametrize("N,d", [(48, 64), (37, 16), (21, 32)])
 def test_attn_mfma_in_kernel_random_mask(N, d, gpu, egt_lib):
     """The straight-line MFMA instances with the in-kernel random-mask stream (training, no injected
     bytes): forward + backward equal the fp64 oracle fed the same mask, materialised by mask_sample."""
@@ -210,7 +211,7 @@ def test_attn_mfma_in_kernel_random_mask(N, d, gpu, egt_lib):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("N,d", [(48, 64), (37, 16)])
+@pytest.mark.parametrize("N,d", [(48, 64), (37, 16), (21, 32)])
 def test_attn_mfma_shared_workspace_fwd_to_bwd(N, d, gpu, egt_lib, monkeypatch):
     """EGT_ATTN_WS_SHARED: the forward packs the q / k / v operand copies of BOTH directions into one workspace and the backward
     adds only dO.  The autograd front-end takes that path whenever an input needs a gradient (ctx.needs_input_grad); the

@@ -97,12 +97,13 @@ def test_pair_block_equals_composed_and_is_deterministic(gpu, egt_lib):
         assert_close(ga[k], getattr(getattr(b, m), n).grad, name=k, rtol=1e-3, arel=2e-4, l2=2e-3)
 
 
-def test_pair_block_in_kernel_random_mask_vs_oracle(gpu, egt_lib):
+@pytest.mark.parametrize("B,N,nodes", [(2, 48, [48, 40]), (1, 21, [17])])
+def test_pair_block_in_kernel_random_mask_vs_oracle(B, N, nodes, gpu, egt_lib):
     """training mode: the in-kernel counter-hash mask (forward and backward draw the same sample) == the oracle fed the
-    rng_ref replica of that stream"""
+    rng_ref replica of that stream; full tiles and a ragged last tile (k_pair_fwd / k_pair_bwd<64, 32, 2, true | false>)"""
     from oracle import rng_ref
     p = 0.15
-    inp, params, c = _case(2, 48, [48, 40], seed=11, rand_p=p)
+    inp, params, c = _case(B, N, nodes, seed=11, rand_p=p)
     blk = build_block(c, ATTRS, params, gpu, "auto")
     blk.mha.random_mask_prob = p
     blk.train()
@@ -110,7 +111,7 @@ def test_pair_block_in_kernel_random_mask_vs_oracle(gpu, egt_lib):
     assert blk.last_path == "fused-pair"
     m = blk.mha
     seed = (m.seed * 0x9E3779B97F4A7C15 + m._calls * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
-    inp2 = dict(inp, rand_mask=torch.from_numpy(rng_ref.random_mask(seed, 2, 48, 8, p)))
+    inp2 = dict(inp, rand_mask=torch.from_numpy(rng_ref.random_mask(seed, B, N, 8, p)))
     ref = CS.block_oracle(inp2, params, dict(num_heads=8, **ATTRS))
     _compare(blk, out, ref)
 

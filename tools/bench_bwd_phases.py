@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """The pair kernels of the fused block, parent tree against this tree, on one GPU in one visit: the backward kernels (k_block_bwd_v4 /
-v5 / v4r) or, with --kernel k_block_fwd, the forward ones (k_block_fwd / k_block_fwd_r4).
+v5 / v4r) or, with --kernel k_block_fwd, the forward ones (k_block_fwd / k_block_fwd_r4); with --kernel k_attn_mfma / k_pair the
+d = 64, H = 8 family (k_attn_mfma_fwd + k_attn_mfma_bwd_kv / k_pair_fwd + k_pair_bwd: an entry names the kernels it records).
 
-    python tools/bench_bwd_phases.py --parent-tree PARENT [--kernel k_block_bwd|k_block_fwd] [--rounds 3] [--out profiles/bwd_phases.jsonl]
+    python tools/bench_bwd_phases.py --parent-tree PARENT [--kernel k_block_bwd|k_block_fwd|k_attn_mfma|k_pair] [--rounds 3] [--out profiles/bwd_phases.jsonl]
 
 PARENT is a built checkout of the parent commit.  Every measurement is a fresh child process under its own time limit, run in the
 tree it measures; parent and this tree alternate over the rounds.  The first child that fails ends the run (nothing more is started on
@@ -20,7 +21,13 @@ the GPU).  Cases:
   library's own launch profiler (egt_prof_*); no bench.py workload reaches these instances:
     h [128, 64, 64], De = 64 with an attention mask   k_block_bwd_v4<64, true, false, false>;  k_block_fwd<64, true, true, false, false>
     h [32, 90, 64], De = 64 without one (forward)     k_block_fwd<64, false, false, false, false>: K / V do not fit in LDS
-  Before the first round, every case's answer of egt_block_launch_form (in each tree, under the case's environment) goes into the file.
+  k_attn_mfma / k_pair: synthetic_n512 (k_attn_mfma_fwd / _bwd_kv<64, 2>), synthetic_n512_block and synthetic_n512_block_nomask
+  (k_pair_fwd / k_pair_bwd<64, 32, 2 | 1, true>); single cases on memcontract's mfma_case / pair_case at N = 69 -- five key tiles, the
+  last one ragged: the smallest N at which every part of the pair kernels' trip structure runs (peeled first trip, one unrolled group of
+  three steady forward trips / two backward ones, the remainder, the peeled last trip): k_attn_mfma_fwd / _bwd_kv<64, 1> and
+  k_pair_fwd / k_pair_bwd<64, 32, 2 | 1, false> (V = 1: the case's descriptor with random_mask_prob = 0).
+  Before the first round, every case's answer of egt_block_launch_form (in each tree, under the case's environment) goes into the file
+  (the fused block's entries only).
 Verdict per case and figure: this tree may be slower than the parent by no more than the parent's own spread (max - min over its
 rounds)."""
 import argparse
@@ -41,6 +48,15 @@ CASES = {
                ("zinc500k_n64_bf16", ["--workload", "zinc500k_n64", "--edge-dtype", "bf16"], {}, Z64B),
                ("cifar10_n150_fp32_no_narrow", ["--workload", "cifar10_n150_fp32"], {"EGT_NO_NARROW": "1"}, (128, 150, 8, 8, False))],
         single=[("mask_b128_n64_de64", MASK_ROW)]),
+    "k_attn_mfma": dict(
+        kernels=["k_attn_mfma_fwd", "k_attn_mfma_bwd_kv"], forms=False, out="attn_phases.jsonl",
+        bench=[("synthetic_n512", ["--workload", "synthetic_n512"], {}, None)],
+        single=[("mfma_b2_n69_d64", ("mfma", 2, 69, 64, False))]),
+    "k_pair": dict(
+        kernels=["k_pair_fwd", "k_pair_bwd"], forms=False, out="attn_phases.jsonl",
+        bench=[("synthetic_n512_block", ["--workload", "synthetic_n512_block"], {}, None),
+               ("synthetic_n512_block_nomask", ["--workload", "synthetic_n512_block_nomask"], {}, None)],
+        single=[("pair_b2_n69_v2", ("pair", 2, 69, 61, False, True)), ("pair_b2_n69_v1", ("pair", 2, 69, 61, False, False))]),
     "k_block_fwd": dict(
         bench=[("zinc500k_n64", ["--workload", "zinc500k_n64"], {}, Z64),
                ("zinc100k_n37", ["--workload", "zinc100k_n37"], {}, Z37),
@@ -71,21 +87,36 @@ def child_forms(kernel, env):
             print(json.dumps(dict(case=name, env=env, form=form.decode() if form else None)))
 
 
+def kernels_of(kernel):
+    return CASES[kernel].get("kernels", [kernel])      # the kernels an entry records (their launch-profiler names)
+
+
 def child_single(kernel, name, steps):
     M, L, lib = _tree_imports()
     import torch
     gpu = torch.device("cuda", 0)
-    case = M.block_case(lib, dict(CASES[kernel]["single"])[name])
-    form = lib.egt_block_launch_form(C.byref(case.claims["desc"])).decode()
+    row = dict(CASES[kernel]["single"])[name]
+    if row[0] == "mfma":
+        case, form = M.mfma_case(lib, *row[1:]), None
+    elif row[0] == "pair":
+        case, form = M.pair_case(lib, *row[1:5]), None
+        if not row[5]:
+            case.claims["desc"].random_mask_prob = 0.0      # (the steps hold the descriptor by reference) V = 1: no in-kernel random mask
+    else:
+        case = M.block_case(lib, row)
+        form = lib.egt_block_launch_form(C.byref(case.claims["desc"])).decode()
     M.run(case, M.ZERO, gpu, sync=torch.cuda.synchronize, check_rc=L.check)          # warm-up
     lib.egt_prof_filter(b""); lib.egt_prof_enable(2)
     for _ in range(steps):
         M.run(case, M.ZERO, gpu, sync=torch.cuda.synchronize, check_rc=L.check)
     lib.egt_prof_enable(0)
-    cnt, ms = C.c_int64(0), C.c_double(0.0)
-    lib.egt_prof_read(kernel.encode(), C.byref(cnt), C.byref(ms))
-    assert cnt.value == steps, cnt.value
-    print(json.dumps({"form": form, "launches": cnt.value, kernel + "_us": ms.value / cnt.value * 1e3}))
+    rec = {"form": form, "launches": steps}
+    for k in kernels_of(kernel):
+        cnt, ms = C.c_int64(0), C.c_double(0.0)
+        lib.egt_prof_read(k.encode(), C.byref(cnt), C.byref(ms))
+        assert cnt.value == steps, (k, cnt.value)
+        rec[k + "_us"] = ms.value / cnt.value * 1e3
+    print(json.dumps(rec))
 
 
 def main():
@@ -96,7 +127,9 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--mask-steps", type=int, default=8)
-    ap.add_argument("--out", default=None, help="default: profiles/bwd_phases.jsonl, profiles/fwd_phases.jsonl for k_block_fwd")
+    ap.add_argument("--out", default=None, help="default: profiles/bwd_phases.jsonl, profiles/fwd_phases.jsonl for k_block_fwd, "
+                                                "profiles/attn_phases.jsonl for k_attn_mfma and k_pair")
+    ap.add_argument("--append", action="store_true", help="add to the file (a second entry of the same visit)")
     ap.add_argument("--child-timeout", type=int, default=240)
     ap.add_argument("--child-single", default=None, help="(internal) the single-block case this child runs")
     ap.add_argument("--child-forms", default=None, help="(internal) print the launch form of every case of this environment (JSON)")
@@ -105,8 +138,8 @@ def main():
         return child_forms(args.kernel, json.loads(args.child_forms))
     if args.child_single:
         return child_single(args.kernel, args.child_single, args.mask_steps)
-    kfig, cases = args.kernel + "_us", CASES[args.kernel]
-    args.out = args.out or os.path.join(REPO, "profiles", ("fwd" if args.kernel == "k_block_fwd" else "bwd") + "_phases.jsonl")
+    kfigs, cases = [k + "_us" for k in kernels_of(args.kernel)], CASES[args.kernel]
+    args.out = args.out or os.path.join(REPO, "profiles", cases.get("out", ("fwd" if args.kernel == "k_block_fwd" else "bwd") + "_phases.jsonl"))
     trees = ([(os.path.abspath(args.parent_tree), "parent")] if args.parent_tree else []) + [(REPO, "this")]
     recs = []
 
@@ -119,8 +152,9 @@ def main():
             raise SystemExit(f"{name} ({tag}, round {rnd}): child exit status {r.returncode}; nothing more is run")
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
         if "roofline" in d:
-            rec = {kfig: d["roofline"]["kernels"][args.kernel]["avg_us"], "ms_per_step": d["ms_per_step"],
-                   "median_ms_per_step": d.get("median_ms_per_step"), "step_mode": (d.get("config") or {}).get("step_mode")}
+            rec = {k + "_us": d["roofline"]["kernels"][k]["avg_us"] for k in kernels_of(args.kernel)}
+            rec.update({"ms_per_step": d["ms_per_step"], "median_ms_per_step": d.get("median_ms_per_step"),
+                        "step_mode": (d.get("config") or {}).get("step_mode")})
         else:
             rec = d
         rec = dict(case=name, tree=tag, round=rnd, env=env_extra, **rec)
@@ -129,7 +163,7 @@ def main():
 
     me = os.path.abspath(__file__)
     envs = [json.loads(x) for x in dict.fromkeys(json.dumps(e, sort_keys=True) for _, _, e, _ in cases["bench"])]
-    for tree, tag in trees:
+    for tree, tag in trees if cases.get("forms", True) else []:
         for e in envs + ([] if {} in envs else [{}]):
             env = dict(os.environ, **e)
             env.pop("EGT_AMD_LIB", None)
@@ -152,7 +186,7 @@ def main():
     ok, runs = True, [r for r in recs if "round" in r]
     if args.parent_tree:
         for name in dict.fromkeys(r["case"] for r in runs):
-            for fig in (kfig, "ms_per_step"):
+            for fig in kfigs + ["ms_per_step"]:
                 par = [r[fig] for r in runs if r["case"] == name and r["tree"] == "parent" and fig in r]
                 new = [r[fig] for r in runs if r["case"] == name and r["tree"] == "this" and fig in r]
                 if not par:
@@ -166,7 +200,7 @@ def main():
                 recs.append(v)
                 print(json.dumps(v), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
+    with open(args.out, "a" if args.append else "w") as f:
         for r in recs:
             f.write(json.dumps(r) + "\n")
     sys.exit(0 if ok else 1)

@@ -2,7 +2,7 @@
 """A sha256 per output tensor of single ops, over the cases of their GPU tests, for comparing two builds of the library bit by bit.
 One process loads one library: run it once per build (each run under its own time limit, chained with &&) and diff the listings.
 
-    python tools/op_bits.py [--ops head,embed,block,ffn] [--lib path/to/libegt_amd.so] > listing.txt      (--lib: the EGT_AMD_LIB of this process)
+    python tools/op_bits.py [--ops head,embed,block,ffn,attn,pair] [--lib path/to/libegt_amd.so] > listing.txt      (--lib: the EGT_AMD_LIB of this process)
     python tools/op_bits.py --condense listing.txt      (the listing in one line per case: a sha256 over the case's lines; for keeping a comparison's result)
 
 head:  the fused edge head and node head over the cases of tests/test_distance_head_gpu.py and tests/test_node_head_gpu.py (their
@@ -19,7 +19,15 @@ block: one forward and backward of the fused block / stack through the C ABI: h'
 ffn:   the channel FFN: y, dx and the six parameter gradients over every (W, matmul, shape, act) of the parametrisations of
        tests/test_ffn_gpu.py (fp32 storage, the tests' seeds), CASES of tests/test_bf16_edges_gpu.py with bf16 storage, and the
        several-tiles-per-wave cases; then, on the cases of test_ffn_bwd_on_a_fresh_workspace_equals_the_prepared_one, egt_ffn_bwd
-       on a fresh workspace (flags = 0: it prepares its own operands) next to the autograd path's prepared one."""
+       on a fresh workspace (flags = 0: it prepares its own operands) next to the autograd path's prepared one.
+attn:  the MFMA inner op (d in {16, 32, 64}) forward and backward through the C ABI: v_att, h_hat, rowstats, d_qkv, d_E, d_G over the
+       mfma_cases of tests/memcontract.py and the shapes, options and inputs (the tests' seeds) of test_attn_mfma_kernel_vs_oracle,
+       test_attn_mfma_in_kernel_random_mask and test_attn_mfma_shared_workspace_fwd_to_bwd (tests/test_attn_gpu.py).  The instance
+       choice is read once per process: run it again under EGT_ATTN_GENERIC=1 (the main configuration on the V = 0 instances).
+pair:  the fused pair operator forward and backward through the C ABI: v_att, e_out, rowstats, d_qkv, d_e and the eight parameter
+       gradients over the pair_cases of tests/memcontract.py and, in its format, the shapes of
+       test_pair_block_in_kernel_random_mask_vs_oracle (tests/test_pair_gpu.py), each with the in-kernel random mask (V = 2) and with
+       random_mask_prob = 0 (V = 1)."""
 import argparse
 import hashlib
 import itertools
@@ -187,6 +195,73 @@ def ffn(gpu):
         emit(tag.replace("ffn_prepared", "ffn_fresh"), [("dx", dx)] + [("d " + n, g) for n, g in zip(TF.NAMES, grads)])
 
 
+def attn(gpu):
+    import ctypes as C
+    import torch
+    import memcontract as M
+    import test_attn_gpu as TA
+    from egt_amd import _lib as L
+    from egt_amd.functional import AttnConfig, _attn_desc
+    lib, H = L.load(), 8
+    for case in M.mfma_cases(lib):
+        emit(f"attn {case.name}", sorted(M.run(case, M.ZERO, gpu, sync=torch.cuda.synchronize, check_rc=L.check).items()))
+
+    def run(tag, B, N, d, seed, opts, masked, cfg):
+        g = torch.Generator().manual_seed(seed)          # the draws in the tests' order
+        r = lambda *s: torch.randn(*s, generator=g)
+        QKV, E = r(B, N, 3 * d * H) * 0.7, r(B, N, N, H)
+        G = r(B, N, N, H) if opts.get("gate", True) else None
+        km = None
+        if not opts.get("nomask"):
+            km = torch.ones(B, N, dtype=torch.uint8); km[masked[0], N - masked[1]:] = 0
+        Mt = (torch.rand(B, N, N, generator=g) > 0.4).float()[..., None].repeat(1, 1, 1, H).contiguous() if opts.get("attn_mask") else None
+        rm = (torch.rand(B, N, N, H, generator=g) < opts["rand_p"]).to(torch.uint8) if opts.get("rand_p") else None
+        dV, dH = r(B, N, d * H), r(B, N, N, H)
+        cu = lambda t: None if t is None else t.to(gpu)
+        QKV, E, G, km, Mt, rm, dV, dH = map(cu, (QKV, E, G, km, Mt, rm, dV, dH))
+        desc = _attn_desc(cfg, B, N, d, True, G is not None, Mt is not None)
+        desc.reserved = L.ATTN_WS_SHARED
+        p = C.byref(desc)
+        new = lambda *s: torch.zeros(*s, device=gpu)
+        v_att, h_hat, rowstats, d_qkv, d_E = new(B, N, d * H), new(B, N, N, H), new(B, N, H, 4), new(B, N, 3 * d * H), new(B, N, N, H)
+        d_G = new(B, N, N, H) if G is not None else None
+        ws = torch.zeros(lib.egt_attn_mfma_workspace_bytes(p), dtype=torch.uint8, device=gpu)
+        common = [L.ptr(t) for t in (QKV, E, G, km, Mt, rm)]
+        L.check(lib.egt_attn_mfma_fwd(p, *common, L.ptr(v_att), L.ptr(h_hat), L.ptr(rowstats), L.ptr(ws), L.current_stream()))
+        L.check(lib.egt_attn_mfma_bwd(p, *common, L.ptr(v_att), L.ptr(rowstats), L.ptr(dV), L.ptr(dH), L.ptr(d_qkv), L.ptr(d_E), L.ptr(d_G),
+                                      L.ptr(ws), L.current_stream()))
+        torch.cuda.synchronize()
+        emit(tag, [(n, t) for n, t in (("v_att", v_att), ("h_hat", h_hat), ("rowstats", rowstats), ("d_qkv", d_qkv), ("d_E", d_E), ("d_G", d_G))
+                   if t is not None])
+
+    for B, N, d, opts in params_of(TA.test_attn_mfma_kernel_vs_oracle, "B,N,d,opts"):
+        cfg = AttnConfig(num_heads=H, clip_logits_value=opts.get("clip", (-5.0, 5.0)), random_mask_prob=0.5 if opts.get("rand_p") else 0.0,
+                         training=bool(opts.get("rand_p")), need_a_tild=False)
+        run(f"attn vs_oracle B{B}-N{N}-d{d}-{'-'.join(f'{k}={v}' for k, v in opts.items()) or 'main'}", B, N, d, B * 100 + N + d, opts, (0, 5), cfg)
+    for N, d in params_of(TA.test_attn_mfma_in_kernel_random_mask, "N,d"):
+        run(f"attn in_kernel_random_mask N{N}-d{d}", 2, N, d, N + d, {}, (1, 7),
+            AttnConfig(num_heads=H, random_mask_prob=0.25, training=True, seed=4242, need_a_tild=False))
+    for N, d in params_of(TA.test_attn_mfma_shared_workspace_fwd_to_bwd, "N,d"):
+        run(f"attn shared_workspace N{N}-d{d}", 2, N, d, N * 3 + d, {}, (1, 7), AttnConfig(num_heads=H, need_a_tild=False))
+
+
+def pair(gpu):
+    import torch
+    import memcontract as M
+    import test_pair_gpu as TP
+    from egt_amd import _lib as L
+    lib = L.load()
+    cases = [(c, 2) for c in M.pair_cases(lib)]
+    for B, N, nodes in params_of(TP.test_pair_block_in_kernel_random_mask_vs_oracle, "B,N,nodes"):
+        for v in (2, 1):
+            case = M.pair_case(lib, B, N, nodes[-1], True)
+            if v == 1:
+                case.claims["desc"].random_mask_prob = 0.0      # (the steps hold the descriptor by reference) no in-kernel random mask
+            cases.append((case, v))
+    for case, v in cases:
+        emit(f"pair {case.name} V{v}", sorted(M.run(case, M.ZERO, gpu, sync=torch.cuda.synchronize, check_rc=L.check).items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lib", default=None)
@@ -196,14 +271,14 @@ def main():
     if args.condense:
         return condense(args.condense)
     ops = args.ops.split(",")
-    if not ops or set(ops) - {"head", "embed", "block", "ffn"}:
-        ap.error("--ops takes head, embed, block, ffn or several of them")
+    if not ops or set(ops) - {"head", "embed", "block", "ffn", "attn", "pair"}:
+        ap.error("--ops takes head, embed, block, ffn, attn, pair or several of them")
     if args.lib:
         os.environ["EGT_AMD_LIB"] = os.path.abspath(args.lib)      # read when egt_amd._lib is imported
     sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
     import torch
     gpu = torch.device("cuda", 0)
-    for op, fn in (("head", head), ("embed", embed), ("block", block), ("ffn", ffn)):
+    for op, fn in (("head", head), ("embed", embed), ("block", block), ("ffn", ffn), ("attn", attn), ("pair", pair)):
         if op in ops:
             fn(gpu)
 
