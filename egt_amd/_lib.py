@@ -147,6 +147,29 @@ class OptimSegment(C.Structure):
     _fields_ = [("param", C.c_void_p), ("offset", C.c_int64), ("count", C.c_int64)]
 
 
+BATCH_NONE, BATCH_I32, BATCH_F32 = 0, 1, 2                     # egt_batch_desc.node_kind / edge_kind
+BATCH_PE_NONE, BATCH_PE_SVD, BATCH_PE_EIGEN = 0, 1, 2           # egt_batch_desc.pe_kind
+BATCH_TGT_GRAPH_F32, BATCH_TGT_GRAPH_I32, BATCH_TGT_NODE_I32 = 0, 1, 2   # egt_batch_desc.target_kind
+BATCH_MARK_INVALID = 0x1                                        # egt_batch_desc.flags
+BATCH_STORE_FIELDS = ("num_nodes", "node_off", "edge_off", "row_off", "edge_dst", "edge_feat", "node_rows", "pe_rows", "targets")
+BATCH_OUT_FIELDS = ("graph_matrix", "feature_matrix", "node_features", "pe", "target", "num_nodes")
+
+
+class BatchDesc(C.Structure):
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("records", C.c_int32), ("node_kind", C.c_int32), ("node_width", C.c_int32),
+                ("edge_kind", C.c_int32), ("edge_width", C.c_int32), ("pe_kind", C.c_int32), ("pe_features", C.c_int32),
+                ("target_kind", C.c_int32), ("flags", C.c_uint32), ("matrix_pad", C.c_float), ("mask_f", C.c_float),
+                ("mask_i", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class BatchStore(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in BATCH_STORE_FIELDS]
+
+
+class BatchOut(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in BATCH_OUT_FIELDS]
+
+
 def params_struct(cls, fields, tensors):
     """A parameter struct of the C-ABI (`cls`, its `fields` in order) filled with the tensors' device pointers (None -> NULL)."""
     st = cls()
@@ -250,6 +273,8 @@ _PROTOS = {
     "egt_optim_supported": (C.c_int, [C.POINTER(OptimDesc)]),
     "egt_optim_prepare": (C.c_int, [C.POINTER(OptimDesc), _VP, _VP]),
     "egt_optim_step": (C.c_int, [C.POINTER(OptimDesc)] + [_VP] * 6),
+    "egt_batch_supported": (C.c_int, [C.POINTER(BatchDesc)]),
+    "egt_batch_assemble": (C.c_int, [C.POINTER(BatchDesc), C.POINTER(BatchStore), _VP, C.POINTER(BatchOut), _VP]),
 }
 
 

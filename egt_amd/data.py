@@ -401,12 +401,27 @@ class GraphDataset:
         self._excluded |= set(names)
 
     # ---- records --------------------------------------------------------------------------------
-    def _load_record(self, token: str) -> dict:
+    def _raw_record(self, token: str) -> dict:
+        """the record's fields as the store holds them (what level 'records' returns)"""
         sp = self.spec
         vals = self.store.read_record(token, [f.key for f in sp.fields])
         rec = {"record_name": token.encode()}
         for f, v in zip(sp.fields, vals):
             rec[f.name] = np.asarray(v, dtype=f.dtype).reshape([d if d is not None else -1 for d in f.shape])
+        return rec
+
+    def _pe_features(self, rec: dict, n: int, graph_matrix) -> dict:
+        """the level's positional encoding of one record ({} at level 'matrix'): ONE text for the host path and pack_split"""
+        if self.level == "svd":
+            sv, s = svd_features(graph_matrix, self.num_features, self.mult_sing_vals, self.norm_for_svd, self.norm_sym_for_svd)
+            return dict(singular_vectors=sv, singular_values=s)
+        if self.level == "eigen":
+            return dict(eigen_vectors=eigen_features(rec["edges"], n, self.num_features, self.sparse))
+        return {}
+
+    def _load_record(self, token: str) -> dict:
+        sp = self.spec
+        rec = self._raw_record(token)
         if self.level == "records":
             return rec
         n = int(rec["num_nodes"])
@@ -417,11 +432,7 @@ class GraphDataset:
         if sp.fm_tail is not None:
             kw = dict(increment_by_1=True, decrement_by_1=True) if self.mark_invalid_features else {}
             rec["feature_matrix"] = get_graph_matrix(rec["edges"], n, rec["edge_features"], **kw)
-        if self.level == "svd":
-            rec["singular_vectors"], rec["singular_values"] = svd_features(
-                rec["graph_matrix"], self.num_features, self.mult_sing_vals, self.norm_for_svd, self.norm_sym_for_svd)
-        elif self.level == "eigen":
-            rec["eigen_vectors"] = eigen_features(rec["edges"], n, self.num_features, self.sparse)
+        rec.update(self._pe_features(rec, n, rec["graph_matrix"]))
         for k in self._dropped:
             rec.pop(k, None)
         return rec
@@ -440,14 +451,14 @@ class GraphDataset:
         r = c[token]
         return {k: v for k, v in r.items() if k not in self._excluded} if self._excluded else r
 
-    def iter_records(self, split: str, shuffle: Optional[bool] = None) -> Iterator[dict]:
-        """one epoch of records: tokens reshuffled per epoch, then the bounded shuffle buffer"""
+    def iter_tokens(self, split: str, shuffle: Optional[bool] = None) -> Iterator[str]:
+        """one epoch of record tokens: reshuffled per epoch, then the bounded shuffle buffer (the order both the host and
+        the device-resident path batch in)"""
         self.load_data()
         toks = list(self.record_tokens[split])
         shuffle = (split in self.shuffle_splits) if shuffle is None else shuffle
         if not shuffle:
-            for t in toks:
-                yield self.record(split, t)
+            yield from toks
             return
         self._rng.shuffle(toks)
         buf_len = max(1, min(len(toks), self.max_shuffle_len))
@@ -458,11 +469,22 @@ class GraphDataset:
                 continue
             j = int(self._rng.integers(len(buf)))
             out, buf[j] = buf[j], t
-            yield self.record(split, out)
+            yield out
         while buf:
             j = int(self._rng.integers(len(buf)))
             buf[j], buf[-1] = buf[-1], buf[j]
-            yield self.record(split, buf.pop())
+            yield buf.pop()
+
+    def iter_records(self, split: str, shuffle: Optional[bool] = None) -> Iterator[dict]:
+        """one epoch of records, in the order of iter_tokens"""
+        for t in self.iter_tokens(split, shuffle):
+            yield self.record(split, t)
+
+    def to_device(self, device):
+        """the same dataset with every split's packed records resident on `device` and the padded batches assembled there
+        (egt_amd.device_data.DeviceGraphDataset): same batches, same epoch order for the same seed"""
+        from .device_data import DeviceGraphDataset
+        return DeviceGraphDataset(self, device)
 
     # ---- batches --------------------------------------------------------------------------------
     def collate(self, recs: List[dict]) -> dict:

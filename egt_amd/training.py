@@ -97,6 +97,8 @@ def default_config(scheme: str = "zinc.svd") -> Config:
                                  # bf16 in HBM: BASELINE config 3); handed to the model by get_model, not part of model_config
         fused_optimizer=False,   # (not a reference key) the parameter update as two launches over the flat gradient buffer:
                                  # egt_amd.optim.FlatOptimizer (same arithmetic and checkpoints as torch.optim); needs a GPU
+        device_dataset=False,    # (not a reference key) the dataset's packed records resident on the GPU, padded batches assembled
+                                 # there: egt_amd.device_data (same batches and epoch order as the host pipeline); needs a GPU
     )
     c.update(  # BaseDCModelScheme
         model_name="dc", dataset_name="dataset",
@@ -445,6 +447,7 @@ class ZincSVDScheme:
             raise ValueError("config.use_hipgraph needs the model on a GPU (device='cuda')")
         if self._fused_opt and not on_gpu:
             raise ValueError("config.fused_optimizer needs the model on a GPU (device='cuda')")
+        self._device_dataset_check()
         if self._use_graph or self._fused_opt or (self.config.distributed and torch.distributed.is_available() and torch.distributed.is_initialized()):
             from .dp import FlatGradAllReduce
             self.flat = FlatGradAllReduce(params, direct=True)     # one flat-buffer all-reduce per step (MirroredStrategy, :230-247)
@@ -542,6 +545,11 @@ class ZincSVDScheme:
         _barrier()
 
     # ---- data ----
+    def _device_dataset_check(self):
+        on_gpu = self.device is not None and torch.device(self.device).type == "cuda"
+        if self.config.device_dataset and not on_gpu:
+            raise ValueError("config.device_dataset needs the model on a GPU (device='cuda')")
+
     def load_data(self, trainset: Iterable = None, valset: Iterable = None, testset: Iterable = None,
                   splits=("training", "validation")):
         """:207-218.  Iterables of batches in the reference's input format are used as they are (SyntheticZinc ...);
@@ -571,7 +579,12 @@ class ZincSVDScheme:
             # batch_size * prediction_bmult; a training run batches every split at batch_size
             mult = c.prediction_bmult if (getattr(self, "eval_flag", False) or getattr(self, "pred_flag", False)) else 1
             bs = {sp: c.batch_size * mult for sp in splits}
-            out = self.dataset.get_batched_data(bs, shard=shard)
+            source = self.dataset
+            if c.device_dataset:          # every split's packed records on the GPU; the batches are assembled there
+                self._device_dataset_check()
+                source = self.device_dataset = self.dataset.to_device(self.device)
+                self.print(f"DEVICE DATASET: {', '.join(splits)} resident on {self.device}: {source.nbytes} bytes")
+            out = source.get_batched_data(bs, shard=shard)
             out = out if isinstance(out, tuple) else (out,)
             trainset, valset, testset = (list(out) + [None, None])[:3]
         self.trainset, self.valset, self.testset = trainset, valset, testset

@@ -701,6 +701,74 @@ int egt_optim_prepare(const egt_optim_desc* desc, void* state, void* stream);
 int egt_optim_step(const egt_optim_desc* desc, const egt_optim_segment* table /* device */, float* grad, float* m, float* v,
                    void* state, void* stream);
 
+/* ---- device-resident datasets: the padded tensors of a batch from a split's packed records ----
+ * What egt_amd.data.GraphDataset (collate + the per-record maps; lib/data/graph.py:4-42, dataset_base.py:100-130) builds on
+ * the host, bit for bit, from records that live in device memory: only the B record indices `idx` change per batch.
+ * Store (all const, device; egt_amd.device_data.pack_split writes it).  Record r has n = num_nodes[r] nodes whose rows start
+ * at node_off[r], and edge_off[r+1] - edge_off[r] edges starting at edge_off[r], STABLY sorted by source row, so the
+ * duplicates of one (i,j) keep the order of the edge list:
+ *   num_nodes [R] int32;  node_off [R+1] int64;  edge_off [R+1] int64
+ *   row_off   [node_off[R] + R] int32: entries node_off[r] + r + i, i = 0..n: first edge of row i, relative to edge_off[r]
+ *   edge_dst  [E] int32 (0 <= dst < n);  edge_feat [E] int32 / fp32 (edge_kind)
+ *   node_rows [node_off[R], node_width] int32 / fp32 (node_kind);  pe_rows [node_off[R], F, 2] (SVD) / [node_off[R], F] (EIGEN) fp32
+ *   targets   [R] fp32 (TGT_GRAPH_F32: the output is [B,1]) / [R] int32 (TGT_GRAPH_I32) / [node_off[R]] int32 (TGT_NODE_I32)
+ * Outputs (device, 16-byte aligned, exactly these element counts; NULL = not asked for and not written):
+ *   graph_matrix   [B,N,N] fp32: inside n x n the count of (i,j) in the edge list + 1 on the diagonal; matrix_pad outside
+ *   feature_matrix [B,N,N] int32 / fp32: inside n x n (sum over the (i,j) duplicates, in edge-list order, of (feat + m)) - m
+ *                  starting from 0, m = 1 under EGT_BATCH_MARK_INVALID else 0; mask_i / mask_f outside
+ *   node_features  [B,N,node_width]: the record's rows, then mask_i / mask_f;   pe [B,N,F,2] / [B,N,F]: rows, then 0
+ *   target         [B] words, or [B,N] int32: rows, then 0;   num_nodes [B] int32
+ * Every element of every requested output is written exactly once per call and nothing is read back: the result does not
+ * depend on what the outputs held.  No output may overlap the store, idx or another output.  Only records idx[b] of the store
+ * are read; an idx[b] outside [0, R) gives an empty graph (all padding, num_nodes 0, target 0).  N must be >= every n of the
+ * batch (rows beyond N would be dropped).  No workspace, no host synchronisation, no atomics; capturable.
+ * Covered: 1 <= N <= 512, B N N < 2^31, node / PE rows of at most 64 words, one value per edge. */
+#define EGT_BATCH_NONE 0
+#define EGT_BATCH_I32 1
+#define EGT_BATCH_F32 2
+#define EGT_BATCH_PE_NONE 0
+#define EGT_BATCH_PE_SVD 1   /* rows of [F,2] floats */
+#define EGT_BATCH_PE_EIGEN 2 /* rows of [F] floats */
+#define EGT_BATCH_TGT_GRAPH_F32 0
+#define EGT_BATCH_TGT_GRAPH_I32 1
+#define EGT_BATCH_TGT_NODE_I32 2
+#define EGT_BATCH_MARK_INVALID 0x1u /* feature_matrix: feat + 1 summed, - 1 at the end (non-edges become -1) */
+typedef struct egt_batch_desc {
+  int32_t B, N;
+  int32_t records;                /* R */
+  int32_t node_kind, node_width;  /* EGT_BATCH_I32 (width 1) or EGT_BATCH_F32 */
+  int32_t edge_kind, edge_width;  /* EGT_BATCH_NONE (width 0), _I32 or _F32 (width 1) */
+  int32_t pe_kind, pe_features;   /* EGT_BATCH_PE_*; F (0 without) */
+  int32_t target_kind;            /* EGT_BATCH_TGT_* */
+  uint32_t flags;                 /* EGT_BATCH_MARK_INVALID */
+  float matrix_pad;               /* graph_matrix outside n x n */
+  float mask_f;                   /* fp32 node rows / feature_matrix outside the graph */
+  int32_t mask_i;                 /* int32 node rows / feature_matrix outside the graph */
+  int32_t reserved[2];            /* 0 */
+} egt_batch_desc;
+typedef struct egt_batch_store {
+  const int32_t* num_nodes;
+  const int64_t* node_off;
+  const int64_t* edge_off;
+  const int32_t* row_off;
+  const int32_t* edge_dst;
+  const void* edge_feat;
+  const void* node_rows;
+  const float* pe_rows;
+  const void* targets;
+} egt_batch_store;
+typedef struct egt_batch_out {
+  float* graph_matrix;
+  void* feature_matrix;
+  void* node_features;
+  float* pe;
+  void* target;
+  int32_t* num_nodes;
+} egt_batch_out;
+int egt_batch_supported(const egt_batch_desc* desc);
+int egt_batch_assemble(const egt_batch_desc* desc, const egt_batch_store* store, const int32_t* idx /* device, [B] */,
+                       const egt_batch_out* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
