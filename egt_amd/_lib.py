@@ -257,6 +257,7 @@ _PROTOS = {
                       + [C.POINTER(BlockParams)] + [_VP] * 2),
     "egt_stack_saved_bytes": (C.c_size_t, [C.POINTER(BlockDesc), C.c_int32]),
     "egt_stack_workspace_bytes": (C.c_size_t, [C.POINTER(BlockDesc), C.c_int32]),
+    "egt_stack_tail_form": (C.c_char_p, [C.POINTER(BlockDesc), C.c_int32]),
     "egt_stack_fwd": (C.c_int, [C.POINTER(BlockDesc), C.c_int32, C.POINTER(BlockParams)] + [_VP] * 9),
     "egt_stack_bwd": (C.c_int, [C.POINTER(BlockDesc), C.c_int32, C.POINTER(BlockParams)] + [_VP] * 9
                       + [C.POINTER(BlockParams)] + [_VP] * 2),

@@ -110,3 +110,8 @@ int egt_node_wgrad_chunks(int rows, int layers);   // row chunks (= partial slot
 void egt_node_launch_prep(BlockArgs* as, int n, hipStream_t st);   // n <= 64 layers
 bool egt_node_launch_pre_stack(BlockArgs* as, int n, hipStream_t st);   // layer 0's k_node_pre + the preparation of all n layers in one launch
 void egt_node_launch_reduce(BlockArgs* as, int n, int nwg_bwd, int EP, hipStream_t st);
+// the launch plane of the backward tail, as the launchers above compute it (egt_stack_tail_form reads these)
+int egt_node_wgrad_rows(int rows, int layers);     // node rows per workgroup of the k_node_wgrads launch
+int egt_node_reduce_launches(int n);               // k_sum_segments launches of n layers
+int egt_node_edge_grad_launches(int n);            // k_edge_param_grads launches of n layers
+int egt_node_pre_stack_slots(int n);               // layer slots of the k_node_pre_stack instance that takes n layers (0: k_edge_prep instead)

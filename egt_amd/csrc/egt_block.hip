@@ -557,6 +557,21 @@ extern "C" size_t egt_block_workspace_bytes(const egt_block_desc* d) { return ch
 extern "C" size_t egt_stack_saved_bytes(const egt_block_desc* d, int32_t layers) { return chain_bytes(d, layers, true, false); }
 extern "C" size_t egt_stack_workspace_bytes(const egt_block_desc* d, int32_t layers) { return chain_bytes(d, layers, true, true); }
 
+// The launch plane of egt_stack_bwd's tail for `d` and `layers` (no mask tensor), as text:
+// "wgrad=<rows per workgroup>r/<chunks>c partials=<edge-parameter partials> reduce=<k_sum_segments launches>
+//  epg=<k_edge_param_grads launches> prep=<stack16|stack40|edge_prep>", e.g. "wgrad=160r/27c partials=384 reduce=2 epg=1 prep=stack16".
+// Every figure comes from the function the launch itself calls.  Thread-local string; NULL when the call is not covered.
+extern "C" const char* egt_stack_tail_form(const egt_block_desc* d, int32_t layers) {
+  if (stack_flags_check(d, false) || block_check(d, false) || layers < 1 || layers > 64) return nullptr;
+  const BlockPlan P = plan_block(d, mask_tensor(d, nullptr));
+  const int rows = d->B * d->N, slots = egt_node_pre_stack_slots(layers);
+  static thread_local char buf[128];
+  snprintf(buf, sizeof buf, "wgrad=%dr/%dc partials=%d reduce=%d epg=%d prep=%s", egt_node_wgrad_rows(rows, layers),
+           egt_node_wgrad_chunks(rows, layers), P.nwg_bwd, egt_node_reduce_launches(layers), egt_node_edge_grad_launches(layers),
+           slots == 16 ? "stack16" : slots == 40 ? "stack40" : "edge_prep");
+  return buf;
+}
+
 // the saved / workspace regions of layer l
 static void bind_layer(const StackLayout& S, const BlockPlan& P, int l, BlockArgs& a, float* saved, float* ws) {
   float* bs = saved + S.blk + P.saved_total * (size_t)l;

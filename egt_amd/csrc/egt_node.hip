@@ -790,7 +790,8 @@ __global__ void __launch_bounds__(512, 4) k_node_wgrads(WGradArgs wa) {
 
 // ------------------------------------------------------------ final reduce -----
 struct SumSeg { const float* src; float* dst; int n, np, stride, blk0; };   // blk0: first workgroup of the segment in the flat grid
-#define SUM_MAX_SEG 77  // 11 layers x 7 segments: fits the 4 KiB kernel-argument block
+#define SUM_MAX_LAYERS 11
+#define SUM_MAX_SEG (7 * SUM_MAX_LAYERS)  // 11 layers x 7 segments = 77: fits the 4 KiB kernel-argument block
 struct SumArgs { SumSeg seg[SUM_MAX_SEG]; int nseg; };
 
 // 32 outputs per workgroup, the partial axis split over SUM_G groups of 32 lanes, SUM_U loads in flight per lane and ONE wait per
@@ -943,12 +944,14 @@ static void launch_pre_stack(BlockArgs* as, int n, size_t lds, hipStream_t st) {
   EGT_MAX_LDS_ONCE(k_node_pre_stack<NL>);
   EGT_LAUNCH("k_node_pre", k_node_pre_stack<NL>, dim3(as[0].B * node_chunks(as[0]) + n), dim3(512), lds, st, as[0], pa);
 }
+int egt_node_pre_stack_slots(int n) { return n <= 16 ? 16 : n <= 40 ? 40 : 0; }
 bool egt_node_launch_pre_stack(BlockArgs* as, int n, hipStream_t st) {
-  if (n > 40) return false;
+  const int slots = egt_node_pre_stack_slots(n);
+  if (!slots) return false;
   const BlockArgs& a = as[0];
   size_t lds = lds_rows(a.Dh, 1) + (size_t)a.Dh * (3 * a.Dh + LDP) * 4;
   if (lds < 1024) lds = 1024;  // prep workgroup scratch
-  if (n <= 16) launch_pre_stack<16>(as, n, lds, st);
+  if (slots == 16) launch_pre_stack<16>(as, n, lds, st);
   else launch_pre_stack<40>(as, n, lds, st);
   return true;
 }
@@ -996,6 +999,7 @@ static int wgrad_rows_per_wg(int rows, int layers) {
   const int r = (((rows + per_layer - 1) / per_layer + 31) / 32) * 32;
   return r < WG_ROWS ? WG_ROWS : r;
 }
+int egt_node_wgrad_rows(int rows, int layers) { return wgrad_rows_per_wg(rows, layers); }
 int egt_node_wgrad_chunks(int rows, int layers) { const int r = wgrad_rows_per_wg(rows, layers); return (rows + r - 1) / r; }
 
 // deferred GEMM-shaped weight gradients of `n` layers (n <= 64) in one launch
@@ -1030,9 +1034,11 @@ void egt_node_launch_prep(BlockArgs* as, int n, hipStream_t st) {
 
 // Reduce the per-workgroup partials of `n` layers (one BlockArgs each, with their own
 // spart / sbo / wpart / epart / ered and gradient pointers) and finish the edge-parameter gradients.
+int egt_node_reduce_launches(int n) { return (n + SUM_MAX_LAYERS - 1) / SUM_MAX_LAYERS; }
+int egt_node_edge_grad_launches(int n) { return (n + EPG_MAX_LAYERS - 1) / EPG_MAX_LAYERS; }
 void egt_node_launch_reduce(BlockArgs* as, int n, int nwg_bwd, int EP, hipStream_t st) {
-  for (int l0 = 0; l0 < n; l0 += 11) {
-    const int nl = (n - l0 < 11) ? (n - l0) : 11;
+  for (int l0 = 0; l0 < n; l0 += SUM_MAX_LAYERS) {
+    const int nl = (n - l0 < SUM_MAX_LAYERS) ? (n - l0) : SUM_MAX_LAYERS;
     SumArgs s{};
     int nblk = 0, k = 0;
     auto seg = [&](const float* src, float* dst, int cnt, int npart, int stride) {

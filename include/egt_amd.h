@@ -350,6 +350,13 @@ int egt_block_bwd(const egt_block_desc* desc, const egt_block_params* params,
  * the counter hash seeded with desc->seed ^ 0x9E3779B97F4A7C15*(l+1). */
 size_t egt_stack_saved_bytes(const egt_block_desc* desc, int32_t layers);
 size_t egt_stack_workspace_bytes(const egt_block_desc* desc, int32_t layers);
+/* The launch plane of egt_stack_bwd's three closing launches for `desc` and `layers` (no mask tensor), as text:
+ * "wgrad=<rows per workgroup>r/<row chunks>c partials=<edge-parameter partials> reduce=<reduction launches>
+ *  epg=<edge-parameter-gradient launches> prep=<stack16|stack40|edge_prep>", e.g.
+ * "wgrad=160r/27c partials=384 reduce=2 epg=1 prep=stack16" (prep: how the forward prepares the edge weights).
+ * A read-only query computed by the functions the launches call; it needs no device.  Thread-local string, valid until
+ * the thread's next call; NULL when the call is not covered (1 <= layers <= 64).  For tests and bench lines. */
+const char* egt_stack_tail_form(const egt_block_desc* desc, int32_t layers);
 int egt_stack_fwd(const egt_block_desc* desc, int32_t layers,
                   const egt_block_params* params, const void* h, const void* e,
                   const uint8_t* key_mask, const void* attn_mask, void* h_out,

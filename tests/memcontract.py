@@ -311,6 +311,13 @@ STACK_TABLE = [
     ("stack_n21_de16", 2, 21, 8, 16, False, "", "k_block_fwd_r4/4w", "k_block_bwd_v4r/4w/tl4"),
     ("stack_n37_d6_de48", 3, 37, 6, 48, False, "", "k_block_fwd/4w", "k_block_bwd_v5/4w/tl4"),
 ]
+# (row, layers): two shapes of tests/stack_tail.py's table (the 128-graph row: 27 five-step weight-gradient chunks and 384 edge
+# partials per layer; the C ABI's 64-layer limit: six-step chunks, 176 partials, 6 + 4 closing launches) -- the backward tail's
+# partial slots in the guarded workspace.  Run by tests/test_stack_tail_gpu.py (runs Z and P); stack_cases() keeps STACK_TABLE.
+STACK_TAIL_TABLE = [
+    (("tail_b128_n33_de8_ly16", 128, 33, 8, 8, False, "", "k_narrow_fwd/4w", "k_narrow_bwd/4w/tl11"), 16),
+    (("tail_b44_n30_de16_ly64", 44, 30, 8, 16, False, "", "k_block_fwd_r4/4w", "k_block_bwd_v4r/4w/tl8"), 64),
+]
 # what the union of the two tables must reach (the issue's list)
 REQUIRED_FORMS = {"fwd": {"k_narrow_fwd/4w", "k_narrow_fwd/8w", "k_narrow_fwd/8w/half", "k_block_fwd_r4/4w", "k_block_fwd_r4/8w",
                           "k_block_fwd"},
