@@ -9,6 +9,7 @@ Public surface (mirrors the reference's operator interface for this path):
     distance_target, DistanceHead                (egt_amd.head: the distance objective of the *_spe_do configs)
     node_head_loss, node_head_composed           (egt_amd.node_head: readout + class-weighted loss of PATTERN / CLUSTER)
     graph_head_loss, graph_head_composed         (egt_amd.graph_head: graph-level readout + loss of ZINC / CIFAR10 / MNIST)
+    node_embed.node_embed, node_embed_composed   (egt_amd.node_embed: node features -> the stack's h and mask, every model)
     FlatOptimizer, plan_items                    (egt_amd.optim: Adam / RMSprop / SGD as two launches over the flat gradient buffer)
     DeviceSeeds, GraphedStep                     (egt_amd.graph: hipGraph capture of a step, device-resident mask seeds)
 """
@@ -20,6 +21,7 @@ from .model import (ZincDCTransformer, PatternDCTransformer, Cifar10DCTransforme
 from .head import distance_target, DistanceHead, distance_head, distance_head_composed  # noqa: F401
 from .node_head import node_head_loss, node_head_composed, node_head_supported  # noqa: F401
 from .graph_head import graph_head_loss, graph_head_composed, graph_head_supported  # noqa: F401
+from .node_embed import node_embed_composed, node_embed_supported  # noqa: F401  (node_embed itself stays in its module: the name is the module's)
 from .graph import DeviceSeeds, GraphedStep  # noqa: F401
 from .optim import FlatOptimizer, plan_items, flat_to_state, state_to_flat  # noqa: F401
 from .masks import node_mask_from_features, node_mask_from_masking, constrained_edge_mask  # noqa: F401
@@ -31,4 +33,5 @@ __all__ = ["EGT", "EGTBlock", "EGTStack", "EGTLayerStack", "custom_layers", "Att
            "distance_target", "DistanceHead", "distance_head", "distance_head_composed",
            "node_head_loss", "node_head_composed", "node_head_supported",
            "graph_head_loss", "graph_head_composed", "graph_head_supported",
+           "node_embed_composed", "node_embed_supported",
            "FlatOptimizer", "plan_items", "flat_to_state", "state_to_flat"]

@@ -133,6 +133,24 @@ class GraphHeadDesc(C.Structure):   # (its parameter / gradient structs are Node
                 ("ln_eps", C.c_float), ("reserved", C.c_int32)]
 
 
+NE_INT, NE_FLOAT = 0, 1                       # egt_node_embed_desc.kind
+NE_PE_NONE, NE_PE_SVD, NE_PE_EIG = 0, 1, 2    # egt_node_embed_desc.pe_kind
+NE_TRANSFORM, NE_SIGNS = 0x1, 0x2             # egt_node_embed_desc.flags
+
+
+class NodeEmbedDesc(C.Structure):
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("Dh", C.c_int32), ("nv", C.c_int32), ("kind", C.c_int32), ("R", C.c_int32),
+                ("F", C.c_int32), ("pe_kind", C.c_int32), ("T", C.c_int32), ("sel", C.c_int32), ("flags", C.c_int32),
+                ("mask_value", C.c_float), ("sign_stride", C.c_int32), ("reserved", C.c_int32)]
+
+
+NODE_EMBED_PARAM_FIELDS = ("node_emb", "node_emb_bias", "pe_kernel", "pe_bias", "virtual_node_emb")
+
+
+class NodeEmbedParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in NODE_EMBED_PARAM_FIELDS]
+
+
 OPT_ADAM, OPT_RMSPROP, OPT_SGD = 0, 1, 2     # egt_optim_desc.algo
 OPT_CLIP, OPT_ZERO_GRAD = 0x1, 0x2            # egt_optim_desc.flags
 OPTIM_STATE_BYTES = 64                        # EGT_OPTIM_STATE_BYTES
@@ -234,6 +252,10 @@ _PROTOS = {
     "egt_graph_head_fwd": (C.c_int, [C.POINTER(GraphHeadDesc), C.POINTER(NodeHeadParams)] + [_VP] * 7),
     "egt_graph_head_bwd": (C.c_int, [C.POINTER(GraphHeadDesc), C.POINTER(NodeHeadParams)] + [_VP] * 5
                            + [C.POINTER(NodeHeadParams)] + [_VP] * 2),
+    "egt_node_embed_supported": (C.c_int, [C.POINTER(NodeEmbedDesc)]),
+    "egt_node_embed_workspace_bytes": (C.c_size_t, [C.POINTER(NodeEmbedDesc)]),
+    "egt_node_embed_fwd": (C.c_int, [C.POINTER(NodeEmbedDesc), C.POINTER(NodeEmbedParams)] + [_VP] * 6),
+    "egt_node_embed_bwd": (C.c_int, [C.POINTER(NodeEmbedDesc)] + [_VP] * 4 + [C.POINTER(NodeEmbedParams)] + [_VP] * 2),
     "egt_dp_unique_id": (C.c_int, [_VP]),
     "egt_dp_init": (C.c_int, [_VP, C.c_int32, C.c_int32]),
     "egt_dp_allreduce": (C.c_int, [_VP, C.c_size_t, C.c_int32, _VP]),

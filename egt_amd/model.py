@@ -6,11 +6,12 @@
 
 Pair-sized work runs in the HIP kernels through the C-ABI: the edge-channel input embedding
 (egt_edge_embed_fwd/bwd: hop stacking + adj_emb + fm_emb), every attention block (egt_block_*) and
-every channel FFN (egt_ffn_*), the node mask producer (egt_node_mask_from_features).  Node-sized
-[B,N,Dh] pieces (embedding lookup, final LayerNorm, masked mean pooling, the MLP head, the loss) are
-torch ops -- except the training step of the node-classification models, whose readout + loss is one fused op
-(classification_loss -> egt_amd.node_head).  num_virtual_nodes > 0 (ZINC / CIFAR10): the embedding kernel writes e with its border of
-virtual edge embeddings (egt_edge_embed_vn_fwd/bwd), the virtual node rows join h as a torch cat, the readout takes them.  Parameters carry the reference's Keras variable names (keras_named_parameters) so a
+every channel FFN (egt_ffn_*), the node mask producer (egt_node_mask_from_features).  The node input
+(embedding lookup or Masking + Dense, SVD / eigenvector encoding, virtual rows, node mask) is one fused op (`inputs` ->
+egt_amd.node_embed: egt_node_embed_fwd/bwd), and so are the readout + loss of a training step (graph_loss -> egt_amd.graph_head,
+classification_loss -> egt_amd.node_head); each has its composed torch route for CPU tensors and uncovered geometries.
+num_virtual_nodes > 0 (ZINC / CIFAR10): the embedding kernel writes e with its border of
+virtual edge embeddings (egt_edge_embed_vn_fwd/bwd), the node-input kernel puts the virtual node rows in front of h, the readout takes them.  Parameters carry the reference's Keras variable names (keras_named_parameters) so a
 weight file of the reference loads unchanged.
 
 Reference (relative to /root/reference/): lib/models/zinc/dc.py:17-120,
@@ -245,31 +246,24 @@ class ZincDCTransformer(nn.Module):
         """h + the SVD / eigenvector embedding of the batch.  Training applies the reference's random sign flip
         (RandomNeg / RandomNegEig, misc.py:53-94): one sign per (graph, feature), drawn on the device unless `pe_signs`
         ([B,1,F,1] for SVD, [B,1,F] for eigenvectors) injects the sample."""
+        from .node_embed import positional_composed
         c = self.cfg
+        draw = bool(c["random_neg"] and self.training)
+        signs = pe_signs if draw else None
         if c["use_svd"]:
             if singular_vectors is None:
                 raise ValueError("use_svd=True: the batch must carry singular_vectors [B,N,num_svd_features,2]")
-            v = singular_vectors.to(h.dtype)[:, :, :c["sel_svd_features"], :]
-            if not c["transform_svd"]:
-                v = F.pad(v, (0, 0, 0, max(0, c["model_width"] // 2 - c["sel_svd_features"])))
-            if c["random_neg"] and self.training:
-                sg = pe_signs if pe_signs is not None else \
-                    torch.where(torch.rand(v.shape[0], 1, v.shape[2], 1, device=v.device) < 0.5, -1.0, 1.0)
-                v = v * sg.to(v.dtype)
-            v = torch.cat(torch.unbind(v, dim=-1), dim=-1)
-            h = h + (self.svd_emb(v) if c["transform_svd"] else v)
+            h = positional_composed(h, singular_vectors, "svd", c["sel_svd_features"], c["transform_svd"], self._pe_dense(), signs, draw)
         if c["use_eig"]:
             if eigen_vectors is None:
                 raise ValueError("use_eig=True: the batch must carry eigen_vectors [B,N,num_eig_features]")
-            v = eigen_vectors.to(h.dtype)[:, :, :c["sel_eig_features"]]
-            if not c["transform_eig"]:
-                v = F.pad(v, (0, max(0, c["model_width"] - c["sel_eig_features"])))
-            if c["random_neg"] and self.training:
-                sg = pe_signs if pe_signs is not None else \
-                    torch.where(torch.rand(v.shape[0], 1, v.shape[2], device=v.device) < 0.5, -1.0, 1.0)
-                v = v * sg.to(v.dtype)
-            h = h + (self.eig_emb(v) if c["transform_eig"] else v)
+            h = positional_composed(h, eigen_vectors, "eig", c["sel_eig_features"], c["transform_eig"], self._pe_dense(), signs, draw)
         return h
+
+    def _pe_dense(self):
+        """(kernel, bias) of svd_emb / eig_emb, None where the encoding is added without a Dense"""
+        m = getattr(self, "svd_emb", None) or getattr(self, "eig_emb", None)
+        return None if m is None else (m.kernel, m.bias)
 
     def edge_mask(self, graph_matrix, attn_mask):
         """'constrained' edge channels: M = the adjacency tiled over the heads (AdjMatModel.get_edge_mask,
@@ -285,7 +279,8 @@ class ZincDCTransformer(nn.Module):
         encodings were added to the real nodes (VNModel.combine_node_embeddings, graph_model_base.py:227-235)"""
         if not self.num_virtual_nodes:
             return h
-        return torch.cat([self.virtual_node_emb.to(h.dtype)[None].expand(h.shape[0], -1, -1), h], dim=1)
+        from .node_embed import virtual_rows_composed
+        return virtual_rows_composed(h, self.virtual_node_emb)
 
     def graph_readout(self, h, mask):
         """[B,N',Dh] -> [B, .]: the virtual nodes' rows flattened (GetVirtualNodes -> Flatten, zinc/dc.py:105-108), or the
@@ -344,14 +339,74 @@ class ZincDCTransformer(nn.Module):
     def _virtual_edge_table(self):
         return self.virtual_edge_emb if self.num_virtual_nodes else None
 
-    def embeddings(self, node_features, feature_matrix, graph_matrix):
-        """h [B,N,Dh] (real nodes: the virtual ones join after the positional encodings), e and mask with the virtual nodes"""
+    def _node_embedding(self, node_features):
+        """h [B,N,Dh] of the real nodes and the mask [B,nv+N] from the composed ops"""
         mask = node_mask_from_features(node_features, self.num_virtual_nodes)           # masking.py:42-43, virtual_nodes.py:47-50
         h = F.embedding((node_features + 1).long(), self.node_emb)                      # zinc/dc.py:66-69
-        e = edge_embed(feature_matrix, graph_matrix, self.fm_emb, self.adj_emb.kernel, self.adj_emb.bias,
-                       clip_hops=self.cfg["clip_hops"], edge_dtype=self._edge_key(),   # :70-73 + graph_model_base.py:97-127
-                       virtual_edge_table=self._virtual_edge_table())
-        return h, e, mask
+        return h, mask
+
+    def _edge_embedding(self, feature_matrix, graph_matrix):
+        return edge_embed(feature_matrix, graph_matrix, self.fm_emb, self.adj_emb.kernel, self.adj_emb.bias,
+                          clip_hops=self.cfg["clip_hops"], edge_dtype=self._edge_key(),   # :70-73 + graph_model_base.py:97-127
+                          virtual_edge_table=self._virtual_edge_table())
+
+    def embeddings(self, node_features, feature_matrix, graph_matrix):
+        """h [B,N,Dh] (real nodes: the virtual ones join after the positional encodings), e and mask with the virtual nodes"""
+        h, mask = self._node_embedding(node_features)
+        return h, self._edge_embedding(feature_matrix, graph_matrix), mask
+
+    def _node_params(self):
+        """(node_emb, node_emb_bias) as egt_amd.node_embed takes them"""
+        return self.node_emb, None
+
+    def _fused_node_input(self, node_features, singular_vectors=None, eigen_vectors=None, pe_signs=None):
+        """(h [B,nv+N,Dh], mask [B,nv+N]) from the fused op (egt_amd.node_embed), or None where it does not apply: the tensors
+        are fp32 on the GPU, the library covers the geometry (egt_node_embed_supported) and EGT_NO_NODE_EMBED is not set.  The
+        sign sample of the random flip is drawn here with the expression `positional` uses, so a seeded run sees the same
+        stream."""
+        from .node_embed import draw_pe_signs, node_embed, node_embed_disabled, node_embed_supported
+        c, nv = self.cfg, self.num_virtual_nodes
+        kind = "svd" if c["use_svd"] else ("eig" if c["use_eig"] else None)
+        pe = singular_vectors if kind == "svd" else (eigen_vectors if kind == "eig" else None)
+        sel, transform = (c[f"sel_{kind}_features"], c[f"transform_{kind}"]) if kind else (0, False)
+        emb, emb_bias = self._node_params()
+        Dh = emb.shape[1]
+        is_float = node_features.dtype.is_floating_point
+        if not node_features.is_cuda or emb.dtype != torch.float32 or node_features.dim() != (3 if is_float else 2) \
+                or node_embed_disabled():
+            return None
+        if kind is not None and not (pe is not None and pe.is_cuda and pe.dim() == (4 if kind == "svd" else 3) and
+                                     (kind != "svd" or pe.shape[3] == 2) and pe.shape[:2] == node_features.shape[:2]):
+            return None
+        B, N = node_features.shape[:2]
+        if not node_embed_supported(B, N, Dh, nv, 0 if is_float else emb.shape[0], node_features.shape[2] if is_float else 0,
+                                    kind, pe.shape[2] if kind else 0, sel, transform):
+            return None
+        signs = None
+        if kind is not None and c["random_neg"] and self.training:
+            width = sel if transform else max(sel, Dh // 2 if kind == "svd" else Dh)      # (the untransformed encoding is zero-padded first)
+            signs = pe_signs if pe_signs is not None else \
+                draw_pe_signs((B, 1, width, 1) if kind == "svd" else (B, 1, width), node_features.device)
+        return node_embed(node_features, emb, emb_bias, pe, kind, sel, self._pe_dense() if transform else None, signs,
+                          self.virtual_node_emb if nv else None, getattr(self, "mask_value", -1.0))
+
+    def node_input(self, node_features, singular_vectors=None, eigen_vectors=None, pe_signs=None):
+        """(h [B,nv+N,Dh], mask [B,nv+N]): the node embedding, the positional encoding and the virtual rows -- ONE op where
+        `_fused_node_input` applies, the composed ops otherwise"""
+        out = self._fused_node_input(node_features, singular_vectors, eigen_vectors, pe_signs)
+        if out is None:
+            h, mask = self._node_embedding(node_features)
+            out = self.with_virtual_nodes(self.positional(h, singular_vectors, eigen_vectors, pe_signs)), mask
+        return out
+
+    def inputs(self, node_features, feature_matrix, graph_matrix, singular_vectors=None, eigen_vectors=None, pe_signs=None):
+        """(h [B,nv+N,Dh], e, mask) as they enter the layer stack: `node_input` and the edge embedding; where the fused node op
+        does not apply, `embeddings` -> `positional` -> `with_virtual_nodes` as before"""
+        out = self._fused_node_input(node_features, singular_vectors, eigen_vectors, pe_signs)
+        if out is None:
+            h, e, mask = self.embeddings(node_features, feature_matrix, graph_matrix)
+            return self.with_virtual_nodes(self.positional(h, singular_vectors, eigen_vectors, pe_signs)), e, mask
+        return out[0], self._edge_embedding(feature_matrix, graph_matrix), out[1]
 
     def distance_aux(self, e, graph_matrix):
         """{"distance_loss": per_graph [B]}: the distance objective on the final edge channels (graph_model_base.py:66-94)"""
@@ -365,8 +420,7 @@ class ZincDCTransformer(nn.Module):
 
     def forward(self, node_features, feature_matrix, graph_matrix, attn_mask=None, singular_vectors=None,
                 eigen_vectors=None, pe_signs=None, return_aux=False):
-        h, e, mask = self.embeddings(node_features, feature_matrix, graph_matrix)
-        h = self.with_virtual_nodes(self.positional(h, singular_vectors, eigen_vectors, pe_signs))
+        h, e, mask = self.inputs(node_features, feature_matrix, graph_matrix, singular_vectors, eigen_vectors, pe_signs)
         h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask),
                            skip_last_edge_ffn=self.dist_head is None)                   # :336-341
         if self.node_norm_final is not None:
@@ -405,8 +459,7 @@ class ZincDCTransformer(nn.Module):
         [sum |y - t|, 0, B C] (GRAPH_LOSS 'mae') or [sum CE, sum [argmax == t], B] ('xent'), loss = stats[0] / stats[2] (the
         Keras batch mean), pred [B,C] what `forward` returns (no gradient), aux as `forward(return_aux=True)` returns it."""
         from .graph_head import graph_head_composed, graph_head_loss
-        h, e, mask = self.embeddings(node_features, feature_matrix, graph_matrix)
-        h = self.with_virtual_nodes(self.positional(h, singular_vectors, eigen_vectors, pe_signs))
+        h, e, mask = self.inputs(node_features, feature_matrix, graph_matrix, singular_vectors, eigen_vectors, pe_signs)
         h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask), skip_last_edge_ffn=self.dist_head is None)
         head = graph_head_loss if self.graph_head_fused(h) else graph_head_composed
         stats, pred = head(h, target, mask, self.graph_head_params(), self.GRAPH_LOSS, self.num_virtual_nodes,
@@ -451,8 +504,7 @@ class PatternDCTransformer(ZincDCTransformer):
     def forward(self, node_features, graph_matrix, attn_mask=None, return_mask=False, singular_vectors=None,
                 eigen_vectors=None, pe_signs=None, return_aux=False):
         fmat = torch.full(graph_matrix.shape, -1, dtype=torch.int32, device=graph_matrix.device)
-        h, e, mask = self.embeddings(node_features, fmat, graph_matrix)
-        h = self.positional(h, singular_vectors, eigen_vectors, pe_signs)
+        h, e, mask = self.inputs(node_features, fmat, graph_matrix, singular_vectors, eigen_vectors, pe_signs)
         h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask), skip_last_edge_ffn=self.dist_head is None)
         if self.node_norm_final is not None:
             h = self.node_norm_final(h)
@@ -489,8 +541,7 @@ class PatternDCTransformer(ZincDCTransformer):
         counts the padded slots: weighted_sparse_xent_loss), aux as `forward(return_aux=True)` returns it."""
         from .node_head import node_head_composed, node_head_loss
         fmat = torch.full(graph_matrix.shape, -1, dtype=torch.int32, device=graph_matrix.device)
-        h, e, mask = self.embeddings(node_features, fmat, graph_matrix)
-        h = self.positional(h, singular_vectors, eigen_vectors, pe_signs)
+        h, e, mask = self.inputs(node_features, fmat, graph_matrix, singular_vectors, eigen_vectors, pe_signs)
         h, e = self.layers(h, e, mask, self.edge_mask(graph_matrix, attn_mask), skip_last_edge_ffn=self.dist_head is None)
         head = node_head_loss if self.node_head_fused(h) else node_head_composed
         stats = head(h, target, mask, class_weights, self.head_params(), self.cfg["activation"])
@@ -533,18 +584,23 @@ class Cifar10DCTransformer(ZincDCTransformer):
                     "edge_emb/kernel": self.edge_emb.kernel, "edge_emb/bias": self.edge_emb.bias})
         return out
 
-    def embeddings(self, node_features, feature_matrix, graph_matrix):
+    def _node_embedding(self, node_features):
         from .masks import node_mask_from_masking
         nv = self.num_virtual_nodes
         mask = node_mask_from_masking(node_features, self.mask_value, nv)               # keras Masking, cifar10/dc.py:68
         h = self.node_emb(node_features * mask[:, nv:, None].to(node_features.dtype))   # Masking zeroes the padded rows
+        return h, mask
+
+    def _edge_embedding(self, feature_matrix, graph_matrix):
         fmat = torch.full(graph_matrix.shape, -1, dtype=torch.int32, device=graph_matrix.device)
-        e = edge_embed(fmat, graph_matrix, self.fm_emb, self.adj_emb.kernel, self.adj_emb.bias,
-                       clip_hops=self.cfg["clip_hops"], float_features=feature_matrix, float_kernel=self.edge_emb.kernel,
-                       float_bias=self.edge_emb.bias, mask_value=self.mask_value,
-                       edge_dtype=self._edge_key(),                                     # :71-73 + graph_model_base.py:97-127
-                       virtual_edge_table=self._virtual_edge_table())
-        return h, e, mask
+        return edge_embed(fmat, graph_matrix, self.fm_emb, self.adj_emb.kernel, self.adj_emb.bias,
+                          clip_hops=self.cfg["clip_hops"], float_features=feature_matrix, float_kernel=self.edge_emb.kernel,
+                          float_bias=self.edge_emb.bias, mask_value=self.mask_value,
+                          edge_dtype=self._edge_key(),                                  # :71-73 + graph_model_base.py:97-127
+                          virtual_edge_table=self._virtual_edge_table())
+
+    def _node_params(self):
+        return self.node_emb.kernel, self.node_emb.bias
 
 
 class MnistDCTransformer(Cifar10DCTransformer):

@@ -625,6 +625,68 @@ int egt_graph_head_bwd(const egt_graph_head_desc* desc, const egt_node_head_para
                        const void* target, const uint8_t* mask, const float* d_loss /* device, [1] */, float* d_h,
                        const egt_node_head_params* grads, void* workspace, void* stream);
 
+/* ---- node-input embedding: from a batch's node features to the stack's h and mask ----
+ * One launch writes h_out [B,nv+N,Dh] fp32 and mask_out [B,nv+N] uint8 (1 = real node):
+ *   rows 0..nv-1 : virtual_node_emb [nv,Dh], mask 1                          lib/base/graph_layers/virtual_nodes.py:31-50
+ *   row nv+n     : base + encoding
+ *     EGT_NE_INT    base = node_emb[features[b,n] + 1]    features [B,N] int32, padding -1 -> row 0 (an ordinary trainable
+ *                   row), mask = features != -1; node_emb [R,Dh]             lib/base/xformer_layers/masking.py:31-43
+ *     EGT_NE_FLOAT  base = (x m) node_emb + node_emb_bias, m = any_f(x[f] != mask_value): keras Masking + Dense, mask = m;
+ *                   features [B,N,F] fp32, node_emb [F,Dh]                   lib/models/cifar10/dc.py:66-69
+ *     EGT_NE_PE_SVD pe [B,N,T,2]: x = (s_0 u_0 .. s_{sel-1} u_{sel-1}, s_0 v_0 .. s_{sel-1} v_{sel-1}) from the first sel of the T
+ *                   stored pairs (u = pe[..,k,0], v = pe[..,k,1]); under EGT_NE_TRANSFORM the encoding is x pe_kernel + pe_bias
+ *                   (pe_kernel [2 sel, Dh]), otherwise u is added to channels 0..sel-1 and v to Dh/2..Dh/2+sel-1
+ *     EGT_NE_PE_EIG pe [B,N,T]: x = (s_0 w_0 .. s_{sel-1} w_{sel-1}); x pe_kernel + pe_bias (pe_kernel [sel, Dh]) under
+ *                   EGT_NE_TRANSFORM, otherwise added to channels 0..sel-1   lib/models/graph_model_base.py:284-414
+ *   signs (EGT_NE_SIGNS): s_k = signs[b * sign_stride + k], the caller's sample of the training-time sign flip (+-1 floats,
+ *   lib/base/genutil/misc.py:53-94); without the flag every s_k is 1 and `signs` may be NULL.  The library draws nothing.
+ * The backward takes d_h [B,nv+N,Dh] and writes, through `grads` (the same struct), the gradients of node_emb, node_emb_bias
+ * (float kind), pe_kernel / pe_bias (EGT_NE_TRANSFORM) and virtual_node_emb (nv > 0); pointers the geometry does not use are
+ * never touched and may be NULL.  The sums run over ALL B N rows, padded rows included (a Dense bias gradient counts them; a
+ * padded integer row adds to table row 0), as autograd of the composed ops gives.  There are no input gradients.  It needs no
+ * parameter values.  Per-workgroup partials in `workspace` (egt_node_embed_workspace_bytes; scratch) and a fixed-order
+ * finish launch: no atomics, two calls on the same inputs give the same bits.  Parameters and gradient sinks need 4-byte
+ * alignment only (16-byte accesses are used where a pointer allows them); h_out, d_h likewise.  features, pe, signs and d_h are
+ * const; every element of h_out, mask_out and of each used sink is written exactly once per call.
+ * Covered: Dh in {16,32,48,64}, 1 <= R <= 32, 1 <= F <= 8, 1 <= sel <= 32 with T >= sel, 2 sel <= Dh (SVD) / sel <= Dh (EIG)
+ * without EGT_NE_TRANSFORM, 0 <= nv <= 16, any N >= 1, B >= 1 with B (nv+N) 64 < 2^31. */
+#define EGT_NE_INT 0
+#define EGT_NE_FLOAT 1
+#define EGT_NE_PE_NONE 0
+#define EGT_NE_PE_SVD 1
+#define EGT_NE_PE_EIG 2
+#define EGT_NE_TRANSFORM 0x1 /* the encoding goes through its Dense (pe_kernel, pe_bias) */
+#define EGT_NE_SIGNS 0x2     /* `signs` holds the sign sample */
+typedef struct egt_node_embed_desc {
+  int32_t B, N, Dh;
+  int32_t nv;          /* virtual nodes in front of every graph's N nodes */
+  int32_t kind;        /* EGT_NE_INT or EGT_NE_FLOAT */
+  int32_t R;           /* EGT_NE_INT: rows of node_emb (num_node_features + 1); 0 otherwise */
+  int32_t F;           /* EGT_NE_FLOAT: feature columns; 0 otherwise */
+  int32_t pe_kind;     /* EGT_NE_PE_* */
+  int32_t T;           /* stored pairs / eigenvector entries per node (the stride of pe); 0 without an encoding */
+  int32_t sel;         /* how many of them are used */
+  int32_t flags;       /* EGT_NE_TRANSFORM | EGT_NE_SIGNS */
+  float mask_value;    /* EGT_NE_FLOAT: keras Masking's value */
+  int32_t sign_stride; /* floats between two graphs' signs; 0 = sel */
+  int32_t reserved;    /* 0 */
+} egt_node_embed_desc;
+
+typedef struct egt_node_embed_params {
+  void* node_emb;         /* [R, Dh] table / [F, Dh] Dense kernel */
+  void* node_emb_bias;    /* [Dh], EGT_NE_FLOAT */
+  void* pe_kernel;        /* [2 sel, Dh] (SVD) / [sel, Dh] (EIG), EGT_NE_TRANSFORM */
+  void* pe_bias;          /* [Dh], EGT_NE_TRANSFORM */
+  void* virtual_node_emb; /* [nv, Dh], nv > 0 */
+} egt_node_embed_params;
+
+int egt_node_embed_supported(const egt_node_embed_desc* desc);
+size_t egt_node_embed_workspace_bytes(const egt_node_embed_desc* desc);
+int egt_node_embed_fwd(const egt_node_embed_desc* desc, const egt_node_embed_params* params, const void* features,
+                       const float* pe, const float* signs, float* h_out, uint8_t* mask_out, void* stream);
+int egt_node_embed_bwd(const egt_node_embed_desc* desc, const void* features, const float* pe, const float* signs,
+                       const float* d_h, const egt_node_embed_params* grads, void* workspace, void* stream);
+
 /* ---- batch data parallelism: the gradient all-reduce on RCCL -------------------
  * Replaces what tf.distribute.MirroredStrategy does for the reference
  * (lib/training/training_base.py:230-247): one synchronous all-reduce of every
