@@ -100,6 +100,14 @@ size_t egt_narrow_bwd_lds(int nw);
 void egt_narrow_launch_fwd(BlockArgs& a, int nw, bool half, const EgtLaunch& s, hipStream_t st);   // half: eight-row workgroups (nw = 8)
 void egt_narrow_launch_bwd(BlockArgs& a, int nw, const EgtLaunch& s, hipStream_t st);   // same a.pro / partial-buffer contract as k_block_bwd_v4r
 
+// Degree-scaler instances (EGT_BF_SCALE_DEGREE) of the MFMA-tile pair kernels: egt_block_sd.hip, launched in the shape plan_block
+// chose.  r4_waves: 4 | 8 = k_block_fwd_r4 with that many waves, 0 = k_block_fwd {kvl, ml, full}; family: EGT_SD_BWD_*.
+constexpr int V4R_RR = 2;   // k_block_bwd_v4r: rows per iteration (four spill: the rows' carried state + prefetch exceed 256 VGPRs)
+#define EGT_SD_BWD_V4R 1
+#define EGT_SD_BWD_V5 2
+#define EGT_SD_BWD_V4 3
+void egt_block_sd_launch_fwd(BlockArgs& a, int r4_waves, bool kvl, bool ml, bool full, const EgtLaunch& s, hipStream_t st);
+void egt_block_sd_launch_bwd(BlockArgs& a, int family, int mm, bool ml, bool full, const EgtLaunch& s, hipStream_t st);
 
 // launchers implemented in egt_node.hip
 void egt_node_launch_pre(BlockArgs& a, hipStream_t st);

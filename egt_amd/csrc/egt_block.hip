@@ -110,6 +110,13 @@ static int block_check(const egt_block_desc* d, bool report) {
     if (d->De != 8) EGT_BAD(EGT_E_SHAPE, "EGT_BF_STATIC_EDGE covers edge_width 8 (got %d)", d->De);
     if (block_env().no_narrow_fwd || block_env().no_narrow_bwd) EGT_BAD(EGT_E_FLAGS, "EGT_BF_STATIC_EDGE needs the De = 8 pair kernels (EGT_NO_NARROW* is set)");
   }
+  if ((d->flags & EGT_BF_SCALER_LINEAR) && !(d->flags & EGT_BF_SCALE_DEGREE))
+    EGT_BAD(EGT_E_FLAGS, "EGT_BF_SCALER_LINEAR is only valid together with EGT_BF_SCALE_DEGREE");
+  if (d->flags & EGT_BF_SCALE_DEGREE) {   // degree scalers: the SD instances of the MFMA-tile kernels (egt_block_sd.hip)
+    if (!(d->flags & EGT_BF_GATE)) EGT_BAD(EGT_E_FLAGS, "EGT_BF_SCALE_DEGREE needs EGT_BF_GATE (scale_degree only works with gate_attention)");
+    if (d->flags & EGT_BF_STATIC_EDGE) EGT_BAD(EGT_E_FLAGS, "EGT_BF_SCALE_DEGREE does not take EGT_BF_STATIC_EDGE");
+    if (d->dtype == EGT_BF16) EGT_BAD(EGT_E_DTYPE, "EGT_BF_SCALE_DEGREE with bf16 edge tensors is not covered (fp32 edge tensors only)");
+  }
   return EGT_OK;
 }
 
@@ -125,9 +132,9 @@ static size_t al(size_t x) { return (x + 63) & ~(size_t)63; }  // in floats
 enum class FwdKernel { narrow, r4, tile };      // k_narrow_fwd {NW, half rows} | k_block_fwd_r4 {NW} | k_block_fwd {KVL, ML, FULL}
 enum class BwdKernel { narrow, v4r, v5, v4 };   // k_narrow_bwd {NW} | k_block_bwd_v4r | k_block_bwd_v5 {MM} | k_block_bwd_v4 {ML}
 static const char* const g_bwd_kernel_name[] = {"k_narrow_bwd", "k_block_bwd_v4r", "k_block_bwd_v5", "k_block_bwd_v4"};
-constexpr int V4R_RR = 2;   // k_block_bwd_v4r: rows per iteration (four spill: the rows' carried state + prefetch exceed 256 VGPRs)
 
 struct BlockPlan {
+  bool sd;     // EGT_BF_SCALE_DEGREE: the SD instances (egt_block_sd.hip) of the MFMA-tile kernels; never the De = 8 VALU kernels
   bool ml;     // a mask TENSOR is read: the attention mask or a host random-mask buffer (the in-kernel random mask is not one)
   bool full;   // N is a multiple of 16 (else the kernels' ragged forms)
   FwdKernel fwd;
@@ -157,8 +164,10 @@ static BlockPlan plan_for(const egt_block_desc* d, bool ml) {
   const EgtBlockEnv& E = block_env();
   const int B = d->B, N = d->N, cus = egt_device_cus();
   const int groups = (N + BWD_TL - 1) / BWD_TL;   // 16-row groups per graph
+  const bool sd = (d->flags & EGT_BF_SCALE_DEGREE) != 0;   // degree scalers: MFMA-tile kernels only (De = 8 as under EGT_NO_NARROW)
   BlockPlan P{};
   P.ml = ml;
+  P.sd = sd;
   P.full = (N % 16) == 0;
 
   // Row groups per graph of the MFMA-tile kernels (two workgroups per CU), where the forward and backward row rules start:
@@ -188,7 +197,7 @@ static BlockPlan plan_for(const egt_block_desc* d, bool ml) {
   const size_t lds_r4 = (size_t)16 * GG::TILE_FLOATS * 4 + lds_kv;
   const size_t lds_r8 = (size_t)32 * GG::TILE_FLOATS * 4 + ((size_t)N * KV_LD + 32 * QS_LD + N) * 4;
   const bool r4 = lds_r4 <= 80 * 1024 - 512, r8 = !r4 && lds_r8 <= 156 * 1024;
-  if (DE == 8 && !ml && !E.no_narrow_fwd) {
+  if (DE == 8 && !ml && !E.no_narrow_fwd && !sd) {
     // VALU pair kernel (egt_narrow.hip): lane = (row, head/channel pair), 4 key quarters per workgroup.  At most one 16-row
     // workgroup per CU: eight key ranges (eight waves); ... per two CUs: eight-row workgroups.  A forced wave count wins over the
     // rule; EGT_NRW_FWD_HALF only matters with eight waves.
@@ -235,7 +244,7 @@ static BlockPlan plan_for(const egt_block_desc* d, bool ml) {
   P.NLR = (N + P.TL - 1) / P.TL;
   P.nwg_bwd = B * P.NLR;
   P.EP = GG::EP;
-  if (DE == 8 && !ml && !E.no_narrow_bwd) {
+  if (DE == 8 && !ml && !E.no_narrow_bwd && !sd) {
     // De = 8 pair kernel (egt_narrow.hip: k_narrow_bwd, three workgroups per CU), ragged N included.  Measured at config 3
     // against v4r / the round-2 quad-lane kernel (two waves per SIMD both): bf16 edge tensors 226 vs 314 us, fp32 243 vs 320 us.
     // At most one workgroup per CU: eight waves share its key tiles (a forced wave count wins).
@@ -458,7 +467,8 @@ static int launch_fwd(BlockArgs& a, const BlockPlan& P, hipStream_t st, bool ski
   if (!(P.epi_ok && node_fused_ok(a))) a.epi = 0;
   a.guard = 0;   // (the always-taken phase branches of the kernels only shape hipcc's scheduling regions)
   a.RGF = P.RGF;
-  switch (P.fwd) {
+  if (P.sd) egt_block_sd_launch_fwd(a, P.fwd == FwdKernel::r4 ? P.fwd_nw : 0, P.kvl, P.ml, P.full, P.fl, st);
+  else switch (P.fwd) {
     case FwdKernel::narrow: egt_narrow_launch_fwd(a, P.fwd_nw, P.fwd_half, P.fl, st); break;
     case FwdKernel::r4:
       if constexpr (DE <= 16) { if (a.bf16) launch_r4<DE, true>(a, P, st); else launch_r4<DE, false>(a, P, st); }
@@ -494,7 +504,9 @@ static void launch_bwd(BlockArgs& a, const BlockPlan& P, hipStream_t st, bool to
   }
   a.NQP = (a.N + 15) / 16;
   a.guard = 0;   // (the always-taken phase branches of the kernels only shape hipcc's scheduling regions)
-  switch (P.bwd) {
+  if (P.sd)
+    egt_block_sd_launch_bwd(a, P.bwd == BwdKernel::v4r ? EGT_SD_BWD_V4R : P.bwd == BwdKernel::v5 ? EGT_SD_BWD_V5 : EGT_SD_BWD_V4, P.mm, P.ml, P.full, P.bl, st);
+  else switch (P.bwd) {
     case BwdKernel::narrow: egt_narrow_launch_bwd(a, P.bwd_nw, P.bl, st); break;
     case BwdKernel::v4r:
       if constexpr (DE <= 16) {
@@ -528,6 +540,10 @@ struct StackLayout {
 static int stack_flags_check(const egt_block_desc* d, bool report) {
   if (d && (d->flags & EGT_BF_STATIC_EDGE)) {
     if (report) egt_set_error("egt_stack_* does not take EGT_BF_STATIC_EDGE (use egt_block_fwd / egt_block_bwd per layer)");
+    return EGT_E_FLAGS;
+  }
+  if (d && (d->flags & (EGT_BF_SCALE_DEGREE | EGT_BF_SCALER_LINEAR))) {   // the chained epilogue / prologue of a stack carry no degree
+    if (report) egt_set_error("egt_stack_* does not take EGT_BF_SCALE_DEGREE (use egt_block_fwd / egt_block_bwd per layer)");
     return EGT_E_FLAGS;
   }
   return EGT_OK;

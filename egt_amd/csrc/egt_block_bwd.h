@@ -1,6 +1,7 @@
 // Backward pair kernels of the fused attention block (included by egt_block.hip, which holds the dispatch):
 // k_block_bwd_v4 (mask tensors / ragged N / bf16), k_block_bwd_v5 (LDS-DMA staged e tiles: the headline),
-// k_block_bwd_v4r (narrow edge channels, R rows per iteration).  The phases of the per-tile body (weight slabs, P1 .. P5,
+// k_block_bwd_v4r (narrow edge channels, R rows per iteration); their SD = true instances (degree scalers: bwd_sd_rows, bwd_pair_grad<.., SD>)
+// are instantiated by egt_block_sd.hip.  The phases of the per-tile body (weight slabs, P1 .. P5,
 // the hand-off, dK / dV / dQ, the partial stores) are the bwd_* functions below (the K / V fragment reader kv_frags_row and the
 // key-padding term key_mask_add are the forward's too: egt_block_dev.h); a kernel is its LDS carve-up, its staging
 // and its loop around them.  The kernels sit at the register edge: a change to a phase moves the register counts of all of them
@@ -26,6 +27,27 @@
 // Two kernels keep copies of their own where the shared function measured slower than the parent's pasted text (DESIGN 4.2 has the
 // figures): k_block_bwd_v5 its fp32 P1, P2 and P5 (interleaved with the MM != 0 branches), dQ / dK / dV and P4; k_block_bwd_v4 its P4.
 // A change to one of those phases is made here and in these copies.
+
+// EGT_BF_SCALE_DEGREE: the staged rows qd hold what the unflagged block's would -- dV_att' = dh'.Wo^T, delta = sum_k dV_att'_k V_att'_k
+// (V_att' = s V_att is what the forward saved; the softmax term is unchanged in value) -- and deg in slot 3.  Per (row, head), once:
+//   dV_att = s dV_att'          (what dS and dV read)
+//   c      = sum_k dV_att'_k V_att_k = delta / s     (s = 0 <=> deg = 0 <=> every gate of the row is 0: c is never used; 0, not 0 / 0)
+//   slot 3 = d deg = c / (1 + deg)  ('log')  |  c  ('linear')
+// Threads (row, head) = (t >> 3, t & 7) of the first 128; the caller syncs before (prologue / staging) and after.
+__device__ __forceinline__ void bwd_sd_rows(const BlockArgs& a, float* qd, int nl) {
+  const int t = threadIdx.x, row = t >> 3, hd = t & 7;
+  if (t < 128 && row < nl) {
+    float* st = qd + row * QD_LD + 128 + hd * 4;
+    const bool linear = (a.flags & EGT_BF_SCALER_LINEAR) != 0;
+    const float deg = st[3];
+    const float s = linear ? deg : log1pf(deg);
+    const float c = s > 0.f ? st[2] / s : 0.f;
+    st[3] = linear ? c : c / (1.0f + deg);
+    float* dv = qd + row * QD_LD + 64 + (hd >> 1) * 16 + (hd & 1);   // channel k of head hd: + 2 k
+#pragma unroll
+    for (int k = 0; k < 8; ++k) dv[2 * k] *= s;
+  }
+}
 
 __device__ __forceinline__ void bwd_dkv_zero(float (&dKa)[16], float (&dVa)[16]) {
 #pragma unroll
@@ -103,7 +125,9 @@ __device__ __forceinline__ v4f bwd_p2_dhext(const float* dt, const float* wsB, i
 // backward.  dge = (dG, dH) per head, hh = the clipped logits + E (H_hat), dA = d(Q.K) scaled, at = S * gate.
 // The Q / dV_att fragments are fetched from LDS here and again in bwd_dqkv_accum instead of being held across the exp / sigmoid chain.
 // RAG: a key past N (!kvalid) gets probability and gate exactly 0.  GP: its gate goes through the sigmoid also without EGT_BF_GATE.
-template <bool ML, bool RAG, bool GP>
+// SD (EGT_BF_SCALE_DEGREE): slot 3 of the row's statistics holds d deg of (row, head) (bwd_sd_rows), and every key's gate logit
+// takes d deg . g (1 - g) whatever its softmax probability; without SD slot 3 is never read.
+template <bool ML, bool RAG, bool GP, bool SD = false>
 __device__ __forceinline__ void bwd_pair_grad(const BlockArgs& a, const float* qr, const float (&Kf)[16], const float (&Vf)[16],
                                               const v4f& acc, const v4f& dhx, float kadd, const MaskRegs& mr, size_t idx8, int q,
                                               bool kvalid, bool gated, bool clip, float (&dge)[4], float (&hh)[2], float (&dA)[2],
@@ -125,7 +149,7 @@ __device__ __forceinline__ void bwd_pair_grad(const BlockArgs& a, const float* q
   }
   const float4* sp = reinterpret_cast<const float4*>(qr + 128 + q * 8);
   const float4 s0 = sp[0], s1 = sp[1];
-  const float st[8] = {s0.x, s0.y, s0.z, 0.f, s1.x, s1.y, s1.z, 0.f};
+  const float st[8] = {s0.x, s0.y, s0.z, SD ? s0.w : 0.f, s1.x, s1.y, s1.z, SD ? s1.w : 0.f};
   float xl[2], gl[2], inr[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -147,7 +171,8 @@ __device__ __forceinline__ void bwd_pair_grad(const BlockArgs& a, const float* q
     const float S = __expf(xl[j] - st[4 * j]) * st[4 * j + 1];
     const float g = (gated || (GP && RAG && !kvalid)) ? egt_sigmoid(gl[j]) : 1.0f;
     const float dS = dAd[j] * g;
-    const float dGl = gated ? dAd[j] * S * g * (1.0f - g) : 0.f;
+    float dGl = gated ? dAd[j] * S * g * (1.0f - g) : 0.f;
+    if constexpr (SD) dGl = fmaf(st[4 * j + 3], g * (1.0f - g), dGl);
     const float dH = S * (dS - st[4 * j + 2]) + dhx[j];
     dA[j] = dH * inr[j] * a.scale;
     at[j] = S * g;
@@ -314,7 +339,7 @@ __device__ __forceinline__ void bwd_store_epart(const BlockArgs& a, float* sm, i
 //    registers, 116 -> 104 us.
 // RAG: N is not a multiple of 16 -- the last key tile is zero-filled past N and its lanes get probability and
 // gate exactly 0, the last row group is short (the row loop and the prologue already take nl < 16).
-template <int DE, bool ML, bool BF, bool RAG>
+template <int DE, bool ML, bool BF, bool RAG, bool SD = false>
 __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
   seed_from_device(a);
   using G = Geo<DE>;
@@ -349,6 +374,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
     __syncthreads();
     bwd_node_prologue<DE>(a, sm, qd, b, l_begin, wg);
   }
+  if constexpr (SD) { __syncthreads(); bwd_sd_rows(a, qd, nl); }
   bwd_fill_slabs<DE>(a, wsA, wsB, wsD);
   float c2r[4], ssum[4];
   v4f accT[G::TILES], accR[G::TILES];
@@ -396,7 +422,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
       SCHED_FENCE();
       // ---- P3: logits, softmax/gate backward ----
       float dge[4], hh[2], dA[2], at[2];
-      bwd_pair_grad<ML, RAG, false>(a, qr, Kf, Vf, acc, dhx, kadd, mr, (pair0 + p) * BH, q, kvalid, gated, clip, dge, hh, dA, at);
+      bwd_pair_grad<ML, RAG, false, SD>(a, qr, Kf, Vf, acc, dhx, kadd, mr, (pair0 + p) * BH, q, kvalid, gated, clip, dge, hh, dA, at);
       bwd_handoff(sc1, sc2, p, q, dge, hh, ssum);
       lds_sync();
       SCHED_FENCE();
@@ -470,7 +496,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
 // buffers + the node-side prologue's scratch behind them
 #define V5_AREA(DE_) ((4 * (3 * Geo<DE_>::TILE_FLOATS + 448) > 4 * Geo<DE_>::TILE_FLOATS + BWD_PRO_WS) \
                           ? 4 * (3 * Geo<DE_>::TILE_FLOATS + 448) : 4 * Geo<DE_>::TILE_FLOATS + BWD_PRO_WS)
-template <int DE, int MM, bool RAG>
+template <int DE, int MM, bool RAG, bool SD = false>
 __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
   seed_from_device(a);
   constexpr bool SPLIT = MM == EGT_MM_BF16X3;
@@ -585,6 +611,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
     __syncthreads();
     bwd_node_prologue_finish<DE>(a, pro_ws, qd, b, l_begin, wg, proR);
   }
+  if constexpr (SD) { __syncthreads(); bwd_sd_rows(a, qd, nl); }
   // weight slabs: element (t, lane, u)
   if constexpr (MM != 0) {
     // bf16 operands.  wsA / wsB: [step s][part hi|lo][lane][8 slots], slot i <-> channel 16 (2s + (i >> 2)) + 4q + (i & 3);
@@ -714,7 +741,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
       SCHED_FENCE();
       // ---- P3: logits, softmax/gate backward ----
       float dge[4], hh[2], dA[2], at[2];
-      bwd_pair_grad<false, RAG, true>(a, qr, Kf, Vf, acc, dhx, kadd, mr, (pair0 + p) * BH, q, kvalid, gated, clip, dge, hh, dA, at);
+      bwd_pair_grad<false, RAG, true, SD>(a, qr, Kf, Vf, acc, dhx, kadd, mr, (pair0 + p) * BH, q, kvalid, gated, clip, dge, hh, dA, at);
       bwd_handoff(sc1, sc2, p, q, dge, hh, ssum);
       lds_sync();
       SCHED_FENCE();
@@ -841,7 +868,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
 // mask tensors): one iteration = the wave's key tile x R query rows (R = V4R_RR).  The rows' P1..P5 chains are independent, the LDS
 // hand-offs are shared (5 per R rows instead of 5 per row), the e / de' tiles of the next R rows are
 // in flight during the arithmetic.  Same arguments, partial layouts and prologue as v4.
-template <int DE, bool BF, int R>
+template <int DE, bool BF, int R, bool SD = false>
 __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R rows per iteration
   seed_from_device(a);
   using G = Geo<DE>;
@@ -880,6 +907,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
     __syncthreads();
     bwd_node_prologue<DE>(a, sm, qd, b, l_begin, wg);
   }
+  if constexpr (SD) { __syncthreads(); bwd_sd_rows(a, qd, nl); }
   bwd_fill_slabs<DE>(a, wsA, wsB, wsD);
   float c2r[4], ssum[4];
   v4f accT[G::TILES], accR[G::TILES];
@@ -948,7 +976,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
       for (int i = 0; i < R; ++i) {
         if (i >= nr) continue;
         float hh[2];
-        bwd_pair_grad<false, true, false>(a, qd + (R * lq + i) * QD_LD, Kf, Vf, acc[i], dhx[i], kadd, mr, (pair0[i] + p) * BH, q, kvalid,
+        bwd_pair_grad<false, true, false, SD>(a, qd + (R * lq + i) * QD_LD, Kf, Vf, acc[i], dhx[i], kadd, mr, (pair0[i] + p) * BH, q, kvalid,
                                           gated, clip, dge[i], hh, dA[i], at[i]);
         bwd_handoff(sc10 + i * 256, sc20 + i * 192, p, q, dge[i], hh, ssum);
         SCHED_FENCE();   // one row's Q / dV_att fragments (32 registers) at a time

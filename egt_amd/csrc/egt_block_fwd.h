@@ -1,5 +1,6 @@
 // Forward pair kernels of the fused attention block (included by egt_block.hip, which holds the dispatch):
-// k_block_fwd<De,KVL,ML,FULL,BF> and the four-rows-per-iteration k_block_fwd_r4<De,FULL,NW,BF> for narrow edge channels.
+// k_block_fwd<De,KVL,ML,FULL,BF,SD> and the four-rows-per-iteration k_block_fwd_r4<De,FULL,NW,BF,SD> for narrow edge channels
+// (SD = true: the degree-scaler instances, instantiated by egt_block_sd.hip).
 // The phases of the per-pair body (lane-constant operands, logits, online softmax and A.V, dense_edge_r, the row finish) are the
 // fwd_* functions below, with kv_frags / frag16 / key_mask_add of egt_block_dev.h; a kernel is its LDS carve-up, its staging and
 // prefetch, and its loop around them (profiles/fwd_phases_kres.txt has the register counts of this split against the pasted copies).
@@ -123,13 +124,68 @@ __device__ __forceinline__ void fwd_row_finish(const BlockArgs& a, size_t rowl, 
   }
 }
 
+// ---- degree scalers (EGT_BF_SCALE_DEGREE, egt_layers.py:122-136): the SD instances of the two kernels below ----
+// deg of (row, head) = the sum of the gates over the keys; V_att leaves the row finish multiplied by s(deg), so dense_mha (node
+// epilogue, k_node_post) and the dWo contraction read V_att' from where they read V_att.  Slot 3 of the row statistics keeps deg
+// for the backward (bwd_sd_rows).  The unflagged instances call neither function.
+__device__ __forceinline__ float egt_degree_scaler(float deg, bool linear) { return linear ? deg : log1pf(deg); }
+
+// fwd_softmax_av of a gated block, with the degree: a key past N adds 0, a masked key's gate IS 0 (egt_sigmoid(-1e9))
+__device__ __forceinline__ void fwd_softmax_av_sd(bool valid, const float (&xl)[2], const float (&gl)[2], const float (&Vf)[16],
+                                                  float (&mx)[2], float (&sum)[2], float (&deg)[2], float (&O)[16]) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const float xv = xl[j];
+    const float mn = valid ? fmaxf(mx[j], xv) : mx[j];
+    const float alpha = __expf(mx[j] - mn);
+    const float pe = valid ? __expf(xv - mn) : 0.f;
+    const float g = valid ? egt_sigmoid(gl[j]) : 0.f;
+    mx[j] = mn;
+    sum[j] = fmaf(sum[j], alpha, pe);
+    deg[j] += g;
+    const float av = pe * g;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) O[2 * k + j] = fmaf(O[2 * k + j], alpha, av * Vf[2 * k + j]);
+  }
+}
+
+// fwd_row_finish with the degree merged over the 16 key lanes: V_att' = s(deg) V_att to HBM (and the Q slot), deg into slot 3.
+// The scaler is evaluated here, once per (row, head), with log1pf (deg reaches 1e-5, where log(1 + deg) has lost its digits).
+__device__ __forceinline__ void fwd_row_finish_sd(const BlockArgs& a, size_t rowl, int p, int q, float (&mx)[2], float (&sum)[2],
+                                                  float (&deg)[2], float (&O)[16], bool keep, float* qrow) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const float mr2 = row_max16(mx[j]);
+    const float f = __expf(mx[j] - mr2);
+    mx[j] = mr2;
+    sum[j] = row_sum16(sum[j] * f);
+    deg[j] = row_sum16(deg[j]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) O[2 * k + j] *= f;
+  }
+  const float o = reduce16_keep_own(O, p);
+  const int k = p >> 1, j = p & 1;
+  const float sj = j ? sum[1] : sum[0];
+  const float dj = j ? deg[1] : deg[0];
+  const float vo = (o / sj) * egt_degree_scaler(dj, (a.flags & EGT_BF_SCALER_LINEAR) != 0);
+  if (k < a.DK) a.v_att[rowl * a.Dh + k * BH + 2 * q + j] = vo;
+  if (keep) qrow[k * BH + 2 * q + j] = vo;
+  if (p < 2) {
+    float* st = a.stats + (rowl * BH + 2 * q + p) * 4;
+    st[0] = p ? mx[1] : mx[0];
+    st[1] = sj;
+    st[3] = dj;
+  }
+}
+
 // ================================================================= forward =====
 // Workgroup = (graph b, 16 query rows); wave w owns rows l = 16*lg + w + 4*i.
 // KVL: K/V of the graph, Q of the 16 rows and the key-mask adds are staged in LDS.
 // ML: attention-mask / injected-random-mask byte streams are present (their loads are
 // compiled out of the headline kernel).
 // FULL: N is a multiple of 16 (no ragged key tile): validity selects and address clamps fold away.
-template <int DE, bool KVL, bool ML, bool FULL, bool BF>
+// SD: EGT_BF_SCALE_DEGREE (gated blocks, fp32 edge tensors): the degree rides next to the softmax sum (fwd_softmax_av_sd / fwd_row_finish_sd).
+template <int DE, bool KVL, bool ML, bool FULL, bool BF, bool SD = false>
 __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd(BlockArgs a) {   // narrow tiles without K/V in LDS: more resident waves (with K/V in LDS the LDS footprint caps a CU at two workgroups anyway)
   seed_from_device(a);
   using G = Geo<DE>;
@@ -217,6 +273,8 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
   }
 
   float Qf[16], mx[2], sum[2], O[16];
+  float deg[2] = {0.f, 0.f};   // (SD)
+  (void)deg;
   auto step = [&](const int it_, TileRegs<DE>& tr) __attribute__((always_inline)) {
     const bool live = PFD == 1 || it_ < total;
     const int it = PFD == 1 ? it_ : min(it_, total - 1);
@@ -230,6 +288,7 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
       frag16(KVL ? reinterpret_cast<const float4*>(qs + (wave + 4 * li) * QS_LD + q * 16)
                  : reinterpret_cast<const float4*>(a.qkvp + rowl * QKVP + q * 16), Qf);
       fwd_row_init(mx, sum, O);
+      if constexpr (SD) deg[0] = deg[1] = 0.f;
     }
     // ---- stage this tile, start the next one's loads ----
     MaskRegs mr{make_float2(1.f, 1.f), 0};   // issued before the prefetch, consumed after the MFMAs
@@ -273,7 +332,8 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
     float hh[2] = {0.f, 0.f}, xl[2] = {0.f, 0.f}, gl[2] = {0.f, 0.f};
     fwd_pair_logits(a, clip, Qf, Kf, acc, hh, xl, gl);
     apply_masks<ML>(a, kadd, mr, (pair0 + p) * BH, q, xl, gl);
-    fwd_softmax_av(valid, gated, xl, gl, Vf, mx, sum, O);
+    if constexpr (SD) fwd_softmax_av_sd(valid, xl, gl, Vf, mx, sum, deg, O);
+    else fwd_softmax_av(valid, gated, xl, gl, Vf, mx, sum, O);
     fwd_edge_update<DE>(tl, p, q, valid, hh, wrA, brv);
     if (it_ + 1 == total) {   // last tile of the wave: flush
       lds_sync();
@@ -281,7 +341,8 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
     }
     if (mt == ntile - 1 && live) {
       // the row's Q is dead (read at mt == 0 by this wave only): its slot keeps V_att for the epilogue
-      if (!ML) fwd_row_finish(a, rowl, p, q, mx, sum, O, KVL && a.epi, qs + (wave + 4 * li) * QS_LD);
+      if constexpr (SD) fwd_row_finish_sd(a, rowl, p, q, mx, sum, deg, O, KVL && a.epi, qs + (wave + 4 * li) * QS_LD);
+      else if (!ML) fwd_row_finish(a, rowl, p, q, mx, sum, O, KVL && a.epi, qs + (wave + 4 * li) * QS_LD);
       else {
         // Own copy of fwd_row_finish in the mask-tensor instances: with the shared one <64, true, true, false, false> (attention mask,
         // h [128, 64, 64]) ran 69.8 us against the parent's 66.4 (its max - min over three runs: 0.5), with this copy 66.8.  In the
@@ -342,7 +403,7 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
 // NW = 4: 16 rows per workgroup, two workgroups per CU; NW = 8: 32 rows (two 16-row halves), ONE
 // workgroup per CU -- same occupancy, but K/V of a graph up to N ~ 250 still fits in LDS and is staged
 // once per 32 rows.
-template <int DE, bool FULL, int NW, bool BF>
+template <int DE, bool FULL, int NW, bool BF, bool SD = false>
 __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
   seed_from_device(a);
   typedef typename EdgeT<BF>::type ET;   // element type of the edge tensors in HBM
@@ -397,6 +458,8 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
     };
     prefetch(0);
     float mx[4][2], sum[4][2], O[4][16];
+    float deg[4][2] = {};   // (SD)
+    (void)deg;
 #pragma unroll
     for (int i = 0; i < 4; ++i) fwd_row_init(mx[i], sum[i], O[i]);
     for (int mt = 0; mt < ntile; ++mt) {
@@ -435,6 +498,8 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
           // ---- online softmax x gate, A.V (per lane).  Own copy of fwd_softmax_av: with the shared one r4<8, false, 8, false> ran
           // 165.5 us against the parent's 161.4 (max - min 0.7) and r4<8, false, 4, false> 98.5 against 97.2 (0.3); with this copy
           // 160.4 and 96.2 ----
+          if constexpr (SD) fwd_softmax_av_sd(valid, xl, gl, Vf, mx[i], sum[i], deg[i], O[i]);
+          else
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             const float xv = xl[j];
@@ -458,7 +523,10 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
     // ---- per row: 16-lane merge, V_att (also into the row's Q slot: dead from here on), statistics ----
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      if (i < nrows) fwd_row_finish(a, rowl[i], p, q, mx[i], sum[i], O[i], a.epi != 0, qs + (row0 + 4 * i) * QS_LD);
+      if (i < nrows) {
+        if constexpr (SD) fwd_row_finish_sd(a, rowl[i], p, q, mx[i], sum[i], deg[i], O[i], a.epi != 0, qs + (row0 + 4 * i) * QS_LD);
+        else fwd_row_finish(a, rowl[i], p, q, mx[i], sum[i], O[i], a.epi != 0, qs + (row0 + 4 * i) * QS_LD);
+      }
   }
   // each 16-row half runs the 4-wave epilogue on its own rows (staging area hs = its own tiles)
   if (a.epi) fwd_node_epilogue(a, sm + hf * 16 * QS_LD, qs + hf * 16 * QS_LD, b, lg * RW + hf * 16, min(16, N - (lg * RW + hf * 16)), N, wv, p, q);

@@ -30,6 +30,17 @@ def static_edge_disabled() -> bool:
     return _NO_STATIC_EDGE
 
 
+_NO_SCALE_DEGREE = None
+
+
+def scale_degree_disabled() -> bool:
+    """EGT_NO_SCALE_DEGREE=1 (read once per process): blocks with degree scalers keep the composed route."""
+    global _NO_SCALE_DEGREE
+    if _NO_SCALE_DEGREE is None:
+        _NO_SCALE_DEGREE = os.environ.get("EGT_NO_SCALE_DEGREE", "") not in ("", "0")
+    return _NO_SCALE_DEGREE
+
+
 def _flags(blk, training=False, seed_device=False, static_edge=False) -> int:
     """egt_block_desc.flags of a block"""
     flags = L.BF_STATIC_EDGE if static_edge else 0
@@ -45,6 +56,10 @@ def _flags(blk, training=False, seed_device=False, static_edge=False) -> int:
         flags |= L.BF_NO_EDGE_LN
     if blk.mha.clip_logits_value is not None:
         flags |= L.BF_CLIP
+    if blk.mha.scale_degree:         # degree scalers: the library answers for the flagged descriptor (fp32 edges, no static edge)
+        flags |= L.BF_SCALE_DEGREE
+        if blk.mha.scaler_type == "linear":
+            flags |= L.BF_SCALER_LINEAR
     return flags
 
 
@@ -86,8 +101,12 @@ def _unsupported(blk, training):
         return f"edge_channel_type {blk.edge_channel_type!r}"
     if blk.add_n_norm or blk.edge_activation is not None:
         return "add_n_norm / edge_activation"
-    if blk.mha.scale_degree or blk.mha.attn_dropout > 0 or blk.mha.num_virtual_nodes > 0:
+    if blk.mha.scale_degree and blk.mha.num_virtual_nodes > 0:
+        return "scale_degree with virtual nodes (the scaler of the virtual-node rows is not in the kernels)"
+    if blk.mha.attn_dropout > 0 or blk.mha.num_virtual_nodes > 0:
         return "scale_degree / attn_dropout / virtual nodes"
+    if blk.mha.scale_degree and scale_degree_disabled():
+        return "scale_degree (EGT_NO_SCALE_DEGREE is set)"
     if training and (blk.node_dropout > 0 or blk.edge_dropout > 0):
         return "node / edge dropout"
     if blk.model_width % blk.num_heads:
@@ -153,6 +172,8 @@ def bf16_refusal(blk):
     why = _unsupported(blk, True)
     if why is not None:
         return why
+    if blk.mha.scale_degree:
+        return "scale_degree with bf16 edge tensors (the degree-scaler kernels take fp32 edge tensors)"
     if _covered(blk, 1, 16, torch.float32, torch.bfloat16, True, True, False, True)[0] is None:
         return (f"geometry (num_heads {blk.num_heads}, head dim {blk.model_width // blk.num_heads}, "
                 f"edge_width {blk.edge_width}) is not covered by the fused block")
@@ -419,7 +440,7 @@ def stack_supported(stack, h, e, attn_mask) -> bool:
         return False
     b0 = blocks[0]
     for b in blocks:
-        if route(b, h, e, attn_mask)[0] != "fused":
+        if route(b, h, e, attn_mask)[0] != "fused" or b.mha.scale_degree:   # (egt_stack_* carries no degree: block by block)
             return False
         same = (b.model_width == b0.model_width and b.edge_width == b0.edge_width and
                 b.edge_channel_type == b0.edge_channel_type and b.gated == b0.gated and

@@ -236,13 +236,14 @@ int egt_edge_update_bwd(const egt_edge_desc* desc, const void* d_e_out,
 /* ---- outer op: the fused attention block (the data-parallel hot path) ---------
  *   (h', e') = edge_update_residual(h, e) with mha_block inside, pre-norm
  * Replaces graph_xformer_model_base.py:192-223 + :106-145 for
- * edge_channel_type 'residual' / 'constrained' (add_n_norm=False, no dropout,
- * scale_degree=False): norm_edge -> attention_gates / dense_edge_b -> norm_mha ->
+ * edge_channel_type 'residual' / 'constrained' (add_n_norm=False, no dropout;
+ * scale_degree with EGT_BF_SCALE_DEGREE, fp32 edge tensors): norm_edge -> attention_gates / dense_edge_b -> norm_mha ->
  * dense_qkv -> EGT -> dense_mha + res_mha ; dense_edge_r + res_edge.
  * One launch streams e once: LN, the two De->H projections, QK^T, clip, +E,
  * masks, softmax x sigmoid gate, A.V and e' = e + H_hat.Wr + br never leave the
  * CU (E, G, H_hat, A_tild are not materialised).  Everything else (other
- * variants, dropout, degree scalers, d > 8) composes the kernels above.
+ * variants, dropout, degree scalers with virtual nodes or bf16 edges, d > 8)
+ * composes the kernels above.
  * Parameter pointers carry the reference's Keras layer names. */
 #define EGT_BF_GATE 0x1u      /* gate_attention                                  */
 #define EGT_BF_ATTN_MASK 0x2u /* 'constrained': attn_mask [B,N,N,H] fp32 present */
@@ -269,6 +270,15 @@ int egt_edge_update_bwd(const egt_edge_desc* desc, const void* d_e_out,
                                   only (rand_mask must be NULL).  egt_block_supported() answers 1 with this flag
                                   exactly where the De = 8 pair kernels run: De = 8, d <= 8, H = 8, fp32 or bf16
                                   edges, no EGT_BF_ATTN_MASK; egt_stack_* refuses it (EGT_E_FLAGS) */
+#define EGT_BF_SCALE_DEGREE (1u << 7) /* 0x80: scale_degree (egt_layers.py:122-136, no virtual nodes): V_att of (row, head) is
+                                  multiplied by s(deg), deg = the row's sum of gates over the keys (0 for a masked or
+                                  padded key), s = log1p (default) or the identity (EGT_BF_SCALER_LINEAR).  Needs
+                                  EGT_BF_GATE; not with EGT_BF_STATIC_EDGE (both EGT_E_FLAGS).  fp32 edge tensors only
+                                  (EGT_BF16: not covered).  Runs on the MFMA-tile pair kernels for every De (De = 8
+                                  included); `saved` does not grow: slot 3 of the per-(row, head) statistics carries deg
+                                  forward and d deg into the backward pair kernel.  egt_stack_* and the pair operator
+                                  refuse it (EGT_E_FLAGS / egt_pair_supported = 0) */
+#define EGT_BF_SCALER_LINEAR (1u << 8) /* 0x100: scaler_type 'linear' (s = deg); only valid with EGT_BF_SCALE_DEGREE */
 
 typedef struct egt_block_desc {
   int32_t B, N, H, d, De;   /* model_width Dh = d*H                             */

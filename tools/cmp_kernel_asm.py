@@ -5,7 +5,7 @@ symbol names normalised).  Kernels are matched by their demangled names.  Prints
     python tools/cmp_kernel_asm.py OLD.s NEW.s [-v] [--show 'demangled kernel name']     (hipcc --save-temps=obj leaves <unit>-hip-amdgcn-amd-amdhsa-gfx950.s)
     python tools/cmp_kernel_asm.py --trees OLD_TREE NEW_TREE SCRATCH_DIR
 --trees: every file of build.SOURCES of each tree compiled as build.py compiles it (this tree's build.EXTRA_FLAGS, at most 8 compilations
-at a time) into SCRATCH_DIR/old and /new, one count line per translation unit; exit status 1 if any unit has differ, new-only or old unmatched above 0.
+at a time) into SCRATCH_DIR/old and /new, one count line per translation unit (a unit that OLD does not have is named as new); exit status 1 if any unit has differ, new-only or old unmatched above 0.
 --mnemonics (either mode): the opcode sequences only -- operands and .amdhsa metadata dropped (for a change that moves kernel-argument
 offsets; tools/kres.py compares registers, spills, scratch and LDS).
 --rename 'REGEX=>REPL' (either mode, repeatable, applied in order to OLD's demangled names before matching): for a change that renames
@@ -77,6 +77,10 @@ else:
     spec = importlib.util.spec_from_file_location('egt_build', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'egt_amd', 'build.py'))
     build = importlib.util.module_from_spec(spec); spec.loader.exec_module(build)
     with concurrent.futures.ThreadPoolExecutor(max_workers=8) as pool:
-        asm = {(d, s): pool.submit(compile_unit, build, os.path.abspath(t), os.path.join(pos[2], d), s) for t, d in ((pos[0], 'old'), (pos[1], 'new')) for s in build.SOURCES}
-        bad = sum(compare(asm['old', s].result(), asm['new', s].result(), label=f'{s[:-4]}: ') for s in build.SOURCES)
+        have = lambda t, s: os.path.exists(os.path.join(t, 'egt_amd', 'csrc', s))
+        asm = {(d, s): pool.submit(compile_unit, build, os.path.abspath(t), os.path.join(pos[2], d), s) for t, d in ((pos[0], 'old'), (pos[1], 'new')) for s in build.SOURCES if have(t, s)}
+        bad = 0
+        for s in build.SOURCES:
+            if ('old', s) in asm: bad += compare(asm['old', s].result(), asm['new', s].result(), label=f'{s[:-4]}: ')
+            else: print(f"{s[:-4]}: a new translation unit (not in OLD): {len(funcs(asm['new', s].result()))} kernels and device functions, nothing to compare")
     sys.exit(1 if bad else 0)
