@@ -189,6 +189,13 @@ class BatchOut(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in BATCH_OUT_FIELDS]
 
 
+class AccItem(C.Structure):     # egt_acc_item
+    _fields_ = [("sum", C.c_void_p), ("count", C.c_void_p), ("count_value", C.c_float)]
+
+
+ACC_MAX_ITEMS = 32              # egt_accumulate: 1 <= K <= 32
+
+
 def params_struct(cls, fields, tensors):
     """A parameter struct of the C-ABI (`cls`, its `fields` in order) filled with the tensors' device pointers (None -> NULL)."""
     st = cls()
@@ -299,6 +306,8 @@ _PROTOS = {
     "egt_optim_step": (C.c_int, [C.POINTER(OptimDesc)] + [_VP] * 6),
     "egt_batch_supported": (C.c_int, [C.POINTER(BatchDesc)]),
     "egt_batch_assemble": (C.c_int, [C.POINTER(BatchDesc), C.POINTER(BatchStore), _VP, C.POINTER(BatchOut), _VP]),
+    "egt_batch_assemble_at": (C.c_int, [C.POINTER(BatchDesc), C.POINTER(BatchStore), _VP, _VP, C.POINTER(BatchOut), _VP]),
+    "egt_accumulate": (C.c_int, [_VP, _VP, C.c_int32, _VP]),
 }
 
 

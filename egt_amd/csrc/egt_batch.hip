@@ -23,6 +23,7 @@
 // word is written exactly once; nothing is read back from HBM and there are no atomics, so the result does not depend on
 // what the buffers held.  Node rows, PE rows and node targets are 4-byte words whatever their type: one flat
 // copy-then-pad (span_copy_pad) moves them all.
+// k_batch_assemble_at is the same text with the indices taken from a table at a device-resident cursor (egt_batch_assemble_at).
 #include "egt_common.h"
 
 namespace {
@@ -163,43 +164,52 @@ __device__ __forceinline__ void matrix_tile(const BatchArgs& a, int b, int tile_
   if (fm) span_store_lds(fm, s0, len, tfu, tid);
 }
 
-__global__ __launch_bounds__(BA_THREADS) void k_batch_assemble(BatchArgs a) {
-  extern __shared__ __align__(16) uint32_t ba_lds[];
-  const int B = a.d.B, N = a.d.N, tid = threadIdx.x;
-  const int mat_wgs = B * a.tiles;
-  const bool is_mat = (int)blockIdx.x < mat_wgs;
-  const int b = is_mat ? (int)blockIdx.x / a.tiles : (int)blockIdx.x - mat_wgs;
-  const int r = a.idx[b];
-  const bool ok = (unsigned)r < (unsigned)a.d.records;             // an index outside the split writes an empty graph
-  const int n = ok ? min(max(a.s.num_nodes[r], 0), N) : 0;
-  const int64_t nd0 = ok ? a.s.node_off[r] : 0;
-  if (is_mat) {
-    const int64_t e0 = ok && a.s.edge_off ? a.s.edge_off[r] : 0;
-    if (a.d.edge_kind == EGT_BATCH_F32) matrix_tile<true>(a, b, (int)blockIdx.x % a.tiles, n, e0, nd0 + r, ba_lds);
-    else matrix_tile<false>(a, b, (int)blockIdx.x % a.tiles, n, e0, nd0 + r, ba_lds);
-    return;
-  }
-  // node-level and per-graph outputs of graph b
-  if (a.o.node_features) {
-    const int W = a.d.node_width;
-    const uint32_t pad = a.d.node_kind == EGT_BATCH_F32 ? __float_as_uint(a.d.mask_f) : (uint32_t)a.d.mask_i;
-    span_copy_pad(reinterpret_cast<uint32_t*>(a.o.node_features), (int64_t)b * N * W, N * W,
-                  reinterpret_cast<const uint32_t*>(a.s.node_rows) + nd0 * W, n * W, pad, tid);
-  }
-  if (a.o.pe) {
-    const int W = a.d.pe_kind == EGT_BATCH_PE_SVD ? 2 * a.d.pe_features : a.d.pe_features;
-    span_copy_pad(reinterpret_cast<uint32_t*>(a.o.pe), (int64_t)b * N * W, N * W,
-                  reinterpret_cast<const uint32_t*>(a.s.pe_rows) + nd0 * W, n * W, 0u, tid);
-  }
-  if (a.o.target) {
-    const uint32_t* const tg = reinterpret_cast<const uint32_t*>(a.s.targets);
-    if (a.d.target_kind == EGT_BATCH_TGT_NODE_I32)
-      span_copy_pad(reinterpret_cast<uint32_t*>(a.o.target), (int64_t)b * N, N, tg + nd0, n, 0u, tid);
-    else if (tid == 0)
-      reinterpret_cast<uint32_t*>(a.o.target)[b] = ok ? tg[r] : 0u;
-  }
-  if (a.o.num_nodes && tid == 0) a.o.num_nodes[b] = ok ? a.s.num_nodes[r] : 0;
+// The kernel's text, instantiated twice below.  k_batch_assemble takes the B indices of the batch; k_batch_assemble_at takes the
+// index table and reads the batch's first entry `*cursor` when it RUNS: a replayed hipGraph walks the table as egt_seed_advance
+// moves the cursor behind it.  Neither the cursor nor the table is written.  (A macro and not an inlined function: the plain
+// kernel's machine code stays what it was, instruction for instruction -- profiles/resident_step_asm.txt.)
+#define BA_KERNEL(NAME, PARAMS, IDX) \
+__global__ __launch_bounds__(BA_THREADS) void NAME PARAMS {                                                               \
+  extern __shared__ __align__(16) uint32_t ba_lds[];                                                                      \
+  const int B = a.d.B, N = a.d.N, tid = threadIdx.x;                                                                      \
+  const int mat_wgs = B * a.tiles;                                                                                        \
+  const bool is_mat = (int)blockIdx.x < mat_wgs;                                                                          \
+  const int b = is_mat ? (int)blockIdx.x / a.tiles : (int)blockIdx.x - mat_wgs;                                           \
+  const int r = (IDX)[b];                                                                                                 \
+  const bool ok = (unsigned)r < (unsigned)a.d.records;             /* an index outside the split writes an empty graph */ \
+  const int n = ok ? min(max(a.s.num_nodes[r], 0), N) : 0;                                                                \
+  const int64_t nd0 = ok ? a.s.node_off[r] : 0;                                                                           \
+  if (is_mat) {                                                                                                           \
+    const int64_t e0 = ok && a.s.edge_off ? a.s.edge_off[r] : 0;                                                          \
+    if (a.d.edge_kind == EGT_BATCH_F32) matrix_tile<true>(a, b, (int)blockIdx.x % a.tiles, n, e0, nd0 + r, ba_lds);       \
+    else matrix_tile<false>(a, b, (int)blockIdx.x % a.tiles, n, e0, nd0 + r, ba_lds);                                     \
+    return;                                                                                                               \
+  }                                                                                                                       \
+  /* node-level and per-graph outputs of graph b */                                                                       \
+  if (a.o.node_features) {                                                                                                \
+    const int W = a.d.node_width;                                                                                         \
+    const uint32_t pad = a.d.node_kind == EGT_BATCH_F32 ? __float_as_uint(a.d.mask_f) : (uint32_t)a.d.mask_i;             \
+    span_copy_pad(reinterpret_cast<uint32_t*>(a.o.node_features), (int64_t)b * N * W, N * W,                              \
+                  reinterpret_cast<const uint32_t*>(a.s.node_rows) + nd0 * W, n * W, pad, tid);                           \
+  }                                                                                                                       \
+  if (a.o.pe) {                                                                                                           \
+    const int W = a.d.pe_kind == EGT_BATCH_PE_SVD ? 2 * a.d.pe_features : a.d.pe_features;                                \
+    span_copy_pad(reinterpret_cast<uint32_t*>(a.o.pe), (int64_t)b * N * W, N * W,                                         \
+                  reinterpret_cast<const uint32_t*>(a.s.pe_rows) + nd0 * W, n * W, 0u, tid);                              \
+  }                                                                                                                       \
+  if (a.o.target) {                                                                                                       \
+    const uint32_t* const tg = reinterpret_cast<const uint32_t*>(a.s.targets);                                            \
+    if (a.d.target_kind == EGT_BATCH_TGT_NODE_I32)                                                                        \
+      span_copy_pad(reinterpret_cast<uint32_t*>(a.o.target), (int64_t)b * N, N, tg + nd0, n, 0u, tid);                    \
+    else if (tid == 0)                                                                                                    \
+      reinterpret_cast<uint32_t*>(a.o.target)[b] = ok ? tg[r] : 0u;                                                       \
+  }                                                                                                                       \
+  if (a.o.num_nodes && tid == 0) a.o.num_nodes[b] = ok ? a.s.num_nodes[r] : 0;                                            \
 }
+
+BA_KERNEL(k_batch_assemble, (BatchArgs a), a.idx)
+BA_KERNEL(k_batch_assemble_at, (BatchArgs a, const uint64_t* cursor), a.idx + *cursor)
+#undef BA_KERNEL
 
 // one text behind egt_batch_supported and egt_batch_assemble
 int batch_desc_check(const egt_batch_desc* d, bool report) {
@@ -240,12 +250,16 @@ BatchPlan plan_batch(const egt_batch_desc* d, int fields) {
 
 extern "C" int egt_batch_supported(const egt_batch_desc* desc) { return batch_desc_check(desc, false) == EGT_OK ? 1 : 0; }
 
-extern "C" int egt_batch_assemble(const egt_batch_desc* desc, const egt_batch_store* store, const int32_t* idx,
-                                  const egt_batch_out* out, void* stream) {
+namespace {
+// egt_batch_assemble (cursor == nullptr, idx = the B indices) and egt_batch_assemble_at (idx = the table)
+int batch_assemble_launch(const egt_batch_desc* desc, const egt_batch_store* store, const int32_t* idx, const uint64_t* cursor, bool at,
+                          const egt_batch_out* out, void* stream) {
   const int rc = batch_desc_check(desc, true);
   if (rc != EGT_OK) return rc;
   if (!store) EGT_FAIL(EGT_E_NULL, "store is NULL");
-  if (!idx) EGT_FAIL(EGT_E_NULL, "idx is NULL");
+  if (!idx) EGT_FAIL(EGT_E_NULL, at ? "idx_table is NULL" : "idx is NULL");
+  if (at && !cursor) EGT_FAIL(EGT_E_NULL, "cursor is NULL");
+  if (at && (reinterpret_cast<uintptr_t>(cursor) & 7)) EGT_FAIL(EGT_E_SHAPE, "cursor must be 8-byte aligned");
   if (!out) EGT_FAIL(EGT_E_NULL, "out is NULL");
   if (!store->num_nodes || !store->node_off) EGT_FAIL(EGT_E_NULL, "store.num_nodes / store.node_off is NULL");
   const bool mats = out->graph_matrix || out->feature_matrix;
@@ -265,7 +279,23 @@ extern "C" int egt_batch_assemble(const egt_batch_desc* desc, const egt_batch_st
   a.d = *desc; a.s = *store; a.o = *out; a.idx = idx;
   a.rows = p.rows; a.tiles = mats ? p.tiles : 0; a.stride = p.stride;
   const dim3 grid((unsigned)(desc->B * a.tiles + desc->B)), block(BA_THREADS);
-  EGT_LAUNCH("k_batch_assemble", k_batch_assemble, grid, block, mats ? p.lds : 0, (hipStream_t)stream, a);
-  EGT_HIP_LAUNCH_CHECK("egt_batch_assemble");
+  if (at) {
+    EGT_LAUNCH("k_batch_assemble_at", k_batch_assemble_at, grid, block, mats ? p.lds : 0, (hipStream_t)stream, a, cursor);
+    EGT_HIP_LAUNCH_CHECK("egt_batch_assemble_at");
+  } else {
+    EGT_LAUNCH("k_batch_assemble", k_batch_assemble, grid, block, mats ? p.lds : 0, (hipStream_t)stream, a);
+    EGT_HIP_LAUNCH_CHECK("egt_batch_assemble");
+  }
   return EGT_OK;
+}
+}  // namespace
+
+extern "C" int egt_batch_assemble(const egt_batch_desc* desc, const egt_batch_store* store, const int32_t* idx,
+                                  const egt_batch_out* out, void* stream) {
+  return batch_assemble_launch(desc, store, idx, nullptr, false, out, stream);
+}
+
+extern "C" int egt_batch_assemble_at(const egt_batch_desc* desc, const egt_batch_store* store, const int32_t* idx_table,
+                                     const uint64_t* cursor, const egt_batch_out* out, void* stream) {
+  return batch_assemble_launch(desc, store, idx_table, cursor, true, out, stream);
 }

@@ -9,6 +9,11 @@ host's signature: the epoch order is the host dataset's own token generator (sam
 batches equal the host's bit for bit, with the same keys, dtypes and shapes.  Per batch the host does index arithmetic on B
 integers, takes N from a host copy of the node counts, copies the indices from a pinned buffer and launches; it never
 synchronises.
+
+For the resident step (``config.resident_step``, egt_amd.graph.ResidentStep) a whole epoch goes to the device at once:
+``epoch_plan`` draws the epoch from the same generator, copies its record indices to the split's device table and returns the
+per-batch ``(B, N)``; ``assemble_at`` (egt_batch_assemble_at) then writes the batch at the table's device cursor into tensors
+the caller owns (``static_batch``), from inside a captured graph.
 """
 from __future__ import annotations
 
@@ -115,30 +120,92 @@ def batch_desc(kinds: dict, B: int, N: int, records: int) -> L.BatchDesc:
     return L.BatchDesc(B=B, N=N, records=records, **kinds)
 
 
-def assemble_batch(desc: L.BatchDesc, store: Dict[str, "torch.Tensor"], idx, want: Sequence[str]) -> Dict[str, "torch.Tensor"]:
+def batch_shapes(desc: L.BatchDesc) -> Dict[str, tuple]:
+    """egt_batch_out's fields -> (shape, torch dtype) for the descriptor, in the shapes of the header"""
+    import torch
+    B, N = desc.B, desc.N
+    f32, i32 = torch.float32, torch.int32
+    pe_tail = (desc.pe_features, 2) if desc.pe_kind == L.BATCH_PE_SVD else (desc.pe_features,)
+    return dict(graph_matrix=((B, N, N), f32),
+                feature_matrix=((B, N, N, 1), f32) if desc.edge_kind == L.BATCH_F32 else ((B, N, N), i32),
+                node_features=((B, N, desc.node_width), f32) if desc.node_kind == L.BATCH_F32 else ((B, N), i32),
+                pe=((B, N) + pe_tail, f32),
+                target={L.BATCH_TGT_GRAPH_F32: ((B, 1), f32), L.BATCH_TGT_GRAPH_I32: ((B,), i32),
+                        L.BATCH_TGT_NODE_I32: ((B, N), i32)}[desc.target_kind],
+                num_nodes=((B,), i32))
+
+
+def assemble_batch(desc: L.BatchDesc, store: Dict[str, "torch.Tensor"], idx, want: Sequence[str],
+                   out: Optional[Dict[str, "torch.Tensor"]] = None, cursor=None) -> Dict[str, "torch.Tensor"]:
     """egt_batch_assemble on the current stream: ``store`` maps the fields of egt_batch_store to device tensors (absent =
     NULL), ``idx`` is the int32 device tensor of record indices, ``want`` names the outputs (egt_batch_out's fields).  The
-    outputs are fresh tensors in the shapes of the header."""
+    outputs are fresh tensors in the shapes of the header, or -- with ``out`` -- the caller's own tensors of those shapes
+    (a captured step's static batch).  With ``cursor`` (a device int64 word) the call is egt_batch_assemble_at: ``idx`` is
+    the index table and the batch is its B entries from ``*cursor`` on, read when the kernel runs."""
     import torch
     lib = L.load()
     if lib.egt_batch_supported(C.byref(desc)) != 1:
         lib.egt_batch_assemble(C.byref(desc), None, None, None, None)       # (leaves the reason)
         raise ValueError("egt_batch_assemble does not cover this batch: " + lib.egt_last_error_string().decode(errors="replace"))
-    B, N, dev = desc.B, desc.N, idx.device
-    f32, i32 = torch.float32, torch.int32
-    pe_tail = (desc.pe_features, 2) if desc.pe_kind == L.BATCH_PE_SVD else (desc.pe_features,)
-    shapes = dict(graph_matrix=((B, N, N), f32),
-                  feature_matrix=((B, N, N, 1), f32) if desc.edge_kind == L.BATCH_F32 else ((B, N, N), i32),
-                  node_features=((B, N, desc.node_width), f32) if desc.node_kind == L.BATCH_F32 else ((B, N), i32),
-                  pe=((B, N) + pe_tail, f32),
-                  target={L.BATCH_TGT_GRAPH_F32: ((B, 1), f32), L.BATCH_TGT_GRAPH_I32: ((B,), i32),
-                          L.BATCH_TGT_NODE_I32: ((B, N), i32)}[desc.target_kind],
-                  num_nodes=((B,), i32))
-    out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
+    dev = idx.device
+    shapes = batch_shapes(desc)
+    if out is None:
+        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
+    else:
+        for k in want:
+            t = out.get(k)
+            if t is None or tuple(t.shape) != shapes[k][0] or t.dtype != shapes[k][1] or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"assemble_batch: out[{k!r}] must be a contiguous {shapes[k][1]} tensor of shape {shapes[k][0]} on {dev}")
+        out = {k: out[k] for k in want}
     st = L.params_struct(L.BatchStore, L.BATCH_STORE_FIELDS, [store.get(f) for f in L.BATCH_STORE_FIELDS])
     ot = L.params_struct(L.BatchOut, L.BATCH_OUT_FIELDS, [out.get(f) for f in L.BATCH_OUT_FIELDS])
-    L.check(lib.egt_batch_assemble(C.byref(desc), C.byref(st), L.ptr(idx), C.byref(ot), L.current_stream()))
+    if cursor is None:
+        L.check(lib.egt_batch_assemble(C.byref(desc), C.byref(st), L.ptr(idx), C.byref(ot), L.current_stream()))
+    else:
+        if cursor.dtype != torch.int64 or cursor.numel() != 1 or cursor.device != dev:
+            raise ValueError(f"assemble_batch: the cursor is one int64 word on {dev}")
+        if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() < desc.B:
+            raise ValueError(f"assemble_batch: the index table is a contiguous int32 tensor; one of {idx.numel()} entries cannot hold a batch of {desc.B}")
+        L.check(lib.egt_batch_assemble_at(C.byref(desc), C.byref(st), L.ptr(idx), L.ptr(cursor), C.byref(ot), L.current_stream()))
     return out
+
+
+class EpochPlan:
+    """One epoch of a split for the resident step: ``ids`` (record indices in the epoch's order, int32), ``batches``
+    [(B_i, N_i)] and ``offsets`` (where batch i starts in ``ids``); ``table`` is the device table the indices were copied
+    to (``ids`` occupies its first len(ids) entries) and ``cursor`` the device word the captured steps read."""
+
+    def __init__(self, split, ids, batches, table=None, cursor=None):
+        self.split, self.ids, self.batches = split, ids, batches
+        self.offsets = np.concatenate([[0], np.cumsum([b for b, _ in batches], dtype=np.int64)])[:-1].astype(np.int64) if batches \
+            else np.zeros(0, np.int64)
+        self.table, self.cursor = table, cursor
+
+    def __len__(self):
+        return len(self.batches)
+
+
+def plan_epoch(host: GraphDataset, split: str, index: Dict[str, int], num_nodes: np.ndarray, batch_size: int,
+               drop_remainder=False) -> EpochPlan:
+    """One epoch of ``host.iter_tokens(split)`` -- the draws ``batches`` would make from the dataset's generator, in its order
+    -- cut into batches of ``batch_size`` (a short last one unless ``drop_remainder``).  ``index`` maps a token to its record
+    in the packed split, ``num_nodes`` is the host copy of the split's node counts: N_i is the batch's longest graph, or the
+    dataset's fixed ``max_length``.  Host only."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+    ids = np.fromiter((index[t] for t in host.iter_tokens(split)), np.int32)
+    full = len(ids) // batch_size
+    sizes = [batch_size] * full + ([len(ids) - full * batch_size] if len(ids) % batch_size and not drop_remainder else [])
+    ids = ids[:sum(sizes)]
+    fixed = None if host.max_length is None else int(host.max_length)
+    batches, o = [], 0
+    for b in sizes:
+        longest = int(num_nodes[ids[o:o + b]].max())
+        if fixed is not None and longest > fixed:
+            raise ValueError(f"a record with {longest} nodes exceeds the padded shape ({fixed},)")
+        batches.append((b, longest if fixed is None else fixed))
+        o += b
+    return EpochPlan(split, ids, batches)
 
 
 class _Split:
@@ -152,6 +219,9 @@ class _Split:
         self.num_nodes_host = packed["num_nodes"]
         self.store = {f: torch.from_numpy(np.ascontiguousarray(packed[f])).to(device) for f in STORE_FIELDS if f in packed}
         self.nbytes = sum(t.numel() * t.element_size() for t in self.store.values())
+        self.table = self.cursor = None              # epoch_plan: the split's index table and its cursor, made on first use
+        self.staging = []                            # [pinned int32 buffer, event of its last copy] x 2
+        self.plans = 0
 
 
 class DeviceGraphDataset:
@@ -211,8 +281,9 @@ class DeviceGraphDataset:
             raise ValueError(f"{_pe_name(h)} was excluded when the dataset went to the device: its rows were never computed")
         return keys
 
-    def assemble(self, split: str, ids: Sequence[int]) -> dict:
-        """the padded batch of the records ``ids`` (indices into the split, store order) as device tensors"""
+    def assemble(self, split: str, ids: Sequence[int], out: Optional[dict] = None) -> dict:
+        """the padded batch of the records ``ids`` (indices into the split, store order) as device tensors: fresh ones, or
+        ``out`` (a ``static_batch`` of the batch's shape)"""
         import torch
         sp = self._splits[split]
         ids = np.asarray(ids, np.int32)
@@ -224,8 +295,59 @@ class DeviceGraphDataset:
         staged.numpy()[:] = ids
         idx = staged.to(self.device, non_blocking=True)
         keys = self._keys(sp)
-        out = assemble_batch(batch_desc(sp.kinds, len(ids), N, sp.records), sp.store, idx, [f for _, f in keys])
+        out = assemble_batch(batch_desc(sp.kinds, len(ids), N, sp.records), sp.store, idx, [f for _, f in keys],
+                             out=None if out is None else {f: out[k] for k, f in keys})
         return {k: out[f] for k, f in keys}
+
+    # ---- the resident step: a whole epoch's indices on the device, batches written into the caller's tensors ----
+    def plan_tokens(self, split: str, batch_size: int, drop_remainder=False) -> EpochPlan:
+        """``plan_epoch`` over this dataset's split: host only, nothing is copied"""
+        sp = self._splits[split]
+        return plan_epoch(self.host, split, sp.index, sp.num_nodes_host, batch_size, drop_remainder)
+
+    def epoch_plan(self, split: str, batch_size: int, drop_remainder=False) -> EpochPlan:
+        """``plan_tokens`` with the indices in the split's persistent device table (one asynchronous copy from pinned memory on
+        the current stream) and the split's cursor set to 0.  Two pinned buffers take turns and each waits for the event of
+        its last copy, so a buffer is never rewritten before that copy has run; the host never waits for the GPU unless two
+        plans are still in flight."""
+        import torch
+        plan = self.plan_tokens(split, batch_size, drop_remainder)
+        sp = self._splits[split]
+        if sp.table is None:
+            sp.table = torch.zeros(max(sp.records, 1), dtype=torch.int32, device=self.device)
+            sp.cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+            sp.staging = [[torch.empty(max(sp.records, 1), dtype=torch.int32).pin_memory(), None] for _ in range(2)]
+        slot = sp.staging[sp.plans % 2]
+        sp.plans += 1
+        if slot[1] is not None and not slot[1].query():
+            slot[1].synchronize()                    # (the copy of two plans ago: long done unless epochs are a few steps long)
+        n = len(plan.ids)
+        slot[0].numpy()[:n] = plan.ids
+        sp.table[:n].copy_(slot[0][:n], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        sp.cursor.zero_()
+        plan.table, plan.cursor = sp.table, sp.cursor
+        return plan
+
+    def batch_keys(self, split: str) -> List[Tuple[str, str]]:
+        return self._keys(self._splits[split])
+
+    def static_batch(self, split: str, B: int, N: int) -> dict:
+        """uninitialised tensors of one (B, N) batch, keyed as the batches are: what ``assemble_at`` writes into"""
+        import torch
+        sp = self._splits[split]
+        shapes = batch_shapes(batch_desc(sp.kinds, B, N, sp.records))
+        return {k: torch.empty(shapes[f][0], dtype=shapes[f][1], device=self.device) for k, f in self._keys(sp)}
+
+    def assemble_at(self, plan: EpochPlan, B: int, N: int, out: dict) -> dict:
+        """the batch of the B records at the plan's cursor, written into ``out`` (a ``static_batch``): one launch of
+        egt_batch_assemble_at on the current stream, capturable; the cursor is not moved"""
+        sp = self._splits[plan.split]
+        keys = self._keys(sp)
+        assemble_batch(batch_desc(sp.kinds, B, N, sp.records), sp.store, plan.table, [f for _, f in keys],
+                       out={f: out[k] for k, f in keys}, cursor=plan.cursor)
+        return out
 
     def _finish(self, split, ids, map_fn, shard, train):
         counts = None

@@ -8,6 +8,9 @@ every call) — moves into device memory: `egt_block_desc.flags & EGT_BF_SEED_DE
 uint64 at `desc.seed_device` into their seed when they RUN.  `DeviceSeeds.advance()` is itself a captured
 launch, so every replay draws a fresh sample, and the sequence of samples is bit-identical to the eager
 path's host-side `EGT.next_seed()` sequence (tests/test_graph_gpu.py).
+
+`ResidentStep` captures the rest of a training step around it -- the batch's assembly in front, the fused update and the epoch's
+metric sums (`DeviceAccumulator`, egt_accumulate) behind -- so that a warm step is one replay and nothing is read back.
 """
 from __future__ import annotations
 
@@ -116,6 +119,95 @@ class GraphedStep:
         self.replays = 0
 
     def replay(self):
+        self.graph.replay()
+        self.replays += 1
+        return self.result
+
+
+class DeviceAccumulator:
+    """K (sum, count) pairs summed in fp64 on the device by egt_accumulate (csrc/egt_accum.hip): what a loop of
+    ``a[0] += float(s); a[1] += float(c)`` keeps on the host, without the two read-backs per pair and step.  ``add`` copies
+    the step's values into a static fp32 stage (the item table points there, so it is written once) and launches the
+    accumulation: no synchronisation, capturable.  ``read`` is the one read-back, at the end of an epoch or a pass."""
+
+    def __init__(self, K: int, device):
+        import ctypes as C
+        from . import _lib as L
+        if not 1 <= K <= L.ACC_MAX_ITEMS:
+            raise ValueError(f"DeviceAccumulator: K must be in 1..{L.ACC_MAX_ITEMS} (got {K})")
+        self.K, self._L, self._lib = K, L, L.load()
+        self.acc = torch.zeros(2 * K, dtype=torch.float64, device=device)
+        self.stage = torch.zeros(2 * K, dtype=torch.float32, device=device)
+        items = (L.AccItem * K)()
+        for k in range(K):
+            items[k].sum, items[k].count = self.stage.data_ptr() + 8 * k, self.stage.data_ptr() + 8 * k + 4
+        self._host = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).pin_memory()    # (kept: the copy is asynchronous)
+        self.items = torch.empty(C.sizeof(L.AccItem) * K, dtype=torch.uint8, device=device)
+        self.items.copy_(self._host, non_blocking=True)
+
+    def zero(self):
+        self.acc.zero_()
+
+    def add(self, pairs):
+        """pairs: K (sum, count), each a 0-dim device tensor or a Python number"""
+        if len(pairs) != self.K:
+            raise ValueError(f"DeviceAccumulator: {len(pairs)} pairs for K = {self.K}")
+        for i, v in enumerate(x for p in pairs for x in p):
+            if torch.is_tensor(v):
+                self.stage[i].copy_(v.detach().reshape(()))
+            else:
+                self.stage[i].fill_(float(v))
+        L = self._L
+        L.check(self._lib.egt_accumulate(L.ptr(self.acc), L.ptr(self.items), self.K, L.current_stream()))
+
+    def read(self):
+        """[[sum, count]] * K as Python floats (synchronises)"""
+        v = self.acc.tolist()
+        return [[v[2 * k], v[2 * k + 1]] for k in range(self.K)]
+
+
+class ResidentStep:
+    """A whole training step of one batch geometry as ONE hipGraph: the captured chain is
+
+        seeds.advance() -> assemble() -> fn() -> optimizer.step() -> accumulate(result) -> advance()
+
+    assemble    writes the step's batch into the static tensors fn reads (egt_batch_assemble_at at the epoch's cursor)
+    fn          forward + loss + backward on those tensors (GraphedStep's contract); its return value is ``result``
+    optimizer   a FlatOptimizer: its two launches read the flat gradient buffer fn wrote
+    accumulate  adds the step's loss and metric sums (``result``) to the epoch's device accumulator
+    advance     moves the cursor past the batch (egt_seed_advance by B)
+    The eager warm-up in front of the capture runs seeds.advance, assemble and fn only -- no update, no accumulation, no
+    cursor move -- and its mask sample is discarded, as GraphedStep's is.  ``optimizer.push_lr()`` runs before the capture and
+    before every replay, never inside: a captured 16-byte copy would re-apply the rate of the capture on every replay."""
+
+    def __init__(self, assemble, fn, optimizer, accumulate, advance, seeds: DeviceSeeds | None = None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("ResidentStep needs a GPU (hipGraph capture)")
+        self.optimizer, self.seeds = optimizer, seeds
+        optimizer.push_lr()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            if seeds is not None:
+                seeds.advance()
+            assemble()
+            r = fn()
+            del r
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=side):
+            if seeds is not None:
+                seeds.advance()
+            assemble()
+            self.result = fn()
+            optimizer.step()               # (its push_lr finds the rate already on the device: nothing is copied in here)
+            accumulate(self.result)
+            advance()
+        self.replays = 0
+
+    def replay(self):
+        self.optimizer.push_lr()
         self.graph.replay()
         self.replays += 1
         return self.result

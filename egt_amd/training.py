@@ -99,6 +99,9 @@ def default_config(scheme: str = "zinc.svd") -> Config:
                                  # egt_amd.optim.FlatOptimizer (same arithmetic and checkpoints as torch.optim); needs a GPU
         device_dataset=False,    # (not a reference key) the dataset's packed records resident on the GPU, padded batches assembled
                                  # there: egt_amd.device_data (same batches and epoch order as the host pipeline); needs a GPU
+        resident_step=False,     # (not a reference key) batch assembly, step, update and the epoch's metric sums replayed as ONE
+                                 # hipGraph per step, no per-step synchronisation: egt_amd.graph.ResidentStep; needs use_hipgraph,
+                                 # fused_optimizer and device_dataset, one process
     )
     c.update(  # BaseDCModelScheme
         model_name="dc", dataset_name="dataset",
@@ -359,6 +362,32 @@ def _barrier():
         torch.distributed.barrier()
 
 
+class _ResidentBatch:
+    """config.resident_step: batch `i` of an epoch plan -- B graphs padded to N, starting at `offset` of the plan's index
+    table.  What the training set yields in place of tensors: the batch is assembled inside the step's graph."""
+    __slots__ = ("dataset", "plan", "i", "B", "N", "offset")
+
+    def __init__(self, dataset, plan, i):
+        self.dataset, self.plan, self.i = dataset, plan, i
+        (self.B, self.N), self.offset = plan.batches[i], int(plan.offsets[i])
+
+
+class _ResidentEpochs:
+    """the training split under config.resident_step: an iteration draws one epoch from the host dataset's token generator
+    (the draws, and the order, of the device dataset's ``batches``), copies its record indices to the device table once and
+    yields the epoch's _ResidentBatch descriptors"""
+
+    def __init__(self, dataset, split, batch_size):
+        self.ds, self.split, self.batch_size = dataset, split, batch_size
+
+    def __iter__(self):
+        plan = self.ds.epoch_plan(self.split, self.batch_size)
+        return (_ResidentBatch(self.ds, plan, i) for i in range(len(plan)))
+
+    def __len__(self):
+        return -(-len(self.ds.record_tokens[self.split]) // self.batch_size)
+
+
 # ------------------------------------------------------------------------------------------ scheme --
 class ZincSVDScheme:
     """lib.training.schemes.zinc.svd.SCHEME: TrainingBase protocol around the ZINC model."""
@@ -443,16 +472,25 @@ class ZincSVDScheme:
         self.loss_fn = self.get_loss()
         self.flat = None
         self._graphs, self._seeds = {}, None
+        self._train_acc = None
         if self._use_graph and not on_gpu:
             raise ValueError("config.use_hipgraph needs the model on a GPU (device='cuda')")
         if self._fused_opt and not on_gpu:
             raise ValueError("config.fused_optimizer needs the model on a GPU (device='cuda')")
         self._device_dataset_check()
+        self._resident = bool(self.config.resident_step)
+        self._resident_check()
         if self._use_graph or self._fused_opt or (self.config.distributed and torch.distributed.is_available() and torch.distributed.is_initialized()):
             from .dp import FlatGradAllReduce
             self.flat = FlatGradAllReduce(params, direct=True)     # one flat-buffer all-reduce per step (MirroredStrategy, :230-247)
         if self._fused_opt:                           # the update reads that buffer: built after it
             self.optimizer = self.get_optimizer(params)
+        if self._resident:
+            from .graph import DeviceAccumulator
+            # the epoch's sums: the loss (count 1 per step), then -- distance objective -- every metric of the scheme
+            self._train_acc_keys = list(self.get_metrics()) if self._distance_on() else []
+            self._train_acc = DeviceAccumulator(1 + len(self._train_acc_keys), self.device)
+            self._eval_acc, self._plan_of, self._cursor_host, self._resident_captures = {}, None, 0, 0
         if self._use_graph:                           # every captured geometry writes its gradients into this one flat buffer
             from .graph import DeviceSeeds
             from .layers import EGT
@@ -544,6 +582,83 @@ class ZincSVDScheme:
             save_config_to_file(self.config_input, self.config.config_path + "_input.json")
         _barrier()
 
+    # ---- the resident step (config.resident_step) ----
+    def _resident_check(self):
+        """config.resident_step composes the three opt-in keys into one graph replay per step: refused without any of them,
+        off the GPU, and with more than one rank (the gradient all-reduce sits between backward and update)"""
+        c = self.config
+        if not c.resident_step:
+            return
+        missing = [k for k in ("use_hipgraph", "fused_optimizer", "device_dataset") if not c[k]]
+        if missing:
+            raise ValueError("config.resident_step needs " + ", ".join(f"config.{k}" for k in missing) + " as well")
+        if not (self.device is not None and torch.device(self.device).type == "cuda"):
+            raise ValueError("config.resident_step needs the model on a GPU (device='cuda')")
+        if _dist_on() and torch.distributed.get_world_size() > 1:
+            raise ValueError("config.resident_step is a one-process path: the gradient all-reduce of "
+                             f"{torch.distributed.get_world_size()} ranks is not part of the captured step")
+
+    def _sync_graphs(self):
+        """wait for the stream before a captured graph is dropped: nothing synchronises per step under config.resident_step,
+        so a replay of the graph may still be running"""
+        if getattr(self, "_resident", False) and getattr(self, "_graphs", None):
+            torch.cuda.current_stream().synchronize()
+
+    def release_graphs(self):
+        """drop every captured step graph (teardown): synchronises first where replays may be in flight"""
+        self._sync_graphs()
+        if getattr(self, "_graphs", None):
+            self._graphs.clear()
+
+    def __del__(self):
+        try:
+            if getattr(self, "_resident", False):      # (with the key off nothing changes at deletion)
+                self.release_graphs()
+        except Exception:      # noqa: BLE001 (interpreter shutdown: nothing left to wait for)
+            pass
+
+    def _resident_loss(self, rb):
+        """config.resident_step: the whole step of batch `rb` (a _ResidentBatch of the epoch's plan) as one graph replay.  A
+        graph is captured per geometry (B, N); its static batch is written by egt_batch_assemble_at from the epoch's index
+        table at the device cursor, which the graph moves past the batch as its last node."""
+        from .graph import ResidentStep
+        from . import _lib as L
+        plan, dd = rb.plan, rb.dataset
+        if plan is not self._plan_of:                  # a new epoch: epoch_plan left the device cursor at 0
+            self._plan_of, self._cursor_host = plan, 0
+        if rb.offset != self._cursor_host:             # a step out of the plan's order (steps skipped, a batch repeated)
+            plan.cursor.fill_(int(rb.offset))
+        key = (plan.split, rb.B, rb.N)
+        ent = self._graphs.get(key)
+        if ent is None:
+            static = dd.static_batch(plan.split, rb.B, rb.N)
+            lib, cursor, B = L.load(), plan.cursor, rb.B
+
+            def fn():
+                self.flat.zero(); self.flat.rebind()
+                loss, ms = self.batch_loss(static)
+                loss.backward()
+                return loss.detach(), ms
+
+            def accumulate(result):
+                loss, ms = result
+                self._train_acc.add([(loss, 1.0)] + [ms[k] for k in self._train_acc_keys])
+
+            def advance():
+                L.check(lib.egt_seed_advance(L.ptr(cursor), 1, B, L.current_stream()))
+            while len(self._graphs) >= self.MAX_GRAPHS:
+                self._sync_graphs()                    # the least recently used graph may still be replaying
+                self._graphs.pop(next(iter(self._graphs)))
+            ent = self._graphs[key] = (static, ResidentStep(lambda: dd.assemble_at(plan, B, rb.N, static), fn, self.optimizer,
+                                                            accumulate, advance, self._seeds), cursor)
+            self._resident_captures += 1
+        else:
+            if ent[2] is not plan.cursor:
+                raise RuntimeError("the split's device cursor changed under a captured step")
+            self._graphs[key] = self._graphs.pop(key)          # most recently used last
+        self._cursor_host = rb.offset + rb.B
+        return ent[1].replay()
+
     # ---- data ----
     def _device_dataset_check(self):
         on_gpu = self.device is not None and torch.device(self.device).type == "cuda"
@@ -587,6 +702,9 @@ class ZincSVDScheme:
             out = source.get_batched_data(bs, shard=shard)
             out = out if isinstance(out, tuple) else (out,)
             trainset, valset, testset = (list(out) + [None, None])[:3]
+            if c.resident_step and "training" in splits and not (getattr(self, "eval_flag", False) or getattr(self, "pred_flag", False)):
+                self._resident_check()
+                trainset = _ResidentEpochs(source, "training", bs["training"])
         self.trainset, self.valset, self.testset = trainset, valset, testset
 
     # ---- one step / one epoch ----
@@ -677,6 +795,13 @@ class ZincSVDScheme:
                 self.set_lr(lr)
             self.stop_training |= stop
         self.model.train()
+        if self._resident:
+            if not isinstance(batch, _ResidentBatch):
+                raise ValueError("config.resident_step trains from the scheme's own device-resident dataset (load_data without iterables)")
+            loss, ms = self._resident_loss(batch)
+            self._step_metrics = ms if self._distance_on() else None
+            self.state.global_step += 1              # on_batch_end (:136)
+            return loss                              # a 0-dim device tensor (rewritten by the geometry's next replay): no read-back
         if self._use_graph:
             loss, ms = self._graphed_loss(batch)
         else:
@@ -701,16 +826,42 @@ class ZincSVDScheme:
         return float(loss.detach())
 
     @torch.no_grad()
-    def evaluate(self, dataset, max_steps=None):
-        """validation metrics: {name: weighted mean}"""
+    def evaluate_on_device(self, dataset, max_steps=None):
+        """config.resident_step: the batches of an evaluation pass (eager forward), their (sum, count) pairs added on the device
+        by egt_accumulate in batch order.  Returns (metric names, the accumulator) without synchronising: its ``read()`` is the
+        pass's one read-back."""
+        from .graph import DeviceAccumulator
         self.model.eval()
-        acc = {}
+        keys, dacc = (), None
         for i, b in enumerate(dataset):
             if max_steps is not None and i >= max_steps:
                 break
             _, ms = self.batch_loss(b)
-            for k, (sm, cnt) in ms.items():
-                a = acc.setdefault(k, [0.0, 0.0]); a[0] += float(sm); a[1] += float(cnt)
+            if dacc is None:
+                keys = tuple(ms)
+                dacc = self._eval_acc.get(keys)
+                if dacc is None:
+                    dacc = self._eval_acc[keys] = DeviceAccumulator(len(keys), self.device)
+                dacc.zero()
+            dacc.add([ms[k] for k in keys])
+        return keys, dacc
+
+    @torch.no_grad()
+    def evaluate(self, dataset, max_steps=None):
+        """validation metrics: {name: weighted mean}"""
+        self.model.eval()
+        acc = {}
+        if getattr(self, "_resident", False):         # the (sum, count) pairs stay on the device: one read-back per pass
+            keys, dacc = self.evaluate_on_device(dataset, max_steps)
+            if keys:
+                acc = dict(zip(keys, dacc.read()))
+        else:
+            for i, b in enumerate(dataset):
+                if max_steps is not None and i >= max_steps:
+                    break
+                _, ms = self.batch_loss(b)
+                for k, (sm, cnt) in ms.items():
+                    a = acc.setdefault(k, [0.0, 0.0]); a[0] += float(sm); a[1] += float(cnt)
         if self.config.distributed and _dist_on():    # the split is sharded: sums and counts of all ranks
             keys = self.metric_keys()                 # a fixed list per scheme: a rank without batches sends zeros of the same shape
             t = torch.tensor([x for k in keys for x in acc.get(k, [0.0, 0.0])], dtype=torch.float64,
@@ -731,18 +882,31 @@ class ZincSVDScheme:
                 break
             losses = []
             msum = {}                                # distance objective: training sums of every metric but the loss
+            if self._resident:
+                self._train_acc.zero()
             for i, b in enumerate(self.trainset):
                 if c.steps_per_epoch is not None and i >= c.steps_per_epoch:
                     break
-                losses.append(self.train_step(b))
-                for k, (sm, cnt) in (getattr(self, "_step_metrics", None) or {}).items():
-                    if k != "loss":
-                        a = msum.setdefault(k, [0.0, 0.0]); a[0] += float(sm); a[1] += float(cnt)
+                if self._resident:
+                    self.train_step(b)               # loss and metric sums go to the device accumulator inside the graph
+                else:
+                    losses.append(self.train_step(b))
+                    for k, (sm, cnt) in (getattr(self, "_step_metrics", None) or {}).items():
+                        if k != "loss":
+                            a = msum.setdefault(k, [0.0, 0.0]); a[0] += float(sm); a[1] += float(cnt)
                 if self.stop_training:
                     break
-            loss_mean = float(np.mean(losses)) if losses else math.nan
+            if self._resident:                       # the epoch's one read-back
+                got = self._train_acc.read()
+                msum = dict(zip(self._train_acc_keys, got[1:]))
+                stepped = got[0][1] > 0
+                loss_mean = got[0][0] / got[0][1] if stepped else math.nan
+            else:
+                stepped = bool(losses)
+                loss_mean = float(np.mean(losses)) if stepped else math.nan
+            self.epoch_sums = {k: list(v) for k, v in msum.items()}      # this rank's training (sum, count) of the epoch, per metric
             if c.distributed and _dist_on():         # the logged training loss is the mean over all ranks (a rank-local value would let a train-metric monitor desynchronise them)
-                t = torch.tensor([loss_mean if losses else 0.0, 1.0 if losses else 0.0], dtype=torch.float64,
+                t = torch.tensor([loss_mean if stepped else 0.0, 1.0 if stepped else 0.0], dtype=torch.float64,
                                  device=self.device if torch.distributed.get_backend() == "nccl" else "cpu")
                 torch.distributed.all_reduce(t)
                 loss_mean = float(t[0] / t[1]) if float(t[1]) > 0 else math.nan
@@ -851,6 +1015,8 @@ class ZincSVDScheme:
         self.load_state()
         self.train_model()
         self.finalize_training()
+        if self._resident:                           # replays may still be in flight: wait before the graphs go
+            self.release_graphs()
 
 
 class PatternSVDScheme(ZincSVDScheme):

@@ -847,6 +847,25 @@ typedef struct egt_batch_out {
 int egt_batch_supported(const egt_batch_desc* desc);
 int egt_batch_assemble(const egt_batch_desc* desc, const egt_batch_store* store, const int32_t* idx /* device, [B] */,
                        const egt_batch_out* out, void* stream);
+/* egt_batch_assemble with idx = idx_table + *cursor: the B indices of the batch are idx_table[*cursor .. *cursor + B).  `cursor`
+ * (device, 8-byte aligned) is read by the kernel when it RUNS, as egt_block_desc.seed_device is, so a captured launch walks the
+ * table from replay to replay while egt_seed_advance(cursor, 1, B, stream) moves the cursor behind it.  The caller keeps
+ * *cursor + B inside the table.  Checks, outputs and coverage are egt_batch_assemble's; the table and the cursor are only read. */
+int egt_batch_assemble_at(const egt_batch_desc* desc, const egt_batch_store* store, const int32_t* idx_table /* device, int32[capacity] */,
+                          const uint64_t* cursor /* device */, const egt_batch_out* out, void* stream);
+
+/* ---- resident training step: epoch sums of (metric sum, count) pairs on the device ----
+ * One launch of one wave: for k < K   acc[2k] += (double)*items[k].sum;   acc[2k+1] += items[k].count ? (double)*items[k].count
+ * : (double)items[k].count_value.  `items` (device, 8-byte aligned) and what it points to are only read, when the kernel runs;
+ * nothing outside acc[0 .. 2K) is written.  The additions of a pair happen in launch order, in fp64: the accumulator holds
+ * what the same sequence of `a += (double)x` gives on the host.  Plain stores, no atomics, no workspace; capturable.
+ * EGT_E_NULL (acc / items) and EGT_E_SHAPE (K outside 1..32, an unaligned pointer) are returned before any launch. */
+typedef struct egt_acc_item {
+  const float* sum;   /* device: this step's sum */
+  const float* count; /* device: this step's count, or NULL */
+  float count_value;  /* the count where `count` is NULL */
+} egt_acc_item;       /* 24 bytes */
+int egt_accumulate(double* acc /* device, [2K] */, const egt_acc_item* items /* device, [K] */, int32_t K, void* stream);
 
 #ifdef __cplusplus
 }
