@@ -296,6 +296,13 @@ _PROTOS = {
     "egt_pair_fwd": (C.c_int, [C.POINTER(BlockDesc), C.POINTER(BlockParams)] + [_VP] * 8),
     "egt_pair_bwd": (C.c_int, [C.POINTER(BlockDesc), C.POINTER(BlockParams)] + [_VP] * 9
                      + [C.POINTER(BlockParams)] + [_VP] * 2),
+    "egt_pair_block_supported": (C.c_int, [C.POINTER(BlockDesc)]),
+    "egt_pair_block_launch_form": (C.c_char_p, [C.POINTER(BlockDesc)]),
+    "egt_pair_block_saved_bytes": (C.c_size_t, [C.POINTER(BlockDesc)]),
+    "egt_pair_block_workspace_bytes": (C.c_size_t, [C.POINTER(BlockDesc)]),
+    "egt_pair_block_fwd": (C.c_int, [C.POINTER(BlockDesc), C.POINTER(BlockParams)] + [_VP] * 8),
+    "egt_pair_block_bwd": (C.c_int, [C.POINTER(BlockDesc), C.POINTER(BlockParams)] + [_VP] * 8
+                           + [C.POINTER(BlockParams)] + [_VP] * 2),
     "egt_ffn_supported": (C.c_int, [C.POINTER(FfnDesc)]),
     "egt_ffn_workspace_bytes": (C.c_size_t, [C.POINTER(FfnDesc)]),
     "egt_ffn_fwd": (C.c_int, [C.POINTER(FfnDesc), C.POINTER(FfnParams)] + [_VP] * 4),

@@ -399,6 +399,35 @@ int egt_pair_bwd(const egt_block_desc* desc, const egt_block_params* params, con
                  const void* d_v_att, const void* d_e_out, void* d_qkv, void* d_e,
                  const egt_block_params* grads, void* workspace, void* stream);
 
+/* ---- the whole block at large heads: the node side of mha_block on the library's own fp32 MFMA GEMMs around the pair operator ----
+ *   (h', e') = edge_update_residual(h, e) with mha_block inside (graph_xformer_model_base.py:192-223 + :106-145), covered
+ * exactly where egt_pair_supported() answers 1 (d = 64, H = 8, De = 32, gated 'residual' edge channels, fp32; every flag the pair
+ * operator refuses is refused here the same way, EGT_BF_SEED_DEVICE included).  egt_block_fwd / egt_block_bwd's signature without
+ * attn_mask / rand_mask; all fourteen egt_block_params pointers are read and all fourteen `grads` pointers are written.
+ * Forward: per-row LayerNorm statistics, QKV = LN(h).Wqkv + bqkv (rows normalised while the operand is staged: no [B N, 512] LN(h)
+ * tensor exists in memory, in either direction), egt_pair_fwd, h' = V_att.Wo + bo + h.  Backward: dV_att = dh'.Wo^T, egt_pair_bwd,
+ * d(LN out) = dQKV.Wqkv^T, dh = dh' + LN_bwd, and the node-side parameter gradients as per-row-chunk partials summed in chunk
+ * order (bit-reproducible: no floating-point atomics).  Products are exact fp32 (v_mfma_f32_32x32x2_f32).
+ * `saved` (egt_pair_block_saved_bytes) carries QKV, V_att, the attention row statistics, the LayerNorm row statistics [B N, 2] and
+ * the pair operator's shared workspace from the forward to the backward, which completes parts of it (it is not const there);
+ * `workspace` (egt_pair_block_workspace_bytes) is scratch.  desc->reserved must be 0.  d_e may alias d_e_out; d_h must NOT alias
+ * d_h_out.  Same parameter values in both directions; no allocation, no synchronisation, everything on `stream` (capturable).
+ * egt_pair_block_launch_form: the launch plan, a pure host function of B N, as text:
+ * "tile=<rows per row tile>r/<row tiles>t[/ragged] wgrad=<rows per chunk>r/<row chunks>c[/ragged] ln=<rows>r/<partials>p
+ *  reduce=<reduction launches>", e.g. "tile=128r/9t/ragged wgrad=256r/5c/ragged ln=64r/17p reduce=1".  Thread-local string, valid
+ * until the thread's next call; needs no device; NULL when `desc` is not covered. */
+int egt_pair_block_supported(const egt_block_desc* desc);
+const char* egt_pair_block_launch_form(const egt_block_desc* desc);
+size_t egt_pair_block_saved_bytes(const egt_block_desc* desc);
+size_t egt_pair_block_workspace_bytes(const egt_block_desc* desc);
+int egt_pair_block_fwd(const egt_block_desc* desc, const egt_block_params* params, const void* h,
+                       const void* e, const uint8_t* key_mask, void* h_out, void* e_out, void* saved,
+                       void* workspace, void* stream);
+int egt_pair_block_bwd(const egt_block_desc* desc, const egt_block_params* params, const void* h,
+                       const void* e, const uint8_t* key_mask, const void* saved, const void* d_h_out,
+                       const void* d_e_out, void* d_h, void* d_e, const egt_block_params* grads,
+                       void* workspace, void* stream);
+
 /* ---- channel FFN (the step after the attention block in every layer) ----
  * Replaces ffnlr1 / ffnact / ffnlr2 of lib/models/graph_xformer_model_base.py:230-258 as
  * ffn_block applies them (:309-324; pre-norm, no cross-talk, ffn_multiplier = 2):
