@@ -27,6 +27,13 @@ ACT_NONE, ACT_LRELU, ACT_RELU, ACT_ELU = 0, 1, 2, 3
 BF_GATE, BF_ATTN_MASK, BF_TRAINING, BF_CLIP, BF_NO_EDGE_LN, BF_SEED_DEVICE = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 BF_STATIC_EDGE = 0x40   # 'bias' edge channels: e is an input only (with BF_NO_EDGE_LN; De = 8 pair kernels)
 BF_SCALE_DEGREE, BF_SCALER_LINEAR = 0x80, 0x100   # degree scalers on the MFMA-tile pair kernels (fp32 edges, gated)
+BF_ATTN_DROPOUT = 0x200   # attention dropout in the MFMA-tile pair kernels (training only); the rate: BlockDesc.reserved = rate_bits(rate)
+
+
+def rate_bits(rate: float) -> int:
+    """fp32 bit pattern of a dropout rate as the int32 that egt_block_desc.reserved carries under BF_ATTN_DROPOUT"""
+    import struct
+    return struct.unpack("<i", struct.pack("<f", float(rate)))[0]
 
 
 class AttnDesc(C.Structure):

@@ -942,7 +942,7 @@ extern "C" int egt_pair_supported(const egt_block_desc* d) {
   if (!d || d->dtype != EGT_F32 || d->H != AH) return 0;
   if (d->d != 64 || d->De != 32) return 0;                                   // the instantiated geometry (BASELINE config 5)
   if (!(d->flags & EGT_BF_GATE)) return 0;                                    // gated attention with edge bias ('residual' edge channels)
-  if (d->flags & (EGT_BF_ATTN_MASK | EGT_BF_NO_EDGE_LN | EGT_BF_SEED_DEVICE | EGT_BF_STATIC_EDGE | EGT_BF_SCALE_DEGREE | EGT_BF_SCALER_LINEAR)) return 0;
+  if (d->flags & (EGT_BF_ATTN_MASK | EGT_BF_NO_EDGE_LN | EGT_BF_SEED_DEVICE | EGT_BF_STATIC_EDGE | EGT_BF_SCALE_DEGREE | EGT_BF_SCALER_LINEAR | EGT_BF_ATTN_DROPOUT)) return 0;
   if (d->B < 1 || d->N < 1 || d->N > 2048) return 0;
   if ((size_t)d->B * d->N * d->N * AH > 0xFFFFFFFFull) return 0;              // 32-bit element index of the mask hash
   return 1;

@@ -33,7 +33,7 @@ struct BlockArgs {
   int spart_n, sbo_n;   // how many workgroup partials the reduction finds in spart / sbo
   int wpart_n;          // ... and in wpart: the row chunks egt_node_launch_wgrads launched (stored there, read by the reduction)
   int guard;    // backward phase guards (always 0 in production, see k_block_bwd_v4)
-  unsigned* dbg; unsigned dbg_t0;   // unused, kept for the argument layout (with dbg2 below)
+  unsigned* dbg; unsigned dbg_t0;   // unused, kept for the argument layout
   int prep;     // node kernels: add the edge-weight preparation workgroup
   const float *nx_nm_g, *nx_nm_b, *nx_Wqkv, *nx_bqkv;   // next block (epi == 2)
   // MFMA-fragment-major copies of Wqkv / Wo (prepared by the forward beside pw, kept in `saved`): what the node-side epilogue /
@@ -59,7 +59,9 @@ struct BlockArgs {
   float *dh, *de;
   float *g_ne_g, *g_ne_b, *g_Wg, *g_bg, *g_We, *g_be, *g_nm_g, *g_nm_b, *g_Wqkv, *g_bqkv, *g_Wo,
       *g_bo, *g_Wr, *g_br;
-  unsigned* dbg2;
+  // EGT_BF_ATTN_DROPOUT (the DO instances, egt_block_do.hip): keep <=> hash >> 8 >= dk_thr on the dropout stream, kept elements x dk_scale.
+  // (These eight bytes used to hold an unused pointer, dbg2: no kernel's argument layout moved.)
+  uint32_t dk_thr; float dk_scale;
 };
 
 template <int DE>
@@ -108,6 +110,9 @@ constexpr int V4R_RR = 2;   // k_block_bwd_v4r: rows per iteration (four spill: 
 #define EGT_SD_BWD_V4 3
 void egt_block_sd_launch_fwd(BlockArgs& a, int r4_waves, bool kvl, bool ml, bool full, const EgtLaunch& s, hipStream_t st);
 void egt_block_sd_launch_bwd(BlockArgs& a, int family, int mm, bool ml, bool full, const EgtLaunch& s, hipStream_t st);
+// Attention-dropout instances (EGT_BF_ATTN_DROPOUT) of the same kernels: egt_block_do.hip, same arguments (a.bf16 picks the edge type)
+void egt_block_do_launch_fwd(BlockArgs& a, int r4_waves, bool kvl, bool ml, bool full, const EgtLaunch& s, hipStream_t st);
+void egt_block_do_launch_bwd(BlockArgs& a, int family, int mm, bool ml, bool full, const EgtLaunch& s, hipStream_t st);
 
 // launchers implemented in egt_node.hip
 void egt_node_launch_pre(BlockArgs& a, hipStream_t st);

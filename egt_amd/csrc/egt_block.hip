@@ -92,6 +92,13 @@ int egt_device_cus() {
   return n;
 }
 
+// EGT_BF_ATTN_DROPOUT: the rate travels as its fp32 bit pattern in desc->reserved
+static float block_drop_rate(const egt_block_desc* d) {
+  float r;
+  memcpy(&r, &d->reserved, sizeof r);
+  return r;
+}
+
 static int block_check(const egt_block_desc* d, bool report) {
   if (!d) EGT_BAD(EGT_E_NULL, "desc is NULL");
   if (d->dtype != EGT_F32 && d->dtype != EGT_BF16) EGT_BAD(EGT_E_DTYPE, "dtype must be EGT_F32 or EGT_BF16 (got %d)", d->dtype);
@@ -117,6 +124,13 @@ static int block_check(const egt_block_desc* d, bool report) {
     if (d->flags & EGT_BF_STATIC_EDGE) EGT_BAD(EGT_E_FLAGS, "EGT_BF_SCALE_DEGREE does not take EGT_BF_STATIC_EDGE");
     if (d->dtype == EGT_BF16) EGT_BAD(EGT_E_DTYPE, "EGT_BF_SCALE_DEGREE with bf16 edge tensors is not covered (fp32 edge tensors only)");
   }
+  if (d->flags & EGT_BF_ATTN_DROPOUT) {   // attention dropout: the DO instances of the MFMA-tile kernels (egt_block_do.hip)
+    if (!(d->flags & EGT_BF_TRAINING)) EGT_BAD(EGT_E_FLAGS, "EGT_BF_ATTN_DROPOUT needs EGT_BF_TRAINING (dropout acts in training only; clear the flag for evaluation)");
+    if (d->flags & EGT_BF_SCALE_DEGREE) EGT_BAD(EGT_E_FLAGS, "EGT_BF_ATTN_DROPOUT does not take EGT_BF_SCALE_DEGREE");
+    if (d->flags & EGT_BF_STATIC_EDGE) EGT_BAD(EGT_E_FLAGS, "EGT_BF_ATTN_DROPOUT does not take EGT_BF_STATIC_EDGE");
+    const float rate = block_drop_rate(d);
+    if (!(rate > 0.0f && rate < 1.0f)) EGT_BAD(EGT_E_FLAGS, "EGT_BF_ATTN_DROPOUT needs a rate in (0, 1) in desc->reserved (fp32 bits; got %g)", (double)rate);
+  }
   return EGT_OK;
 }
 
@@ -134,6 +148,7 @@ enum class BwdKernel { narrow, v4r, v5, v4 };   // k_narrow_bwd {NW} | k_block_b
 static const char* const g_bwd_kernel_name[] = {"k_narrow_bwd", "k_block_bwd_v4r", "k_block_bwd_v5", "k_block_bwd_v4"};
 
 struct BlockPlan {
+  bool dro;    // EGT_BF_ATTN_DROPOUT: the DO instances (egt_block_do.hip) of the MFMA-tile kernels; never the De = 8 VALU kernels
   bool sd;     // EGT_BF_SCALE_DEGREE: the SD instances (egt_block_sd.hip) of the MFMA-tile kernels; never the De = 8 VALU kernels
   bool ml;     // a mask TENSOR is read: the attention mask or a host random-mask buffer (the in-kernel random mask is not one)
   bool full;   // N is a multiple of 16 (else the kernels' ragged forms)
@@ -164,10 +179,14 @@ static BlockPlan plan_for(const egt_block_desc* d, bool ml) {
   const EgtBlockEnv& E = block_env();
   const int B = d->B, N = d->N, cus = egt_device_cus();
   const int groups = (N + BWD_TL - 1) / BWD_TL;   // 16-row groups per graph
-  const bool sd = (d->flags & EGT_BF_SCALE_DEGREE) != 0;   // degree scalers: MFMA-tile kernels only (De = 8 as under EGT_NO_NARROW)
+  // degree scalers, attention dropout: MFMA-tile kernels only (De = 8 as under EGT_NO_NARROW)
+  const bool dro = (d->flags & EGT_BF_ATTN_DROPOUT) != 0;
+  const bool sd = (d->flags & EGT_BF_SCALE_DEGREE) != 0;
+  const bool tile_only = sd || dro;
   BlockPlan P{};
   P.ml = ml;
   P.sd = sd;
+  P.dro = dro;
   P.full = (N % 16) == 0;
 
   // Row groups per graph of the MFMA-tile kernels (two workgroups per CU), where the forward and backward row rules start:
@@ -197,7 +216,7 @@ static BlockPlan plan_for(const egt_block_desc* d, bool ml) {
   const size_t lds_r4 = (size_t)16 * GG::TILE_FLOATS * 4 + lds_kv;
   const size_t lds_r8 = (size_t)32 * GG::TILE_FLOATS * 4 + ((size_t)N * KV_LD + 32 * QS_LD + N) * 4;
   const bool r4 = lds_r4 <= 80 * 1024 - 512, r8 = !r4 && lds_r8 <= 156 * 1024;
-  if (DE == 8 && !ml && !E.no_narrow_fwd && !sd) {
+  if (DE == 8 && !ml && !E.no_narrow_fwd && !tile_only) {
     // VALU pair kernel (egt_narrow.hip): lane = (row, head/channel pair), 4 key quarters per workgroup.  At most one 16-row
     // workgroup per CU: eight key ranges (eight waves); ... per two CUs: eight-row workgroups.  A forced wave count wins over the
     // rule; EGT_NRW_FWD_HALF only matters with eight waves.
@@ -244,7 +263,7 @@ static BlockPlan plan_for(const egt_block_desc* d, bool ml) {
   P.NLR = (N + P.TL - 1) / P.TL;
   P.nwg_bwd = B * P.NLR;
   P.EP = GG::EP;
-  if (DE == 8 && !ml && !E.no_narrow_bwd && !sd) {
+  if (DE == 8 && !ml && !E.no_narrow_bwd && !tile_only) {
     // De = 8 pair kernel (egt_narrow.hip: k_narrow_bwd, three workgroups per CU), ragged N included.  Measured at config 3
     // against v4r / the round-2 quad-lane kernel (two waves per SIMD both): bf16 edge tensors 226 vs 314 us, fp32 243 vs 320 us.
     // At most one workgroup per CU: eight waves share its key tiles (a forced wave count wins).
@@ -374,6 +393,11 @@ static void fill_block(const egt_block_desc* d, const egt_block_params* p, Block
   a.scale = 1.0f / sqrtf((float)d->d);
   a.ln_eps = d->ln_eps;
   a.rm_thr = egt_threshold24(d->random_mask_prob);
+  if (d->flags & EGT_BF_ATTN_DROPOUT) {   // (block_check: training, rate in (0, 1)); as fill_args of egt_attn.hip
+    const float rate = block_drop_rate(d);
+    a.dk_thr = egt_threshold24(rate);
+    a.dk_scale = 1.0f / (1.0f - rate);
+  }
   a.s0 = (uint32_t)(d->seed & 0xFFFFFFFFull);
   a.s1 = (uint32_t)(d->seed >> 32);
   a.sd = (d->flags & EGT_BF_SEED_DEVICE) ? (const uint32_t*)d->seed_device : nullptr;
@@ -468,6 +492,7 @@ static int launch_fwd(BlockArgs& a, const BlockPlan& P, hipStream_t st, bool ski
   a.guard = 0;   // (the always-taken phase branches of the kernels only shape hipcc's scheduling regions)
   a.RGF = P.RGF;
   if (P.sd) egt_block_sd_launch_fwd(a, P.fwd == FwdKernel::r4 ? P.fwd_nw : 0, P.kvl, P.ml, P.full, P.fl, st);
+  else if (P.dro) egt_block_do_launch_fwd(a, P.fwd == FwdKernel::r4 ? P.fwd_nw : 0, P.kvl, P.ml, P.full, P.fl, st);
   else switch (P.fwd) {
     case FwdKernel::narrow: egt_narrow_launch_fwd(a, P.fwd_nw, P.fwd_half, P.fl, st); break;
     case FwdKernel::r4:
@@ -506,6 +531,8 @@ static void launch_bwd(BlockArgs& a, const BlockPlan& P, hipStream_t st, bool to
   a.guard = 0;   // (the always-taken phase branches of the kernels only shape hipcc's scheduling regions)
   if (P.sd)
     egt_block_sd_launch_bwd(a, P.bwd == BwdKernel::v4r ? EGT_SD_BWD_V4R : P.bwd == BwdKernel::v5 ? EGT_SD_BWD_V5 : EGT_SD_BWD_V4, P.mm, P.ml, P.full, P.bl, st);
+  else if (P.dro)
+    egt_block_do_launch_bwd(a, P.bwd == BwdKernel::v4r ? EGT_SD_BWD_V4R : P.bwd == BwdKernel::v5 ? EGT_SD_BWD_V5 : EGT_SD_BWD_V4, P.mm, P.ml, P.full, P.bl, st);
   else switch (P.bwd) {
     case BwdKernel::narrow: egt_narrow_launch_bwd(a, P.bwd_nw, P.bl, st); break;
     case BwdKernel::v4r:
@@ -544,6 +571,10 @@ static int stack_flags_check(const egt_block_desc* d, bool report) {
   }
   if (d && (d->flags & (EGT_BF_SCALE_DEGREE | EGT_BF_SCALER_LINEAR))) {   // the chained epilogue / prologue of a stack carry no degree
     if (report) egt_set_error("egt_stack_* does not take EGT_BF_SCALE_DEGREE (use egt_block_fwd / egt_block_bwd per layer)");
+    return EGT_E_FLAGS;
+  }
+  if (d && (d->flags & EGT_BF_ATTN_DROPOUT)) {   // a stack call has one seed per layer for the random mask only
+    if (report) egt_set_error("egt_stack_* does not take EGT_BF_ATTN_DROPOUT (use egt_block_fwd / egt_block_bwd per layer)");
     return EGT_E_FLAGS;
   }
   return EGT_OK;

@@ -1,7 +1,7 @@
 // Backward pair kernels of the fused attention block (included by egt_block.hip, which holds the dispatch):
 // k_block_bwd_v4 (mask tensors / ragged N / bf16), k_block_bwd_v5 (LDS-DMA staged e tiles: the headline),
 // k_block_bwd_v4r (narrow edge channels, R rows per iteration); their SD = true instances (degree scalers: bwd_sd_rows, bwd_pair_grad<.., SD>)
-// are instantiated by egt_block_sd.hip.  The phases of the per-tile body (weight slabs, P1 .. P5,
+// are instantiated by egt_block_sd.hip, their DO = true instances (attention dropout: bwd_pair_grad<.., DO>) by egt_block_do.hip.  The phases of the per-tile body (weight slabs, P1 .. P5,
 // the hand-off, dK / dV / dQ, the partial stores) are the bwd_* functions below (the K / V fragment reader kv_frags_row and the
 // key-padding term key_mask_add are the forward's too: egt_block_dev.h); a kernel is its LDS carve-up, its staging
 // and its loop around them.  The kernels sit at the register edge: a change to a phase moves the register counts of all of them
@@ -127,7 +127,10 @@ __device__ __forceinline__ v4f bwd_p2_dhext(const float* dt, const float* wsB, i
 // RAG: a key past N (!kvalid) gets probability and gate exactly 0.  GP: its gate goes through the sigmoid also without EGT_BF_GATE.
 // SD (EGT_BF_SCALE_DEGREE): slot 3 of the row's statistics holds d deg of (row, head) (bwd_sd_rows), and every key's gate logit
 // takes d deg . g (1 - g) whatever its softmax probability; without SD slot 3 is never read.
-template <bool ML, bool RAG, bool GP, bool SD = false>
+// DO (EGT_BF_ATTN_DROPOUT): with D = the keep factor of (pair, head), recomputed from the counter, dA_t = D . (dV_att . V) is what
+// dS, dG and the softmax backward are formed from, and at = D . S . gate is the dropped A_tild that enters dV.  delta stays the node
+// side's sum_k dV_att_k V_att_k: V_att is the dropped sum, so it equals sum_m D . A_tild . dA_t.
+template <bool ML, bool RAG, bool GP, bool SD = false, bool DO = false>
 __device__ __forceinline__ void bwd_pair_grad(const BlockArgs& a, const float* qr, const float (&Kf)[16], const float (&Vf)[16],
                                               const v4f& acc, const v4f& dhx, float kadd, const MaskRegs& mr, size_t idx8, int q,
                                               bool kvalid, bool gated, bool clip, float (&dge)[4], float (&hh)[2], float (&dA)[2],
@@ -146,6 +149,11 @@ __device__ __forceinline__ void bwd_pair_grad(const BlockArgs& a, const float* q
       e0 = fmaf(v.z, Vf[4*i+2], e0); e1 = fmaf(v.w, Vf[4*i+3], e1);
     }
     dots[0] = d0; dots[1] = d1; dAd[0] = e0; dAd[1] = e1;
+  }
+  float Dk[2] = {1.0f, 1.0f};
+  if constexpr (DO) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { Dk[j] = attn_drop_factor(a, idx8, q, j); dAd[j] *= Dk[j]; }
   }
   const float4* sp = reinterpret_cast<const float4*>(qr + 128 + q * 8);
   const float4 s0 = sp[0], s1 = sp[1];
@@ -175,7 +183,8 @@ __device__ __forceinline__ void bwd_pair_grad(const BlockArgs& a, const float* q
     if constexpr (SD) dGl = fmaf(st[4 * j + 3], g * (1.0f - g), dGl);
     const float dH = S * (dS - st[4 * j + 2]) + dhx[j];
     dA[j] = dH * inr[j] * a.scale;
-    at[j] = S * g;
+    if constexpr (DO) at[j] = S * g * Dk[j];
+    else at[j] = S * g;
     dge[2 * j] = dGl;
     dge[2 * j + 1] = dH;
   }
@@ -339,7 +348,7 @@ __device__ __forceinline__ void bwd_store_epart(const BlockArgs& a, float* sm, i
 //    registers, 116 -> 104 us.
 // RAG: N is not a multiple of 16 -- the last key tile is zero-filled past N and its lanes get probability and
 // gate exactly 0, the last row group is short (the row loop and the prologue already take nl < 16).
-template <int DE, bool ML, bool BF, bool RAG, bool SD = false>
+template <int DE, bool ML, bool BF, bool RAG, bool SD = false, bool DO = false>
 __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
   seed_from_device(a);
   using G = Geo<DE>;
@@ -422,7 +431,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
       SCHED_FENCE();
       // ---- P3: logits, softmax/gate backward ----
       float dge[4], hh[2], dA[2], at[2];
-      bwd_pair_grad<ML, RAG, false, SD>(a, qr, Kf, Vf, acc, dhx, kadd, mr, (pair0 + p) * BH, q, kvalid, gated, clip, dge, hh, dA, at);
+      bwd_pair_grad<ML, RAG, false, SD, DO>(a, qr, Kf, Vf, acc, dhx, kadd, mr, (pair0 + p) * BH, q, kvalid, gated, clip, dge, hh, dA, at);
       bwd_handoff(sc1, sc2, p, q, dge, hh, ssum);
       lds_sync();
       SCHED_FENCE();
@@ -496,7 +505,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4(BlockArgs a) {
 // buffers + the node-side prologue's scratch behind them
 #define V5_AREA(DE_) ((4 * (3 * Geo<DE_>::TILE_FLOATS + 448) > 4 * Geo<DE_>::TILE_FLOATS + BWD_PRO_WS) \
                           ? 4 * (3 * Geo<DE_>::TILE_FLOATS + 448) : 4 * Geo<DE_>::TILE_FLOATS + BWD_PRO_WS)
-template <int DE, int MM, bool RAG, bool SD = false>
+template <int DE, int MM, bool RAG, bool SD = false, bool DO = false>
 __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
   seed_from_device(a);
   constexpr bool SPLIT = MM == EGT_MM_BF16X3;
@@ -741,7 +750,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
       SCHED_FENCE();
       // ---- P3: logits, softmax/gate backward ----
       float dge[4], hh[2], dA[2], at[2];
-      bwd_pair_grad<false, RAG, true, SD>(a, qr, Kf, Vf, acc, dhx, kadd, mr, (pair0 + p) * BH, q, kvalid, gated, clip, dge, hh, dA, at);
+      bwd_pair_grad<false, RAG, true, SD, DO>(a, qr, Kf, Vf, acc, dhx, kadd, mr, (pair0 + p) * BH, q, kvalid, gated, clip, dge, hh, dA, at);
       bwd_handoff(sc1, sc2, p, q, dge, hh, ssum);
       lds_sync();
       SCHED_FENCE();
@@ -868,7 +877,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v5(BlockArgs a) {
 // mask tensors): one iteration = the wave's key tile x R query rows (R = V4R_RR).  The rows' P1..P5 chains are independent, the LDS
 // hand-offs are shared (5 per R rows instead of 5 per row), the e / de' tiles of the next R rows are
 // in flight during the arithmetic.  Same arguments, partial layouts and prologue as v4.
-template <int DE, bool BF, int R, bool SD = false>
+template <int DE, bool BF, int R, bool SD = false, bool DO = false>
 __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R rows per iteration
   seed_from_device(a);
   using G = Geo<DE>;
@@ -976,7 +985,7 @@ __global__ void __launch_bounds__(256, 2) k_block_bwd_v4r(BlockArgs a) {   // R 
       for (int i = 0; i < R; ++i) {
         if (i >= nr) continue;
         float hh[2];
-        bwd_pair_grad<false, true, false, SD>(a, qd + (R * lq + i) * QD_LD, Kf, Vf, acc[i], dhx[i], kadd, mr, (pair0[i] + p) * BH, q, kvalid,
+        bwd_pair_grad<false, true, false, SD, DO>(a, qd + (R * lq + i) * QD_LD, Kf, Vf, acc[i], dhx[i], kadd, mr, (pair0[i] + p) * BH, q, kvalid,
                                           gated, clip, dge[i], hh, dA[i], at[i]);
         bwd_handoff(sc10 + i * 256, sc20 + i * 192, p, q, dge[i], hh, ssum);
         SCHED_FENCE();   // one row's Q / dV_att fragments (32 registers) at a time

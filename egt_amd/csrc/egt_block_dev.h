@@ -83,6 +83,12 @@ __device__ __forceinline__ void apply_masks(const BlockArgs& a, float kadd, cons
   }
 }
 
+// EGT_BF_ATTN_DROPOUT: keep factor of (pair, head 2q + j) -- 1 / (1 - rate) for a kept element, 0 for a dropped one -- from the counter
+// hash on the dropout stream (drop_factor of egt_attn.hip, oracle/rng_ref.py: dropout_keep).  Recomputed by the backward: nothing is stored.
+__device__ __forceinline__ float attn_drop_factor(const BlockArgs& a, size_t idx8, int q, int j) {
+  return ((egt_hash32((uint32_t)(idx8 + 2 * q + j), a.s0, a.s1 ^ EGT_DROPOUT_STREAM) >> 8) >= a.dk_thr) ? a.dk_scale : 0.0f;
+}
+
 // transpose-reduce 16 per-lane values over the 16 key lanes (same q): lane p returns the
 // sum of element p.  VALU and MFMA issue add up on a gfx950 SIMD (profiles/r03_mfma_valu_issue.md), so instruction count is
 // what this costs: the "xor 8" and "xor 4" levels are DPP adds whose SECOND instruction of a pair writes only the banks

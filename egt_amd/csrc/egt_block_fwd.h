@@ -1,6 +1,6 @@
 // Forward pair kernels of the fused attention block (included by egt_block.hip, which holds the dispatch):
-// k_block_fwd<De,KVL,ML,FULL,BF,SD> and the four-rows-per-iteration k_block_fwd_r4<De,FULL,NW,BF,SD> for narrow edge channels
-// (SD = true: the degree-scaler instances, instantiated by egt_block_sd.hip).
+// k_block_fwd<De,KVL,ML,FULL,BF,SD,DO> and the four-rows-per-iteration k_block_fwd_r4<De,FULL,NW,BF,SD,DO> for narrow edge channels
+// (SD = true: the degree-scaler instances, instantiated by egt_block_sd.hip; DO = true: the attention-dropout instances, egt_block_do.hip).
 // The phases of the per-pair body (lane-constant operands, logits, online softmax and A.V, dense_edge_r, the row finish) are the
 // fwd_* functions below, with kv_frags / frag16 / key_mask_add of egt_block_dev.h; a kernel is its LDS carve-up, its staging and
 // prefetch, and its loop around them (profiles/fwd_phases_kres.txt has the register counts of this split against the pasted copies).
@@ -178,6 +178,25 @@ __device__ __forceinline__ void fwd_row_finish_sd(const BlockArgs& a, size_t row
   }
 }
 
+// ---- attention dropout (EGT_BF_ATTN_DROPOUT, egt_layers.py:116-117): the DO instances of the two kernels below ----
+// fwd_softmax_av with the keep factor of (pair, head) on av = p . g before it enters O: V_att is the dropped sum.  The softmax sum
+// (and with it H_hat, the edge update and the row statistics) does not see the mask.  idx8 = the pair's element index x 8 heads.
+__device__ __forceinline__ void fwd_softmax_av_do(const BlockArgs& a, size_t idx8, int q, bool valid, bool gated, const float (&xl)[2],
+                                                  const float (&gl)[2], const float (&Vf)[16], float (&mx)[2], float (&sum)[2], float (&O)[16]) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const float xv = xl[j];
+    const float mn = valid ? fmaxf(mx[j], xv) : mx[j];
+    const float alpha = __expf(mx[j] - mn);
+    const float pe = valid ? __expf(xv - mn) : 0.f;
+    mx[j] = mn;
+    sum[j] = fmaf(sum[j], alpha, pe);
+    const float av = (gated ? pe * egt_sigmoid(gl[j]) : pe) * attn_drop_factor(a, idx8, q, j);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) O[2 * k + j] = fmaf(O[2 * k + j], alpha, av * Vf[2 * k + j]);
+  }
+}
+
 // ================================================================= forward =====
 // Workgroup = (graph b, 16 query rows); wave w owns rows l = 16*lg + w + 4*i.
 // KVL: K/V of the graph, Q of the 16 rows and the key-mask adds are staged in LDS.
@@ -185,7 +204,8 @@ __device__ __forceinline__ void fwd_row_finish_sd(const BlockArgs& a, size_t row
 // compiled out of the headline kernel).
 // FULL: N is a multiple of 16 (no ragged key tile): validity selects and address clamps fold away.
 // SD: EGT_BF_SCALE_DEGREE (gated blocks, fp32 edge tensors): the degree rides next to the softmax sum (fwd_softmax_av_sd / fwd_row_finish_sd).
-template <int DE, bool KVL, bool ML, bool FULL, bool BF, bool SD = false>
+// DO: EGT_BF_ATTN_DROPOUT: the keep factor on av (fwd_softmax_av_do); never together with SD.
+template <int DE, bool KVL, bool ML, bool FULL, bool BF, bool SD = false, bool DO = false>
 __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd(BlockArgs a) {   // narrow tiles without K/V in LDS: more resident waves (with K/V in LDS the LDS footprint caps a CU at two workgroups anyway)
   seed_from_device(a);
   using G = Geo<DE>;
@@ -333,6 +353,7 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
     fwd_pair_logits(a, clip, Qf, Kf, acc, hh, xl, gl);
     apply_masks<ML>(a, kadd, mr, (pair0 + p) * BH, q, xl, gl);
     if constexpr (SD) fwd_softmax_av_sd(valid, xl, gl, Vf, mx, sum, deg, O);
+    else if constexpr (DO) fwd_softmax_av_do(a, (pair0 + p) * BH, q, valid, gated, xl, gl, Vf, mx, sum, O);
     else fwd_softmax_av(valid, gated, xl, gl, Vf, mx, sum, O);
     fwd_edge_update<DE>(tl, p, q, valid, hh, wrA, brv);
     if (it_ + 1 == total) {   // last tile of the wave: flush
@@ -403,7 +424,7 @@ __global__ void __launch_bounds__(256, ((DE <= 16 && !KVL) ? 4 : 2)) k_block_fwd
 // NW = 4: 16 rows per workgroup, two workgroups per CU; NW = 8: 32 rows (two 16-row halves), ONE
 // workgroup per CU -- same occupancy, but K/V of a graph up to N ~ 250 still fits in LDS and is staged
 // once per 32 rows.
-template <int DE, bool FULL, int NW, bool BF, bool SD = false>
+template <int DE, bool FULL, int NW, bool BF, bool SD = false, bool DO = false>
 __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
   seed_from_device(a);
   typedef typename EdgeT<BF>::type ET;   // element type of the edge tensors in HBM
@@ -499,6 +520,7 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
           // 165.5 us against the parent's 161.4 (max - min 0.7) and r4<8, false, 4, false> 98.5 against 97.2 (0.3); with this copy
           // 160.4 and 96.2 ----
           if constexpr (SD) fwd_softmax_av_sd(valid, xl, gl, Vf, mx[i], sum[i], deg[i], O[i]);
+          else if constexpr (DO) fwd_softmax_av_do(a, (rowl[i] * N + m0 + p) * BH, q, valid, gated, xl, gl, Vf, mx[i], sum[i], O[i]);
           else
 #pragma unroll
           for (int j = 0; j < 2; ++j) {

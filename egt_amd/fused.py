@@ -41,9 +41,17 @@ def scale_degree_disabled() -> bool:
     return _NO_SCALE_DEGREE
 
 
-def _flags(blk, training=False, seed_device=False, static_edge=False) -> int:
-    """egt_block_desc.flags of a block"""
+def attn_dropout_fused(blk) -> bool:
+    """The block asks for its attention dropout inside the fused pair kernels (EGTBlock(fused_attn_dropout=True), rate > 0)"""
+    return bool(getattr(blk, "fused_attn_dropout", False)) and blk.mha.attn_dropout > 0
+
+
+def _flags(blk, training=False, seed_device=False, static_edge=False, dropout=False) -> int:
+    """egt_block_desc.flags of a block.  `dropout`: the call draws the attention-dropout mask in the kernels (training only:
+    the library takes EGT_BF_ATTN_DROPOUT together with EGT_BF_TRAINING)"""
     flags = L.BF_STATIC_EDGE if static_edge else 0
+    if dropout:
+        flags |= L.BF_ATTN_DROPOUT | L.BF_TRAINING
     if seed_device:                  # egt_amd.graph.DeviceSeeds: the kernels complete the seed from HBM
         flags |= L.BF_SEED_DEVICE
     if blk.gated:
@@ -67,29 +75,32 @@ def _edge_code(edge_dtype) -> int:
     return L.EGT_BF16 if edge_dtype == torch.bfloat16 else L.EGT_F32
 
 
-def _desc(blk, B, N, training, seed, edge_dtype=torch.float32, seed_device=None, static_edge=False) -> L.BlockDesc:
+def _desc(blk, B, N, training, seed, edge_dtype=torch.float32, seed_device=None, static_edge=False, dropout=False) -> L.BlockDesc:
     lo = hi = 0.0
     if blk.mha.clip_logits_value is not None:
         lo, hi = float(blk.mha.clip_logits_value[0]), float(blk.mha.clip_logits_value[1])
     return L.BlockDesc(B=B, N=N, H=blk.num_heads, d=blk.model_width // blk.num_heads,
-                       De=blk.edge_width, dtype=_edge_code(edge_dtype), flags=_flags(blk, training, seed_device is not None, static_edge),
+                       De=blk.edge_width, dtype=_edge_code(edge_dtype),
+                       flags=_flags(blk, training, seed_device is not None, static_edge, dropout),
                        clip_lo=lo, clip_hi=hi,
-                       random_mask_prob=float(blk.mha.random_mask_prob), ln_eps=1e-3, reserved=0,
+                       random_mask_prob=float(blk.mha.random_mask_prob), ln_eps=1e-3,
+                       reserved=L.rate_bits(blk.mha.attn_dropout) if dropout else 0,   # (the rate rides in `reserved`)
                        seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
                        seed_device=None if seed_device is None else seed_device[0].ptr(seed_device[1]))
 
 
-_LIB_ANSWERS = {}   # (entry point, B, N, H, d, De, dtype, flags) -> bool
+_LIB_ANSWERS = {}   # (entry point, B, N, H, d, De, dtype, flags, rate bits) -> bool
 
 
-def _lib_covers(entry, blk, B, N, edge_dtype, static_edge=False) -> bool:
+def _lib_covers(entry, blk, B, N, edge_dtype, static_edge=False, dropout=False) -> bool:
     """The library's answer (`entry`: egt_block_supported / egt_pair_supported) for a block's geometry, asked once per
-    descriptor: the key is every descriptor field those read, built from the block's attributes as they are now."""
+    descriptor: the key is every descriptor field those read, built from the block's attributes as they are now.
+    `dropout`: the question is about the descriptor flagged EGT_BF_ATTN_DROPOUT, with the block's rate."""
     key = (entry, B, N, blk.num_heads, blk.model_width // blk.num_heads, blk.edge_width, _edge_code(edge_dtype),
-           _flags(blk, static_edge=static_edge))
+           _flags(blk, static_edge=static_edge, dropout=dropout), L.rate_bits(blk.mha.attn_dropout) if dropout else 0)
     ok = _LIB_ANSWERS.get(key)
     if ok is None:
-        d = _desc(blk, B, N, False, 0, edge_dtype, static_edge=static_edge)
+        d = _desc(blk, B, N, False, 0, edge_dtype, static_edge=static_edge, dropout=dropout)
         ok = _LIB_ANSWERS[key] = bool(getattr(L.load(), entry)(C.byref(d)))
     return ok
 
@@ -103,7 +114,12 @@ def _unsupported(blk, training):
         return "add_n_norm / edge_activation"
     if blk.mha.scale_degree and blk.mha.num_virtual_nodes > 0:
         return "scale_degree with virtual nodes (the scaler of the virtual-node rows is not in the kernels)"
-    if blk.mha.attn_dropout > 0 or blk.mha.num_virtual_nodes > 0:
+    if attn_dropout_fused(blk):          # the opt-in: the attribute itself is no reason any more
+        if blk.mha.scale_degree:
+            return "attn_dropout together with scale_degree (the two kernel instances are not combined)"
+        if blk.mha.num_virtual_nodes > 0:
+            return "scale_degree / attn_dropout / virtual nodes"
+    elif blk.mha.attn_dropout > 0 or blk.mha.num_virtual_nodes > 0:
         return "scale_degree / attn_dropout / virtual nodes"
     if blk.mha.scale_degree and scale_degree_disabled():
         return "scale_degree (EGT_NO_SCALE_DEGREE is set)"
@@ -124,15 +140,17 @@ def _covered(blk, B, N, node_dtype, edge_dtype, on_gpu, attn_mask, rand_mask, tr
         return None, False
     ect = blk.edge_channel_type
     edge_route = None
+    drop = attn_dropout_fused(blk)       # training and evaluation both: the unflagged kernels run the evaluation
     if (node_dtype in _FLOATS and edge_dtype in _FLOATS and (ect != "constrained" or attn_mask)
-            and _lib_covers("egt_block_supported", blk, B, N, edge_dtype)):
+            and _lib_covers("egt_block_supported", blk, B, N, edge_dtype)
+            and (not drop or _lib_covers("egt_block_supported", blk, B, N, edge_dtype, dropout=True))):
         # static: the block was opted in by its EGTLayerStack (`_static_edge`), the process switch is off, the random mask is
         # the kernels' own, and the library covers the flagged descriptor
-        static = (ect == "bias" and blk._static_edge and not rand_mask and not static_edge_disabled()
+        static = (ect == "bias" and blk._static_edge and not rand_mask and not static_edge_disabled() and not drop
                   and _lib_covers("egt_block_supported", blk, B, N, edge_dtype, static_edge=True))
         edge_route = "static" if static else "per-layer-bias" if ect == "bias" else "chained-residual"
     # the pair operator (large heads): 'residual' edge channels, gated, fp32, no mask tensor of either kind
-    pair = (ect == "residual" and blk.gated and not attn_mask and not rand_mask
+    pair = (ect == "residual" and blk.gated and not attn_mask and not rand_mask and not drop
             and node_dtype == torch.float32 and edge_dtype == torch.float32
             and _lib_covers("egt_pair_supported", blk, B, N, edge_dtype))
     return edge_route, pair
@@ -322,9 +340,13 @@ def block_fused(blk, h, e, mask, attn_mask, rand_mask=None, edge_route=None):
         edge_route = route(blk, h, e, attn_mask, rand_mask)[1]
     static = edge_route == "static"
     training = blk.training and blk.mha.random_mask_prob > 0.0
-    sdev = blk.mha.seed_device if (training and rand_mask is None) else None
-    seed = blk.mha.next_seed() if (training and rand_mask is None and sdev is None) else 0
-    desc = _desc(blk, h.shape[0], h.shape[1], training, seed, e.dtype, sdev, static_edge=static)
+    # attention dropout in the kernels: in training mode only (evaluation runs the unflagged kernels).  Such a call always
+    # consumes one seed -- also with an injected random mask or random_mask_prob == 0 -- as the composed operator does
+    drop = blk.training and attn_dropout_fused(blk)
+    draws = drop or (training and rand_mask is None)
+    sdev = blk.mha.seed_device if draws else None
+    seed = blk.mha.next_seed() if (draws and sdev is None) else 0
+    desc = _desc(blk, h.shape[0], h.shape[1], training, seed, e.dtype, sdev, static_edge=static, dropout=drop)
     if static:
         # no identity / zero constants here: norm_edge and dense_edge_r do not exist for the kernels either
         mods = blk._modules
@@ -440,7 +462,8 @@ def stack_supported(stack, h, e, attn_mask) -> bool:
         return False
     b0 = blocks[0]
     for b in blocks:
-        if route(b, h, e, attn_mask)[0] != "fused" or b.mha.scale_degree:   # (egt_stack_* carries no degree: block by block)
+        # (egt_stack_* carries no degree and draws no dropout: block by block)
+        if route(b, h, e, attn_mask)[0] != "fused" or b.mha.scale_degree or attn_dropout_fused(b):
             return False
         same = (b.model_width == b0.model_width and b.edge_width == b0.edge_width and
                 b.edge_channel_type == b0.edge_channel_type and b.gated == b0.gated and

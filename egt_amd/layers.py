@@ -165,7 +165,7 @@ class EGTBlock(nn.Module):
                  clip_logits_value=[-5, 5], edge_activation=None,
                  edge_channel_type='residual', scale_degree=False, scaler_type='log',
                  num_virtual_nodes=0, random_mask_prob=0., attn_dropout=0.,
-                 node_dropout=0., edge_dropout=0., add_n_norm=False, seed=0, fused='auto'):
+                 node_dropout=0., edge_dropout=0., add_n_norm=False, seed=0, fused='auto', fused_attn_dropout=False):
         super().__init__()
         if not gate_attention and scale_degree:                   # graph_xformer_model_base.py:47-48
             raise ValueError('scale_degree only works with gate_attention')
@@ -176,6 +176,9 @@ class EGTBlock(nn.Module):
         self.edge_activation = edge_activation
         self.node_dropout, self.edge_dropout, self.add_n_norm = node_dropout, edge_dropout, add_n_norm
         self.fused = fused
+        # attn_dropout > 0 on the fused block (EGT_BF_ATTN_DROPOUT: the keep mask is drawn in the pair kernels) is opt-in;
+        # without it such a block keeps the composed route, its messages and its seed draws
+        self.fused_attn_dropout = bool(fused_attn_dropout)
         # static-edge route of the fused block (fused.route): off unless an EGTLayerStack opts its 'bias' blocks in
         self._static_edge, self._static_first = False, True
         has_edge = edge_channel_type != 'none'

@@ -146,10 +146,15 @@ class ZincDCTransformer(nn.Module):
                  l2_reg=0, distance_loss=0., distance_target=8, add_n_norm=False, combine_layer_repr=False,
                  node2edge_xtalk=0., edge2node_xtalk=0., node2edge_embed=False, node_normalization='layer',
                  edge_normalization='layer', global_step_layer=False, max_length=None,
-                 seed=0, ffn_matmul='f32', edge_dtype='f32', **unknown):
+                 seed=0, ffn_matmul='f32', edge_dtype='f32', fused_attn_dropout=False, **unknown):
         super().__init__()
         if unknown:
             raise TypeError(f"{type(self).__name__}: unknown model_config keys {sorted(unknown)}")
+        # fused_attn_dropout (a project key): attn_dropout > 0 drawn inside the fused pair kernels (EGTBlock) instead of sending
+        # every layer to the composed operator; off by default
+        if not isinstance(fused_attn_dropout, bool):
+            raise ValueError(f"fused_attn_dropout must be True or False (got {fused_attn_dropout!r})")
+        self.fused_attn_dropout = fused_attn_dropout
         # edge_dtype (a project key, like ffn_matmul): storage of the [B,N,N,De] edge tensor between the edge embedding, the
         # attention blocks and the edge FFNs.  "bf16" halves its HBM traffic; node tensors, parameters and math stay fp32.
         self.edge_dtype = _edge_dtype(edge_dtype)
@@ -219,6 +224,7 @@ class ZincDCTransformer(nn.Module):
                                     edge_channel_type=edge_channel_type, clip_logits_value=clip_logits_value,
                                     random_mask_prob=random_mask_prob, scale_degree=scale_degree, scaler_type=scaler_type,
                                     attn_dropout=attn_dropout, edge_activation=edge_activation, seed=seed,
+                                    fused_attn_dropout=fused_attn_dropout,
                                     # the operator reads num_virtual_nodes in its degree scaler only (egt_layers.py:123-136)
                                     num_virtual_nodes=nv if scale_degree else 0,
                                     ffn_matmul=ffn_matmul, ffn_multiplier=ffn_multiplier)

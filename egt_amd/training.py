@@ -95,6 +95,9 @@ def default_config(scheme: str = "zinc.svd") -> Config:
                                  # captured per batch geometry: egt_amd.graph; for launch-bound per-GPU batches
         edge_dtype="f32",        # (not a reference key) storage of the [B,N,N,De] edge tensor: "f32" or "bf16" (fp32 math,
                                  # bf16 in HBM: BASELINE config 3); handed to the model by get_model, not part of model_config
+        fused_attn_dropout=False,   # (not a reference key) attn_dropout > 0 drawn inside the fused pair kernels instead of on the
+                                 # composed route (which is fp32 only and cannot be captured); handed to the model by get_model,
+                                 # not part of model_config
         fused_optimizer=False,   # (not a reference key) the parameter update as two launches over the flat gradient buffer:
                                  # egt_amd.optim.FlatOptimizer (same arithmetic and checkpoints as torch.optim); needs a GPU
         device_dataset=False,    # (not a reference key) the dataset's packed records resident on the GPU, padded batches assembled
@@ -161,6 +164,8 @@ def make_config(user: Optional[dict], scheme: Optional[str] = None) -> Config:
     from .model import EDGE_DTYPES      # the models' edge_dtype keys: one list
     if c.edge_dtype not in EDGE_DTYPES:
         raise ValueError(f'config "edge_dtype" must be one of {list(EDGE_DTYPES)} (got {c.edge_dtype!r})')
+    if not isinstance(c.fused_attn_dropout, bool):
+        raise ValueError(f'config "fused_attn_dropout" must be true or false (got {c.fused_attn_dropout!r})')
     return c
 
 
@@ -412,9 +417,14 @@ class ZincSVDScheme:
 
     def model_kwargs(self):
         """the model's constructor keywords: model_config plus the project keys that are not reference keys and differ from
-        their defaults (edge_dtype); a model_factory gets the same dict, so a bf16 config is never silently trained in fp32"""
+        their defaults (edge_dtype, fused_attn_dropout); a model_factory gets the same dict, so a bf16 config is never silently
+        trained in fp32"""
         mc = self.get_model_config()
-        return mc if self.config.edge_dtype == "f32" else dict(mc, edge_dtype=self.config.edge_dtype)
+        if self.config.edge_dtype != "f32":
+            mc = dict(mc, edge_dtype=self.config.edge_dtype)
+        if self.config.fused_attn_dropout:
+            mc = dict(mc, fused_attn_dropout=True)
+        return mc
 
     def get_model(self):
         if self.model_factory is not None:

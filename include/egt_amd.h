@@ -242,8 +242,8 @@ int egt_edge_update_bwd(const egt_edge_desc* desc, const void* d_e_out,
  * One launch streams e once: LN, the two De->H projections, QK^T, clip, +E,
  * masks, softmax x sigmoid gate, A.V and e' = e + H_hat.Wr + br never leave the
  * CU (E, G, H_hat, A_tild are not materialised).  Everything else (other
- * variants, dropout, degree scalers with virtual nodes or bf16 edges, d > 8)
- * composes the kernels above.
+ * variants, node / edge dropout, attention dropout without EGT_BF_ATTN_DROPOUT,
+ * degree scalers with virtual nodes or bf16 edges, d > 8) composes the kernels above.
  * Parameter pointers carry the reference's Keras layer names. */
 #define EGT_BF_GATE 0x1u      /* gate_attention                                  */
 #define EGT_BF_ATTN_MASK 0x2u /* 'constrained': attn_mask [B,N,N,H] fp32 present */
@@ -279,6 +279,19 @@ int egt_edge_update_bwd(const egt_edge_desc* desc, const void* d_e_out,
                                   forward and d deg into the backward pair kernel.  egt_stack_* and the pair operator
                                   refuse it (EGT_E_FLAGS / egt_pair_supported = 0) */
 #define EGT_BF_SCALER_LINEAR (1u << 8) /* 0x100: scaler_type 'linear' (s = deg); only valid with EGT_BF_SCALE_DEGREE */
+#define EGT_BF_ATTN_DROPOUT (EGT_BF_SCALER_LINEAR << 1) /* 0x200, the next bit: attn_dropout (egt_layers.py:116-117): A_tild of (b, l, m, h) is dropped before A.V,
+                                  keep <=> (egt_hash32(i, s0, s1 ^ 0x5BD1E995) >> 8) >= floor(rate * 2^24) with
+                                  i = ((b N + l) N + m) H + h as a uint32 and (s0, s1) the low / high word of the
+                                  effective seed (desc->seed, ^ *seed_device under EGT_BF_SEED_DEVICE); a kept element is
+                                  scaled by 1 / (1 - rate) in fp32 -- the stream of egt_attn_fwd and
+                                  egt_mask_sample(which = 1).  The random mask of the call draws from the same seed on
+                                  its own stream.  The rate travels in desc->reserved as its fp32 bit pattern and must
+                                  lie in (0, 1) (else EGT_E_FLAGS).  Needs EGT_BF_TRAINING (EGT_E_FLAGS without: clear
+                                  the flag for evaluation); not with EGT_BF_SCALE_DEGREE or EGT_BF_STATIC_EDGE (both
+                                  EGT_E_FLAGS).  fp32 and bf16 edge tensors, gated or not, every De (De = 8 runs on the
+                                  MFMA-tile pair kernels); sizes do not change and nothing is saved for the mask: both
+                                  directions recompute it.  H_hat, e' and the softmax statistics do not see the mask.
+                                  egt_stack_* and the pair operator refuse it (EGT_E_FLAGS / egt_pair_supported = 0) */
 
 typedef struct egt_block_desc {
   int32_t B, N, H, d, De;   /* model_width Dh = d*H                             */
@@ -287,7 +300,7 @@ typedef struct egt_block_desc {
   float clip_lo, clip_hi;
   float random_mask_prob;
   float ln_eps;             /* 1e-3                                             */
-  int32_t reserved;
+  int32_t reserved;         /* EGT_BF_ATTN_DROPOUT: the fp32 bit pattern of the rate; else ignored              */
   uint64_t seed;
   const void* seed_device;  /* EGT_BF_SEED_DEVICE: const uint64_t* on the device, else ignored (NULL) */
 } egt_block_desc;
