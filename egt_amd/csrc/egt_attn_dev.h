@@ -127,6 +127,12 @@ __device__ __forceinline__ unsigned dma_lane_off(int lane) {   // source byte of
   return (unsigned)((lane >> 2) * 64 + (((lane & 3) ^ chunk_xor(lane >> 2)) << 4));
 }
 #define OPS_STAGE 32768   // bytes of one operand stage: 4 heads x (two 4 KB tiles)
+#define OPS_BYTES (2 * OPS_STAGE)
+// launch geometry of the inner-op kernels (egt_attn_mfma.hip and their bf16-operand twins in egt_attn_bf16.hip: one plan, plan_attn)
+#define FQ 2         // forward: query tiles per compute wave
+#define BK 2         // backward: key tiles per compute wave
+#define QW_TILES 8   // dQ: query tiles per workgroup
+#define QW_STAGES 4  // dQ: LDS ring; the DMA of a stage is issued QW_STAGES - 1 trips ahead of its use (issue -> landed is ~1.1 us, a trip ~1 us)
 
 // ================================================================ the phases =====
 // element (graph b, query row l, key m, head h) of a [B,N,N,8] tensor: the index of the mask bytes and of the mask hash (< 2^32: *_supported)
@@ -335,3 +341,8 @@ __device__ __forceinline__ void attn_fwd_finalize(const AttnMfmaArgs& a, float* 
   if (l < a.N && q == 0)
     *reinterpret_cast<float4*>(a.rowstats + (((size_t)b * a.N + l) * AH + h) * 4) = make_float4(mrun, lrun, 0.f, 0.f);
 }
+
+// ---- egt_attn_bf16.hip: the inner op with bf16 products (egt_attn_desc.reserved & EGT_ATTN_MM_BF16), launched from plan_attn's
+// geometry; var: the Feat instance of the direction
+void egt_attn_bf16_launch_fwd(int var, const EgtLaunch& pack, const EgtLaunch& fwd, const AttnMfmaArgs& a, hipStream_t st);
+void egt_attn_bf16_launch_bwd(int var, const EgtLaunch& pack, const EgtLaunch& kv, const EgtLaunch& q, const AttnMfmaArgs& a, hipStream_t st);

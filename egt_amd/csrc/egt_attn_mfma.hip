@@ -140,15 +140,12 @@ __global__ void __launch_bounds__(512) k_attn_pack(AttnMfmaArgs a) {
   }
 }
 
-#define OPS_BYTES (2 * OPS_STAGE)
-
 // ================================================================== forward =====
 // workgroup = (graph b, 32 query rows, 4 heads); compute wave w = head 4 hg + w.  Lane (ll = lane&15, q = lane>>4)
 // owns query rows l0 + 16 qt + ll (two query tiles: every K / V^T operand register feeds two MFMAs) and, in the key
 // tile of an iteration, keys m0 + 4q + r.  S^T = K.Q^T puts the key index on the MFMA row axis: the softmax
 // reductions over keys are in-lane ops + two permlane swaps, the online-softmax rescale is lane-uniform, and the
 // gated probabilities feed the A.V MFMA as its B operand in place.
-#define FQ 2   // query tiles per compute wave
 template <int D, int V>
 __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
   constexpr int KT = D / 16, DH = D * AH, NIN = V ? 2 : 3, TS = FQ * 4 * PT_PL;   // TS: one tensor, one stage of planes
@@ -372,7 +369,6 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_fwd(AttnMfmaArgs a) {
 //   k_attn_mfma_bwd_q  : wave = (graph, head, 32 query rows), walks the key tiles: dQ^T += K^T.dA^T straight from the
 //                        dA tiles and the packed K^T
 // Compute lane (mm = lane&15, q): keys m0 + 16 kb + mm; in every query tile rows l0 + 4q + r.
-#define BK 2   // key tiles per compute wave
 template <int D, int V>
 __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
   constexpr int KT = D / 16, DH = D * AH, NIN = 3, TS = BK * 4 * PT_PL;   // planes E | G | X (an attention-mask tensor is folded into E and G by the loaders)
@@ -620,8 +616,6 @@ __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_kv(AttnMfmaArgs a) {
 // cycles of loads as of MFMAs.  Compute lane (ll = lane&15, q): query rows 16 j + ll of its tiles; keys 4q + u as the
 // contraction index: K^T fragments by ds_read_b128 (chunk-swizzled like every operand tile), dA[key][query] read
 // transposed by ds_read_b32.
-#define QW_TILES 8   // query tiles per workgroup
-#define QW_STAGES 4  // LDS ring: the DMA of a stage is issued QW_STAGES - 1 trips ahead of its use (issue -> landed is ~1.1 us, a trip ~1 us)
 template <int D>
 __global__ void __launch_bounds__(512, 2) k_attn_mfma_bwd_q(AttnMfmaArgs a) {
   constexpr int KT = D / 16, DH = D * AH, STG = (2 * KT + 2 * QW_TILES) * 256;   // floats per stage
@@ -772,6 +766,8 @@ static int np_of(int N) { return (N + 15) & ~15; }
 // from it.  Workspace, in floats: the packed operand arrays (PK_* order, B*H*NP*d each; a forward alone needs only the first
 // PK_FWD_COUNT), stats2 [B,H,NP,4], dA [B,H,NP,NP]; the pair operator appends its parameter-gradient partials, nwg + 1 of each
 // kind (the last one: the reduced image), the 1 KB store dump (PairArgs::dump) and the prepared weight table (PairArgs::wprep).
+// EGT_ATTN_MM_BF16 (egt_attn_bf16.hip) keeps the layout and every launch shape but the dA tiles: those are bf16 there (half the bytes,
+// half the dA pieces of a k_attn_bf16_bwd_q stage); the operand arrays keep fp32 containers.
 struct AttnPlan {
   int NP;
   size_t stats2, dA, fwd_total, total;   // fwd_total: egt_attn_mfma_fwd's workspace (all of it with EGT_ATTN_WS_SHARED)
@@ -779,6 +775,7 @@ struct AttnPlan {
   size_t part_proj, red_proj, part_upd, red_upd, dump, wprep;
   int pack_fwd, pack_bwd;                // PACK_* bits of each direction's k_attn_pack: a shared workspace packs q / k / v once
   int var_fwd, var_bwd;                  // attention: 1 / 2 the straight-line instances (see Feat), 0 the run-time-switched one; pair: V
+  bool bf16;                             // attention: EGT_ATTN_MM_BF16 -- the kernels of egt_attn_bf16.hip (same geometry; bf16 dA tiles)
   bool full;                             // pair: N is a multiple of 16 (k_pair_* FULL)
   EgtLaunch pack, fwd, bwd_kv, bwd_q, prep, pair_fwd, pair_bwd;
 };
@@ -790,9 +787,10 @@ static AttnPlan plan_attn(int B, int N, int D, int reserved, bool pair, int var_
   AttnPlan P{};
   const int NP = P.NP = np_of(N);
   const size_t arr = (size_t)B * AH * NP * D;
+  P.bf16 = !pair && (reserved & EGT_ATTN_MM_BF16) != 0;
   P.stats2 = PK_COUNT * arr;
   P.dA = P.stats2 + (size_t)B * AH * NP * 4;
-  P.total = P.dA + (size_t)B * AH * NP * NP;
+  P.total = P.dA + (size_t)B * AH * NP * NP / (P.bf16 ? 2 : 1);   // (bf16 dA tiles: NP is a multiple of 16)
   P.fwd_total = shared ? P.total : PK_FWD_COUNT * arr;
   P.nwg = B * (NP / 16);
   if (pair) {
@@ -812,7 +810,7 @@ static AttnPlan plan_attn(int B, int N, int D, int reserved, bool pair, int var_
   P.pack = {B * (NP / 16), 512, (size_t)AH * (16 * (D == 16 ? 16 : 80) + 4) * 4};
   P.fwd = {B * ((NP / 16 + FQ - 1) / FQ) * 2, 512, OPS_BYTES + (2 * keys + (size_t)(2 * (var_fwd ? 2 : 3) + 2) * FQ * 4 * PT_PL) * 4};
   P.bwd_kv = {B * ((NP / 16 + BK - 1) / BK) * 2, 512, OPS_BYTES + ((size_t)2 * 4 * 64 + (size_t)(2 * 3 + 4) * BK * 4 * PT_PL) * 4};
-  P.bwd_q = {B * AH * ((NP / 16 + QW_TILES - 1) / QW_TILES), 512, (size_t)QW_STAGES * (2 * (D / 16) + 2 * QW_TILES) * 1024};
+  P.bwd_q = {B * AH * ((NP / 16 + QW_TILES - 1) / QW_TILES), 512, (size_t)QW_STAGES * (2 * (D / 16) + (P.bf16 ? 1 : 2) * QW_TILES) * 1024};   // (bf16: both key tiles of a trip in one dA piece)
   P.prep = {1, 64, 0};
   P.pair_fwd = {P.nwg, 64 * PR_WAVES, ((size_t)2 * AH * HS + 2 * keys + (size_t)6 * AH * PT_PL + 16 + DE) * sizeof(float)};
   P.pair_bwd = {P.nwg, 64 * PR_WAVES, ((size_t)2 * 4 * 2 * HS + (size_t)2 * 3 * AH * PT_PL + (size_t)2 * AH * 64 + (size_t)4 * 2 * 16 * DE +
@@ -845,7 +843,8 @@ static int fill(const egt_attn_desc* desc, const void* qkv, const void* E, const
                 AttnMfmaArgs& a) {
   if (!egt_attn_mfma_supported(desc, 0)) EGT_FAIL(EGT_E_SHAPE, "configuration not covered by the MFMA inner-op kernel");
   if (!qkv || !workspace) EGT_FAIL(EGT_E_NULL, "qkv/workspace is NULL");
-  if (desc->reserved & ~EGT_ATTN_WS_SHARED) EGT_FAIL(EGT_E_FLAGS, "egt_attn_desc.reserved: unknown bits 0x%x (EGT_ATTN_WS_SHARED is the only one)", desc->reserved);
+  if (desc->reserved & ~(EGT_ATTN_WS_SHARED | EGT_ATTN_MM_BF16))
+    EGT_FAIL(EGT_E_FLAGS, "egt_attn_desc.reserved: unknown bits 0x%x (EGT_ATTN_WS_SHARED | EGT_ATTN_MM_BF16 are defined)", desc->reserved);
   if ((desc->flags & EGT_F_EDGE_INPUT) && !E) EGT_FAIL(EGT_E_NULL, "edge_input set but E is NULL");
   if ((desc->flags & EGT_F_GATE_INPUT) && !G) EGT_FAIL(EGT_E_NULL, "gate_input set but G is NULL");
   if ((desc->flags & EGT_F_ATTN_MASK) && !attn_mask) EGT_FAIL(EGT_E_NULL, "attn_mask set but M is NULL");
@@ -888,7 +887,8 @@ extern "C" int egt_attn_mfma_fwd(const egt_attn_desc* desc, const void* qkv, con
   a.v_att = (float*)v_att; a.h_hat = (float*)h_hat; a.rowstats = (float*)rowstats;
   const AttnPlan P = plan_attn(desc, &a);
   a.pack_what = P.pack_fwd;
-  switch (desc->d) {
+  if (P.bf16) egt_attn_bf16_launch_fwd(P.var_fwd, P.pack, P.fwd, a, (hipStream_t)stream);
+  else switch (desc->d) {
     case 16: launch_fwd<16>(P, a, (hipStream_t)stream); break;
     case 32: launch_fwd<32>(P, a, (hipStream_t)stream); break;
     default: launch_fwd<64>(P, a, (hipStream_t)stream); break;
@@ -928,7 +928,8 @@ extern "C" int egt_attn_mfma_bwd(const egt_attn_desc* desc, const void* qkv, con
   const AttnPlan P = plan_attn(desc, &a);
   a.stats2 = a.pk + P.stats2; a.ws_dA = a.pk + P.dA;
   a.pack_what = P.pack_bwd;
-  switch (desc->d) {
+  if (P.bf16) egt_attn_bf16_launch_bwd(P.var_bwd, P.pack, P.bwd_kv, P.bwd_q, a, (hipStream_t)stream);
+  else switch (desc->d) {
     case 16: launch_bwd<16>(P, a, (hipStream_t)stream); break;
     case 32: launch_bwd<32>(P, a, (hipStream_t)stream); break;
     default: launch_bwd<64>(P, a, (hipStream_t)stream); break;

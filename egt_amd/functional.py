@@ -56,6 +56,13 @@ class AttnConfig:
     seed: int = 0
     need_a_tild: bool = False
     use_mfma: bool = True   # MFMA-tiled kernels where they cover the configuration
+    # arithmetic of QK^T / A.V and their backward on the MFMA path: "f32" (exact, the default) or "bf16" (bf16 operands,
+    # fp32 accumulate: EGT_ATTN_MM_BF16 in include/egt_amd.h).  "bf16" on a call the MFMA path does not take is an error
+    matmul: str = "f32"
+
+    def __post_init__(self):
+        if self.matmul not in ("f32", "bf16"):
+            raise ValueError(f"AttnConfig.matmul must be 'f32' or 'bf16' (got {self.matmul!r})")
 
 
 def _attn_desc(cfg: AttnConfig, B, N, d, has_E, has_G, has_M) -> L.AttnDesc:
@@ -97,6 +104,11 @@ class _EGTAttention(torch.autograd.Function):
         d = C3 // (H * 3)
         desc = _attn_desc(cfg, B, N, d, E is not None, G is not None, M is not None)
         mfma_ws = None
+        mm_bits = L.ATTN_MM_BF16 if cfg.matmul == "bf16" else 0
+        if mm_bits and not (cfg.use_mfma and drop_keep is None
+                            and lib.egt_attn_mfma_supported(C.byref(desc), 1 if cfg.need_a_tild else 0)):
+            raise ValueError("AttnConfig(matmul='bf16') needs the MFMA inner op: H = 8, d in {16, 32, 64}, no degree scalers, "
+                             "no attention dropout, no A_tild output, use_mfma=True")
         v_att = torch.empty(B, N, d * H, device=qkv.device, dtype=torch.float32)
         h_hat = torch.empty(B, N, N, H, device=qkv.device, dtype=torch.float32)
         a_tild = torch.empty(B, N, N, H, device=qkv.device, dtype=torch.float32) if cfg.need_a_tild else None
@@ -110,8 +122,9 @@ class _EGTAttention(torch.autograd.Function):
             # N = 512, d = 64) then lives from forward to backward of EVERY MFMA attention node of a deep model;
             # EGT_ATTN_WS_SHARED=0 opts out (the backward re-packs: one more k_attn_pack section per layer, nothing kept).
             shared = any(ctx.needs_input_grad[:3]) and os.environ.get("EGT_ATTN_WS_SHARED", "1") != "0"
+            desc.reserved = mm_bits
             if shared:
-                desc.reserved = L.ATTN_WS_SHARED
+                desc.reserved = L.ATTN_WS_SHARED | mm_bits
                 ws = torch.empty(lib.egt_attn_mfma_workspace_bytes(C.byref(desc)), device=qkv.device, dtype=torch.uint8)
                 mfma_ws = ws
             else:
@@ -151,7 +164,7 @@ class _EGTAttention(torch.autograd.Function):
         if mfma and mfma_ws is not None:
             ws = mfma_ws                          # the forward's workspace: q/k/v operand copies already in place
         else:
-            desc.reserved = 0
+            desc.reserved = L.ATTN_MM_BF16 if (mfma and ctx.cfg.matmul == "bf16") else 0
             nbytes = (lib.egt_attn_mfma_workspace_bytes if mfma else lib.egt_attn_bwd_workspace_bytes)(C.byref(desc))
             ws = torch.empty(nbytes, device=qkv.device, dtype=torch.uint8)
         if mfma:

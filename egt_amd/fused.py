@@ -163,6 +163,8 @@ def route_core(blk, B, N, node_dtype, edge_dtype, on_gpu, attn_mask=False, rand_
     raises RuntimeError where neither fused route covers the configuration."""
     if blk.fused is False or blk.fused == "off":
         return "composed", None
+    if getattr(blk, "attn_matmul", "f32") != "f32":
+        return "composed", None     # bf16 attention products exist on the MFMA inner op only: neither fused route has the mode
     edge_route, pair = _covered(blk, B, N, node_dtype, edge_dtype, on_gpu, attn_mask, rand_mask,
                                 blk.training if training is None else training)
     if edge_route is not None:

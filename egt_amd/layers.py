@@ -43,10 +43,16 @@ class EGT(nn.Module):
                  attn_dropout=0.0,
                  name=None,
                  seed=0,
+                 matmul='f32',
                  **kwargs):
         super().__init__()
         if scale_degree and not gate_input:                       # egt_layers.py:20-21
             raise ValueError('scale_degree requires gate_input')
+        if matmul not in ('f32', 'bf16'):
+            raise ValueError("matmul must be 'f32' or 'bf16'")
+        # 'bf16': bf16 operands / fp32 accumulate for QK^T, A.V and their backward on the MFMA inner op (functional.AttnConfig.matmul);
+        # a call that path does not take raises instead of running fp32
+        self.matmul = matmul
         if scaler_type not in ('log', 'linear'):                  # egt_layers.py:23-24
             raise ValueError('scaler_type must be log or linear')
         self.supports_masking = True
@@ -109,7 +115,7 @@ class EGT(nn.Module):
                             random_mask_prob=self.random_mask_prob,
                             attn_dropout=self.attn_dropout, training=bool(training),
                             seed=self.next_seed() if stochastic else 0,
-                            need_a_tild=self.return_a_tild)
+                            need_a_tild=self.return_a_tild, matmul=self.matmul)
         V_att, H_hat, A_tild = EF.egt_attention(QKV, E, G, M, mask, cfg=cfg,
                                                 rand_mask=rand_mask, drop_keep=drop_keep)
         return V_att, H_hat, (A_tild if self.return_a_tild else None)
@@ -165,8 +171,23 @@ class EGTBlock(nn.Module):
                  clip_logits_value=[-5, 5], edge_activation=None,
                  edge_channel_type='residual', scale_degree=False, scaler_type='log',
                  num_virtual_nodes=0, random_mask_prob=0., attn_dropout=0.,
-                 node_dropout=0., edge_dropout=0., add_n_norm=False, seed=0, fused='auto', fused_attn_dropout=False):
+                 node_dropout=0., edge_dropout=0., add_n_norm=False, seed=0, fused='auto', fused_attn_dropout=False,
+                 attn_matmul='f32'):
         super().__init__()
+        if attn_matmul not in ('f32', 'bf16'):
+            raise ValueError("attn_matmul must be 'f32' or 'bf16'")
+        if attn_matmul == 'bf16':
+            # the mode exists on the MFMA inner op only (composed route: fused.route_core); what that op does not cover is
+            # refused here, not at the first step
+            d = model_width / num_heads
+            if num_heads != 8 or d not in (16, 32, 64):
+                raise ValueError(f"attn_matmul='bf16' needs num_heads = 8 and model_width / num_heads in {{16, 32, 64}} "
+                                 f"(got num_heads {num_heads}, head dim {d:g})")
+            if scale_degree or attn_dropout > 0:
+                raise ValueError("attn_matmul='bf16' is not available with scale_degree or attn_dropout")
+            if fused in (True, 'on'):
+                raise ValueError("attn_matmul='bf16' runs the composed operator: the fused block and the pair operator have no such mode")
+        self.attn_matmul = attn_matmul
         if not gate_attention and scale_degree:                   # graph_xformer_model_base.py:47-48
             raise ValueError('scale_degree only works with gate_attention')
         if edge_channel_type not in ('none', 'constrained', 'bias', 'residual'):
@@ -196,7 +217,7 @@ class EGTBlock(nn.Module):
                        scale_degree=scale_degree, scaler_type=scaler_type, edge_input=has_edge,
                        gate_input=self.gated, attn_mask=(edge_channel_type == 'constrained'),
                        num_virtual_nodes=num_virtual_nodes, random_mask_prob=random_mask_prob,
-                       attn_dropout=attn_dropout, name='mha', seed=seed)
+                       attn_dropout=attn_dropout, name='mha', seed=seed, matmul=attn_matmul)
         self.mha.return_a_tild = False
         self.dense_mha = KerasDense(model_width, model_width)
         if edge_channel_type in ('residual', 'constrained'):

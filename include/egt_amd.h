@@ -101,6 +101,21 @@ typedef struct egt_attn_desc {
  * the forward then packs the q/k/v operand copies of both directions once and the backward packs
  * only dV_att.  Without the bit each call packs what it needs into its own workspace. */
 #define EGT_ATTN_WS_SHARED 0x1
+/* egt_attn_desc.reserved, MFMA path, opt-in arithmetic mode: QK^T, A.V and their backward products take
+ * bfloat16 operands on v_mfma_f32_16x16x{32,16}_bf16 and accumulate in fp32.  Every tensor at the interface
+ * keeps its fp32 type and layout; egt_attn_mfma_fwd / _bwd cover exactly the descriptors
+ * egt_attn_mfma_supported answers 1 for.  Exactly these values are rounded to bfloat16 (round to nearest
+ * even), each once: s.Q (s = d^-1/2, rounded after the fp32 scaling), K, V, dV_att, the gated probabilities P
+ * that enter A.V and P^T.dV_att, and the logit gradient dS (after the clip mask, d_h_ext already added;
+ * the one rounded value feeds dK = dS^T.(sQ) and, through the workspace, dQ = dS.K.s).  Everything else is
+ * fp32 on unrounded values: the accumulators, scale / clip / +E / masks, exp, the softmax max and sum
+ * (rowstats slots 0 / 1), sigmoid, delta = sum dO.O, dA = dO.V^T, H_hat, dE, dG.  So H_hat and dG are as
+ * accurate as in the default mode relative to a reference fed the rounded operands; V_att, dQKV and (through
+ * delta) dE carry the bf16 noise (normalised L2 error ~1.7e-3).  Forward and backward of one step must agree
+ * on the bit.  The rowstats layout is unchanged, so egt_attn_bwd pairs with this forward as well.  The
+ * workspace queries answer for the bit: the dA tiles are bf16 there, so the size for both directions is smaller than
+ * without it (84 MB against 118 MB at B = 8, N = 512, d = 64); with EGT_ATTN_WS_SHARED the forward's size is the total.  Any other bit of `reserved` is EGT_E_FLAGS. */
+#define EGT_ATTN_MM_BF16 0x2
 
 const char* egt_last_error_string(void);
 int egt_abi_version(void);
