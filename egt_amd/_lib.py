@@ -288,6 +288,7 @@ _PROTOS = {
     "egt_block_supported": (C.c_int, [C.POINTER(BlockDesc)]),
     "egt_block_bwd_kernel": (C.c_char_p, [C.POINTER(BlockDesc)]),
     "egt_block_launch_form": (C.c_char_p, [C.POINTER(BlockDesc)]),
+    "egt_block_plan_static": (C.c_int, [C.POINTER(BlockDesc)]),
     "egt_block_saved_bytes": (C.c_size_t, [C.POINTER(BlockDesc)]),
     "egt_block_workspace_bytes": (C.c_size_t, [C.POINTER(BlockDesc)]),
     "egt_block_fwd": (C.c_int, [C.POINTER(BlockDesc), C.POINTER(BlockParams)] + [_VP] * 10),

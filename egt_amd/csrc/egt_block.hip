@@ -40,7 +40,7 @@
 #include "egt_block_dev.h"
 #include "egt_dma.h"
 
-#include "egt_block_fwd.h"   // k_block_fwd, k_block_fwd_r4
+#include "egt_block_fwd.h"   // k_block_fwd, k_block_fwd_r4, k_block_fwd_s64
 #include "egt_block_bwd.h"   // k_block_bwd_v4, k_block_bwd_v5, k_block_bwd_v4r
 
 // ================================================================ host glue ====
@@ -51,9 +51,10 @@
 //     MFMA-tile kernels (tests exercise both);  EGT_BWD_MATMUL=bf16x3: the backward's channel contractions as 3-term bf16 split
 //     products (opt-in; default exact fp32);  EGT_BWD_TL / EGT_FWD_ROWS = 4 .. 16: query rows per backward / forward workgroup
 //     (tests, sweeps; other values are ignored);  EGT_NRW_FWD_WAVES / EGT_NRW_BWD_WAVES = 4 | 8: waves per De = 8 workgroup, and
-//     EGT_NRW_FWD_HALF = 0 | 1: eight-row forward workgroups when that runs eight waves (tests, A/B; other values keep the rule).
+//     EGT_NRW_FWD_HALF = 0 | 1: eight-row forward workgroups when that runs eight waves (tests, A/B; other values keep the rule);
+//     EGT_NO_STATIC: the headline descriptor takes the generic k_block_fwd instance instead of k_block_fwd_s64 (tests, A/B).
 struct EgtBlockEnv {
-  bool no_narrow_fwd, no_narrow_bwd;
+  bool no_narrow_fwd, no_narrow_bwd, no_static;
   int bwd_mm;
   int bwd_tl, fwd_rows;                            // 0 when unset
   int nrw_fwd_waves, nrw_bwd_waves, nrw_fwd_half;  // 0 when unset; nrw_fwd_half -1
@@ -71,6 +72,7 @@ static const EgtBlockEnv& block_env() {
     EgtBlockEnv v{};
     v.no_narrow_fwd = env_flag_raw("EGT_NO_NARROW_FWD") || env_flag_raw("EGT_NO_NARROW");
     v.no_narrow_bwd = env_flag_raw("EGT_NO_NARROW_BWD") || env_flag_raw("EGT_NO_NARROW");
+    v.no_static = env_flag_raw("EGT_NO_STATIC");
     const char* mm = getenv("EGT_BWD_MATMUL");
     v.bwd_mm = (mm && !strcmp(mm, "bf16x3")) ? EGT_MM_BF16X3 : EGT_MM_F32;
     v.bwd_tl = env_int("EGT_BWD_TL", 0);
@@ -152,6 +154,7 @@ struct BlockPlan {
   bool sd;     // EGT_BF_SCALE_DEGREE: the SD instances (egt_block_sd.hip) of the MFMA-tile kernels; never the De = 8 VALU kernels
   bool ml;     // a mask TENSOR is read: the attention mask or a host random-mask buffer (the in-kernel random mask is not one)
   bool full;   // N is a multiple of 16 (else the kernels' ragged forms)
+  bool stat;   // the descriptor is the headline one that k_block_fwd_s64 is compiled for (plan_for has the list); EGT_NO_STATIC clears it
   FwdKernel fwd;
   EgtLaunch fl;
   int fwd_nw;      // k_narrow_fwd / k_block_fwd_r4: waves per workgroup
@@ -234,6 +237,12 @@ static BlockPlan plan_for(const egt_block_desc* d, bool ml) {
     P.fl = {B * ((N + P.RGF - 1) / P.RGF), 256, lds_tiles + (P.kvl ? lds_kv : 0)};
   }
   P.epi_ok = P.fwd != FwdKernel::tile || P.kvl;
+  // the compile-time instance of the headline shape (k_block_fwd_s64): exactly ZINC-500K's descriptor -- N = 64, De = 64, d = 8, fp32,
+  // gate + clip + edge LayerNorm, training with the in-kernel random mask, no mask tensor, no scalers / dropout, 16-row groups.  What
+  // a descriptor does not say (a key mask is passed, the node epilogue runs) launch_tile_fwd checks on the call.
+  P.stat = !E.no_static && DE == 64 && N == 64 && d->d == 8 && d->dtype == EGT_F32 && !ml && d->random_mask_prob > 0.0f &&
+           (d->flags & ~EGT_BF_SEED_DEVICE) == (EGT_BF_GATE | EGT_BF_CLIP | EGT_BF_TRAINING) &&
+           P.fwd == FwdKernel::tile && P.kvl && P.RGF == 16;
 
   // ---- backward
   // Query rows per backward workgroup (<= 16: the MFMA tiles of the node-side prologue):
@@ -453,6 +462,12 @@ static void launch_r4(BlockArgs& a, const BlockPlan& P, hipStream_t st) {
 }
 template <int DE, bool BF>   // k_block_fwd<DE, KVL, ML, FULL, BF>: five forms, FULL only for the headline one (K/V in LDS, no mask tensor)
 static void launch_tile_fwd(BlockArgs& a, const BlockPlan& P, hipStream_t st) {
+  if constexpr (DE == 64 && !BF) {
+    if (P.stat && a.km && a.rng_rm && a.epi) {   // the headline descriptor, called the headline way: the compile-time instance
+      egt_launch_planned<k_block_fwd_s64<DE>>("k_block_fwd", P.fl, st, a);
+      return;
+    }
+  }
   if (!P.kvl) {
     if (P.ml) egt_launch_planned<k_block_fwd<DE, false, true, false, BF>>("k_block_fwd", P.fl, st, a);
     else egt_launch_planned<k_block_fwd<DE, false, false, false, BF>>("k_block_fwd", P.fl, st, a);
@@ -591,6 +606,14 @@ static StackLayout stack_layout(const egt_block_desc* d, const BlockPlan& P, int
   S.saved_total = o;
   S.ws_total = P.common_total + P.layer_total * (size_t)layers;
   return S;
+}
+
+// 1 when plan_block gives `d` (no mask tensor) the compile-time instance of the headline shape, k_block_fwd_s64 -- which a call then
+// runs if it passes a key mask and the geometry takes the node epilogue; else 0 (EGT_NO_STATIC, any other descriptor, NULL or not
+// covered).  For tests and bench lines that must know which form ran.
+extern "C" int egt_block_plan_static(const egt_block_desc* d) {
+  if (block_check(d, false)) return 0;
+  return plan_block(d, mask_tensor(d, nullptr)).stat ? 1 : 0;
 }
 
 // saved / workspace bytes of a chain of `layers` blocks (0: not covered)

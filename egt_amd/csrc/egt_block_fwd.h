@@ -1,6 +1,7 @@
 // Forward pair kernels of the fused attention block (included by egt_block.hip, which holds the dispatch):
 // k_block_fwd<De,KVL,ML,FULL,BF,SD,DO> and the four-rows-per-iteration k_block_fwd_r4<De,FULL,NW,BF,SD,DO> for narrow edge channels
-// (SD = true: the degree-scaler instances, instantiated by egt_block_sd.hip; DO = true: the attention-dropout instances, egt_block_do.hip).
+// (SD = true: the degree-scaler instances, instantiated by egt_block_sd.hip; DO = true: the attention-dropout instances, egt_block_do.hip),
+// and k_block_fwd_s64, k_block_fwd written for the headline descriptor alone (everything the generic kernel tests per tile is a constant there).
 // The phases of the per-pair body (lane-constant operands, logits, online softmax and A.V, dense_edge_r, the row finish) are the
 // fwd_* functions below, with kv_frags / frag16 / key_mask_add of egt_block_dev.h; a kernel is its LDS carve-up, its staging and
 // prefetch, and its loop around them (profiles/fwd_phases_kres.txt has the register counts of this split against the pasted copies).
@@ -554,3 +555,118 @@ __global__ void __launch_bounds__(64 * NW, 2) k_block_fwd_r4(BlockArgs a) {
   if (a.epi) fwd_node_epilogue(a, sm + hf * 16 * QS_LD, qs + hf * 16 * QS_LD, b, lg * RW + hf * 16, min(16, N - (lg * RW + hf * 16)), N, wv, p, q);
 }
 
+
+// ---------------------------------------------------------------- forward, the headline shape at compile time ---
+// k_block_fwd<64, true, false, true, false> for ONE descriptor, with everything the generic kernel tests per tile known to the
+// compiler: N = 64 (four key tiles per row), De = 64, d = 8 (Dh = 64), gate + clip + edge LayerNorm, training with the in-kernel
+// random mask, a key mask, no mask tensors, 16-row groups, the node epilogue on (plan_for / launch_tile_fwd check every one of these;
+// any other call takes the generic instance).  Same LDS carve-up, same staging, same phase functions in the same order on the same
+// operands -- the results are bit-identical -- but the wave's loop is written per row with its four key tiles unrolled: the Q fragment,
+// fwd_row_init and fwd_row_finish sit outside the tile body, the first tile of the wave (no previous e' to store) and the last one (flush,
+// no prefetch) are peeled, the LDS ping-pong buffer of a tile is a constant, and a global address is a wave-uniform base plus a 32-bit
+// lane offset.  The launch constants reach the phase functions through `a` itself: the kernel overwrites its own copy of those fields
+// with the literals.  (One row loop that tests the row index at its first and last tile instead of the peeled rows measured 55.2 us
+// per launch against 54.7; the generic instance 57.3.)  DE = 64 is the only instance.
+template <int DE>
+__global__ void __launch_bounds__(256, 2) k_block_fwd_s64(BlockArgs a) {
+  static_assert(DE == 64, "k_block_fwd_s64 is written for the headline shape");
+  seed_from_device(a);
+  constexpr int N = 64, NTILE = N / 16;
+  using G = Geo<DE>;
+  a.N = N; a.De = DE; a.DK = 8; a.Dh = 64;
+  a.flags = EGT_BF_GATE | EGT_BF_CLIP | EGT_BF_TRAINING;
+  a.rng_rm = 1; a.rm = nullptr; a.M = nullptr;
+  __builtin_assume(a.km != nullptr);
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int p = lane & 15, q = lane >> 4;
+  const int wg = a.xcd ? egt_xcd_remap(blockIdx.x, gridDim.x) : (int)blockIdx.x;
+  const int b = wg / NTILE, l0 = (wg % NTILE) * 16;   // four 16-row groups per graph
+  float* tl0 = sm + wave * 2 * G::TILE_FLOATS;  // two tiles per wave (ping-pong)
+  float* kvs = sm + 8 * G::TILE_FLOATS;         // [N][KV_LD]
+  float* qs = kvs + N * KV_LD;                  // [16][QS_LD]
+  float* kms = qs + 16 * QS_LD;                 // [N]
+
+  // start-up loads as in k_block_fwd: one batch of K / V rows, the Q rows and the key-mask adds, the lane-constant operands behind them
+  float4 kvb[8], qb;
+  float kmb = 0.f;
+  const float* kvsrc = a.qkvp + (size_t)b * N * QKVP;
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int i = threadIdx.x + 256 * u, row = i >> 5, f = i & 31;
+    kvb[u] = *reinterpret_cast<const float4*>(kvsrc + row * QKVP + 64 + f * 4);
+  }
+  qb = *reinterpret_cast<const float4*>(kvsrc + (l0 + (threadIdx.x >> 4)) * QKVP + (threadIdx.x & 15) * 4);
+  if ((int)threadIdx.x < N) kmb = key_mask_add(a, (size_t)b * N + threadIdx.x);
+  float wA[4 * G::TILES], wrA[G::TILES][2], c2r[4];
+  float4 brv[G::TILES];
+  fwd_lane_weights<DE>(a, p, q, wA, c2r, wrA, brv);
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const int i = threadIdx.x + 256 * u, row = i >> 5, f = i & 31;
+    *reinterpret_cast<float4*>(kvs + row * KV_LD + f * 4) = kvb[u];
+  }
+  *reinterpret_cast<float4*>(qs + (threadIdx.x >> 4) * QS_LD + (threadIdx.x & 15) * 4) = qb;
+  if ((int)threadIdx.x < N) kms[threadIdx.x] = kmb;
+  __syncthreads();
+
+  // the wave's rows: l0 + wave + 4 li, li < 4.  Tile (li, mt) of e / e' lies ROW * li + 16 * DE * mt floats behind the wave's base.
+  constexpr int ROW = 4 * N * DE;
+  const uint32_t row0 = (uint32_t)(b * N + l0 + wave);             // [B * N] index of row li = 0 (wave-uniform)
+  const float* e_w = a.e + (size_t)row0 * N * DE;
+  float* eo_w = a.e_out + (size_t)row0 * N * DE;
+  const float* kvl = kvs + p * KV_LD + q * 16;                     // the lane's key of tile 0
+  const uint32_t lane8 = (uint32_t)p * BH;                         // the lane's part of the mask counter (pair index x 8 heads)
+  TileRegs<DE> tr;
+  tile_gload<DE, EGT_NT_FWD_E>(tr, e_w, lane, 16);
+
+  float Qf[16], mx[2], sum[2], O[16];
+  // one key tile.  Memory order as in k_block_fwd: [store of the previous tile's e'] then [loads of the next tile]
+  auto tile = [&](const int li, const int mt, const bool first, const bool last) __attribute__((always_inline)) {
+    float* tl = tl0 + (mt & 1) * G::TILE_FLOATS;
+    float* tlp = tl0 + ((mt & 1) ^ 1) * G::TILE_FLOATS;
+    const int off = li * ROW + mt * 16 * DE;   // (< 2^20 floats)
+    lds_sync();
+    if (!first) tile_from_lds<DE, EGT_NT_FWD_ST>(tlp, eo_w + (off - (mt ? 16 * DE : ROW - 3 * 16 * DE)), lane, 16);
+    tile_lds_put<DE>(tl, tr, lane, 16);
+    if (!last) tile_gload<DE, EGT_NT_FWD_E>(tr, e_w + (off + (mt < NTILE - 1 ? 16 * DE : ROW - 3 * 16 * DE)), lane, 16);
+    lds_sync();
+    float4 x[G::TILES];
+#pragma unroll
+    for (int t = 0; t < G::TILES; ++t) x[t] = frag_read<DE>(tl, p, q, t);
+    float Kf[16], Vf[16];
+    kv_frags(reinterpret_cast<const float4*>(kvl + mt * 16 * KV_LD), reinterpret_cast<const float4*>(kvl + mt * 16 * KV_LD + 64), Kf, Vf);
+    const float kadd = kms[mt * 16 + p];
+    // ---- norm_edge + [attention_gates | dense_edge_b] ----
+    v4f acc = {c2r[0], c2r[1], c2r[2], c2r[3]};
+    ln_frags<DE>(x, q, a.ln_eps, true);
+    acc = project<DE>(x, wA, acc);
+    float hh[2] = {0.f, 0.f}, xl[2] = {0.f, 0.f}, gl[2] = {0.f, 0.f};
+    fwd_pair_logits(a, true, Qf, Kf, acc, hh, xl, gl);
+    const MaskRegs mr{make_float2(1.f, 1.f), 0};
+    const uint32_t idx8 = ((row0 + 4u * li) * N + 16u * mt) * BH + lane8;   // == (uint32_t)((pair0 + p) * BH) of k_block_fwd
+    apply_masks<false>(a, kadd, mr, (size_t)idx8, q, xl, gl);
+    fwd_softmax_av(true, true, xl, gl, Vf, mx, sum, O);
+    fwd_edge_update<DE>(tl, p, q, true, hh, wrA, brv);
+    if (last) {   // last tile of the wave: flush
+      lds_sync();
+      tile_from_lds<DE, EGT_NT_FWD_ST>(tl, eo_w + off, lane, 16);
+    }
+  };
+  auto row = [&](const int li, const bool first, const bool last) __attribute__((always_inline)) {
+    float* qrow = qs + (wave + 4 * li) * QS_LD;
+    frag16(reinterpret_cast<const float4*>(qrow + q * 16), Qf);
+    fwd_row_init(mx, sum, O);
+    tile(li, 0, first, false);
+    tile(li, 1, false, false);
+    tile(li, 2, false, false);
+    tile(li, 3, false, last);
+    // the row's Q is dead (read above by this wave only): its slot keeps V_att for the epilogue
+    fwd_row_finish(a, (size_t)(row0 + 4u * li), p, q, mx, sum, O, true, qrow);
+  };
+  row(0, true, false);
+#pragma unroll 1
+  for (int li = 1; li < 3; ++li) row(li, false, false);
+  row(3, false, true);
+  fwd_node_epilogue(a, sm, qs, b, l0, 16, N, wave, p, q);
+}

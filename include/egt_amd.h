@@ -347,6 +347,11 @@ const char* egt_block_bwd_kernel(const egt_block_desc* desc);
  * "fwd=<family>/<waves>w[/half] bwd=<family>/<waves>w/tl<rows per workgroup>", e.g. "fwd=k_narrow_fwd/8w/half bwd=k_narrow_bwd/8w/tl8".
  * Thread-local string, valid until the thread's next call; NULL when `desc` is not covered.  For tests and bench lines. */
 const char* egt_block_launch_form(const egt_block_desc* desc);
+/* 1 when the dispatch gives `desc` (no mask tensor passed) the compile-time forward instance of the headline shape, k_block_fwd_s64
+ * (N = 64, De = 64, d = 8, fp32, gate + clip, training with the in-kernel random mask, 16-row groups) -- which a call then runs
+ * if it passes a key mask and its geometry takes the node epilogue; else 0 (any other descriptor, EGT_NO_STATIC=1, NULL, not
+ * covered).  Results are bit-identical either way.  Read-only; for tests and bench lines that must know which form ran. */
+int egt_block_plan_static(const egt_block_desc* desc);
 /* bytes of the forward->backward buffer (V_att, softmax row statistics, packed
  * Q/K/V, the LN-folded edge weights and the MFMA-fragment-major copies of Wqkv / Wo the forward prepares: the backward
  * must be given the `saved` buffer of ITS forward call, made with the same parameter values) and of the scratch
