@@ -1,8 +1,9 @@
-// Device side of the d in {16,32,64}, H = 8 family: what the MFMA inner-op kernels (egt_attn_mfma.hip: k_attn_mfma_fwd / _bwd_kv) and
-// the fused pair operator (egt_pair.h: k_pair_fwd / k_pair_bwd) share -- arguments, LDS layouts, LDS-DMA, and ONE copy of every
-// attention phase: the key terms of a slot, the forward and the backward elementwise unit, the MFMA contractions, the backward's
-// operand addresses, the forward's finalize.  The phases are pure arithmetic, LDS accesses and MFMAs: every wait, barrier, priority
-// change, scheduling fence and stamp stays in the kernel bodies, whose instruction order is pinned there.
+// Device side of the d in {16,32,64}, H = 8 family: what the MFMA inner-op kernels (egt_attn_kernels.h: k_attn_mfma_fwd / _bwd_kv /
+// _bwd_q, one body each for the exact-fp32 and the bf16-product operand form) and the fused pair operator (egt_pair.h: k_pair_fwd /
+// k_pair_bwd) share -- arguments, LDS layouts, LDS-DMA, and ONE copy of every attention phase: the key terms of a slot, the forward
+// and the backward elementwise unit, the fp32 MFMA contractions and the bf16 form's primitives, the backward's operand addresses, the
+// forward's finalize.  The phases are pure arithmetic, LDS accesses and MFMAs: every wait, barrier, priority change, scheduling
+// fence and stamp stays in the kernel bodies, whose instruction order is pinned there.
 #pragma once
 #include <limits.h>
 
@@ -52,6 +53,66 @@ __device__ __forceinline__ v4f MFMA(float a, float b, v4f c) { c[0] += a * b; re
 #else
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 #endif
+
+// ---- the bf16 operand form (MM = 1: egt_attn_desc.reserved & EGT_ATTN_MM_BF16): products on v_mfma_f32_16x16x16_bf16 / _16x16x32_bf16,
+// fp32 accumulate.  The fp32 form's contraction order kappa(T, u, q) = 16 T + 4 q + u gives a lane (row, q) the four consecutive
+// channels 16 T + 4 q .. + 3 of its row in one 16-byte fragment: exactly the K = 16 bf16 operand (lane l: A[l & 15][4 (l >> 4) + j]).
+// Four fp32 MFMAs (u = 0..3) become ONE bf16 MFMA on the fragment packed with v_cvt_pk_bf16_f32.
+typedef short v4s __attribute__((ext_vector_type(4)));
+typedef short v8s __attribute__((ext_vector_type(8)));
+typedef __bf16 v2b __attribute__((ext_vector_type(2)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x16bf16_1k((a), (b), (c), 0, 0, 0)
+#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+// (lo, hi) -> one dword of two bf16, round to nearest even (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ unsigned pk_bf16(float lo, float hi) {
+  const v2f x = {lo, hi};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(x, v2b));
+}
+__device__ __forceinline__ float bf16_round(float x) { return __uint_as_float(pk_bf16(x, x) << 16); }
+__device__ __forceinline__ v4s bf4(float x0, float x1, float x2, float x3) {
+  union { unsigned u[2]; v4s s; } r;
+  r.u[0] = pk_bf16(x0, x1); r.u[1] = pk_bf16(x2, x3);
+  return r.s;
+}
+__device__ __forceinline__ v4s bf4(const float4& v) { return bf4(v.x, v.y, v.z, v.w); }
+__device__ __forceinline__ v4s bf4(const float (&v)[4]) { return bf4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ v8s cat8(v4s a, v4s b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
+// c += sum over the d channels of a lane's fragments: a[T], b[T] = channels 16 T + 4 q .. + 3 of the lane's row.  Two channel blocks
+// pair into one K = 32 MFMA for d >= 32 (both operands take the same (2 T', 2 T' + 1) pairing: the contraction order is free);
+// d = 16 is one K = 16 MFMA -- no zero padding.
+template <int KT>
+__device__ __forceinline__ v4f dot_d(const v4s (&a)[KT], const v4s (&b)[KT], v4f c) {
+  if constexpr (KT == 1) {
+    return MFMA16(a[0], b[0], c);
+  } else {
+#pragma unroll
+    for (int t = 0; t < KT / 2; ++t) c = MFMA32(cat8(a[2 * t], a[2 * t + 1]), cat8(b[2 * t], b[2 * t + 1]), c);
+    return c;
+  }
+}
+
+// What the operand form MM of a kernel decides beside its contractions: the type of a fragment that stays in registers across the
+// trips (Frag: K / V of the backward), of a dA element in the workspace (DA), and how a fragment read from the operand arrays takes
+// its form (cvt).
+template <int MM> struct AttnForm;
+template <> struct AttnForm<0> {
+  typedef float4 Frag;
+  typedef float DA;
+  static __device__ __forceinline__ const float4& cvt(const float4& v) { return v; }
+};
+template <> struct AttnForm<1> {
+  typedef v4s Frag;
+  typedef unsigned short DA;
+  static __device__ __forceinline__ v4s cvt(const float4& v) { return bf4(v.x, v.y, v.z, v.w); }
+};
+// a lane's four dA values of its tile (element offset in `dst`): 16 bytes of fp32, or the 8 bytes packed for dK
+__device__ __forceinline__ void da_store(float* dst, const float (&da)[4]) { *reinterpret_cast<float4*>(dst) = make_float4(da[0], da[1], da[2], da[3]); }
+__device__ __forceinline__ void da_store(unsigned short* dst, v4s da) {
+  union { v4s s; uint2 u; } pk;
+  pk.s = da;
+  *reinterpret_cast<uint2*>(dst) = pk.u;
+}
 
 // LDS hand-off between the waves of a workgroup WITHOUT draining vector memory: __syncthreads() is
 // s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier on gfx950; the operand prefetches and the output stores of
@@ -128,7 +189,7 @@ __device__ __forceinline__ unsigned dma_lane_off(int lane) {   // source byte of
 }
 #define OPS_STAGE 32768   // bytes of one operand stage: 4 heads x (two 4 KB tiles)
 #define OPS_BYTES (2 * OPS_STAGE)
-// launch geometry of the inner-op kernels (egt_attn_mfma.hip and their bf16-operand twins in egt_attn_bf16.hip: one plan, plan_attn)
+// launch geometry of the inner-op kernels (egt_attn_kernels.h, both operand forms: one plan, plan_attn)
 #define FQ 2         // forward: query tiles per compute wave
 #define BK 2         // backward: key tiles per compute wave
 #define QW_TILES 8   // dQ: query tiles per workgroup
@@ -342,7 +403,7 @@ __device__ __forceinline__ void attn_fwd_finalize(const AttnMfmaArgs& a, float* 
     *reinterpret_cast<float4*>(a.rowstats + (((size_t)b * a.N + l) * AH + h) * 4) = make_float4(mrun, lrun, 0.f, 0.f);
 }
 
-// ---- egt_attn_bf16.hip: the inner op with bf16 products (egt_attn_desc.reserved & EGT_ATTN_MM_BF16), launched from plan_attn's
-// geometry; var: the Feat instance of the direction
+// ---- egt_attn_bf16.hip: the MM = 1 instances of egt_attn_kernels.h (egt_attn_desc.reserved & EGT_ATTN_MM_BF16) behind their two
+// entry points, launched from plan_attn's geometry; var: the Feat instance of the direction
 void egt_attn_bf16_launch_fwd(int var, const EgtLaunch& pack, const EgtLaunch& fwd, const AttnMfmaArgs& a, hipStream_t st);
 void egt_attn_bf16_launch_bwd(int var, const EgtLaunch& pack, const EgtLaunch& kv, const EgtLaunch& q, const AttnMfmaArgs& a, hipStream_t st);

@@ -2,7 +2,7 @@
 """A sha256 per output tensor of single ops, over the cases of their GPU tests, for comparing two builds of the library bit by bit.
 One process loads one library: run it once per build (each run under its own time limit, chained with &&) and diff the listings.
 
-    python tools/op_bits.py [--ops head,embed,block,ffn,attn,pair] [--lib path/to/libegt_amd.so] > listing.txt      (--lib: the EGT_AMD_LIB of this process)
+    python tools/op_bits.py [--ops head,embed,block,ffn,attn,attn_bf16,pair] [--lib path/to/libegt_amd.so] > listing.txt      (--lib: the EGT_AMD_LIB of this process)
     python tools/op_bits.py --condense listing.txt      (the listing in one line per case: a sha256 over the case's lines; for keeping a comparison's result)
 
 head:  the fused edge head and node head over the cases of tests/test_distance_head_gpu.py and tests/test_node_head_gpu.py (their
@@ -24,6 +24,9 @@ attn:  the MFMA inner op (d in {16, 32, 64}) forward and backward through the C 
        mfma_cases of tests/memcontract.py and the shapes, options and inputs (the tests' seeds) of test_attn_mfma_kernel_vs_oracle,
        test_attn_mfma_in_kernel_random_mask and test_attn_mfma_shared_workspace_fwd_to_bwd (tests/test_attn_gpu.py).  The instance
        choice is read once per process: run it again under EGT_ATTN_GENERIC=1 (the main configuration on the V = 0 instances).
+attn_bf16: the same op with bf16 products (desc.reserved = ATTN_WS_SHARED | ATTN_MM_BF16, the workspace of the size query for that
+       descriptor) over the same three parametrisations (not the memcontract cases): d in {16, 32, 64}, ragged and odd tile counts, V = 0 / 1 / 2;
+       again once more under EGT_ATTN_GENERIC=1.
 pair:  the fused pair operator forward and backward through the C ABI: v_att, e_out, rowstats, d_qkv, d_e and the eight parameter
        gradients over the pair_cases of tests/memcontract.py and, in its format, the shapes of
        test_pair_block_in_kernel_random_mask_vs_oracle (tests/test_pair_gpu.py), each with the in-kernel random mask (V = 2) and with
@@ -195,7 +198,7 @@ def ffn(gpu):
         emit(tag.replace("ffn_prepared", "ffn_fresh"), [("dx", dx)] + [("d " + n, g) for n, g in zip(TF.NAMES, grads)])
 
 
-def attn(gpu):
+def attn(gpu, bf16=False):
     import ctypes as C
     import torch
     import memcontract as M
@@ -203,7 +206,8 @@ def attn(gpu):
     from egt_amd import _lib as L
     from egt_amd.functional import AttnConfig, _attn_desc
     lib, H = L.load(), 8
-    for case in M.mfma_cases(lib):
+    op = "attn_bf16" if bf16 else "attn"
+    for case in [] if bf16 else M.mfma_cases(lib):
         emit(f"attn {case.name}", sorted(M.run(case, M.ZERO, gpu, sync=torch.cuda.synchronize, check_rc=L.check).items()))
 
     def run(tag, B, N, d, seed, opts, masked, cfg):
@@ -220,7 +224,7 @@ def attn(gpu):
         cu = lambda t: None if t is None else t.to(gpu)
         QKV, E, G, km, Mt, rm, dV, dH = map(cu, (QKV, E, G, km, Mt, rm, dV, dH))
         desc = _attn_desc(cfg, B, N, d, True, G is not None, Mt is not None)
-        desc.reserved = L.ATTN_WS_SHARED
+        desc.reserved = L.ATTN_WS_SHARED | (L.ATTN_MM_BF16 if bf16 else 0)
         p = C.byref(desc)
         new = lambda *s: torch.zeros(*s, device=gpu)
         v_att, h_hat, rowstats, d_qkv, d_E = new(B, N, d * H), new(B, N, N, H), new(B, N, H, 4), new(B, N, 3 * d * H), new(B, N, N, H)
@@ -237,12 +241,12 @@ def attn(gpu):
     for B, N, d, opts in params_of(TA.test_attn_mfma_kernel_vs_oracle, "B,N,d,opts"):
         cfg = AttnConfig(num_heads=H, clip_logits_value=opts.get("clip", (-5.0, 5.0)), random_mask_prob=0.5 if opts.get("rand_p") else 0.0,
                          training=bool(opts.get("rand_p")), need_a_tild=False)
-        run(f"attn vs_oracle B{B}-N{N}-d{d}-{'-'.join(f'{k}={v}' for k, v in opts.items()) or 'main'}", B, N, d, B * 100 + N + d, opts, (0, 5), cfg)
+        run(f"{op} vs_oracle B{B}-N{N}-d{d}-{'-'.join(f'{k}={v}' for k, v in opts.items()) or 'main'}", B, N, d, B * 100 + N + d, opts, (0, 5), cfg)
     for N, d in params_of(TA.test_attn_mfma_in_kernel_random_mask, "N,d"):
-        run(f"attn in_kernel_random_mask N{N}-d{d}", 2, N, d, N + d, {}, (1, 7),
+        run(f"{op} in_kernel_random_mask N{N}-d{d}", 2, N, d, N + d, {}, (1, 7),
             AttnConfig(num_heads=H, random_mask_prob=0.25, training=True, seed=4242, need_a_tild=False))
     for N, d in params_of(TA.test_attn_mfma_shared_workspace_fwd_to_bwd, "N,d"):
-        run(f"attn shared_workspace N{N}-d{d}", 2, N, d, N * 3 + d, {}, (1, 7), AttnConfig(num_heads=H, need_a_tild=False))
+        run(f"{op} shared_workspace N{N}-d{d}", 2, N, d, N * 3 + d, {}, (1, 7), AttnConfig(num_heads=H, need_a_tild=False))
 
 
 def pair(gpu):
@@ -271,14 +275,15 @@ def main():
     if args.condense:
         return condense(args.condense)
     ops = args.ops.split(",")
-    if not ops or set(ops) - {"head", "embed", "block", "ffn", "attn", "pair"}:
-        ap.error("--ops takes head, embed, block, ffn, attn, pair or several of them")
+    if not ops or set(ops) - {"head", "embed", "block", "ffn", "attn", "attn_bf16", "pair"}:
+        ap.error("--ops takes head, embed, block, ffn, attn, attn_bf16, pair or several of them")
     if args.lib:
         os.environ["EGT_AMD_LIB"] = os.path.abspath(args.lib)      # read when egt_amd._lib is imported
     sys.path[:0] = [REPO, os.path.join(REPO, "tests")]
     import torch
     gpu = torch.device("cuda", 0)
-    for op, fn in (("head", head), ("embed", embed), ("block", block), ("ffn", ffn), ("attn", attn), ("pair", pair)):
+    for op, fn in (("head", head), ("embed", embed), ("block", block), ("ffn", ffn), ("attn", attn), ("attn_bf16", lambda g: attn(g, bf16=True)),
+                   ("pair", pair)):
         if op in ops:
             fn(gpu)
 
