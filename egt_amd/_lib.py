@@ -76,6 +76,12 @@ class FfnParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in FFN_PARAM_FIELDS]
 
 
+class XtalkDesc(C.Structure):   # egt_xtalk_desc; its parameter / gradient structs are FfnParams
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("De", C.c_int32), ("Dh", C.c_int32), ("s_e", C.c_int32),
+                ("s_n", C.c_int32), ("dtype", C.c_int32), ("activation", C.c_int32), ("ln_eps", C.c_float),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 BLOCK_PARAM_FIELDS = (
     "norm_edge_gamma", "norm_edge_beta",
     "attention_gates_kernel", "attention_gates_bias",
@@ -317,6 +323,11 @@ _PROTOS = {
     "egt_ffn_fwd": (C.c_int, [C.POINTER(FfnDesc), C.POINTER(FfnParams)] + [_VP] * 4),
     "egt_ffn_bwd": (C.c_int, [C.POINTER(FfnDesc), C.POINTER(FfnParams)] + [_VP] * 3
                     + [C.POINTER(FfnParams)] + [_VP] * 2),
+    "egt_xtalk_supported": (C.c_int, [C.POINTER(XtalkDesc)]),
+    "egt_xtalk_workspace_bytes": (C.c_size_t, [C.POINTER(XtalkDesc)]),
+    "egt_xtalk_fwd": (C.c_int, [C.POINTER(XtalkDesc), C.POINTER(FfnParams)] + [_VP] * 8),
+    "egt_xtalk_bwd": (C.c_int, [C.POINTER(XtalkDesc), C.POINTER(FfnParams)] + [_VP] * 9
+                      + [C.POINTER(FfnParams)] + [_VP] * 2),
     "egt_optim_supported": (C.c_int, [C.POINTER(OptimDesc)]),
     "egt_optim_prepare": (C.c_int, [C.POINTER(OptimDesc), _VP, _VP]),
     "egt_optim_step": (C.c_int, [C.POINTER(OptimDesc)] + [_VP] * 6),

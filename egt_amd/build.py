@@ -16,13 +16,14 @@ REPO = os.path.dirname(ROOT)
 CSRC = os.path.join(ROOT, "csrc")
 LIBDIR = os.path.join(ROOT, "lib")
 LIB = os.path.join(LIBDIR, "libegt_amd.so")
-SOURCES = ["egt_capi.hip", "egt_attn.hip", "egt_attn_mfma.hip", "egt_attn_bf16.hip", "egt_pair_node.hip", "egt_edge.hip", "egt_block.hip", "egt_block_sd.hip", "egt_block_do.hip", "egt_narrow.hip", "egt_node.hip", "egt_ffn.hip", "egt_masks.hip", "egt_embed.hip", "egt_head.hip", "egt_graph_head.hip", "egt_node_embed.hip", "egt_dp.hip", "egt_optim.hip", "egt_batch.hip", "egt_accum.hip"]
+SOURCES = ["egt_capi.hip", "egt_attn.hip", "egt_attn_mfma.hip", "egt_attn_bf16.hip", "egt_pair_node.hip", "egt_edge.hip", "egt_block.hip", "egt_block_sd.hip", "egt_block_do.hip", "egt_narrow.hip", "egt_node.hip", "egt_ffn.hip", "egt_xtalk.hip", "egt_masks.hip", "egt_embed.hip", "egt_head.hip", "egt_graph_head.hip", "egt_node_embed.hip", "egt_dp.hip", "egt_optim.hip", "egt_batch.hip", "egt_accum.hip"]
 ARCH = "gfx950"
 # per-source compiler flags.  egt_ffn.hip: the backward keeps 256 weight-gradient accumulator
 # registers per wave; with hipcc's default (AGPR-form MFMA everywhere) the short-lived GEMM
 # accumulators compete for the same 256 AccVGPRs and 300+ registers spill; VGPR-form MFMA lets
 # the allocator park the long-lived tiles in AccVGPRs instead (0 spills).
 EXTRA_FLAGS = {"egt_ffn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "egt_xtalk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],   # (the same weight-gradient tiles, and more of them)
                # egt_narrow.hip: SLP-packed v_pk_add_f32 cannot take the DPP operand of the dQ reduction
                "egt_narrow.hip": ["-fno-slp-vectorize"]}
 if os.environ.get("EGT_BLOCK_FLAGS"):   # experiments: extra hipcc flags for egt_block.hip

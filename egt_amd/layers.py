@@ -384,7 +384,7 @@ class EGTLayerStack(nn.Module):
     both channels in ffn_block (:312-320); otherwise only the node channels (:322-323)."""
 
     def __init__(self, model_height=4, model_width=64, edge_width=64, activation='elu', ffn_matmul='f32', ffn_multiplier=2.0,
-                 **block_kwargs):
+                 node2edge_xtalk=0., edge2node_xtalk=0., **block_kwargs):
         super().__init__()
         from .ffn import FFN as _FFN
         from functools import partial
@@ -401,11 +401,29 @@ class EGTLayerStack(nn.Module):
         for i, blk in enumerate(self.blocks):
             blk._static_edge, blk._static_first = ect == 'bias', i == 0
         self.last_edge_route = None   # "static" | "per-layer-bias" | "chained-residual" | "composed" | "mixed": what the last forward ran
-        # FFN.__init__ raises ValueError for a width the fused FFN kernels do not cover (at
-        # construction, not at the first forward: ADVICE r1)
-        self.ffn_node = nn.ModuleList([FFN(model_width, activation=activation) for _ in range(model_height)])
-        self.ffn_edge = nn.ModuleList([FFN(edge_width, activation=activation) for _ in range(model_height)]) \
-            if ect in ('residual', 'constrained') else None
+        # cross-talk (node2edge_xtalk / edge2node_xtalk, graph_xformer_model_base.py:260-307) sits between fnn_lr1 and the
+        # activation of BOTH channel types, so it exists only where the edge FFN does: with 'bias' edge channels the reference
+        # never runs it and the numbers are those of fraction 0.  A layer with cross-talk holds the same parameters under the same
+        # Keras names, fnn_lr2_* at the exchanged widths, and runs egt_amd.xtalk after the attention block.
+        self.xtalk = None
+        self.xtalk_fused = True       # False: every cross-talk layer on xtalk_ffn_composed (measurements, debugging)
+        self.last_xtalk_route = None  # "fused" | "composed": what the last forward ran in its cross-talk layers
+        if (node2edge_xtalk > 0 or edge2node_xtalk > 0) and ect in ('residual', 'constrained'):
+            from . import xtalk as XT
+            if ffn_matmul != 'f32' or round(2 * model_width) != round(model_width * ffn_multiplier):
+                raise ValueError("the cross-talk FFN is built for ffn_multiplier = 2 and exact fp32 products (ffn_matmul='f32')")
+            if activation not in ('elu', 'relu'):
+                raise ValueError(f"cross-talk FFN activation must be elu or relu (got {activation!r})")
+            kn, ke = XT.lr2_widths(edge_width, model_width, node2edge_xtalk, edge2node_xtalk, ffn_multiplier)
+            self.xtalk, self.activation = (float(node2edge_xtalk), float(edge2node_xtalk)), activation
+            self.ffn_node = nn.ModuleList([XT.XtalkFFNParams(model_width, kn, ffn_multiplier) for _ in range(model_height)])
+            self.ffn_edge = nn.ModuleList([XT.XtalkFFNParams(edge_width, ke, ffn_multiplier) for _ in range(model_height)])
+        else:
+            # FFN.__init__ raises ValueError for a width the fused FFN kernels do not cover (at
+            # construction, not at the first forward: ADVICE r1)
+            self.ffn_node = nn.ModuleList([FFN(model_width, activation=activation) for _ in range(model_height)])
+            self.ffn_edge = nn.ModuleList([FFN(edge_width, activation=activation) for _ in range(model_height)]) \
+                if ect in ('residual', 'constrained') else None
         self.overlap_ffn = False     # node FFN on a side stream beside the edge FFN (small per-GPU batches; see forward)
         self._side = None
 
@@ -421,6 +439,8 @@ class EGTLayerStack(nn.Module):
             why = FZ.bf16_refusal(blk)
             if why:
                 raise ValueError(f"bf16 edge tensors need the fused block; layer {i}: {why}")
+        if self.xtalk:
+            raise ValueError("bf16 edge tensors: the cross-talk FFN takes fp32 edge tensors")
         if self.ffn_edge is not None:
             import ctypes as C
             from . import _lib as L
@@ -459,6 +479,24 @@ class EGTLayerStack(nn.Module):
                 prm.copy_(w.to(prm.device))
         return missing, unexpected
 
+    def _xtalk_ffn(self, i, h, e, mask, edge_dead=False):
+        """ffn_block of layer i with cross-talk: the fused edge kernels where the library covers the call (fp32 on the GPU,
+        egt_xtalk_supported), the composed op otherwise.  edge_dead: nobody reads this layer's e' (the last layer of a model
+        with readout_edges=False).  With edge2node_xtalk > 0 its fnn_lr1_edge still feeds the nodes and the layer runs whole;
+        with node -> edge cross-talk only, the whole edge side is dead and only the node side runs."""
+        from . import xtalk as XT
+        n2e, e2n = self.xtalk
+        if mask is None:
+            mask = torch.ones(h.shape[:2], dtype=torch.bool, device=h.device)
+        s_e, s_n = XT.split_widths(e.shape[-1], h.shape[-1], n2e, e2n)
+        if edge_dead and s_e == 0:
+            return XT.xtalk_node_only(h, self.ffn_node[i].tensors(), s_n, self.activation), e
+        fused = self.xtalk_fused and h.is_cuda and e.is_cuda and h.dtype == torch.float32 and e.dtype == torch.float32 and \
+            XT.xtalk_supported(h.shape[0], h.shape[1], e.shape[-1], h.shape[-1], s_e, s_n, self.activation)
+        self.last_xtalk_route = "fused" if fused else "composed"
+        op = XT.xtalk_ffn if fused else XT.xtalk_ffn_composed
+        return op(h, e, mask, self.ffn_node[i].tensors(), self.ffn_edge[i].tensors(), n2e, e2n, self.activation)
+
     def forward(self, h, e, mask=None, attn_mask=None, skip_last_edge_ffn=False):
         """skip_last_edge_ffn: a model whose readout ignores the edge channels (e.g. ZINC, readout_edges=False)
         does not contain the last layer's edge FFN in the reference either (a Keras functional model keeps only
@@ -469,6 +507,9 @@ class EGTLayerStack(nn.Module):
             blk.last_edge_route = "composed"
             h, e = blk(h, e, mask, attn_mask)                  # layer/{i}/attention
             routes.add(blk.last_edge_route)
+            if self.xtalk:                                      # layer/{i}/ffn with the exchange
+                h, e = self._xtalk_ffn(i, h, e, mask, edge_dead=skip_last_edge_ffn and i == last)
+                continue
             edge_ffn = self.ffn_edge is not None and not (skip_last_edge_ffn and i == last)
             if self.overlap_ffn and edge_ffn and h.is_cuda:
                 # the node and the edge FFN of a layer are independent (graph_xformer_model_base.py:309-324): the node FFN

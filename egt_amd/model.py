@@ -161,12 +161,27 @@ class ZincDCTransformer(nn.Module):
         unsupported = dict(readout_edges=(readout_edges, False),
                            node_dropout=(node_dropout, 0), edge_dropout=(edge_dropout, 0), l2_reg=(l2_reg, 0),
                            add_n_norm=(add_n_norm, False),
-                           combine_layer_repr=(combine_layer_repr, False), node2edge_xtalk=(node2edge_xtalk, 0),
-                           edge2node_xtalk=(edge2node_xtalk, 0), node2edge_embed=(node2edge_embed, False),
+                           combine_layer_repr=(combine_layer_repr, False), node2edge_embed=(node2edge_embed, False),
                            node_normalization=(node_normalization, 'layer'), edge_normalization=(edge_normalization, 'layer'))
         bad = {k: v for k, (v, d) in unsupported.items() if v != d}
         if bad:    # the reference model applies every one of these: training "a different model without a warning" is not an option
             raise NotImplementedError(f"{type(self).__name__} covers the shipped configs; not built: {bad}")
+        # cross-talk in the FFN (egt_amd.xtalk): fp32 edge tensors, no virtual nodes; with 'bias' edge channels there is no edge
+        # FFN, the reference never runs the exchange and the model is the one without the keys
+        for k, v in (("node2edge_xtalk", node2edge_xtalk), ("edge2node_xtalk", edge2node_xtalk)):
+            if not isinstance(v, (int, float)) or isinstance(v, bool) or not 0 <= v <= 1:
+                raise ValueError(f"{k} must be a fraction in [0, 1] (got {v!r})")
+        if node2edge_xtalk > 0 or edge2node_xtalk > 0:
+            why = {}
+            if self.edge_dtype != torch.float32:
+                why["edge_dtype"] = edge_dtype
+            if int(num_virtual_nodes):
+                why["num_virtual_nodes"] = num_virtual_nodes
+            if edge_channel_type not in ('residual', 'constrained', 'bias'):
+                why["edge_channel_type"] = edge_channel_type
+            if why:
+                raise NotImplementedError(f"{type(self).__name__} covers the shipped configs; not built: node2edge_xtalk="
+                                          f"{node2edge_xtalk}, edge2node_xtalk={edge2node_xtalk} with {why}")
         # virtual nodes (VNModel, graph_model_base.py:212-281): nv learned node embeddings in front of h, e bordered with nv
         # learned edge embeddings, the graph-level readout taken from the virtual nodes (zinc/dc.py:105-110)
         nv = self.num_virtual_nodes = int(num_virtual_nodes)
@@ -227,7 +242,8 @@ class ZincDCTransformer(nn.Module):
                                     fused_attn_dropout=fused_attn_dropout,
                                     # the operator reads num_virtual_nodes in its degree scaler only (egt_layers.py:123-136)
                                     num_virtual_nodes=nv if scale_degree else 0,
-                                    ffn_matmul=ffn_matmul, ffn_multiplier=ffn_multiplier)
+                                    ffn_matmul=ffn_matmul, ffn_multiplier=ffn_multiplier,
+                                    node2edge_xtalk=node2edge_xtalk, edge2node_xtalk=edge2node_xtalk)
         if self.edge_dtype == torch.bfloat16:
             self.layers.check_edge_dtype(self.edge_dtype)   # ValueError now, not a TypeError at the first step
         self.node_norm_final = KerasLayerNorm(model_width) if do_final_norm else None
@@ -304,6 +320,9 @@ class ZincDCTransformer(nn.Module):
             return []                    # EGT-Simple: every layer's gate and bias projections feed h; nothing else is edge-side
         if self.dist_head is not None:
             return []                    # the distance objective reads the final edge channels: the whole edge side is live
+        if self.layers.xtalk and self.layers.xtalk[1] > 0:
+            f = self.layers.ffn_edge[-1]   # edge -> node cross-talk: the last fnn_lr1_edge feeds the nodes, only fnn_lr2_edge is dead
+            return [f.lr2_kernel, f.lr2_bias]
         last = self.layers.blocks[-1]
         dead = [last.dense_edge_r.kernel, last.dense_edge_r.bias]
         if self.layers.ffn_edge is not None:

@@ -105,6 +105,9 @@ def default_config(scheme: str = "zinc.svd") -> Config:
         resident_step=False,     # (not a reference key) batch assembly, step, update and the epoch's metric sums replayed as ONE
                                  # hipGraph per step, no per-step synchronisation: egt_amd.graph.ResidentStep; needs use_hipgraph,
                                  # fused_optimizer and device_dataset, one process
+        node2edge_xtalk=0., edge2node_xtalk=0.,   # (not keys of the reference's schemes; its model has them) the fractions of the
+                                 # FFN's hidden channels the node and edge sides exchange per layer: egt_amd.xtalk; part of
+                                 # model_config only when non-zero
     )
     c.update(  # BaseDCModelScheme
         model_name="dc", dataset_name="dataset",
@@ -166,6 +169,10 @@ def make_config(user: Optional[dict], scheme: Optional[str] = None) -> Config:
         raise ValueError(f'config "edge_dtype" must be one of {list(EDGE_DTYPES)} (got {c.edge_dtype!r})')
     if not isinstance(c.fused_attn_dropout, bool):
         raise ValueError(f'config "fused_attn_dropout" must be true or false (got {c.fused_attn_dropout!r})')
+    for k in ("node2edge_xtalk", "edge2node_xtalk"):
+        v = c[k]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v <= 1:
+            raise ValueError(f'config "{k}" must be a fraction in [0, 1] (got {v!r})')
     return c
 
 
@@ -176,6 +183,9 @@ def model_config(c: Config) -> dict:
         mc.update(readout_edges=False, num_virtual_nodes=c.num_virtual_nodes)
     elif c.dataset_name == "mnist":        # the MNIST scheme adds the first only (mnist/svd.py:29-32)
         mc.update(readout_edges=False)
+    for k in ("node2edge_xtalk", "edge2node_xtalk"):   # project keys: the shipped mappings stay as they are
+        if c.get(k, 0) > 0:
+            mc[k] = c[k]
     return mc
 
 

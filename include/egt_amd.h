@@ -512,6 +512,45 @@ int egt_ffn_bwd(const egt_ffn_desc* desc, const egt_ffn_params* params, const vo
                 const void* dy, void* dx, const egt_ffn_params* grads, void* workspace,
                 void* stream);
 
+/* ---- edge FFN with node<->edge cross-talk (node2edge_xtalk / edge2node_xtalk) ----
+ * The edge side of ffn_block with cross-talk (lib/models/graph_xformer_model_base.py:227-324), ffn_multiplier = 2:
+ *   pre = Dense_1(LayerNorm(e))                      [B,N,N,H], H = 2 De, split along channels into
+ *         [ er (s_e) | ec (s_e) | tail (H - 2 s_e) ]
+ *   hn[b,n,c] = divide_no_nan( sum_i m[b,i] er[b,i,n,c] + sum_j m[b,j] ec[b,n,j,c], sum_k m[b,k] )   [B,N,s_e]
+ *   e_out = e + Dense_2( act( [ tail | hr[b,i,:] + hc[b,j,:] ] ) )
+ * hr / hc [B,N,s_n] are the two leading channel groups of the node side's Dense_1 output, hn joins the node side's
+ * Dense_2 input; the node side (three [B,N,.] operations) stays with the caller.  lr2_kernel is [H - 2 s_e + s_n, De];
+ * the other parameters have the shapes of egt_ffn_params.  mask: [B,N] fp32, 1 = node, 0 = padding; padded pairs are
+ * not masked in e_out, only the summed index is.  Sums are taken in a fixed order, without atomics.
+ * Covered: fp32, De in {16,32,64}, Dh in {48,64}, any N, s_e and s_n multiples of 4 with 2 s_e <= 2 De, 2 s_n <= 2 Dh,
+ * not both 0 (that is egt_ffn_fwd), EGT_ACT_ELU / EGT_ACT_RELU, exact fp32 products.  egt_xtalk_supported answers; the
+ * entry points refuse anything else with a code and a message before any launch.
+ * With s_n = 0, hr / hc / d_hr / d_hc are not touched and may be NULL; with s_e = 0, hn / d_hn likewise.
+ * One workspace size serves both directions; nothing in it is carried from the forward to the backward.
+ * No aliasing: in particular d_e must not alias d_e_out (at De = 64 with s_n > 32 the backward reads d_e_out a second time). */
+typedef struct egt_xtalk_desc {
+  int32_t B, N;
+  int32_t De;         /* edge width */
+  int32_t Dh;         /* node width (bounds s_n) */
+  int32_t s_e;        /* edge -> node channels: round(edge2node_xtalk * De) */
+  int32_t s_n;        /* node -> edge channels: round(node2edge_xtalk * Dh) */
+  int32_t dtype;      /* EGT_F32 */
+  int32_t activation; /* EGT_ACT_ELU or EGT_ACT_RELU */
+  float ln_eps;       /* 1e-3 */
+  int32_t flags;      /* 0 */
+  int32_t reserved;   /* 0 */
+} egt_xtalk_desc;
+
+int egt_xtalk_supported(const egt_xtalk_desc* desc);
+size_t egt_xtalk_workspace_bytes(const egt_xtalk_desc* desc);
+int egt_xtalk_fwd(const egt_xtalk_desc* desc, const egt_ffn_params* params, const void* e, const void* mask,
+                  const void* hr, const void* hc, void* e_out, void* hn, void* workspace, void* stream);
+/* e is the layer INPUT (the hidden activations are recomputed); every pointer of `grads` is written, and so is every
+ * element of d_e, d_hr and d_hc. */
+int egt_xtalk_bwd(const egt_xtalk_desc* desc, const egt_ffn_params* params, const void* e, const void* mask,
+                  const void* hr, const void* hc, const void* d_e_out, const void* d_hn, void* d_e, void* d_hr,
+                  void* d_hc, const egt_ffn_params* grads, void* workspace, void* stream);
+
 /* ---- mask producers (integer / boolean work: bit-exact) ---------
  * The masks the path consumes are produced by the model around it; these entry points replace
  *   Neg1MaskedEmbedding.compute_mask   lib/base/xformer_layers/masking.py:35-43   (x + 1) != 0
