@@ -325,6 +325,7 @@ _PROTOS = {
                     + [C.POINTER(FfnParams)] + [_VP] * 2),
     "egt_xtalk_supported": (C.c_int, [C.POINTER(XtalkDesc)]),
     "egt_xtalk_workspace_bytes": (C.c_size_t, [C.POINTER(XtalkDesc)]),
+    "egt_xtalk_launch_form": (C.c_char_p, [C.POINTER(XtalkDesc)]),
     "egt_xtalk_fwd": (C.c_int, [C.POINTER(XtalkDesc), C.POINTER(FfnParams)] + [_VP] * 8),
     "egt_xtalk_bwd": (C.c_int, [C.POINTER(XtalkDesc), C.POINTER(FfnParams)] + [_VP] * 9
                       + [C.POINTER(FfnParams)] + [_VP] * 2),

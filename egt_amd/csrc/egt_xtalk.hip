@@ -94,8 +94,10 @@ __global__ void __launch_bounds__(256) k_xtalk_prep(XtArgs a) {
   }
 }
 
-__device__ __forceinline__ float xt_act(float v, int relu) {   // relu, or elu with the Keras default alpha = 1
-  return v > 0.f ? v : (relu ? 0.f : __expf(v) - 1.0f);
+// relu, or elu with the Keras default alpha = 1.  expm1f, not the fast exp minus 1: that difference cancels for |v| << 1 (6e-8
+// absolute on a value of |v|; tests/test_conditioning_gpu.py small_weights4).  xt_dact's hid + 1 is exp(v) to the same accuracy.
+__device__ __forceinline__ float xt_act(float v, int relu) {
+  return v > 0.f ? v : (relu ? 0.f : expm1f(v));
 }
 __device__ __forceinline__ float xt_dact(float hid, int relu) {   // derivative from the activation's OUTPUT
   return hid > 0.f ? 1.f : (relu ? 0.f : hid + 1.0f);
@@ -670,6 +672,19 @@ static XtPlan plan_xtalk(const egt_xtalk_desc* d) {
 extern "C" size_t egt_xtalk_workspace_bytes(const egt_xtalk_desc* d) {
   if (!egt_xtalk_supported(d)) return 0;
   return plan_xtalk(d).total * sizeof(float);
+}
+
+// The launch plan plan_xtalk chose for `d`, as text:
+//   "fwd=k_xtalk_fwd<W,SNT>/rb8/g<grid> bwd=k_xtalk_bwd<W,SNT>/rb<rows per wave>/g<grid>[/walk2]"
+// (/walk2: the W = 64, SNT >= 3 instances, whose backward takes the exchange rows of T2 in its second walk).  For tests and
+// bench lines that must not assume which instance and row block a shape reaches.  Thread-local string; NULL when `d` is not covered.
+extern "C" const char* egt_xtalk_launch_form(const egt_xtalk_desc* d) {
+  if (!egt_xtalk_supported(d)) return nullptr;
+  const XtPlan P = plan_xtalk(d);
+  static thread_local char buf[128];
+  snprintf(buf, sizeof buf, "fwd=k_xtalk_fwd<%d,%d>/rb%d/g%d bwd=k_xtalk_bwd<%d,%d>/rb%d/g%d%s", P.W, P.snt, P.rb_f, P.fwd.grid,
+           P.W, P.snt, P.rb_b, P.bwd.grid, P.W == 64 && P.snt >= 3 ? "/walk2" : "");
+  return buf;
 }
 
 static int xtalk_fill(const egt_xtalk_desc* d, const egt_ffn_params* p, const void* e, const void* mask, const void* hr,

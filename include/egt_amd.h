@@ -543,6 +543,11 @@ typedef struct egt_xtalk_desc {
 
 int egt_xtalk_supported(const egt_xtalk_desc* desc);
 size_t egt_xtalk_workspace_bytes(const egt_xtalk_desc* desc);
+/* The launch plan, a pure host function of the descriptor, as text:
+ *   "fwd=k_xtalk_fwd<W,SNT>/rb8/g<grid> bwd=k_xtalk_bwd<W,SNT>/rb<rows per wave>/g<grid>[/walk2]"
+ * W = De, SNT = ceil(s_n / 16); /walk2 marks the W = 64, SNT >= 3 instances whose backward walks its pairs a second time.
+ * Thread-local string, needs no device; NULL for a descriptor egt_xtalk_supported declines. */
+const char* egt_xtalk_launch_form(const egt_xtalk_desc* desc);
 int egt_xtalk_fwd(const egt_xtalk_desc* desc, const egt_ffn_params* params, const void* e, const void* mask,
                   const void* hr, const void* hc, void* e_out, void* hn, void* workspace, void* stream);
 /* e is the layer INPUT (the hidden activations are recomputed); every pointer of `grads` is written, and so is every

@@ -5,7 +5,7 @@ tensors (rounded to bfloat16 afterwards where the case stores bf16); the kernel 
 
     offset32       +32 on the residual streams (h, e, the FFN's x)                LN mean >> std
     const_rows     30 % of the rows (last axis) hold one value, a tenth of them 0  variance exactly 0, rstd = ln_eps^-1/2
-    tiny / big     inputs * 2^-10 / * 64 (STRENGTH: 32 / 16 on the block / stack / FFN)    variance << ln_eps / large x - mu
+    tiny / big     inputs * 2^-10 / * 64 (STRENGTH: 32 / 16 on the block / stack / FFN / xtalk)    variance << ln_eps / large x - mu
     outliers       2 % of the elements * 50 (STRENGTH: 32 on the block / stack)    one element dominates a row's moments
     pad32          padded node rows of h, padded pairs of e set to +-32            padding off the data's scale
     sharp          dense_qkv.kernel * 16 (inner op: QKV * 8), clip (-5, 5)         every logit on the clip
@@ -14,6 +14,7 @@ tensors (rounded to bfloat16 afterwards where the case stores bf16); the kernel 
     edge_bias_big  dense_edge_b.kernel * 16 (inner op: E * 16), clip off          edge bias dominates QK^T
     small_weights  every Dense kernel * 1e-3                                      outputs near 0
     small_weights4 (ELU cases of edge_proj) kernels AND biases * 1e-4             exp(x) - 1 cancels
+                   (ELU cases of ffn and xtalk) lr1 kernel AND bias * 1e-4, lr2 kept: d lr2_kernel carries elu(v), |v| ~ 1e-4
     one_sided_h / one_sided_e   only dh' / only de' given (inner op: only dV_att)  the NULL upstream-gradient branches
 
 The COMPARISON (`compare`) uses util.FWD / util.BWD unchanged.  util.assert_close scales its absolute term by the maximum of
@@ -55,6 +56,7 @@ DEFAULT = dict(offset32=32.0, tiny=2.0 ** -10, big=64.0, outliers=50.0, pad32=32
 STRENGTH = {
     # store rounding of h + update at |h| ~ 64 * 3 is 0.27 - 0.47 of FWD on the update (fp32 oracle); 0.13 - 0.23 at these
     ("block", "big"): 32.0, ("stack", "big"): 16.0, ("ffn", "big"): 32.0,
+    ("xtalk", "big"): 32.0,                                 # 0.15 - 0.51 at 64 on the updates (store rounding at |h|, |e| ~ 100 * 3); 0.10 - 0.22 at 32
     # one h element of ~100: 0.35 (block, bf16 case) / 0.41 (stack, pair operator) at 50
     ("block", "outliers"): 32.0, ("stack", "outliers"): 32.0,
     # one block: kernel * 8 puts 0.85 - 0.88 of the logits on the clip (LN output through a Glorot kernel is below unit scale), * 16
@@ -215,7 +217,7 @@ def leaf(t, dtype):
 
 # the upstream gradients of each operator's case["inp"] (the homogeneity tests scale them)
 UPSTREAM = dict(block=("dh", "de"), stack=("dh", "de"), attn=("dV", "dH"), edge_proj=("dG", "dE"), edge_update=("de",), ffn=("dy",),
-                edge_head=("s",), node_head=("up",))
+                edge_head=("s",), node_head=("up",), xtalk=("dh", "de"))
 
 
 def scaled_upstream(case, factor):
@@ -584,6 +586,10 @@ FFN_CASES = [(W, mm, bf, act) for W, mm in ((64, "f32"), (64, "bf16x3"), (16, "f
 FFN_RECIPES = ("offset32", "const_rows", "tiny", "big", "outliers", "small_weights")
 
 
+def ffn_recipes(act):
+    return FFN_RECIPES + (("small_weights4",) if act == "elu" else ())
+
+
 def make_ffn(W, matmul, bf16, act, recipe):
     g, gr = gen("ffn", W), gen("ffn", W, recipe)
     Hd = 2 * W
@@ -597,6 +603,9 @@ def make_ffn(W, matmul, bf16, act, recipe):
     if recipe == "small_weights":
         for k in ("lr1_kernel", "lr2_kernel"):
             params[k] = params[k] * s
+    elif recipe == "small_weights4":                # every ELU pre-activation ~1e-4; lr2 keeps its scale, so d lr2_kernel shows elu(v)
+        for k in ("lr1_kernel", "lr1_bias"):
+            params[k] = params[k] * s
     else:
         inp["x"] = condition(inp["x"], recipe, gr, s, picks, "x")
     if bf16:
@@ -609,6 +618,8 @@ def make_ffn(W, matmul, bf16, act, recipe):
 def ffn_oracle(case, dtype=torch.float64, inner=False):
     x = leaf(case["inp"]["x"], dtype)
     p = {k: leaf(v, dtype) for k, v in case["params"].items()}
+    if inner:
+        return dict(pre=O.dense(O.layer_norm(x, p["norm_gamma"], p["norm_beta"]), p["lr1_kernel"], p["lr1_bias"]).detach())
     y = O.ffn_forward(x, p, activation=case["act"])
     gr = torch.autograd.grad(y, [x] + [p[k] for k in FFN_NAMES], case["inp"]["dy"].to(dtype))
     out = {"y": y.detach(), "dx": gr[0]}
@@ -625,6 +636,83 @@ def ffn_gpu(case, dev):
     y.backward(case["inp"]["dy"].to(dev).to(dt))
     out = {"y": y.detach(), "dx": x.grad}
     out.update({"d" + k: p[k].grad for k in FFN_NAMES})
+    return out
+
+
+# ================================================================================================ cross-talk FFN ==
+# The full xtalk_ffn (h, e -> h', e'; dh, de and twelve parameter gradients) at cases of xtalk_cases.OP_CASES.  n21_de64_sn64
+# runs with elu here: with its own relu the fp32 oracle reaches 225 on the node-side gradients under offset32 -- one ReLU kink
+# crossing of hr_i + hc_j flips a whole row's contribution -- and 0.08 with elu.
+XTALK_CASES = {"n9_de16": None, "n19_de32_relu": None, "n37_de64": None, "n33_de16_empty": None, "n21_de64_sn64": "elu"}
+XTALK_RECIPES = ("offset32", "const_rows", "tiny", "big", "outliers", "pad32", "small_weights", "one_sided_h", "one_sided_e")
+XTALK_SIDES = ("node", "edge")
+
+
+def xtalk_act(cid):
+    import xtalk_cases as XC
+    return XTALK_CASES[cid] or XC.OP_CASES[cid]["act"]
+
+
+def xtalk_recipes(cid):
+    return XTALK_RECIPES + (("small_weights4",) if xtalk_act(cid) == "elu" else ())
+
+
+def make_xtalk(cid, recipe):
+    import xtalk_cases as XC
+    c, inp, pn, pe = XC.op_inputs(cid)
+    c = dict(c, act=xtalk_act(cid))
+    gr = gen("xtalk", cid, recipe)
+    params = {f"{side}.{k}": v for side, p in zip(XTALK_SIDES, (pn, pe)) for k, v in p.items()}
+    picks = {}
+    s = strength("xtalk", recipe, cid)
+    if recipe in ("offset32", "const_rows", "tiny", "big", "outliers"):
+        for k in ("h", "e"):
+            inp[k] = condition(inp[k], recipe, gr, s, picks, k)
+    elif recipe == "pad32":
+        node, pair = pad_regions(inp["mask"])
+        inp["h"], inp["e"] = pad32(inp["h"], node, gr, s), pad32(inp["e"], pair, gr, s)
+    elif recipe in ("small_weights", "small_weights4"):
+        for side in XTALK_SIDES:
+            for k in ("lr1_kernel", "lr2_kernel") if recipe == "small_weights" else ("lr1_kernel", "lr1_bias"):
+                params[f"{side}.{k}"] = params[f"{side}.{k}"] * s
+    elif recipe == "one_sided_h":
+        inp["de"] = None
+    elif recipe == "one_sided_e":
+        inp["dh"] = None
+    elif recipe != "plain":
+        raise KeyError(recipe)
+    spec = [("h_out", "fwd", "h", "node"), ("e_out", "fwd", "e", "pair"), ("dh", "bwd", None, "node"), ("de", "bwd", None, "pair")] + \
+           [(k, "bwd", None, None) for k in params]
+    return dict(op="xtalk", id=cid, recipe=recipe, c=c, inp=inp, params=params, spec=spec, picks=picks)
+
+
+def xtalk_oracle(case, dtype=torch.float64, inner=False):
+    import xtalk_cases as XC
+    inp, c = case["inp"], case["c"]
+    h, e = leaf(inp["h"], dtype), leaf(inp["e"], dtype)
+    p = {k: leaf(v, dtype) for k, v in case["params"].items()}
+    pn, pe = ({k: p[f"{side}.{k}"] for k in FFN_NAMES} for side in XTALK_SIDES)
+    if inner:       # fnn_lr1's outputs: every ELU pre-activation is one of them, a sum of two, or a masked mean of such sums
+        return dict(pre_node=O.dense(O.layer_norm(h, pn["norm_gamma"], pn["norm_beta"]), pn["lr1_kernel"], pn["lr1_bias"]).detach(),
+                    pre_edge=O.dense(O.layer_norm(e, pe["norm_gamma"], pe["norm_beta"]), pe["lr1_kernel"], pe["lr1_bias"]).detach())
+    h2, e2 = XC.xtalk_ffn_ref(h, e, inp["mask"], pn, pe, c["n2e"], c["e2n"], c["act"])
+    gr = _grads([h2, e2], [h, e] + list(p.values()), [inp["dh"], inp["de"]])
+    out = dict(h_out=h2.detach(), e_out=e2.detach(), dh=gr[0], de=gr[1])
+    out.update(dict(zip(p, gr[2:])))
+    return out
+
+
+def xtalk_gpu(case, dev):
+    from egt_amd.xtalk import xtalk_ffn
+    inp, c = case["inp"], case["c"]
+    h, e = inp["h"].to(dev).requires_grad_(), inp["e"].to(dev).requires_grad_()
+    p = {k: v.to(dev).requires_grad_() for k, v in case["params"].items()}
+    pn, pe = ([p[f"{side}.{k}"] for k in FFN_NAMES] for side in XTALK_SIDES)
+    h2, e2 = xtalk_ffn(h, e, inp["mask"].to(dev), pn, pe, c["n2e"], c["e2n"], c["act"])
+    pairs = [(o, u.to(dev)) for o, u in ((h2, inp["dh"]), (e2, inp["de"])) if u is not None]
+    torch.autograd.backward([o for o, _ in pairs], [u for _, u in pairs])
+    out = dict(h_out=h2.detach(), e_out=e2.detach(), dh=h.grad, de=e.grad)
+    out.update({k: v.grad for k, v in p.items()})
     return out
 
 

@@ -9,7 +9,8 @@ figure next to each entry; the tests' docstrings below name them).
 
 Saturation: sharp puts >= 90 % of the unmasked logits of real rows on a clip bound; sharp_noclip makes the median largest
 softmax weight of real rows >= 0.9; gates_sat puts >= 80 % of the gates outside (1e-3, 1 - 1e-3); const_rows rows have variance
-exactly 0 in fp32; small_weights4 keeps every ELU pre-activation of edge_proj below 1e-2."""
+exactly 0 in fp32; small_weights4 keeps every ELU pre-activation of edge_proj, of the channel FFN and of the cross-talk FFN
+below 1e-2."""
 import pytest
 import torch
 
@@ -132,6 +133,30 @@ def test_ffn_recipes_are_fair(W, act, recipe):
     _fair(case, CD.ffn_oracle)
     if recipe == "const_rows":
         _const_rows_exact(case)
+
+
+@pytest.mark.parametrize("W", [64, 16, 8])
+def test_ffn_small_weights4_is_fair_and_small(W):
+    """the ELU cases' own recipe: lr1 kernel and bias * 1e-4 put every ELU pre-activation below 1e-2, where exp(v) - 1 cancels"""
+    case = CD.make_ffn(W, "f32", False, "elu", "small_weights4")
+    assert "small_weights4" in CD.ffn_recipes("elu") and "small_weights4" not in CD.ffn_recipes("relu")
+    _fair(case, CD.ffn_oracle)
+    assert float(CD.ffn_oracle(case, inner=True)["pre"].abs().max()) < 1e-2
+
+
+@pytest.mark.parametrize("cid,recipe", [(cid, recipe) for cid in CD.XTALK_CASES for recipe in CD.xtalk_recipes(cid)])
+def test_xtalk_recipes_are_fair(cid, recipe):
+    """big runs at * 32 (0.10 - 0.22): the fp32 oracle reaches 0.15 - 0.51 on the updates at * 64.  n21_de64_sn64 runs with elu
+    (conditioning.XTALK_CASES: a ReLU kink crossing of hr_i + hc_j under offset32 is the recipe's doing, not a kernel's)."""
+    case = CD.make_xtalk(cid, recipe)
+    _fair(case, CD.xtalk_oracle)
+    if recipe == "const_rows":
+        _const_rows_exact(case)
+    if recipe == "small_weights4":
+        # the ELU pre-activations are fnn_lr1 outputs, sums of two (hr_i + hc_j) or masked means of two sums (hn): all below
+        # 1e-2 while every fnn_lr1 output is below 5e-3
+        inner = CD.xtalk_oracle(case, inner=True)
+        assert CD.xtalk_act(cid) == "elu" and max(float(inner[k].abs().max()) for k in ("pre_node", "pre_edge")) < 5e-3
 
 
 @pytest.mark.parametrize("recipe", CD.HEAD_RECIPES)

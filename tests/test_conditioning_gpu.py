@@ -19,7 +19,12 @@ pytestmark = pytest.mark.gpu
 MARGINS = {}     # operator -> recipe -> [worst margin, "case / output"]
 
 # (operator, case id, recipe) -> reason with the measured margin: strict expected failures, listed under the gaps of DESIGN.md
-XFAIL = {}
+_FFN_ELU = ("ffn_act (csrc/egt_ffn.hip) takes ELU as the fast exp minus 1: 6e-8 absolute on hidden values of ~1e-4; margin {} on "
+            "d lr2_kernel.  Both accurate forms cost more than the parent's spread of the layers-scope step (DESIGN.md, gaps)")
+XFAIL = {
+    ("ffn", "W64_f32_fp32_elu", "small_weights4"): _FFN_ELU.format("1.118"),
+    ("ffn", "W64_bf16x3_fp32_elu", "small_weights4"): _FFN_ELU.format("1.093"),
+}
 
 
 def _p(op, cid, recipe, *values):
@@ -118,13 +123,21 @@ def test_edge_update(De, recipe, gpu, egt_lib):
 # ------------------------------------------------------------------------------------------------------ channel FFN --
 @pytest.mark.parametrize("W,matmul,bf16,act,recipe", [
     _p("ffn", f"W{W}_{mm}_{'bf16' if bf else 'fp32'}_{act}", recipe, W, mm, bf, act, recipe)
-    for W, mm, bf, act in CD.FFN_CASES for recipe in CD.FFN_RECIPES])
+    for W, mm, bf, act in CD.FFN_CASES for recipe in CD.ffn_recipes(act)])
 def test_ffn(W, matmul, bf16, act, recipe, gpu, egt_lib):
     case = CD.make_ffn(W, matmul, bf16, act, recipe)
     got = CD.ffn_gpu(case, gpu)
     if bf16:
         assert got["y"].dtype == torch.bfloat16 and got["dx"].dtype == torch.bfloat16
     _check(case, got, CD.ffn_oracle(case))
+
+
+# --------------------------------------------------------------------------------------------------- cross-talk FFN --
+@pytest.mark.parametrize("cid,recipe", [_p("xtalk", cid, recipe, cid, recipe) for cid in CD.XTALK_CASES for recipe in CD.xtalk_recipes(cid)])
+def test_xtalk(cid, recipe, gpu, egt_lib):
+    """the full xtalk_ffn (fused edge side, torch node side): h', e', dh, de and the twelve parameter gradients"""
+    case = CD.make_xtalk(cid, recipe)
+    _check(case, CD.xtalk_gpu(case, gpu), CD.xtalk_oracle(case))
 
 
 # ------------------------------------------------------------------------------------------------------------ heads --
@@ -188,6 +201,13 @@ def test_edge_backwards_are_homogeneous(De, act, gpu, egt_lib):
                                                (16, "bf16x3", False, "elu"), (8, "f32", False, "elu"), (8, "f32", True, "relu")])
 def test_ffn_backward_is_homogeneous(W, matmul, bf16, act, gpu, egt_lib):
     _homogeneous(CD.make_ffn(W, matmul, bf16, act, "plain"), CD.ffn_gpu, gpu)
+
+
+@pytest.mark.parametrize("cid", ["n9_de16", "n19_de32_relu", "n21_de64_sn64"])
+def test_xtalk_backward_is_homogeneous(cid, gpu, egt_lib):
+    """egt_xtalk_bwd behind xtalk_ffn at De 16, 32 and 64 (the last with s_n = 64: the backward's second walk); both upstream
+    gradients scaled"""
+    _homogeneous(CD.make_xtalk(cid, "plain"), CD.xtalk_gpu, gpu)
 
 
 def test_head_backwards_are_homogeneous(gpu, egt_lib):
